@@ -3,7 +3,14 @@
     "point-pairs/sec Chamfer (B x N x M) at 1/2/4/8 GPU", configs[1] = Chamfer fwd+bwd, B=32,
     2048 vs 16384; "EMD iters/sec" as an extra field.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  * a plain run is lean: set up, W warm-up steps, K timed steps, the outputs (--dump-outputs), the
+    result line (`metric`, `value`, `unit`, `ms_per_step`, ...).  Everything below that is not the
+    headline -- rooflines and per-kernel figures (runs of their own), the other shapes, workloads and
+    distributions, the CPU baselines -- runs only with --full (--no-extras / --no-cpu-baseline trim it).
+  * --dump-outputs DIR: after the timed steps, what the timed path returned in its LAST step, as
+    DIR/<name>.npy in float32 / float64 (indices as float64), at most 64 MB in all (a seeded sample of
+    batch elements beyond that).  Inputs are seeded, so two builds can be compared output for output.
   * N>1: when WORLD_SIZE is already set (the driver's `python -m torch.distributed.run ...
     bench.py --gpus N`), this process IS one rank.  When it is not, the script starts the N ranks
     ITSELF: the parent -- before any torch.cuda / HIP call -- runs `python -m
@@ -18,7 +25,7 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
     tf_ops/CD/tf_nndistance.py:50), ONE C-ABI call (rf_chamfer_step) on buffers allocated once,
     inputs resident in HBM before the timed region.
   * rank 0 prints ONE JSON line.  `value` = B*N*M*K*world / seconds (pairs/s, whole job).
-  * "roofline": the forward is fp32-VALU bound: NOT HBM (20*B*(N+M) bytes) and
+  * with --full: "roofline": the forward is fp32-VALU bound: NOT HBM (20*B*(N+M) bytes) and
     NOT MFMA ((b-a)^2 is not a product of a row and a column factor).  The dominant kernel is
     nnp_sweep, the culled exact sweep (nn_pruned.hip: sort-tile-recursive sort + box-bound culling,
     bit-identical outputs).  `achieved`/`frac` are what the VALU EXECUTED: 8 flop x the directed
@@ -42,7 +49,7 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
     "emd.roofline": the EMD half of the metric against its transcendental-VALU issue floor.
   * `--workload c5`: BASELINE.json configs[4] on this rank's share (B=32 per GPU): RFNet recurrent
     forward (3 steps to 16384 points) + chamfer_big + earth_mover at 64^2 / 1024^2, per-sample
-    losses all-gathered over the ranks; reported in samples/s.  The default run carries the same
+    losses all-gathered over the ranks; reported in samples/s.  A --full run carries the same
     measurement as the extra field "c5" (few steps).
 """
 import argparse
@@ -120,6 +127,34 @@ def emd_issue_floor_ms(eb, n, m):
 HBM_PEAK_GBPS = 8000.0    # MI355X_MICROARCH.md: HBM3E spec peak
 # transcendental issue roof: v_exp_f32 issues once per 8.14 cycles per SIMD (profiles/issue_costs.json), 1024 SIMDs x 64 lanes, 2.36 GHz
 TRANS_ROOF_EXP_PER_S = 1024 * 64 * 2.36e9 / 8.14
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+# ----------------------------------------------------------------------------- outputs -------
+def host_outputs(named):
+    """{name: host array} of the timed path's outputs, copied off the device NOW (a plan's buffers are
+    overwritten by its next call).  Floating outputs as float32, integer ones (indices) as float64."""
+    out = {}
+    for name, t in named:
+        a = t.detach().cpu().numpy()
+        out[name] = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy for every array (all share the batch as their leading axis).  Beyond
+    DUMP_LIMIT_BYTES in all, the same seeded sample of batch elements of every array is written, and
+    its batch indices as batch_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        batch = next(iter(arrays.values())).shape[0]
+        keep = max(1, min(batch, int(batch * (DUMP_LIMIT_BYTES - 8 * batch) // total)))
+        sel = np.sort(np.random.RandomState(0).choice(batch, keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[sel]) for k, a in arrays.items()}
+        arrays["batch_index"] = sel.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------- launching -----
@@ -449,8 +484,9 @@ def run_c3(rank, dev, fence, reps):
     }
 
 
-def run_c5(args, rank, world, dev, steps, warmup, use_pg):
-    """BASELINE.json configs[4], this rank's share: B=32 samples of (3000 partial, 16384 gt)."""
+def run_c5(args, rank, world, dev, steps, warmup, use_pg, want_outputs=False):
+    """BASELINE.json configs[4], this rank's share: B=32 samples of (3000 partial, 16384 gt).
+    -> (figures, {name: host array} of the last timed step's gathered losses if want_outputs)"""
     from rfnet_amd import glue, shard
     from rfnet_amd.rfnet import GroundTruth, RFNet
     B = args.batch
@@ -533,6 +569,7 @@ def run_c5(args, rank, world, dev, steps, warmup, use_pg):
         full = step()
     fence()
     dt = time.perf_counter() - t0
+    outputs = host_outputs([("per_sample_losses", full)]) if want_outputs else None
     tm = torch.tensor([dt], dtype=torch.float64, device=dev)
     chk = full.double().sum().reshape(1)
     lo, hi = chk.clone(), chk.clone()
@@ -547,7 +584,7 @@ def run_c5(args, rank, world, dev, steps, warmup, use_pg):
     # replayed from a HIP graph (checked against the eager gradients at capture), gradients all-reduced
     # over the ranks (RCCL, one flat 15 MB bucket), TensorFlow-form Adam.  A few steps: an extra, not the metric.
     train = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         from rfnet_amd.trainrun import TrainStep
         ts = TrainStep(net, B, graph=not args.c5_eager)
         for _ in range(2):
@@ -577,7 +614,7 @@ def run_c5(args, rank, world, dev, steps, warmup, use_pg):
         "gathered_losses_shape": list(full.shape), "finite": bool(torch.isfinite(full).all().item()),
         "losses_equal_across_ranks": bool(lo.item() == hi.item()),
         "mean_losses": [float(x) for x in full.double().mean(0).tolist()],
-    }
+    }, outputs
 
 
 def main():
@@ -589,14 +626,22 @@ def main():
     ap.add_argument("--n", type=int, default=2048)
     ap.add_argument("--m", type=int, default=16384)
     ap.add_argument("--workload", choices=["chamfer", "c5"], default="chamfer")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: rooflines and per-kernel figures, the other shapes, workloads and "
+                         "distributions, the CPU baselines (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
     ap.add_argument("--c5-eager", action="store_true", help="run the C5 step with eager launches instead of a captured HIP graph")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline + roofline only (profiling runs)")
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="TEST ONLY: exercise the multi-rank plumbing (self-launch, init, fences, "
                          "max-over-ranks, loss gather, rank-0 JSON) on CPU/gloo with placeholder work; prints "
                          "a line marked dry_run and measures nothing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)  # never returns; nothing above touched the GPU
     # stdout carries exactly ONE line (rank 0's JSON): whatever the libraries underneath print to
@@ -632,7 +677,10 @@ def main():
         torch.cuda.synchronize()
 
     if args.workload == "c5":
-        c5 = run_c5(args, rank, world, dev, args.steps, args.warmup, use_pg)
+        c5, outputs = run_c5(args, rank, world, dev, args.steps, args.warmup, use_pg,
+                             want_outputs=bool(args.dump_outputs) and rank == 0)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         if rank == 0:
             emit({
                 "metric": "samples/sec RFNet forward + CD/EMD loss (BASELINE.json configs[4])",
@@ -667,6 +715,48 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     checksum = float(out[0].double().sum().item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, host_outputs(zip(("dist1", "idx1", "dist2", "idx2", "grad_xyz1", "grad_xyz2"), out)))
+    tm = torch.tensor([dt], dtype=torch.float64, device=dev)
+    if use_pg:
+        torch.distributed.all_reduce(tm, op=torch.distributed.ReduceOp.MAX)
+    dt = float(tm.item())
+    pairs_per_step = B * N * M
+    line = {
+        "metric": "point-pairs/sec Chamfer (BxNxM)",
+        "value": world * pairs_per_step * args.steps / dt,
+        "value_is": "B*N*M pairs per step / time (an effective rate where the forward culls: --full reports the evaluated "
+                    "fraction and the check against the sweep that evaluates every pair)",
+        "unit": "pairs/s",
+        "n_gpus": world,
+        "rccl_ranks": world if use_pg else 1,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"Chamfer nn_distance fwd+bwd, B={B} per GPU, {N} vs {M} points "
+                        "(BASELINE.json configs[1]), randn seed 100",
+            "batch_per_gpu": B, "n": N, "m": M, "sharding": f"batch x{world}",
+            "step": "rf_chamfer_step: one C-ABI call, caller-allocated outputs",
+            "scaling_note": f"weak: every GPU runs B={B}; N GPUs = a global batch of {B}*N (BASELINE.json configs[4]'s "
+                            "B=256 is 8 x 32)",
+        },
+        "checksum": checksum,
+    }
+    if not args.full:
+        if rank == 0:
+            emit(line)
+        if use_pg:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
+
+    # ---- --full from here on --------------------------------------------------------------------
     # the same K steps again with per-kernel hipEvents (librfops records them on the launch
     # stream) -> roofline.achieved; its wall time is reported next to the un-instrumented one
     _lib.profile_collect()
@@ -1004,15 +1094,9 @@ def main():
         # ---- configs[2]: FPS + gather + ball query + group ------------------------------------
         extras["c3"] = run_c3(rank, dev, fence, max(5, min(20, args.steps)))
         # ---- configs[4] on this rank's share (also `--workload c5`) -----------------------------
-        extras["c5"] = run_c5(args, rank, world, dev, steps=3, warmup=1, use_pg=use_pg)
-
-    tm = torch.tensor([dt], dtype=torch.float64, device=dev)
-    if use_pg:
-        torch.distributed.all_reduce(tm, op=torch.distributed.ReduceOp.MAX)
-    dt = float(tm.item())
+        extras["c5"] = run_c5(args, rank, world, dev, steps=3, warmup=1, use_pg=use_pg)[0]
 
     if rank == 0:
-        pairs_per_step = B * N * M
         culled = "nnp_sweep" in prof
         kname = "nnp_sweep" if culled else "nn_sweep"
         sweep_ms, sweep_n = prof.get(kname, (0.0, 0))
@@ -1062,33 +1146,12 @@ def main():
                     "traffic": traffic.get(kname), "flops_per_launch": flops, "avg_launch_ms": sweep_avg_s * 1e3,
                     "launches": sweep_n}
         kernel_sum_ms = sum(v[0] for v in prof.values()) / args.steps
-        line = {
-            "metric": "point-pairs/sec Chamfer (BxNxM)",
-            "value": world * pairs_per_step * args.steps / dt,
-            "value_is": (f"effective rate: B*N*M pairs per step / time; the culled sweep evaluated "
-                         f"{100.0 * evaluated / (2.0 * B * N * M):.1f} % of the 2*B*N*M directed pairs and returns outputs "
-                         "bit-identical to the sweep that evaluates all of them (roofline.identical_to_dense_sweep)") if culled and len(culled_stats) >= 14 and sweep_avg_s
-                        else "B*N*M pairs per step / time; every pair evaluated",
-            "unit": "pairs/s",
-            "n_gpus": world,
-            "rccl_ranks": world if use_pg else 1,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": f"Chamfer nn_distance fwd+bwd, B={B} per GPU, {N} vs {M} points "
-                            "(BASELINE.json configs[1]), randn seed 100",
-                "batch_per_gpu": B, "n": N, "m": M, "sharding": f"batch x{world}",
-                "forward": "culled sweep (nn_pruned.hip)" if culled else "dense sweep (nn_distance.hip)",
-                "step": "rf_chamfer_step: one C-ABI call, caller-allocated outputs",
-                "scaling_note": f"weak: every GPU runs B={B}; N GPUs = a global batch of {B}*N (BASELINE.json configs[4]'s "
-                                "B=256 is 8 x 32)",
-            },
+        line["value_is"] = ((f"effective rate: B*N*M pairs per step / time; the culled sweep evaluated "
+                             f"{100.0 * evaluated / (2.0 * B * N * M):.1f} % of the 2*B*N*M directed pairs and returns outputs "
+                             "bit-identical to the sweep that evaluates all of them (roofline.identical_to_dense_sweep)")
+                            if culled and len(culled_stats) >= 14 and sweep_avg_s else "B*N*M pairs per step / time; every pair evaluated")
+        line["config"]["forward"] = "culled sweep (nn_pruned.hip)" if culled else "dense sweep (nn_distance.hip)"
+        line.update({
             "roofline": roof,
             "roofline_dense": {
                 "bound": "valu", "kernel": "nn_sweep (RF_NN_DENSE: every pair evaluated)",
@@ -1119,7 +1182,6 @@ def main():
             # launches and lengthen it: ms_per_step_instrumented.  The un-instrumented step can therefore be SHORTER than that sum;
             # no "host overhead" is derived from the two.)
             "ms_per_step_instrumented": dt_prof / args.steps * 1e3,
-            "checksum": checksum,
             # how far the checker itself is pinned: the GPU path is bit-exact / in
             # tolerance against oracle/rfops_oracle.c in tests/; this says what pins THAT oracle
             "parity": {
@@ -1131,7 +1193,7 @@ def main():
                                                      "query_ball_point pts_cnt", "auction_match", "prob_sample", "select_top_k",
                                                      "RFNet graph + loss block (oracle/rfnet_oracle.py)"],
             },
-        }
+        })
         line.update(extras)
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(B, N, M, 100, sample_b=B, with_grad=True)

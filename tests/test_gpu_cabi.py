@@ -162,7 +162,7 @@ def test_bench_rccl_path_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(RF_FORCE_PG="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29531", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2",
-                          "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
+                          "--full", "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600,
                          env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

@@ -1,4 +1,4 @@
-"""DESIGN.md = its section sources (design_*.md, this directory) with the @PLACEHOLDERS@ filled from a bench.py line and the
+"""DESIGN.md = its section sources (design_*.md, this directory) with the @PLACEHOLDERS@ filled from a `bench.py --full` line and the
 gradient A/B: python tools/docsrc/assemble_design.py profiles/r06_bench.json profiles/r06_ab_group_grad.txt <gpu tests passed>"""
 import json, sys, re
 bj = json.loads(open(sys.argv[1]).read())

@@ -2,7 +2,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/r05_step_trace; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/stats" -- python3 "$R/bench.py" --steps 50 --warmup 5 --no-cpu-baseline --no-extras > /dev/null 2> "$OUT/err.txt"
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/stats" -- python3 "$R/bench.py" --full --steps 50 --warmup 5 --no-cpu-baseline --no-extras > /dev/null 2> "$OUT/err.txt"
 python3 - <<PY
 import csv,glob,re,statistics
 f=sorted(glob.glob("$OUT/stats/**/*kernel_trace.csv",recursive=True))[-1]
