@@ -267,6 +267,33 @@ size_t rf_grouppoint_grad_workspace_bytes(int b, int n, int c, int m, int nsampl
 int rf_grouppoint_grad_ws(int b, int n, int c, int m, int nsample, const float *grad_out, const int *idx,
                           float *grad_points, void *workspace, size_t workspace_bytes, rf_stream_t stream);
 
+/* Replace knn_point (tf_ops/grouping/tf_grouping.py:48-73: dist = sum((xyz1 - xyz2)^2), then tf.nn.top_k(-dist, k), pure
+ * TF ops in the reference).  xyz1 (b,n,3) candidates, xyz2 (b,m,3) queries; val (b,m,k) = -d float32 and idx (b,m,k) int32:
+ * per query the k candidates of smallest d = ((dx*dx)+(dy*dy))+(dz*dz) (fp32, unfused, dx = x1 - x2), ascending by
+ * (d, index) -- ties go to the lower index, top_k's rule.  A NaN distance ranks before every number and +inf after every
+ * finite one (the order torch.topk(-dist) gives): a query with a NaN coordinate gets idx 0..k-1, val NaN.
+ * Domain: 1 <= k <= min(n, 64), 1 <= n, m <= 65536, 1 <= b <= 65535; anything else is RF_EINVAL (checked before any HIP call).
+ * rf_knn: every candidate against every query (knn.hip knn_scan_kernel). */
+int rf_knn(int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx, rf_stream_t stream);
+/* The same op over spatially sorted copies of the two sets (rf_nn_sort), as rf_threenn_boxes: a wave of 64 neighbouring
+ * queries visits only the 16-point candidate blocks whose box can still hold one of its k nearest.  val / idx bit-identical
+ * to rf_knn, ties and non-finite values included (a sample with a non-finite coordinate is searched without the boxes).
+ * sorted1 / sorted2: rf_nn_sort handles of xyz1 / xyz2 or NULL (sorted here, into the workspace), 16-byte aligned.
+ * workspace: rf_knn_boxes_workspace_bytes(b, n, m) bytes, 16-byte aligned (0 = outside the domain); a shorter one is
+ * RF_EWORKSPACE. */
+size_t rf_knn_boxes_workspace_bytes(int b, int n, int m);
+int rf_knn_boxes(int b, int n, int m, int k, const float *xyz1, const float *xyz2, const void *sorted1, const void *sorted2,
+                 float *val, int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+/* The gradient of val (tf_grouping.py:48-73 through top_k's gradient): with g = grad_val (b,m,k) and i = idx[b][j][t],
+ * grad_xyz2[j] = sum_t 2 g (x1[i] - x2[j]) and grad_xyz1[i] = -(the same terms summed over the slots that name i).  Both are
+ * fully overwritten (a candidate no slot names: zeros); the scatter is a counting sort of the m k slots by candidate, every row
+ * written once from sums in double (scatter_rows.hip), so the values do not depend on the slots' order beyond fp32 rounding.
+ * Slots whose index is outside [0, n) add nothing.  Same domain as rf_knn; workspace: rf_knn_grad_workspace_bytes(b, n, m, k)
+ * bytes, 16-byte aligned. */
+size_t rf_knn_grad_workspace_bytes(int b, int n, int m, int k);
+int rf_knn_grad(int b, int n, int m, int k, const float *xyz1, const float *xyz2, const int *idx, const float *grad_val,
+                float *grad_xyz1, float *grad_xyz2, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+
 /* -------------------------------------------------- interpolation (tf_ops/interpolation) - */
 /* Replace threenn_cpu / threeinterpolate_cpu / threeinterpolate_grad_cpu
  * (tf_interpolate.cpp:60-153; CPU-only ops in the reference).  xyz1 (b,n,3) unknown,

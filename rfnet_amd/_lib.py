@@ -78,6 +78,11 @@ SIGNATURES = {
     "rf_grouppoint_grad": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rf_grouppoint_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "rf_grouppoint_grad_ws": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rf_knn": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "rf_knn_boxes_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_knn_boxes": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
+    "rf_knn_grad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "rf_knn_grad": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_threenn": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_threenn_boxes_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_threenn_boxes": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -698,6 +698,89 @@ def three_nn(xyz1, xyz2, form="auto", sorted1=None, sorted2=None):
     return st.give(dist), st.give(idx)
 
 
+# knn_point: where the boxed form (rf_knn_boxes) beats the scan (tools/ab_knn.py, profiles/knn_ab.txt).  The scan's time is that of
+# one wave's chain over the n candidates, whatever b and m (1.02-1.11 ms at n = 16384, k = 16, from 1 x 1024 to 64 x 1024 queries);
+# the boxed form pays when a sample has many queries, so that a wave's 64 queries sit close together: it won at every measured
+# shape with m >= 8192, n >= 16384 and k <= 32 (0.40 against 1.02 ms at 1 x 16384 x 16384, k = 16; 0.51 against 1.04 at
+# 8 x 16384 x 8192) and lost at every other (m <= 4096 whatever b: 1.51 against 1.04 ms at 64 x 16384 x 1024; n <= 4096; k = 64:
+# 2.68 against 2.63 at 4 x 16384 x 16384).  Caller sort handles moved no shape across the line.
+KNN_BOXES_MIN_QUERIES = 8192
+KNN_BOXES_MIN_CANDIDATES = 16384
+KNN_BOXES_MAX_K = 32
+KNN_MAX_K = 64
+
+
+def _knn_inputs(st, xyz1, xyz2, k, op):
+    a, q = st.take(xyz1, F32), st.take(xyz2, F32)
+    if not _shape3(a, 3):
+        raise H.invalid(f"{op} expects (b,n,3) xyz1 shape")
+    if not (_shape3(q, 3) and q.shape[0] == a.shape[0]):
+        raise H.invalid(f"{op} expects (b,m,3) xyz2 shape, and batch_size must match")
+    b, n, m = a.shape[0], a.shape[1], q.shape[1]
+    if not 1 <= k <= min(n, KNN_MAX_K):
+        raise H.invalid(f"{op} takes 1 <= k <= min(n, {KNN_MAX_K})")
+    if not (1 <= b <= 65535 and 1 <= n <= 65536 and 1 <= m <= 65536):
+        raise H.invalid(f"{op} takes 1 <= b <= 65535 and clouds of 1..65536 points")
+    return a, q, b, n, m
+
+
+def knn_supported(k, b, n, m):
+    """The domain of the kernels (include/rfops.h rf_knn)."""
+    return 1 <= k <= min(n, KNN_MAX_K) and 1 <= b <= 65535 and 1 <= n <= 65536 and 1 <= m <= 65536
+
+
+def knn_auto_boxes(k, n, m):
+    """form="auto" takes the boxed kernel (KNN_BOXES_* above)."""
+    return m >= KNN_BOXES_MIN_QUERIES and n >= KNN_BOXES_MIN_CANDIDATES and k <= KNN_BOXES_MAX_K
+
+
+@H.on_input_device
+def knn_point(k, xyz1, xyz2, form="auto", sorted1=None, sorted2=None):
+    """knn_point (tf_ops/grouping/tf_grouping.py:48-73) on the GPU -> val (b,m,k) = -d, idx (b,m,k) int32: per query of xyz2 the
+    k points of xyz1 of smallest squared distance, ascending, ties to the lower index (tf.nn.top_k's rule).
+
+    form: "auto" (the boxed kernel over sorted copies of the two sets where it measured faster -- m >= KNN_BOXES_MIN_QUERIES,
+    n >= KNN_BOXES_MIN_CANDIDATES, k <= KNN_BOXES_MAX_K -- the scan elsewhere), "boxes", "scan" -- same results, bit for bit; sorted1 / sorted2: rf_nn_sort handles (nn_sort(...).buf) of
+    xyz1 / xyz2, which skip the boxed form's own sort of that set."""
+    if form not in ("auto", "scan", "boxes"):
+        raise H.invalid("knn_point: form must be one of auto, scan, boxes")
+    k = int(k)
+    st = H.Staged()
+    a, q, b, n, m = _knn_inputs(st, xyz1, xyz2, k, "KnnPoint")
+    dev = st.device_()
+    a, q = st.up(a, q)
+    val, idx = H.empty((b, m, k), F32, dev), H.empty((b, m, k), I32, dev)
+    boxes = form == "boxes" or (form == "auto" and knn_auto_boxes(k, n, m))
+    if boxes:
+        wsz = int(lib.rf_knn_boxes_workspace_bytes(b, n, m))
+        ws = H.empty((wsz // 4,), F32, dev)
+        check(lib.rf_knn_boxes(b, n, m, k, H.ptr(a), H.ptr(q), H.ptr(sorted1), H.ptr(sorted2), H.ptr(val), H.ptr(idx),
+                               H.ptr(ws), wsz, H.stream(dev)), "rf_knn_boxes")
+    else:
+        check(lib.rf_knn(b, n, m, k, H.ptr(a), H.ptr(q), H.ptr(val), H.ptr(idx), H.stream(dev)), "rf_knn")
+    return st.give(val), st.give(idx)
+
+
+@H.on_input_device
+def knn_point_grad(xyz1, xyz2, idx, grad_val):
+    """The gradient of knn_point's val -> (grad_xyz1 (b,n,3), grad_xyz2 (b,m,3)) (rf_knn_grad)."""
+    st = H.Staged()
+    ix, g = st.take(idx, I32), st.take(grad_val, F32)
+    if ix.dim() != 3:
+        raise H.invalid("KnnPointGrad expects (b,m,k) idx shape")
+    a, q, b, n, m = _knn_inputs(st, xyz1, xyz2, int(ix.shape[2]), "KnnPointGrad")
+    k = int(ix.shape[2])
+    if tuple(ix.shape) != (b, m, k) or tuple(g.shape) != (b, m, k):
+        raise H.invalid("KnnPointGrad expects (b,m,k) idx and grad_val shapes")
+    dev = st.device_()
+    a, q, ix, g = st.up(a, q, ix, g)
+    g1, g2 = H.empty((b, n, 3), F32, dev), H.empty((b, m, 3), F32, dev)
+    ws, wsz = H.workspace(lib.rf_knn_grad_workspace_bytes(b, n, m, k), dev, "knng")
+    check(lib.rf_knn_grad(b, n, m, k, H.ptr(a), H.ptr(q), H.ptr(ix), H.ptr(g), H.ptr(g1), H.ptr(g2), H.ptr(ws), wsz,
+                          H.stream(dev)), "rf_knn_grad")
+    return st.give(g1), st.give(g2)
+
+
 @H.on_input_device
 def three_interpolate(points, idx, weight):
     """ThreeInterpolateOp, tf_interpolate.cpp:191-222 -> (b,n,c)."""

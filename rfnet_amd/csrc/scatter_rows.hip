@@ -258,8 +258,7 @@ size_t rows_csr_workspace_bytes(int b, int n, long S) {
     return align256(sizeof(int) * (size_t)b * ((size_t)n + 1)) + align256(sizeof(int) * (size_t)b * (size_t)S);
 }
 
-int rows_csr_scatter(int b, int n, int c, long S, int K, const float *src, const int *idx, const float *weight, float *dst,
-                     void *workspace, const char *build_name, const char *gather_name, hipStream_t s) {
+int rows_csr_sort(int b, int n, long S, const int *idx, void *workspace, const char *build_name, hipStream_t s) {
     int *row_start = (int *)workspace;
     int *perm = (int *)((char *)workspace + align256(sizeof(int) * (size_t)b * ((size_t)n + 1)));
     // workgroups per sample: enough to put ~128 CUs to work, every range at least 2048 bins, at most 32768
@@ -277,6 +276,18 @@ int rows_csr_scatter(int b, int n, int c, long S, int K, const float *src, const
         RFS_BUILD(0, CB_STAGE);
     }
 #undef RFS_BUILD
+    return RF_OK;
+}
+
+const int *rows_csr_perm(int b, int n, const void *workspace) {
+    return (const int *)((const char *)workspace + align256(sizeof(int) * (size_t)b * ((size_t)n + 1)));
+}
+
+int rows_csr_scatter(int b, int n, int c, long S, int K, const float *src, const int *idx, const float *weight, float *dst,
+                     void *workspace, const char *build_name, const char *gather_name, hipStream_t s) {
+    if (int e = rows_csr_sort(b, n, S, idx, workspace, build_name, s)) return e;
+    const int *row_start = (const int *)workspace;
+    const int *perm = rows_csr_perm(b, n, workspace);
     const bool vec = c % 4 == 0 && rf::aligned16(src) && rf::aligned16(dst);
     const int cv = vec ? c / 4 : c;
     int tx_log2 = 0;
@@ -286,7 +297,7 @@ int rows_csr_scatter(int b, int n, int c, long S, int K, const float *src, const
     const dim3 grid((unsigned)((long)bpb * b));
 #define RFS_GO(VEC, KK, WT)                                                                                                \
     RF_LAUNCH(gather_name, (rows_csr_gather_kernel<VEC, KK, WT>), grid, dim3(CG_TPB), 0, s, n, c, (int)S, tx_log2, bpb, src, weight, \
-              (const int *)row_start, (const int *)perm, dst)
+              row_start, perm, dst)
     if (K == 1 && !weight) {
         if (vec) { RFS_GO(4, 1, false); } else { RFS_GO(1, 1, false); }
     } else if (K == 3 && weight) {

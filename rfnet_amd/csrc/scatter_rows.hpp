@@ -12,5 +12,9 @@ size_t rows_csr_workspace_bytes(int b, int n, long S);
 // dst is fully overwritten (rows no slot names: zeros).  workspace: rows_csr_workspace_bytes, 16-byte aligned.
 int rows_csr_scatter(int b, int n, int c, long S, int K, const float *src, const int *idx, const float *weight, float *dst,
                      void *workspace, const char *build_name, const char *gather_name, hipStream_t s);
+// The counting sort alone, for gathers of their own: the workspace then holds row_start (b, n + 1) at its start and perm (b, S)
+// at rows_csr_perm -- perm[row_start[r] .. row_start[r + 1]) are the slots s of a sample with idx[s] = r (any order).
+int rows_csr_sort(int b, int n, long S, const int *idx, void *workspace, const char *build_name, hipStream_t s);
+const int *rows_csr_perm(int b, int n, const void *workspace);
 
 }  // namespace rfs

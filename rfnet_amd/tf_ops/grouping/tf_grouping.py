@@ -2,6 +2,7 @@
 (query_ball_point :8-20, group_point :33-41 + gradient :42-46, knn_point :48-73;
 select_top_k :22-31)."""
 import torch
+from torch.autograd.function import once_differentiable
 
 from ... import _raw
 
@@ -50,6 +51,36 @@ def group_point_grad(points, idx, grad_out):
     return _raw.group_point_grad(points, idx, grad_out)
 
 
+def _knn_on_gpu(k, xyz1, xyz2):
+    if not (isinstance(xyz1, torch.Tensor) and isinstance(xyz2, torch.Tensor)):
+        return False
+    if not (xyz1.is_cuda and xyz2.is_cuda and xyz1.device == xyz2.device):
+        return False
+    if xyz1.dtype != torch.float32 or xyz2.dtype != torch.float32 or xyz1.dim() != 3 or xyz2.dim() != 3:
+        return False
+    if xyz1.shape[2] != 3 or xyz2.shape[2] != 3 or xyz1.shape[0] != xyz2.shape[0]:
+        return False
+    return _raw.knn_supported(int(k), xyz1.shape[0], xyz1.shape[1], xyz2.shape[1])
+
+
+class _KnnPoint(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, k, xyz1, xyz2):
+        val, idx = _raw.knn_point(k, xyz1, xyz2)
+        ctx.save_for_backward(xyz1, xyz2, idx)
+        ctx.mark_non_differentiable(idx)
+        return val, idx
+
+    @staticmethod
+    @once_differentiable  # (the HIP gradient has no gradient of its own: no double backward on this path)
+    def backward(ctx, grad_val, grad_idx):
+        xyz1, xyz2, idx = ctx.saved_tensors
+        if grad_val is None:
+            return None, None, None
+        g1, g2 = _raw.knn_point_grad(xyz1, xyz2, idx, grad_val.contiguous())
+        return None, g1 if ctx.needs_input_grad[1] else None, g2 if ctx.needs_input_grad[2] else None
+
+
 def knn_point(k, xyz1, xyz2):
     '''
     Input:
@@ -59,8 +90,16 @@ def knn_point(k, xyz1, xyz2):
     Output:
         val: (batch_size, npoint, k) float32 array, NEGATED squared L2 distances (top_k of -dist)
         idx: (batch_size, npoint, k) int32 array, indices to input points
-    Pure tensor ops in the reference too (tf.nn.top_k of -dist, tf_grouping.py:64-73).
+    Pure tensor ops in the reference (tf.nn.top_k of -dist, tf_grouping.py:64-73).  CUDA float32 tensors on one device with
+    c = 3, 1 <= k <= min(n, 64) and b, n, m within the C ABI's limits go to the HIP kernels (rf_knn / rf_knn_boxes, no
+    (b, m, n) tensor; ties to the lower index, tf.nn.top_k's rule), with the gradient to both inputs (rf_knn_grad, first order
+    only: no double backward there); everything else is the tensor expression below.  val is the unfused fp32 distance
+    ((dx*dx)+(dy*dy))+(dz*dz), which can differ from the expression's CUDA reduction in the last bits.
     '''
+    if _knn_on_gpu(k, xyz1, xyz2):
+        if xyz1.requires_grad or xyz2.requires_grad:
+            return _KnnPoint.apply(int(k), xyz1, xyz2)
+        return _raw.knn_point(int(k), xyz1, xyz2)
     xyz1 = torch.as_tensor(xyz1)
     xyz2 = torch.as_tensor(xyz2)
     dist = ((xyz1.unsqueeze(1) - xyz2.unsqueeze(2)) ** 2).sum(-1)
