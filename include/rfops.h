@@ -130,6 +130,54 @@ int rf_chamfer_step(int b, int n, int m, const float *xyz1, const float *xyz2,
                     float *dist2, int *idx2, float *grad_xyz1, float *grad_xyz2, void *workspace,
                     size_t workspace_bytes, rf_stream_t stream);
 
+/* ---- ragged batches: per-sample point counts (Chamfer, continued) ----------------------- */
+/* Clouds of different sizes in one padded batch.  len1 / len2 are DEVICE int32 arrays of b counts:
+ * sample i uses xyz1[i, :len1[i]] and xyz2[i, :len2[i]]; the coordinates beyond a count are never read into
+ * any result (they may hold anything: NaN, inf, copies of valid points).  Either array may be NULL ("all n",
+ * "all m").  Domain 1 <= len <= n (m); the kernels read the counts themselves (no host synchronisation, so a
+ * call can be captured in a HIP graph) and CLAMP a device value outside the domain into [1, n] (resp. m),
+ * so a bad count can never make a kernel read or write past the tensors -- it just gives that sample's
+ * results for the clamped count.
+ *
+ * rf_nn_distance_lengths: on the valid slots dist / idx are bit for bit what rf_nn_distance_mode returns
+ * on the unpadded slices of that sample alone (ties to the lowest index, non-finite inputs included), and
+ * a valid idx always points into the other cloud's valid range; padded slots get dist = 0.0f and idx = -1.
+ * `mode` is RF_NN_AUTO (routes by (n, m) exactly as rf_nn_distance does), RF_NN_DENSE or RF_NN_CULLED
+ * (n, m <= 65536, else RF_EINVAL).  The dense sweep takes the counts into its kernels, so its work shrinks
+ * with them; the culled sweep's sort keys and boxes only a sample's first len points and the sweep skips the
+ * padding behind them, so its work shrinks with the counts too.  A direction whose two output
+ * pointers are NULL is skipped (one NULL of a pair is RF_EINVAL).  Pointers must be 4-byte aligned, the
+ * workspace 16-byte aligned (RF_EINVAL); a workspace smaller than rf_nn_distance_lengths_workspace_bytes
+ * (b, n, m, mode) is RF_EWORKSPACE -- both checked before any HIP call. */
+size_t rf_nn_distance_lengths_workspace_bytes(int b, int n, int m, int mode);
+int rf_nn_distance_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                           const int *len2, float *dist1, int *idx1, float *dist2, int *idx2, void *workspace,
+                           size_t workspace_bytes, rf_stream_t stream, int mode);
+
+/* NnDistanceGrad restricted to the valid slots: rows beyond a sample's count get a gradient of exactly 0
+ * whatever grad_dist / idx hold there, valid rows are rf_nn_distance_grad's on the sample alone (within
+ * the backward's fp32 add-order tolerance).  grad_xyz1 (b,n,3) / grad_xyz2 (b,m,3) fully overwritten. */
+int rf_nn_distance_grad_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                                const int *len2, const float *grad_dist1, const int *idx1,
+                                const float *grad_dist2, const int *idx2, float *grad_xyz1, float *grad_xyz2,
+                                rf_stream_t stream);
+
+/* rf_chamfer_loss on ragged batches: loss[i][0] = mean of sqrt(dist1) over the len1[i] valid points,
+ * loss[i][1] likewise over len2[i] (0 for a direction whose dist/idx pointers are NULL), next to
+ * rf_nn_distance_lengths' outputs of the computed directions (sweep chosen as RF_NN_AUTO).  No sorted handles:
+ * the culled sweep sorts internally.  rf_chamfer_loss_grad_lengths is its backward, scaling by 1 / len
+ * instead of 1 / n; rows beyond a count get exactly 0.  Before any HIP call: RF_EINVAL for a NULL tensor, a
+ * misaligned count array or workspace, RF_EWORKSPACE for a workspace smaller than
+ * rf_chamfer_loss_lengths_workspace_bytes(b, n, m, want1, want2). */
+size_t rf_chamfer_loss_lengths_workspace_bytes(int b, int n, int m, int want1, int want2);
+int rf_chamfer_loss_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                            const int *len2, float *loss, float *dist1, int *idx1, float *dist2, int *idx2,
+                            void *workspace, size_t workspace_bytes, rf_stream_t stream);
+int rf_chamfer_loss_grad_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                                 const int *len2, const float *dist1, const int *idx1, const float *dist2,
+                                 const int *idx2, const float *grad_loss, float *grad_xyz1, float *grad_xyz2,
+                                 rf_stream_t stream);
+
 /* ----------------------------------------------------------- EMD (pc_distance) ---------- */
 /* Replaces approxmatchLauncher(b,n,m,xyz1,xyz2,match,temp) (pc_distance/tf_approxmatch.cpp:141,
  * tf_approxmatch.cu:180-182).  xyz1 (b,n,3) "dataset", xyz2 (b,m,3) "query" (b <= 65535 for

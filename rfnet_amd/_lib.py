@@ -49,6 +49,12 @@ SIGNATURES = {
     "rf_chamfer_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
     "rf_chamfer_loss": (_i, [_i, _i, _i] + [_vp] * 10 + [_sz, _vp]),
     "rf_chamfer_loss_grad": (_i, [_i, _i, _i] + [_vp] * 10),
+    "rf_nn_distance_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "rf_nn_distance_lengths": (_i, [_i, _i, _i] + [_vp] * 9 + [_sz, _vp, _i]),
+    "rf_nn_distance_grad_lengths": (_i, [_i, _i, _i] + [_vp] * 11),
+    "rf_chamfer_loss_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "rf_chamfer_loss_lengths": (_i, [_i, _i, _i] + [_vp] * 10 + [_sz, _vp]),
+    "rf_chamfer_loss_grad_lengths": (_i, [_i, _i, _i] + [_vp] * 12),
     "rf_merge_layer_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_merge_layer": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_merge_layer_grad": (_i, [_i, _i, _i] + [_vp] * 9),

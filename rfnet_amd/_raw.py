@@ -24,12 +24,51 @@ def _shape3(t, last=None):
 NN_MODES = {"auto": 0, "dense": 1, "culled": 2}
 
 
+def _check_lengths(x, b, n, name):
+    """A per-sample count argument of the ragged entries (include/rfops.h, rf_nn_distance_lengths) -> None or a
+    (b,) integer tensor.  Host-given counts (list, tuple, numpy array, CPU tensor) are checked here -- shape (b,),
+    range [1, n] -- before any GPU work; CUDA counts are only shape-checked (reading them would synchronise: the
+    kernels clamp them into [1, n] instead)."""
+    if x is None:
+        return None
+    if isinstance(x, torch.Tensor):
+        t = x if x.is_cuda else x.detach()  # (integer counts carry no graph; a CUDA tensor is used as it is)
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise H.invalid(f"{name} must hold integer point counts")
+    if t.dim() != 1 or t.shape[0] != b:
+        raise H.invalid(f"{name} must be of shape (batch,)")
+    if not t.is_cuda and b > 0 and (int(t.min()) < 1 or int(t.max()) > n):
+        raise H.invalid(f"{name} must lie in [1, {n}]")
+    return t
+
+
+def _lengths_up(t, dev, n):
+    """Stage checked counts as a contiguous int32 tensor on `dev` (CUDA counts are converted there, on the
+    current stream: no host round trip).  Wider integers are clamped into [1, n] before the narrowing cast, so
+    that a device value beyond the int32 range cannot wrap into the domain (the kernels clamp the rest)."""
+    if t is None:
+        return None
+    if t.is_cuda and t.dtype == I32 and t.device == dev and t.is_contiguous():
+        return t  # the common case of a training loop: nothing to convert (each conversion is host time per call)
+    if t.is_cuda and t.device != dev:
+        raise ValueError(f"all GPU inputs of one op must live on the same device: got {dev} and {t.device}")
+    t = t.to(device=dev)
+    if t.dtype != I32:
+        t = t.clamp(1, max(n, 1)).to(I32)
+    return t.contiguous()
+
+
 @H.on_input_device
-def nn_distance(xyz1, xyz2, mode="auto", stats=None):
+def nn_distance(xyz1, xyz2, mode="auto", stats=None, lengths1=None, lengths2=None):
     """NnDistanceGpuOp::Compute, tf_ops/CD/tf_nndistance.cpp:172-204.
 
     `mode` pins the sweep ("dense": every pair; "culled": nn_pruned.hip) -- same outputs; `stats`
-    (a list) receives the culled sweep's 8 counters (rfops.h)."""
+    (a list) receives the culled sweep's 8 counters (rfops.h).  `lengths1` / `lengths2`: per-sample point
+    counts of a ragged batch (rf_nn_distance_lengths): padded slots come back as (0, -1)."""
+    if lengths1 is not None or lengths2 is not None:
+        return _nn_distance_lengths(xyz1, xyz2, mode, stats, lengths1, lengths2)
     st = H.Staged()
     a, b_ = st.take(xyz1, F32), st.take(xyz2, F32)
     if a.dim() != 3:
@@ -57,9 +96,32 @@ def nn_distance(xyz1, xyz2, mode="auto", stats=None):
     return tuple(st.give(t) for t in (d1, i1, d2, i2))
 
 
+def _nn_distance_lengths(xyz1, xyz2, mode, stats, lengths1, lengths2):
+    """rf_nn_distance_lengths: nn_distance over a ragged batch."""
+    if stats is not None:
+        raise H.invalid("nn_distance: the culled sweep's counters are not collected for ragged batches")
+    if mode not in NN_MODES:
+        raise H.invalid(f"nn_distance: mode must be one of {sorted(NN_MODES)}")
+    st = H.Staged()
+    a, b_ = _nn_inputs(st, xyz1, xyz2)
+    b, n, m = a.shape[0], a.shape[1], b_.shape[1]
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, b_ = st.up(a, b_)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    d1, i1 = H.empty((b, n), F32, dev), H.empty((b, n), I32, dev)
+    d2, i2 = H.empty((b, m), F32, dev), H.empty((b, m), I32, dev)
+    ws, wsz = H.workspace(lib.rf_nn_distance_lengths_workspace_bytes(b, n, m, NN_MODES[mode]), dev, "nn")
+    check(lib.rf_nn_distance_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(d1), H.ptr(i1),
+                                     H.ptr(d2), H.ptr(i2), H.ptr(ws), wsz, H.stream(dev), NN_MODES[mode]),
+          "rf_nn_distance_lengths")
+    return tuple(st.give(t) for t in (d1, i1, d2, i2))
+
+
 @H.on_input_device
-def nn_distance_grad(xyz1, xyz2, grad_dist1, idx1, grad_dist2, idx2):
-    """NnDistanceGradGpuOp::Compute, tf_ops/CD/tf_nndistance.cpp:216-251."""
+def nn_distance_grad(xyz1, xyz2, grad_dist1, idx1, grad_dist2, idx2, lengths1=None, lengths2=None):
+    """NnDistanceGradGpuOp::Compute, tf_ops/CD/tf_nndistance.cpp:216-251.  With `lengths1` / `lengths2`
+    (rf_nn_distance_grad_lengths) rows beyond a sample's count get a zero gradient."""
     st = H.Staged()
     a, b_ = st.take(xyz1, F32), st.take(xyz2, F32)
     gd1, gd2 = st.take(grad_dist1, F32), st.take(grad_dist2, F32)
@@ -83,9 +145,18 @@ def nn_distance_grad(xyz1, xyz2, grad_dist1, idx1, grad_dist2, idx2):
         raise H.invalid("NnDistanceGrad requires grad_dist2 be of shape(batch,#points)")
     if tuple(i2.shape) != (b, m):
         raise H.invalid("NnDistanceGrad requires idx2 be of shape(batch,#points)")
+    ragged = lengths1 is not None or lengths2 is not None
+    if ragged:
+        l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
     dev = st.device_()
     a, b_, gd1, gd2, i1, i2 = st.up(a, b_, gd1, gd2, i1, i2)
     g1, g2 = H.empty((b, n, 3), F32, dev), H.empty((b, m, 3), F32, dev)
+    if ragged:
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        check(lib.rf_nn_distance_grad_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(gd1),
+                                              H.ptr(i1), H.ptr(gd2), H.ptr(i2), H.ptr(g1), H.ptr(g2), H.stream(dev)),
+              "rf_nn_distance_grad_lengths")
+        return st.give(g1), st.give(g2)
     check(lib.rf_nn_distance_grad(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(gd1), H.ptr(i1), H.ptr(gd2),
                                   H.ptr(i2), H.ptr(g1), H.ptr(g2), H.stream(dev)),
           "rf_nn_distance_grad")
@@ -217,11 +288,15 @@ def _sorted_ptr(s, b, n, dev):
 
 
 @H.on_input_device
-def chamfer_loss(xyz1, xyz2, sorted1=None, sorted2=None, want1=True, want2=True):
+def chamfer_loss(xyz1, xyz2, sorted1=None, sorted2=None, want1=True, want2=True, lengths1=None, lengths2=None):
     """rf_chamfer_loss: per-sample mean sqrt(dist) both ways, (b, 2), next to the nn_distance outputs
-    of the computed directions -> (loss, dist1, idx1, dist2, idx2)."""
+    of the computed directions -> (loss, dist1, idx1, dist2, idx2).  `lengths1` / `lengths2`: per-sample
+    counts of a ragged batch (rf_chamfer_loss_lengths: means over each sample's own count); they do not
+    combine with sorted handles."""
     if not (want1 or want2):
         raise H.invalid("chamfer_loss needs at least one direction")
+    if lengths1 is not None or lengths2 is not None:
+        return _chamfer_loss_lengths(xyz1, xyz2, sorted1, sorted2, want1, want2, lengths1, lengths2)
     st = H.Staged()
     a, b_ = _nn_inputs(st, xyz1, xyz2)
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
@@ -240,10 +315,34 @@ def chamfer_loss(xyz1, xyz2, sorted1=None, sorted2=None, want1=True, want2=True)
     return tuple(None if t is None else st.give(t) for t in (loss, d1, i1, d2, i2))
 
 
+def _chamfer_loss_lengths(xyz1, xyz2, sorted1, sorted2, want1, want2, lengths1, lengths2):
+    """rf_chamfer_loss_lengths: chamfer_loss over a ragged batch."""
+    if sorted1 is not None or sorted2 is not None:
+        raise H.invalid("chamfer_loss: per-sample lengths do not combine with sorted handles")
+    st = H.Staged()
+    a, b_ = _nn_inputs(st, xyz1, xyz2)
+    b, n, m = a.shape[0], a.shape[1], b_.shape[1]
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, b_ = st.up(a, b_)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    loss = H.empty((b, 2), F32, dev)
+    d1 = H.empty((b, n), F32, dev) if want1 else None
+    i1 = H.empty((b, n), I32, dev) if want1 else None
+    d2 = H.empty((b, m), F32, dev) if want2 else None
+    i2 = H.empty((b, m), I32, dev) if want2 else None
+    ws, wsz = H.workspace(lib.rf_chamfer_loss_lengths_workspace_bytes(b, n, m, int(want1), int(want2)), dev, "nn")
+    check(lib.rf_chamfer_loss_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(loss), H.ptr(d1),
+                                      H.ptr(i1), H.ptr(d2), H.ptr(i2), H.ptr(ws), wsz, H.stream(dev)),
+          "rf_chamfer_loss_lengths")
+    return tuple(None if t is None else st.give(t) for t in (loss, d1, i1, d2, i2))
+
+
 @H.on_input_device
-def chamfer_loss_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, grad_loss):
+def chamfer_loss_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, grad_loss, lengths1=None, lengths2=None):
     """rf_chamfer_loss_grad -> (grad_xyz1, grad_xyz2); dist/idx of a direction that was not computed
-    are None."""
+    are None.  With `lengths1` / `lengths2` (rf_chamfer_loss_grad_lengths) the means are over each
+    sample's own count and rows beyond it get a zero gradient."""
     st = H.Staged()
     a, b_ = _nn_inputs(st, xyz1, xyz2, "NnDistanceGrad")
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
@@ -259,10 +358,19 @@ def chamfer_loss_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, grad_loss):
         if tuple(t.shape) != shape:
             raise H.invalid("NnDistanceGrad requires idx/dist be of shape(batch,#points)")
         opt.append(t)
+    ragged = lengths1 is not None or lengths2 is not None
+    if ragged:
+        l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
     dev = st.device_()
     a, b_, gl = st.up(a, b_, gl)
     opt = [None if t is None else st.up(t)[0] for t in opt]
     g1, g2 = H.empty((b, n, 3), F32, dev), H.empty((b, m, 3), F32, dev)
+    if ragged:
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        check(lib.rf_chamfer_loss_grad_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(opt[0]),
+                                               H.ptr(opt[1]), H.ptr(opt[2]), H.ptr(opt[3]), H.ptr(gl), H.ptr(g1),
+                                               H.ptr(g2), H.stream(dev)), "rf_chamfer_loss_grad_lengths")
+        return st.give(g1), st.give(g2)
     check(lib.rf_chamfer_loss_grad(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(opt[0]), H.ptr(opt[1]), H.ptr(opt[2]),
                                    H.ptr(opt[3]), H.ptr(gl), H.ptr(g1), H.ptr(g2), H.stream(dev)),
           "rf_chamfer_loss_grad")

@@ -27,22 +27,46 @@
 namespace {
 
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
+bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // loss[bi][dir] = mean_j sqrt(dist_dir[bi][j]): one workgroup per (sample, direction), fixed
 // summation order (strided per-thread partials, DPP inside the wave, waves in order): deterministic.
+// PER_SAMPLE (rf_chamfer_loss_lengths): the mean over the sample's own count (len1 / len2, NULL = all,
+// clamped into [1, n] as in nn_distance.hip), in the order the sample alone would take.  pad_d* / pad_i*
+// (PER_SAMPLE, may be NULL): the same rows' outputs, whose slots beyond the count get (0, -1) here -- on
+// the culled route this replaces a launch of its own (nn_distance.hip pad_outputs_kernel).
 constexpr int LR_TPB = 1024;
+template <int PER_SAMPLE>
 __global__ __launch_bounds__(LR_TPB) void chamfer_loss_reduce_kernel(int n, int m, const float *__restrict__ dist1,
                                                                      const float *__restrict__ dist2,
-                                                                     float *__restrict__ loss) {
+                                                                     float *__restrict__ loss,
+                                                                     const int *__restrict__ len1,
+                                                                     const int *__restrict__ len2,
+                                                                     float *__restrict__ pad_d1, int *__restrict__ pad_i1,
+                                                                     float *__restrict__ pad_d2,
+                                                                     int *__restrict__ pad_i2) {
     __shared__ float part[LR_TPB / 64];
     const int bi = blockIdx.x >> 1, dir = blockIdx.x & 1;
     const float *__restrict__ d = dir ? dist2 : dist1;
-    const int cnt = dir ? m : n;
+    int cnt = dir ? m : n;
     if (!d) {  // direction not computed
         if (threadIdx.x == 0) loss[bi * 2 + dir] = 0.f;
         return;
     }
     d += (size_t)bi * cnt;
+    if constexpr (PER_SAMPLE != 0) {
+        const int *__restrict__ len = dir ? len2 : len1;
+        const int full = cnt;
+        if (len) cnt = len[bi] < 1 ? 1 : (len[bi] > cnt ? cnt : len[bi]);
+        float *__restrict__ pd = dir ? pad_d2 : pad_d1;
+        int *__restrict__ pi = dir ? pad_i2 : pad_i1;
+        if (pd) {
+            for (int k = cnt + threadIdx.x; k < full; k += LR_TPB) {
+                pd[(size_t)bi * full + k] = 0.f;
+                pi[(size_t)bi * full + k] = -1;
+            }
+        }
+    }
     // four independent partial sums per thread: the loads of a trip are all in flight together (one
     // running sum per thread made every trip wait a full memory latency: 22 us at 16384 points)
     float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -282,8 +306,9 @@ int rf_chamfer_loss(int b, int n, int m, const float *xyz1, const float *xyz2, c
     if (int e = run_forward(b, n, m, xyz1, xyz2, sorted1, sorted2, dist1, idx1, dist2, idx2, dirs, workspace,
                             workspace_bytes, s))
         return e;
-    RF_LAUNCH("chamfer_loss_reduce", chamfer_loss_reduce_kernel, dim3(2 * b), dim3(LR_TPB), 0, s, n, m,
-              (const float *)((dirs & 1) ? dist1 : nullptr), (const float *)((dirs & 2) ? dist2 : nullptr), loss);
+    RF_LAUNCH("chamfer_loss_reduce", chamfer_loss_reduce_kernel<0>, dim3(2 * b), dim3(LR_TPB), 0, s, n, m,
+              (const float *)((dirs & 1) ? dist1 : nullptr), (const float *)((dirs & 2) ? dist2 : nullptr), loss,
+              nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     return RF_OK;
 }
 
@@ -296,6 +321,50 @@ int rf_chamfer_loss_grad(int b, int n, int m, const float *xyz1, const float *xy
     const rfd::GradSource g{nullptr, nullptr, dist1, dist2, grad_loss};
     return rfd::nn_distance_grad(b, n, m, xyz1, xyz2, g, dist1 ? idx1 : nullptr, dist2 ? idx2 : nullptr, grad_xyz1,
                                  grad_xyz2, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ fused loss, ragged -----
+size_t rf_chamfer_loss_lengths_workspace_bytes(int b, int n, int m, int want1, int want2) {
+    if (b <= 0 || n <= 0 || m <= 0 || !(want1 || want2)) return 0;
+    return rfd::ragged_workspace_bytes(b, n, m, RF_NN_AUTO, dirs_of(want1, want2));
+}
+
+int rf_chamfer_loss_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                            const int *len2, float *loss, float *dist1, int *idx1, float *dist2, int *idx2,
+                            void *workspace, size_t workspace_bytes, rf_stream_t stream) {
+    if (bad_sizes(b, n, m)) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0 || !xyz1 || !xyz2 || !loss || !workspace) return RF_EINVAL;
+    const int dirs = dirs_of(dist1 && idx1, dist2 && idx2);
+    if (!dirs) return RF_EINVAL;
+    if (!rf::aligned16(workspace) || !aligned4(len1) || !aligned4(len2)) return RF_EINVAL;
+    if (workspace_bytes < rfd::ragged_workspace_bytes(b, n, m, RF_NN_AUTO, dirs)) return RF_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    float *d1 = (dirs & 1) ? dist1 : nullptr, *d2 = (dirs & 2) ? dist2 : nullptr;
+    int *i1 = (dirs & 1) ? idx1 : nullptr, *i2 = (dirs & 2) ? idx2 : nullptr;
+    // the culled route leaves the padded slots to the reduction (the dense sweep writes them itself)
+    const bool culled = rfd::resolve_mode(b, n, m, RF_NN_AUTO) == RF_NN_CULLED;
+    if (int e = rfd::ragged_nn_distance(b, n, m, xyz1, xyz2, len1, len2, d1, i1, d2, i2, workspace, workspace_bytes, s,
+                                        RF_NN_AUTO, dirs, !culled))
+        return e;
+    RF_LAUNCH("chamfer_loss_reduce_len", chamfer_loss_reduce_kernel<1>, dim3(2 * b), dim3(LR_TPB), 0, s, n, m,
+              (const float *)d1, (const float *)d2, loss, len1, len2, culled ? d1 : nullptr, culled ? i1 : nullptr,
+              culled ? d2 : nullptr, culled ? i2 : nullptr);
+    return RF_OK;
+}
+
+int rf_chamfer_loss_grad_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                                 const int *len2, const float *dist1, const int *idx1, const float *dist2,
+                                 const int *idx2, const float *grad_loss, float *grad_xyz1, float *grad_xyz2,
+                                 rf_stream_t stream) {
+    if (bad_sizes(b, n, m)) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0 || !grad_loss) return RF_EINVAL;
+    if (!aligned4(len1) || !aligned4(len2)) return RF_EINVAL;
+    const rfd::GradSource g{nullptr, nullptr, dist1, dist2, grad_loss};
+    // both count arrays NULL: the kernel of rf_chamfer_loss_grad, same results
+    return rfd::nn_distance_grad(b, n, m, xyz1, xyz2, g, dist1 ? idx1 : nullptr, dist2 ? idx2 : nullptr, grad_xyz1,
+                                 grad_xyz2, (hipStream_t)stream, len1, len2);
 }
 
 // ------------------------------------------------------------------ merge_layer ------------

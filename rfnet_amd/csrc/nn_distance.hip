@@ -42,6 +42,11 @@ constexpr int CH = 16;    // candidates per chunk (own-side argmin granularity)
 constexpr int CG = 32;    // candidates per reduce-scatter group (2 chunks)
 constexpr int PADQ = 512; // packed arrays are padded to a multiple of this many points
 
+// Which point counts a kernel instantiation serves: `all` (every sample has the tensor's n / m points -- the
+// instantiations rf_nn_distance has always used, compiled exactly as before) or `per_sample` (ragged
+// batches, rf_nn_distance_lengths: trailing count arrays, see clamp_len).
+enum class Counts { all, per_sample };
+
 // Buffers (separate __restrict__ kernel parameters so the candidate loads can be scalar loads):
 //   own      packed (b, no_pad, 3), padded with -inf
 //   cand     packed (b, nc_pad, 3), padded with +inf
@@ -74,6 +79,41 @@ __global__ void pack_kernel(int b, int n_own, int n_own_pad, const float *__rest
     int j = (int)(g - bi * n_pad);
     float x = padval, y = 0.f, z = 0.f;
     if (j < n) {
+        const float *p = src + (bi * n + j) * 3;
+        x = p[0]; y = p[1]; z = p[2];
+    }
+    dst[g * 3 + 0] = x;
+    dst[g * 3 + 1] = y;
+    dst[g * 3 + 2] = z;
+}
+
+// Ragged batches (rf_nn_distance_lengths): sample bi uses the first len[bi] points of its row.  A NULL
+// array means "all n"; a device value outside [1, n] is clamped into it, so no kernel ever reads past
+// the tensor whatever the caller's lengths hold.
+__device__ __forceinline__ int clamp_len(const int *__restrict__ len, int bi, int n) {
+    if (!len) return n;
+    const int v = len[bi];
+    return v < 1 ? 1 : (v > n ? n : v);
+}
+
+// pack_kernel for ragged batches: each sample padded from its OWN length (own -inf, candidates +inf,
+// as the alignment padding above), so every point beyond a sample's length is a pad of the sweep.
+__global__ void pack_len_kernel(int b, int n_own, int n_own_pad, const float *__restrict__ src_own,
+                                const int *__restrict__ len_own, float *__restrict__ dst_own, int nblk_own,
+                                int n_cand, int n_cand_pad, const float *__restrict__ src_cand,
+                                const int *__restrict__ len_cand, float *__restrict__ dst_cand) {
+    const bool is_cand = (int)blockIdx.x >= nblk_own;
+    const int n = is_cand ? n_cand : n_own, n_pad = is_cand ? n_cand_pad : n_own_pad;
+    const float *__restrict__ src = is_cand ? src_cand : src_own;
+    float *__restrict__ dst = is_cand ? dst_cand : dst_own;
+    const float padval = is_cand ? INFINITY : -INFINITY;
+    long g = (long)(blockIdx.x - (is_cand ? nblk_own : 0)) * blockDim.x + threadIdx.x;
+    long total = (long)b * n_pad;
+    if (g >= total) return;
+    long bi = g / n_pad;
+    int j = (int)(g - bi * n_pad);
+    float x = padval, y = 0.f, z = 0.f;
+    if (j < clamp_len(is_cand ? len_cand : len_own, (int)bi, n)) {
         const float *p = src + (bi * n + j) * 3;
         x = p[0]; y = p[1]; z = p[2];
     }
@@ -152,13 +192,19 @@ __device__ __forceinline__ void who_has_it(const float (&orig)[CG], float cmin, 
 // COLS = false: only the own side is wanted (rf_nn_distance_dir with one direction): the in-lane
 // candidate minima, the reduce-scatter and the winning-lane pass are compiled out (~6.5 VALU per
 // pair instead of ~7.9).
-template <int R, bool COLS>
+// Counts::per_sample: per-sample counts own_len / cand_len (ragged batches).  The
+// candidate range ends at the sample's count, own blocks wholly beyond it sweep nothing, and when this
+// launch writes the final own-side outputs the rows beyond the count get (0, -1).
+template <int R, bool COLS, Counts CNT>
 __global__ __launch_bounds__(TPB) void nn_sweep_kernel(Sweep a, const float *__restrict__ own_all,
                                                        const float *__restrict__ cand_all,
                                                        float *__restrict__ row_dist,
                                                        int *__restrict__ row_idx,
                                                        float *__restrict__ colpart,
-                                                       unsigned char *__restrict__ collane) {
+                                                       unsigned char *__restrict__ collane,
+                                                       const int *__restrict__ own_len,
+                                                       const int *__restrict__ cand_len) {
+    constexpr bool LEN = CNT == Counts::per_sample;
     const int lane = threadIdx.x & 63;
     // wave-uniform work decomposition (readfirstlane => SGPRs => scalar loads of candidates)
     const int w = __builtin_amdgcn_readfirstlane(blockIdx.x * (TPB / 64) + (threadIdx.x >> 6));
@@ -173,7 +219,13 @@ __global__ __launch_bounds__(TPB) void nn_sweep_kernel(Sweep a, const float *__r
     float ax[R], ay[R], az[R], best[R];
     int bchunk[R];
     const int c_begin = split * a.span;
-    const int c_end = min(a.nc, c_begin + a.span);  // exclusive, real candidates
+    int c_end = min(a.nc, c_begin + a.span);  // exclusive, real candidates
+    int no_i = a.no;
+    if constexpr (LEN) {
+        no_i = clamp_len(own_len, bi, a.no);
+        c_end = min(clamp_len(cand_len, bi, a.nc), c_begin + a.span);
+        if (ob * 64 * R >= no_i) c_end = c_begin;  // nothing but padding in this own block
+    }
 #pragma unroll
     for (int r = 0; r < R; r++) {
         const int j = (ob * 64 + lane) * R + r;  // lane-major; < no_pad by construction
@@ -312,6 +364,7 @@ __global__ __launch_bounds__(TPB) void nn_sweep_kernel(Sweep a, const float *__r
                     const float *q = own + (size_t)(ob * 64 * R + pnt) * 3;
                     if (q[0] != q[0] || q[1] != q[1] || q[2] != q[2]) { bd = NAN; bk = 0; }
                 }
+                if (LEN && a.rslots_final && ob * 64 * R + pnt >= no_i) { bd = 0.f; bk = -1; }
                 row_dist[mbase + pnt] = bd;
                 row_idx[mbase + pnt] = bk;
             }
@@ -323,18 +376,33 @@ __global__ __launch_bounds__(TPB) void nn_sweep_kernel(Sweep a, const float *__r
         const int j = (ob * 64 + lane) * R + r;
         if (j < a.no) {
             const bool qnan = a.rslots_final && (ax[r] != ax[r] || ay[r] != ay[r] || az[r] != az[r]);
-            row_dist[obase + j] = qnan ? NAN : best[r];
-            row_idx[obase + j] = qnan ? 0 : besti[r];
+            if (LEN && a.rslots_final && j >= no_i) {
+                row_dist[obase + j] = 0.f;
+                row_idx[obase + j] = -1;
+            } else {
+                row_dist[obase + j] = qnan ? NAN : best[r];
+                row_idx[obase + j] = qnan ? 0 : besti[r];
+            }
         }
     }
 }
 
 // own side: combine the per-split partials in split order; strict '<' keeps the lowest index.
+template <bool LEN>
 __device__ __forceinline__ void rowmerge_body(long g, const float *__restrict__ pd,
                                               const int *__restrict__ pi, float *__restrict__ dist,
                                               int *__restrict__ idx, int nsplit, long total,
-                                              const float *__restrict__ own_all, int no, int no_pad) {
+                                              const float *__restrict__ own_all, int no, int no_pad,
+                                              const int *__restrict__ own_len) {
     if (g >= total) return;
+    if constexpr (LEN) {  // a row beyond its sample's count: the pad values
+        const long bi = g / no;
+        if (g - bi * no >= clamp_len(own_len, (int)bi, no)) {
+            dist[g] = 0.f;
+            idx[g] = -1;
+            return;
+        }
+    }
     float best = pd[g];
     int besti = pi[g];
     for (int s = 1; s < nsplit; s++) {
@@ -357,7 +425,9 @@ __device__ __forceinline__ void rowmerge_body(long g, const float *__restrict__ 
 // partial (strict '<' in block order), then the lowest index among that block's winning lane's R
 // consecutive points with an exactly equal d2.
 // The same launch also finishes the own side: blocks beyond the candidate blocks run rowmerge.
-template <int R>
+// Counts::per_sample: candidates beyond their sample's count get (0, -1), the others
+// look only at the own blocks and points inside the sample's own count.
+template <int R, Counts CNT>
 __global__ __launch_bounds__(TPB) void nn_resolve_kernel(Sweep a, const float *__restrict__ own_all,
                                                          const float *__restrict__ cand_all,
                                                          const float *__restrict__ colpart,
@@ -366,10 +436,13 @@ __global__ __launch_bounds__(TPB) void nn_resolve_kernel(Sweep a, const float *_
                                                          int nblk_col, const float *__restrict__ row_pd,
                                                          const int *__restrict__ row_pi,
                                                          float *__restrict__ row_dist,
-                                                         int *__restrict__ row_idx, int rslots) {
+                                                         int *__restrict__ row_idx, int rslots,
+                                                         const int *__restrict__ own_len,
+                                                         const int *__restrict__ cand_len) {
+    constexpr bool LEN = CNT == Counts::per_sample;
     if ((int)blockIdx.x >= nblk_col) {
-        rowmerge_body((long)(blockIdx.x - nblk_col) * TPB + threadIdx.x, row_pd, row_pi, row_dist, row_idx,
-                      rslots, (long)a.b * a.no, own_all, a.no, a.no_pad);
+        rowmerge_body<LEN>((long)(blockIdx.x - nblk_col) * TPB + threadIdx.x, row_pd, row_pi, row_dist, row_idx,
+                           rslots, (long)a.b * a.no, own_all, a.no, a.no_pad, own_len);
         return;
     }
     // 4 lanes (a quad) per candidate: lane q scans the own blocks o = q, q+4, ... (its loads are
@@ -382,13 +455,25 @@ __global__ __launch_bounds__(TPB) void nn_resolve_kernel(Sweep a, const float *_
     const int q = threadIdx.x & 3;
     const int c = min((int)(blockIdx.x - bi * cblocks) * CPB + (int)(threadIdx.x >> 2), a.nc - 1);
     const bool writer = q == 0 && (int)(blockIdx.x - bi * cblocks) * CPB + (int)(threadIdx.x >> 2) < a.nc;
+    int no_i = a.no, oblocks_i = a.oblocks;
+    if constexpr (LEN) {
+        if (c >= clamp_len(cand_len, bi, a.nc)) {  // (quad-uniform: the quad shares c)
+            if (writer) {
+                dist[(size_t)bi * a.nc + c] = 0.f;
+                idx[(size_t)bi * a.nc + c] = -1;
+            }
+            return;
+        }
+        no_i = clamp_len(own_len, bi, a.no);
+        oblocks_i = (no_i + 64 * R - 1) / (64 * R);
+    }
     const float *own = own_all + (size_t)bi * a.no_pad * 3;
     const float *cand = cand_all + (size_t)bi * a.nc_pad * 3;
     const float *cp = colpart + (size_t)bi * a.nc + c;
     const size_t ostride = (size_t)a.b * a.nc;
     float best = INFINITY;
     int bblk = 0x7fffffff;
-    for (int o = q; o < a.oblocks; o += 4) {
+    for (int o = q; o < oblocks_i; o += 4) {
         const float v = cp[(size_t)o * ostride];
         if (v < best || bblk == 0x7fffffff) {  // strict '<' in block order; the first one always taken
             best = v;
@@ -419,11 +504,11 @@ __global__ __launch_bounds__(TPB) void nn_resolve_kernel(Sweep a, const float *_
     for (int r = R / 4 - 1; r >= 0; r--) {
         const int j = j0 + q * (R / 4) + r;
         float d = rf::d2_fma(cx - own[j * 3 + 0], cy - own[j * 3 + 1], cz - own[j * 3 + 2]);
-        if (j < a.no && d == best) found = j;
+        if (j < no_i && d == best) found = j;
     }
     found = min(found, __shfl_xor(found, 1, 64));
     found = min(found, __shfl_xor(found, 2, 64));
-    if (found == 0x7fffffff) found = j0 < a.no ? j0 : 0;  // all-inf case: block 0, lane 0 -> index 0
+    if (found == 0x7fffffff) found = j0 < no_i ? j0 : 0;  // all-inf case: block 0, lane 0 -> index 0
     if (cx != cx || cy != cy || cz != cz) {  // a NaN point: (NaN, 0), as in the reference
         best = NAN;
         found = 0;
@@ -474,8 +559,13 @@ struct GradArgs {
     const float *gl;  // LOSS mode: (b, 2) upstream grads of the per-sample mean-sqrt losses
 };
 
-template <bool LOSS>
-__global__ __launch_bounds__(GTPB) void nn_grad_kernel(GradArgs a) {
+// Counts::per_sample: per-sample counts len1 / len2 of the two sets.  Only destination rows
+// inside the count get an own term, only sources inside theirs scatter, and the loss mode scales by
+// 1 / count: rows beyond a count come out exactly 0 whatever their idx / upstream entries hold.
+template <bool LOSS, Counts CNT>
+__global__ __launch_bounds__(GTPB) void nn_grad_kernel(GradArgs a, const int *__restrict__ len1,
+                                                       const int *__restrict__ len2) {
+    constexpr bool LEN = CNT == Counts::per_sample;
     // the tile's sums in DOUBLE: ds_add_f64 runs at 18 lane-operations per ns and CU, ds_add_f32 at 0.8 (tools/ubench/lds_atomic_rate.hip)
     typedef double acc_t;
     __shared__ acc_t acc[GT * 3];
@@ -490,6 +580,11 @@ __global__ __launch_bounds__(GTPB) void nn_grad_kernel(GradArgs a) {
     const int jn = min(D.gt, D.nd - j0);
     const float *__restrict__ dxyz = D.dst_xyz + (size_t)bi * D.nd * 3;
     const float *__restrict__ sxyz = D.src_xyz + (size_t)bi * D.ns * 3;
+    int nd_i = D.nd, ns_i = D.ns;
+    if constexpr (LEN) {
+        nd_i = clamp_len(which ? len2 : len1, bi, D.nd);
+        ns_i = clamp_len(which ? len1 : len2, bi, D.ns);
+    }
     for (int i = threadIdx.x; i < jn * 3; i += GTPB) acc[i] = (acc_t)0;
     // own term first: its idx -> gather chain is independent of the scatter scan below, so the two
     // dependent-load chains overlap instead of running back to back (the kernel is latency-bound)
@@ -498,12 +593,12 @@ __global__ __launch_bounds__(GTPB) void nn_grad_kernel(GradArgs a) {
     {
         const int *__restrict__ id = D.idx_dst + (size_t)bi * D.nd;
         const float *__restrict__ gdd = (LOSS ? D.dist_dst : D.gd_dst) + (size_t)bi * D.nd;
-        const float sc = LOSS ? a.gl[bi * 2 + D.col_dst] / (float)D.nd : 0.f;
+        const float sc = LOSS ? a.gl[bi * 2 + D.col_dst] / (float)nd_i : 0.f;
 #pragma unroll
         for (int u = 0; u < OWN; u++) {
             const int i = threadIdx.x + u * GTPB;
             own[u] = 0.f;
-            if (i < jn * 3 && D.has_own) {
+            if (i < jn * 3 && D.has_own && (!LEN || j0 + i / 3 < nd_i)) {
                 const int j = i / 3, c = i - j * 3;
                 const int k = id[j0 + j];
                 const float gd = LOSS ? sc * 0.5f / sqrtf(gdd[j0 + j]) : gdd[j0 + j];
@@ -514,9 +609,10 @@ __global__ __launch_bounds__(GTPB) void nn_grad_kernel(GradArgs a) {
     }
     const int *__restrict__ is = D.idx_src + (size_t)bi * D.ns;
     const float *__restrict__ gs = (LOSS ? D.dist_src : D.gd_src) + (size_t)bi * D.ns;
-    const float scs = LOSS ? a.gl[bi * 2 + D.col_src] / (float)D.ns : 0.f;
+    const float scs = LOSS ? a.gl[bi * 2 + D.col_src] / (float)ns_i : 0.f;
     const int per = (D.ns + D.slices - 1) / D.slices;
-    const int k_end = D.has_scatter ? min(D.ns, (slice + 1) * per) : 0;
+    // (LEN: valid sources point at valid destinations only, so a tile wholly beyond nd_i scans nothing)
+    const int k_end = D.has_scatter && (!LEN || j0 < nd_i) ? min(ns_i, (slice + 1) * per) : 0;
     constexpr int SU = 4;  // sources per thread in flight
     int jj[SU];
     int kb = slice * per + threadIdx.x;
@@ -577,6 +673,26 @@ __global__ __launch_bounds__(GTPB) void nn_grad_kernel(GradArgs a) {
                 atomicAdd(&out[i], slice == 0 ? own[u] + (float)acc[i] : (float)acc[i]);
             }
         }
+    }
+}
+
+// The pad values (0, -1) into the slots beyond each sample's count, both directions in one launch
+// (a direction whose outputs are NULL has none).
+__global__ void pad_outputs_kernel(int b, int n, int m, const int *__restrict__ len1, const int *__restrict__ len2,
+                                   float *__restrict__ dist1, int *__restrict__ idx1, float *__restrict__ dist2,
+                                   int *__restrict__ idx2) {
+    long g = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long t1 = dist1 ? (long)b * n : 0;
+    const bool second = g >= t1;
+    if (second) g -= t1;
+    const int cnt = second ? m : n;
+    float *__restrict__ d = second ? dist2 : dist1;
+    int *__restrict__ id = second ? idx2 : idx1;
+    if (!d || g >= (long)b * cnt) return;
+    const long bi = g / cnt;
+    if (g - bi * cnt >= clamp_len(second ? len2 : len1, (int)bi, cnt)) {
+        d[g] = 0.f;
+        id[g] = -1;
     }
 }
 
@@ -664,8 +780,12 @@ size_t dense_workspace_bytes(int b, int n, int m, int dirs) { return make_plan(b
 // The dense sweep (every pair evaluated).  dirs as above; outputs of a direction that is not
 // wanted may be NULL.
 int dense_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist1, int *idx1,
-                      float *dist2, int *idx2, void *workspace, size_t workspace_bytes, hipStream_t s, int dirs) {
+                      float *dist2, int *idx2, void *workspace, size_t workspace_bytes, hipStream_t s, int dirs,
+                      const int *len1, const int *len2) {
     Plan p = make_plan(b, n, m, dirs);
+    // ragged batches (per-sample counts): always re-packed, each sample padded from its own count
+    const bool ragged = len1 != nullptr || len2 != nullptr;
+    const int *own_len = p.swap ? len2 : len1, *cand_len = p.swap ? len1 : len2;
     if (workspace_bytes < p.bytes) return RF_EWORKSPACE;
     const bool cols = dirs == 3;
     char *w = (char *)workspace;
@@ -677,12 +797,16 @@ int dense_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2,
     // Clouds whose sizes already fit the tiling (own a multiple of 64*R, candidates a multiple of
     // the 32-candidate group) are swept in place; otherwise both are re-packed with -inf / +inf
     // padding (pack_kernel).  BASELINE's shapes (2048, 16384) take the in-place path.
-    const bool in_place = (p.no % (64 * RR) == 0) && (p.nc % CG == 0);
+    const bool in_place = !ragged && (p.no % (64 * RR) == 0) && (p.nc % CG == 0);
     if (in_place) {
         own_p = const_cast<float *>(own_src);
         cand_p = const_cast<float *>(cand_src);
         p.no_pad = p.no;
         p.nc_pad = p.nc;
+    } else if (ragged) {
+        const int nb_own = rf::ceil_div((long)b * p.no_pad, 256), nb_cand = rf::ceil_div((long)b * p.nc_pad, 256);
+        RF_LAUNCH("nn_pack_len", pack_len_kernel, dim3(nb_own + nb_cand), dim3(256), 0, s, b, p.no, p.no_pad, own_src,
+                  own_len, own_p, nb_own, p.nc, p.nc_pad, cand_src, cand_len, cand_p);
     } else {
         const int nb_own = rf::ceil_div((long)b * p.no_pad, 256), nb_cand = rf::ceil_div((long)b * p.nc_pad, 256);
         RF_LAUNCH("nn_pack", pack_kernel, dim3(nb_own + nb_cand), dim3(256), 0, s, b, p.no, p.no_pad, own_src,
@@ -698,24 +822,74 @@ int dense_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2,
     a.oblocks = p.oblocks; a.nsplit = p.nsplit; a.span = p.span; a.wgm = p.wgm;
     a.rslots_final = p.rslots > 1 ? 0 : 1;
     long waves = (long)b * p.oblocks * p.nsplit;
+    if (ragged) {
+        const dim3 grid(rf::ceil_div(waves, TPB / 64));
+        if (cols) {
+            RF_LAUNCH("nn_sweep_len", (nn_sweep_kernel<RR, true, Counts::per_sample>), grid, dim3(TPB), 0, s, a,
+                      (const float *)own_p, (const float *)cand_p, row_dist, row_idx, colpart, collane, own_len,
+                      cand_len);
+        } else {
+            RF_LAUNCH("nn_sweep_len_1dir", (nn_sweep_kernel<RR, false, Counts::per_sample>), grid, dim3(TPB), 0, s, a,
+                      (const float *)own_p, (const float *)cand_p, row_dist, row_idx, colpart, collane, own_len,
+                      cand_len);
+        }
+        const int nblk_col = cols ? rf::ceil_div(p.nc, TPB / 4) * b : 0;
+        const int nblk_row = p.rslots > 1 ? rf::ceil_div((long)b * p.no, TPB) : 0;
+        if (nblk_col + nblk_row > 0) {
+            RF_LAUNCH("nn_resolve_len", (nn_resolve_kernel<RR, Counts::per_sample>), dim3(nblk_col + nblk_row),
+                      dim3(TPB), 0, s, a, (const float *)own_p, (const float *)cand_p, (const float *)colpart,
+                      (const unsigned char *)collane, cand_dist, cand_idx, nblk_col, (const float *)row_dist,
+                      (const int *)row_idx, own_dist, own_idx, p.rslots, own_len, cand_len);
+        }
+        return RF_OK;
+    }
     if (cols) {
-        RF_LAUNCH("nn_sweep", (nn_sweep_kernel<RR, true>), dim3(rf::ceil_div(waves, TPB / 64)), dim3(TPB), 0, s, a,
-                  (const float *)own_p, (const float *)cand_p, row_dist, row_idx, colpart, collane);
+        RF_LAUNCH("nn_sweep", (nn_sweep_kernel<RR, true, Counts::all>), dim3(rf::ceil_div(waves, TPB / 64)), dim3(TPB),
+                  0, s, a, (const float *)own_p, (const float *)cand_p, row_dist, row_idx, colpart, collane, nullptr,
+                  nullptr);
     } else {
-        RF_LAUNCH("nn_sweep_1dir", (nn_sweep_kernel<RR, false>), dim3(rf::ceil_div(waves, TPB / 64)), dim3(TPB), 0, s,
-                  a, (const float *)own_p, (const float *)cand_p, row_dist, row_idx, colpart, collane);
+        RF_LAUNCH("nn_sweep_1dir", (nn_sweep_kernel<RR, false, Counts::all>), dim3(rf::ceil_div(waves, TPB / 64)),
+                  dim3(TPB), 0, s, a, (const float *)own_p, (const float *)cand_p, row_dist, row_idx, colpart, collane,
+                  nullptr, nullptr);
     }
     {
         const int cblocks = rf::ceil_div(p.nc, TPB / 4);  // 4 lanes per candidate
         const int nblk_col = cols ? cblocks * b : 0;
         const int nblk_row = p.rslots > 1 ? rf::ceil_div((long)b * p.no, TPB) : 0;
         if (nblk_col + nblk_row > 0) {
-            RF_LAUNCH("nn_resolve", nn_resolve_kernel<RR>, dim3(nblk_col + nblk_row), dim3(TPB), 0, s, a,
+            RF_LAUNCH("nn_resolve", (nn_resolve_kernel<RR, Counts::all>), dim3(nblk_col + nblk_row), dim3(TPB), 0, s, a,
                       (const float *)own_p, (const float *)cand_p, (const float *)colpart,
                       (const unsigned char *)collane, cand_dist, cand_idx, nblk_col, (const float *)row_dist,
-                      (const int *)row_idx, own_dist, own_idx, p.rslots);
+                      (const int *)row_idx, own_dist, own_idx, p.rslots, nullptr, nullptr);
         }
     }
+    return RF_OK;
+}
+
+// Ragged batches.  The dense sweep takes the counts into its kernels (work shrinks with them); the
+// culled sweep's sort keys, places and boxes only each sample's first len points (nnp_sort_reg_kernel
+// RAGGED), the sweep skips the padding behind them, and the padded output slots, which nothing else
+// writes, get (0, -1) from pad_outputs_kernel.
+size_t ragged_workspace_bytes(int b, int n, int m, int mode, int dirs) {
+    if (resolve_mode(b, n, m, mode) == RF_NN_CULLED) return rfp::pruned_workspace_bytes(b, n, m);
+    return dense_workspace_bytes(b, n, m, dirs);
+}
+
+int ragged_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                       float *dist1, int *idx1, float *dist2, int *idx2, void *workspace, size_t workspace_bytes,
+                       hipStream_t s, int mode, int dirs, bool pad_culled) {
+    if (workspace_bytes < ragged_workspace_bytes(b, n, m, mode, dirs)) return RF_EWORKSPACE;
+    if (resolve_mode(b, n, m, mode) != RF_NN_CULLED)
+        return dense_nn_distance(b, n, m, xyz1, xyz2, dist1, idx1, dist2, idx2, workspace, workspace_bytes, s, dirs,
+                                 len1, len2);
+    if (int e = rfp::pruned_nn_distance(b, n, m, xyz1, xyz2, dist1, idx1, dist2, idx2, workspace, workspace_bytes, s,
+                                        nullptr, dirs, len1, len2))
+        return e;
+    if (!pad_culled) return RF_OK;
+    const long total = ((dirs & 1) ? (long)b * n : 0) + ((dirs & 2) ? (long)b * m : 0);
+    RF_LAUNCH("nn_pad_outputs", pad_outputs_kernel, dim3(rf::ceil_div(total, 256)), dim3(256), 0, s, b, n, m, len1,
+              len2, (dirs & 1) ? dist1 : nullptr, (dirs & 1) ? idx1 : nullptr, (dirs & 2) ? dist2 : nullptr,
+              (dirs & 2) ? idx2 : nullptr);
     return RF_OK;
 }
 
@@ -758,6 +932,56 @@ int rf_nn_distance_mode(int b, int n, int m, const float *xyz1, const float *xyz
     return rfd::dense_nn_distance(b, n, m, xyz1, xyz2, dist1, idx1, dist2, idx2, workspace, workspace_bytes, s, 3);
 }
 
+// ------------------------------------------------------------------ ragged batches -------
+namespace {
+bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+}  // namespace
+
+size_t rf_nn_distance_lengths_workspace_bytes(int b, int n, int m, int mode) {
+    if (b <= 0 || n <= 0 || m <= 0) return 0;
+    if (mode != RF_NN_AUTO && mode != RF_NN_DENSE && mode != RF_NN_CULLED) return 0;
+    if (rfd::resolve_mode(b, n, m, mode) == RF_NN_CULLED && !rfp::pruned_supported(b, n, m)) return 0;
+    size_t w = 0;
+    for (int dirs = 1; dirs <= 3; dirs++) {  // one size for whichever directions the call asks for
+        const size_t d = rfd::ragged_workspace_bytes(b, n, m, mode, dirs);
+        w = d > w ? d : w;
+    }
+    return w;
+}
+
+int rf_nn_distance_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                           const int *len2, float *dist1, int *idx1, float *dist2, int *idx2, void *workspace,
+                           size_t workspace_bytes, rf_stream_t stream, int mode) {
+    if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
+    if (mode != RF_NN_AUTO && mode != RF_NN_DENSE && mode != RF_NN_CULLED) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
+    const int dirs = ((dist1 || idx1) ? 1 : 0) | ((dist2 || idx2) ? 2 : 0);
+    if (!dirs || ((dirs & 1) && (!dist1 || !idx1)) || ((dirs & 2) && (!dist2 || !idx2))) return RF_EINVAL;
+    if (!xyz1 || !xyz2 || !workspace) return RF_EINVAL;
+    if (!aligned4(xyz1) || !aligned4(xyz2) || !aligned4(len1) || !aligned4(len2) || !aligned4(dist1) ||
+        !aligned4(idx1) || !aligned4(dist2) || !aligned4(idx2) || !rf::aligned16(workspace))
+        return RF_EINVAL;
+    if (rfd::resolve_mode(b, n, m, mode) == RF_NN_CULLED && !rfp::pruned_supported(b, n, m)) return RF_EINVAL;
+    if (workspace_bytes < rfd::ragged_workspace_bytes(b, n, m, mode, dirs)) return RF_EWORKSPACE;
+    return rfd::ragged_nn_distance(b, n, m, xyz1, xyz2, len1, len2, dist1, idx1, dist2, idx2, workspace,
+                                   workspace_bytes, (hipStream_t)stream, mode, dirs);
+}
+
+int rf_nn_distance_grad_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                                const int *len2, const float *grad_dist1, const int *idx1, const float *grad_dist2,
+                                const int *idx2, float *grad_xyz1, float *grad_xyz2, rf_stream_t stream) {
+    if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0) return RF_EINVAL;
+    if (!xyz1 || !xyz2 || !grad_dist1 || !idx1 || !grad_dist2 || !idx2 || !grad_xyz1 || !grad_xyz2) return RF_EINVAL;
+    if (!aligned4(len1) || !aligned4(len2)) return RF_EINVAL;
+    const rfd::GradSource g{grad_dist1, grad_dist2, nullptr, nullptr, nullptr};
+    // (a NULL count array stands for "all": with both NULL this is rf_nn_distance_grad's kernel)
+    return rfd::nn_distance_grad(b, n, m, xyz1, xyz2, g, idx1, idx2, grad_xyz1, grad_xyz2, (hipStream_t)stream, len1,
+                                 len2);
+}
+
 int rf_nn_distance_grad(int b, int n, int m, const float *xyz1, const float *xyz2,
                         const float *grad_dist1, const int *idx1, const float *grad_dist2,
                         const int *idx2, float *grad_xyz1, float *grad_xyz2, rf_stream_t stream) {
@@ -772,7 +996,8 @@ int rf_nn_distance_grad(int b, int n, int m, const float *xyz1, const float *xyz
 namespace rfd {
 
 int nn_distance_grad(int b, int n, int m, const float *xyz1, const float *xyz2, const GradSource &src,
-                     const int *idx1, const int *idx2, float *grad_xyz1, float *grad_xyz2, hipStream_t s) {
+                     const int *idx1, const int *idx2, float *grad_xyz1, float *grad_xyz2, hipStream_t s,
+                     const int *len1, const int *len2) {
     if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0 || (n == 0 && m == 0)) return RF_OK;
     if (n == 0 || m == 0) {  // no neighbours exist: the gradient of nothing is zero
@@ -814,10 +1039,22 @@ int nn_distance_grad(int b, int n, int m, const float *xyz1, const float *xyz2, 
                      src.dist2, src.dist1, 1, 0, has2, has1};
     a.nblk0 = b * t0 * s0;
     const int nblk1 = b * t1 * s1;
+    if (len1 || len2) {
+        if (loss) {
+            RF_LAUNCH("nn_grad_loss_len", (nn_grad_kernel<true, Counts::per_sample>), dim3(a.nblk0 + nblk1),
+                      dim3(GTPB), 0, s, a, len1, len2);
+        } else {
+            RF_LAUNCH("nn_grad_len", (nn_grad_kernel<false, Counts::per_sample>), dim3(a.nblk0 + nblk1),
+                      dim3(GTPB), 0, s, a, len1, len2);
+        }
+        return RF_OK;
+    }
     if (loss) {
-        RF_LAUNCH("nn_grad_loss", nn_grad_kernel<true>, dim3(a.nblk0 + nblk1), dim3(GTPB), 0, s, a);
+        RF_LAUNCH("nn_grad_loss", (nn_grad_kernel<true, Counts::all>), dim3(a.nblk0 + nblk1), dim3(GTPB), 0, s, a,
+                  nullptr, nullptr);
     } else {
-        RF_LAUNCH("nn_grad", nn_grad_kernel<false>, dim3(a.nblk0 + nblk1), dim3(GTPB), 0, s, a);
+        RF_LAUNCH("nn_grad", (nn_grad_kernel<false, Counts::all>), dim3(a.nblk0 + nblk1), dim3(GTPB), 0, s, a, nullptr,
+                  nullptr);
     }
     return RF_OK;
 }

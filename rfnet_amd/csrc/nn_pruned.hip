@@ -140,6 +140,13 @@ struct SortArgs {
     unsigned long long *dbg;  // optional (with stats): s_memtime stamps of the sort's phases, [16..31]
 };
 
+// A ragged batch's count of batch element bi (NULL = all n), clamped into [1, n].
+__device__ __forceinline__ int ragged_count(const int *__restrict__ len, int bi, int n) {
+    if (!len) return n;
+    const int v = len[bi];
+    return v < 1 ? 1 : (v > n ? n : v);
+}
+
 // Skilling's axes-to-transpose Hilbert mapping, 5 bits per axis -> 15-bit index.
 __device__ __forceinline__ unsigned hilbert15(unsigned x, unsigned y, unsigned z) {
     unsigned X[3] = {x, y, z};
@@ -251,7 +258,14 @@ constexpr int HALF = 9216;  // records staged in LDS at a time (16 B each, over 
 // later phase is LDS and ALU work.  The sorted records are staged in LDS (over the histogram,
 // dead once every point has its position), 8192 at a time, so that the boxes come from LDS and
 // the arrays leave the CU as coalesced stores (a direct scatter is 4 x 16384 single-dword stores).
-__global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a) {
+// RAGGED (rf_nn_distance_lengths): len0 / len1 (device, per batch element, NULL = all; clamped into [1, n])
+// count the valid points of each set's clouds.  Only those are keyed, placed and boxed: the slots behind them
+// are the set's padding (+inf records, original index -1, empty boxes), which the sweep already skips --
+// padding lanes take no part in a traversal and an empty box is never within a query's bound.  So the frame,
+// the order and the boxes are the sample's own, and the work shrinks with the count.
+template <bool RAGGED>
+__global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const int *__restrict__ len0,
+                                                            const int *__restrict__ len1) {
     __shared__ __attribute__((aligned(16))) unsigned hist[HALF * 4];  // NBINS bins, later HALF staged records
     __shared__ unsigned ahist[3][HB];
     __shared__ unsigned char slabmap[HB];        // x bin -> slab (equal mass)
@@ -281,8 +295,10 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a) {
     const int set = (a.nsets > 1 && rem >= a.split[0]) ? 1 : 0;
     if (set) rem -= a.split[0];
     const int H = a.split[set], half = rem;  // H = 1: half = 0, the whole key space
-    const int n = a.n[set], npad = a.npad[set];
-    const float *__restrict__ src = a.src[set] + (size_t)bi * n * 3;
+    const int nfull = a.n[set], npad = a.npad[set];
+    const float *__restrict__ src = a.src[set] + (size_t)bi * nfull * 3;
+    // RAGGED: only the sample's first len points are sorted; the rest of the set is padding, as past n
+    const int n = RAGGED ? ragged_count(set ? len1 : len0, bi, nfull) : nfull;
     float *__restrict__ oxyz = a.xyz[set] + (size_t)bi * npad * 3;
     int *__restrict__ oorig = a.orig[set] + (size_t)bi * npad;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -689,8 +705,10 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a) {
 
 // REG: the cloud (n <= RPT * STPB points) is loaded once into registers -- every later phase is
 // LDS and ALU work only; otherwise each phase re-reads the points (L2-resident) from `src`.
-template <bool REG>
-__global__ __launch_bounds__(STPB) void nnp_sort_kernel(SortArgs a) {
+// RAGGED: as nnp_sort_reg_kernel.
+template <bool REG, bool RAGGED>
+__global__ __launch_bounds__(STPB) void nnp_sort_kernel(SortArgs a, const int *__restrict__ len0,
+                                                        const int *__restrict__ len1) {
     __shared__ __attribute__((aligned(16))) unsigned hist[NBINS];
     __shared__ unsigned ahist[3][HB];
     __shared__ unsigned char cellmap[3][HB];
@@ -705,8 +723,9 @@ __global__ __launch_bounds__(STPB) void nnp_sort_kernel(SortArgs a) {
     const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (int)(blockIdx.x >> 3);
     const int bi = logical / a.nsets, set = logical - bi * a.nsets;
     if (threadIdx.x == 0) nbad = 0;
-    const int n = a.n[set], npad = a.npad[set];
-    const float *__restrict__ src = a.src[set] + (size_t)bi * n * 3;
+    const int nfull = a.n[set], npad = a.npad[set];
+    const float *__restrict__ src = a.src[set] + (size_t)bi * nfull * 3;
+    const int n = RAGGED ? ragged_count(set ? len1 : len0, bi, nfull) : nfull;  // (as nnp_sort_reg_kernel)
     float *__restrict__ oxyz = a.xyz[set] + (size_t)bi * npad * 3;
     int *__restrict__ oorig = a.orig[set] + (size_t)bi * npad;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2239,7 +2258,7 @@ size_t pruned_workspace_bytes(int b, int n, int m) {
 
 // Sort `nsets` (1 or 2) sets of b clouds in ONE launch (one workgroup per cloud).
 int sort_sets(int b, int nsets, const int *n, const float *const *src, const Sorted *out, hipStream_t s,
-              unsigned long long *dbg) {
+              unsigned long long *dbg, const int *const *lens) {
     if (b <= 0 || nsets < 1 || nsets > 2) return RF_EINVAL;
     SortArgs sa;
     sa.b = b;
@@ -2270,11 +2289,20 @@ int sort_sets(int b, int nsets, const int *n, const float *const *src, const Sor
             sa.str_s[k] = ss < 1 ? 1 : (ss > 16 ? 16 : ss);
         }
     }
+    const int wpb = sa.split[0] + (nsets > 1 ? sa.split[1] : 0);
+    if (lens) {  // per-sample counts (ragged batches)
+        const int *l0 = lens[0], *l1 = nsets > 1 ? lens[1] : nullptr;
+        if (reg) {
+            RF_LAUNCH("nnp_sort", nnp_sort_reg_kernel<true>, dim3(wpb * b), dim3(STPB), 0, s, sa, l0, l1);
+        } else {
+            RF_LAUNCH("nnp_sort", (nnp_sort_kernel<false, true>), dim3(nsets * b), dim3(STPB), 0, s, sa, l0, l1);
+        }
+        return RF_OK;
+    }
     if (reg) {
-        const int wpb = sa.split[0] + (nsets > 1 ? sa.split[1] : 0);
-        RF_LAUNCH("nnp_sort", nnp_sort_reg_kernel, dim3(wpb * b), dim3(STPB), 0, s, sa);
+        RF_LAUNCH("nnp_sort", nnp_sort_reg_kernel<false>, dim3(wpb * b), dim3(STPB), 0, s, sa, nullptr, nullptr);
     } else {
-        RF_LAUNCH("nnp_sort", nnp_sort_kernel<false>, dim3(nsets * b), dim3(STPB), 0, s, sa);
+        RF_LAUNCH("nnp_sort", (nnp_sort_kernel<false, false>), dim3(nsets * b), dim3(STPB), 0, s, sa, nullptr, nullptr);
     }
     return RF_OK;
 }
@@ -2387,7 +2415,7 @@ int pruned_step(int b, int n, int m, const float *xyz1, const float *xyz2, const
 
 int pruned_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist1, int *idx1,
                        float *dist2, int *idx2, void *workspace, size_t workspace_bytes, hipStream_t s,
-                       unsigned long long *stats_out, int dirs) {
+                       unsigned long long *stats_out, int dirs, const int *len1, const int *len2) {
     if (!pruned_supported(b, n, m) || !rf::aligned16(workspace)) return RF_EINVAL;
     if (workspace_bytes < pruned_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     char *w = (char *)workspace;
@@ -2399,7 +2427,8 @@ int pruned_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2
     }
     const int nn[2] = {n, m};
     const float *src[2] = {xyz1, xyz2};
-    if (int e = sort_sets(b, 2, nn, src, so, s, stats)) return e;
+    const int *lens[2] = {len1, len2};
+    if (int e = sort_sets(b, 2, nn, src, so, s, stats, (len1 || len2) ? lens : nullptr)) return e;
     if (int e = sweep_sorted(b, n, m, so[0], so[1], dist1, idx1, dist2, idx2, dirs, s, stats)) return e;
     if (stats_out) {
         RF_HIP(hipMemcpyAsync(stats_out, stats, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

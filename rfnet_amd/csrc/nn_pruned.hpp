@@ -14,9 +14,12 @@ size_t pruned_workspace_bytes(int b, int n, int m);
 // synchronises the stream.
 // dirs: bit 0 = direction 1 (dist1/idx1), bit 1 = direction 2; outputs of a direction not asked
 // for may be NULL.
+// len1 / len2: per-sample counts of a ragged batch (device, NULL = all): the sort keys and boxes only the first
+// len points and pads the rest of the set (nnp_sort_reg_kernel); outputs of padded slots are not written.
 int pruned_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2, float *dist1, int *idx1,
                        float *dist2, int *idx2, void *workspace, size_t workspace_bytes, hipStream_t s,
-                       unsigned long long *stats_out, int dirs = 3);
+                       unsigned long long *stats_out, int dirs = 3, const int *len1 = nullptr,
+                       const int *len2 = nullptr);
 
 // The sort on its own (one cloud per batch element), for other operators that want the Hilbert
 // order: records (x, y, z packed) and original indices in key order, padded to a multiple of 64
@@ -39,7 +42,7 @@ int sort_clouds(int b, int n, const float *src, void *workspace, size_t workspac
 size_t sorted_bytes(int b, int n);
 Sorted sorted_view(int b, int n, const void *buf);
 int sort_sets(int b, int nsets, const int *n, const float *const *src, const Sorted *out, hipStream_t s,
-              unsigned long long *dbg);
+              unsigned long long *dbg, const int *const *lens = nullptr);
 int sweep_sorted(int b, int n, int m, const Sorted &s0, const Sorted &s1, float *dist1, int *idx1, float *dist2,
                  int *idx2, int dirs, hipStream_t s, unsigned long long *stats_dev);
 

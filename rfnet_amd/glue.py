@@ -80,13 +80,43 @@ def merge_layer_unfused(rawpts, newpts, decfactor, knum=16):
     return newpts + (ratio * diff).sum(2)
 
 
-class _ChamferLoss(torch.autograd.Function):
-    """rf_chamfer_loss / rf_chamfer_loss_grad: per-sample mean sqrt(dist) (b, 2) and idx1; the
-    0.5/sqrt(d)/N factor of the backward is formed inside the scatter kernel."""
+class _NnDistanceLengths(torch.autograd.Function):
+    """rf_nn_distance_lengths / rf_nn_distance_grad_lengths: the reference's 4-tuple over a ragged batch."""
 
     @staticmethod
-    def forward(ctx, xyz1, xyz2, sorted1, sorted2, want1, want2):
-        loss, d1, i1, d2, i2 = _raw.chamfer_loss(xyz1, xyz2, sorted1, sorted2, want1, want2)
+    def forward(ctx, xyz1, xyz2, lengths1, lengths2):
+        d1, i1, d2, i2 = _raw.nn_distance(xyz1, xyz2, lengths1=lengths1, lengths2=lengths2)
+        ctx.save_for_backward(xyz1, xyz2, i1, i2)
+        ctx.lens = (lengths1, lengths2)
+        ctx.mark_non_differentiable(i1, i2)
+        return d1, i1, d2, i2
+
+    @staticmethod
+    def backward(ctx, gd1, _gi1, gd2, _gi2):
+        xyz1, xyz2, i1, i2 = ctx.saved_tensors
+        gd1 = torch.zeros_like(i1, dtype=xyz1.dtype) if gd1 is None else gd1.contiguous()
+        gd2 = torch.zeros_like(i2, dtype=xyz2.dtype) if gd2 is None else gd2.contiguous()
+        g1, g2 = _raw.nn_distance_grad(xyz1, xyz2, gd1, i1, gd2, i2, lengths1=ctx.lens[0], lengths2=ctx.lens[1])
+        return g1, g2, None, None
+
+
+def nn_distance_lengths(xyz1, xyz2, lengths1=None, lengths2=None):
+    """nn_distance over a ragged batch: sample i uses xyz1[i, :lengths1[i]] and xyz2[i, :lengths2[i]]
+    (None: all points).  Returns (dist1, idx1, dist2, idx2) with (0, -1) in the padded slots; the
+    gradient of a padded point is 0.  Lengths: list, tuple, numpy array, CPU or CUDA tensor."""
+    return _NnDistanceLengths.apply(xyz1.contiguous(), xyz2.contiguous(), lengths1, lengths2)
+
+
+class _ChamferLoss(torch.autograd.Function):
+    """rf_chamfer_loss / rf_chamfer_loss_grad: per-sample mean sqrt(dist) (b, 2) and idx1; the
+    0.5/sqrt(d)/N factor of the backward is formed inside the scatter kernel.  With per-sample
+    lengths: the _lengths entries (means and their backward over each sample's own count)."""
+
+    @staticmethod
+    def forward(ctx, xyz1, xyz2, sorted1, sorted2, want1, want2, lengths1=None, lengths2=None):
+        loss, d1, i1, d2, i2 = _raw.chamfer_loss(xyz1, xyz2, sorted1, sorted2, want1, want2,
+                                                 lengths1=lengths1, lengths2=lengths2)
+        ctx.lens = (lengths1, lengths2)
         ctx.dirs = (want1, want2)
         ctx.save_for_backward(xyz1, xyz2, *[t for t in (d1, i1, d2, i2) if t is not None])
         idx1 = i1 if i1 is not None else torch.empty(0, dtype=torch.int32, device=loss.device)
@@ -103,25 +133,29 @@ class _ChamferLoss(torch.autograd.Function):
             d1, i1, rest = rest[0], rest[1], rest[2:]
         if ctx.dirs[1]:
             d2, i2 = rest[0], rest[1]
-        g1, g2 = _raw.chamfer_loss_grad(xyz1, xyz2, d1, i1, d2, i2, grad_loss.contiguous())
-        return g1, g2, None, None, None, None
+        g1, g2 = _raw.chamfer_loss_grad(xyz1, xyz2, d1, i1, d2, i2, grad_loss.contiguous(),
+                                        lengths1=ctx.lens[0], lengths2=ctx.lens[1])
+        return g1, g2, None, None, None, None, None, None
 
 
-def chamfer_per_sample(pcd1, pcd2, sorted1=None, sorted2=None, want1=True, want2=True):
-    """(loss (b, 2), idx1): loss[:, 0] = mean_j sqrt(dist1), loss[:, 1] = mean_k sqrt(dist2) per sample."""
-    return _ChamferLoss.apply(pcd1.contiguous(), pcd2.contiguous(), sorted1, sorted2, want1, want2)
+def chamfer_per_sample(pcd1, pcd2, sorted1=None, sorted2=None, want1=True, want2=True, lengths1=None, lengths2=None):
+    """(loss (b, 2), idx1): loss[:, 0] = mean_j sqrt(dist1), loss[:, 1] = mean_k sqrt(dist2) per sample.
+    lengths1 / lengths2: per-sample point counts of a ragged batch (means over each sample's own points,
+    idx1 = -1 in padded slots); not combined with sorted handles."""
+    return _ChamferLoss.apply(pcd1.contiguous(), pcd2.contiguous(), sorted1, sorted2, want1, want2, lengths1, lengths2)
 
 
-def chamfer_big(pcd1, pcd2, sorted1=None, sorted2=None):
+def chamfer_big(pcd1, pcd2, sorted1=None, sorted2=None, lengths1=None, lengths2=None):
     """(mean sqrt(dist1) + mean sqrt(dist2)) / 2 over the whole batch, and idx1 (vv_recon.py:381-385).
-    One fused forward (sweep + sqrt-mean epilogue) and one fused backward."""
-    loss, idx1 = chamfer_per_sample(pcd1, pcd2, sorted1, sorted2)
+    One fused forward (sweep + sqrt-mean epilogue) and one fused backward.  With lengths: the batch mean
+    of the per-sample means."""
+    loss, idx1 = chamfer_per_sample(pcd1, pcd2, sorted1, sorted2, lengths1=lengths1, lengths2=lengths2)
     return (loss[:, 0].mean() + loss[:, 1].mean()) / 2, idx1
 
 
-def fidelity_loss(pcd1, pcd2, sorted1=None, sorted2=None):
+def fidelity_loss(pcd1, pcd2, sorted1=None, sorted2=None, lengths1=None, lengths2=None):
     """mean sqrt(dist1) (vv_recon.py:386-390): direction 1 only is computed."""
-    loss, _ = chamfer_per_sample(pcd1, pcd2, sorted1, sorted2, True, False)
+    loss, _ = chamfer_per_sample(pcd1, pcd2, sorted1, sorted2, True, False, lengths1, lengths2)
     return loss[:, 0].mean()
 
 
