@@ -416,6 +416,43 @@ int rf_earth_mover_mode(int b, int n, int m, const float *xyz1, const float *xyz
                         float *grad1, float *grad2, void *workspace, size_t workspace_bytes,
                         rf_stream_t stream, int mode);
 
+/* ---- ragged batches: per-sample point counts (EMD) ------------------------------------------
+ * The conventions of rf_nn_distance_lengths: sample i is xyz1[i, :len1[i]] against xyz2[i, :len2[i]]; len1 / len2 are DEVICE
+ * int32 arrays of b counts or NULL ("all n" / "all m"), read by the kernels themselves (no host synchronisation: a call can be
+ * captured in a HIP graph) and clamped into [1, n] / [1, m].  Nothing beyond a count reaches a result: neither the padded
+ * coordinates of either cloud nor, in rf_matchcost{,_grad}_lengths, the padded entries of the caller's `match` (NaN, inf,
+ * 1e30 there change no bit of match or cost).
+ *   Multipliers per sample from the clamped counts, the reference's integer rule (am_multipliers): len1 >= len2 gives
+ *   multiL = 1, multiR = len1 / len2, else multiL = len2 / len1, multiR = 1.
+ *   match keeps the shape (b, m, n); every entry with l >= len2[i] or k >= len1[i] is exactly +0.  The cost sums the valid
+ *   pairs only; gradient rows beyond a count are exactly +0.
+ *   Route: always the pinned one (RF_EMD_SWEPT: dense sweeps in the caller's order, launch shapes of a batch of one), or
+ *   am_small's one workgroup per sample when n, m <= 256 -- so sample i's match, cost and fused cost are bit-identical to the
+ *   same ragged call on [i:i+1]; counts (n, m) or NULL give bit for bit rf_approxmatch_mode(..., RF_EMD_SWEPT) (any schedule)
+ *   and rf_matchcost; and at n, m <= 256 the valid block of match is bit for bit rf_approxmatch on the unpadded slices.
+ *   The work shrinks with the counts: row blocks beyond len1 (len2) exit at once, a sweep's column segment ends at the other
+ *   count, and the match / cost / gradient kernels skip whole blocks beyond the counts (still writing match's zeros).  The
+ *   column segments stay those of the padded width, so a sum can differ from a call on the slices in the last place.
+ * Argument rules: b == 0 is RF_OK; n < 1, m < 1, b > 65535, a NULL tensor, a misaligned count array (4 bytes) or workspace
+ * (16 bytes) are RF_EINVAL, as are (rf_approxmatch_lengths) a level multiplier that is positive or not finite; a workspace
+ * smaller than the matching _workspace_bytes is RF_EWORKSPACE -- all before any HIP call.  Outputs fully overwritten. */
+size_t rf_approxmatch_lengths_workspace_bytes(int b, int n, int m, int nlevels /* 0 = reference's 10 */);
+int rf_approxmatch_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                           float *match, const float *levels_host, int nlevels, void *workspace, size_t workspace_bytes,
+                           rf_stream_t stream);
+size_t rf_matchcost_lengths_workspace_bytes(int b, int n, int m);
+int rf_matchcost_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                         const float *match, float *cost, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+/* grad1 (b,n,3), grad2 (b,m,3): MatchCostGrad over the valid pairs (both required). */
+int rf_matchcost_grad_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                              const float *match, float *grad1, float *grad2, rf_stream_t stream);
+/* rf_earth_mover_mode(..., RF_EMD_SWEPT) on ragged batches (grad1 / grad2 both given or both NULL): within rel 1e-5 (cost) and
+ * rel 1e-4 + abs 1e-5 (gradients) of it at full counts. */
+size_t rf_earth_mover_lengths_workspace_bytes(int b, int n, int m);
+int rf_earth_mover_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                           float *cost, float *grad1, float *grad2, void *workspace, size_t workspace_bytes,
+                           rf_stream_t stream);
+
 /* `chamfer_big` / `fidelity_loss` (vv_recon.py:381-390) are reduce_mean(sqrt(dist)) over the
  * nn_distance outputs.  rf_chamfer_loss returns the per-sample means loss (b, 2):
  * loss[i][0] = mean_j sqrt(dist1[i][j]), loss[i][1] = mean_k sqrt(dist2[i][k]) (0 for a direction

@@ -105,6 +105,13 @@ SIGNATURES = {
     "rf_earth_mover": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rf_earth_mover_mode_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_earth_mover_mode": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _i]),
+    "rf_approxmatch_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "rf_approxmatch_lengths": (_i, [_i, _i, _i] + [_vp] * 5 + [C.POINTER(_f), _i, _vp, _sz, _vp]),
+    "rf_matchcost_lengths_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_matchcost_lengths": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
+    "rf_matchcost_grad_lengths": (_i, [_i, _i, _i] + [_vp] * 8),
+    "rf_earth_mover_lengths_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_earth_mover_lengths": (_i, [_i, _i, _i] + [_vp] * 8 + [_sz, _vp]),
     "rf_maxpool_points_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_maxpool_points": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "rf_maxpool_points_idx_workspace_bytes": (_sz, [_i, _i, _i]),

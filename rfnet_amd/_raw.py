@@ -428,21 +428,34 @@ EMD_MODES = {"auto": 0, "swept": 1}
 
 
 @H.on_input_device
-def approx_match(xyz1, xyz2, levels=None, mode="auto"):
+def approx_match(xyz1, xyz2, levels=None, mode="auto", lengths1=None, lengths2=None):
     """ApproxMatchGpuOp::Compute, pc_distance/tf_approxmatch.cpp:148-172 -> match (b,m,n).
 
     `levels` (optional, extension): explicit annealing schedule; default = the reference's 10.
     `mode` (extension): "auto" | "swept" (batch-invariant bits per sample, as the reference's per-sample loop).
+    `lengths1` / `lengths2` (extension): per-sample point counts of a ragged batch (rf_approxmatch_lengths): entries
+    outside a sample's counts come back as 0.  With counts, "auto" and "swept" both run the pinned (swept) route.
     """
     if mode not in EMD_MODES:
         raise H.invalid(f"ApproxMatch: mode must be one of {sorted(EMD_MODES)}")
     st = H.Staged()
     a, b_ = _emd_inputs(st, xyz1, xyz2, "ApproxMatch")
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
+    nlv = 0 if levels is None else len(levels)
+    if lengths1 is not None or lengths2 is not None:
+        l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+        dev = st.device_()
+        a, b_ = st.up(a, b_)
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        match = H.empty((b, m, n), F32, dev)
+        ws, wsz = H.workspace(lib.rf_approxmatch_lengths_workspace_bytes(b, n, m, nlv), dev, "am")
+        lv = None if levels is None else (C.c_float * nlv)(*[float(v) for v in levels])
+        check(lib.rf_approxmatch_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(match), lv, nlv,
+                                         H.ptr(ws), wsz, H.stream(dev)), "rf_approxmatch_lengths")
+        return st.give(match)
     dev = st.device_()
     a, b_ = st.up(a, b_)
     match = H.empty((b, m, n), F32, dev)
-    nlv = 0 if levels is None else len(levels)
     if mode != "auto":
         ws, wsz = H.workspace(lib.rf_approxmatch_mode_workspace_bytes(b, n, m, nlv, EMD_MODES[mode]), dev, "am")
         lv = None if levels is None else (C.c_float * nlv)(*[float(v) for v in levels])
@@ -466,13 +479,24 @@ def _match_check(mt, b, n, m):
 
 
 @H.on_input_device
-def match_cost(xyz1, xyz2, match):
-    """MatchCostGpuOp::Compute, pc_distance/tf_approxmatch.cpp:204-230 -> cost (b)."""
+def match_cost(xyz1, xyz2, match, lengths1=None, lengths2=None):
+    """MatchCostGpuOp::Compute, pc_distance/tf_approxmatch.cpp:204-230 -> cost (b).  With `lengths1` / `lengths2`
+    (rf_matchcost_lengths) only each sample's valid pairs are read and summed."""
     st = H.Staged()
     a, b_ = _emd_inputs(st, xyz1, xyz2, "MatchCost")
     mt = st.take(match, F32)
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
     _match_check(mt, b, n, m)
+    if lengths1 is not None or lengths2 is not None:
+        l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+        dev = st.device_()
+        a, b_, mt = st.up(a, b_, mt)
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        cost = H.empty((b,), F32, dev)
+        ws, wsz = H.workspace(lib.rf_matchcost_lengths_workspace_bytes(b, n, m), dev, "mc")
+        check(lib.rf_matchcost_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(mt), H.ptr(cost),
+                                       H.ptr(ws), wsz, H.stream(dev)), "rf_matchcost_lengths")
+        return st.give(cost)
     dev = st.device_()
     a, b_, mt = st.up(a, b_, mt)
     cost = H.empty((b,), F32, dev)
@@ -483,13 +507,23 @@ def match_cost(xyz1, xyz2, match):
 
 
 @H.on_input_device
-def match_cost_grad(xyz1, xyz2, match):
-    """MatchCostGradGpuOp::Compute, pc_distance/tf_approxmatch.cpp:265-295."""
+def match_cost_grad(xyz1, xyz2, match, lengths1=None, lengths2=None):
+    """MatchCostGradGpuOp::Compute, pc_distance/tf_approxmatch.cpp:265-295.  With `lengths1` / `lengths2`
+    (rf_matchcost_grad_lengths) only the valid pairs enter, and rows beyond a sample's count get a zero gradient."""
     st = H.Staged()
     a, b_ = _emd_inputs(st, xyz1, xyz2, "MatchCostGrad")
     mt = st.take(match, F32)
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
     _match_check(mt, b, n, m)
+    if lengths1 is not None or lengths2 is not None:
+        l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+        dev = st.device_()
+        a, b_, mt = st.up(a, b_, mt)
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        g1, g2 = H.empty((b, n, 3), F32, dev), H.empty((b, m, 3), F32, dev)
+        check(lib.rf_matchcost_grad_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(mt), H.ptr(g1),
+                                            H.ptr(g2), H.stream(dev)), "rf_matchcost_grad_lengths")
+        return st.give(g1), st.give(g2)
     dev = st.device_()
     a, b_, mt = st.up(a, b_, mt)
     g1, g2 = H.empty((b, n, 3), F32, dev), H.empty((b, m, 3), F32, dev)
@@ -499,21 +533,36 @@ def match_cost_grad(xyz1, xyz2, match):
 
 
 @H.on_input_device
-def earth_mover(xyz1, xyz2, with_grad=False, mode="auto"):
+def earth_mover(xyz1, xyz2, with_grad=False, mode="auto", lengths1=None, lengths2=None):
     """Row f1: the fused form of `earth_mover`'s op chain (vv_recon.py:392-399):
     approx_match -> match_cost [-> MatchCostGrad], without materialising match.
     -> cost (b)  or  (cost, grad1 (b,n,3), grad2 (b,m,3)) with `with_grad`.
-    mode="swept": cost[i] bit-identical whatever the batch around sample i (rf_earth_mover_mode)."""
+    mode="swept": cost[i] bit-identical whatever the batch around sample i (rf_earth_mover_mode).
+    `lengths1` / `lengths2`: per-sample point counts of a ragged batch (rf_earth_mover_lengths): the cost of each
+    sample's valid pairs, zero gradient rows beyond the counts.  With counts, "auto" and "swept" both run the pinned
+    (swept) route."""
     if mode not in EMD_MODES:
         raise H.invalid(f"ApproxMatch: mode must be one of {sorted(EMD_MODES)}")
     st = H.Staged()
     a, b_ = _emd_inputs(st, xyz1, xyz2, "ApproxMatch")
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
+    ragged = lengths1 is not None or lengths2 is not None
+    if ragged:
+        l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
     dev = st.device_()
     a, b_ = st.up(a, b_)
     cost = H.empty((b,), F32, dev)
     g1 = H.empty((b, n, 3), F32, dev) if with_grad else None
     g2 = H.empty((b, m, 3), F32, dev) if with_grad else None
+    if ragged:
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        ws, wsz = H.workspace(lib.rf_earth_mover_lengths_workspace_bytes(b, n, m), dev, "emd")
+        check(lib.rf_earth_mover_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(cost),
+                                         H.ptr(g1) if with_grad else None, H.ptr(g2) if with_grad else None,
+                                         H.ptr(ws), wsz, H.stream(dev)), "rf_earth_mover_lengths")
+        if with_grad:
+            return st.give(cost), st.give(g1), st.give(g2)
+        return st.give(cost)
     ws, wsz = H.workspace(lib.rf_earth_mover_mode_workspace_bytes(b, n, m, EMD_MODES[mode]), dev, "emd")
     check(lib.rf_earth_mover_mode(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(cost),
                                   H.ptr(g1) if with_grad else None, H.ptr(g2) if with_grad else None,

@@ -67,16 +67,35 @@ struct AmInit {
     float *vec;        // the vector region: per batch element `stride` floats = nslots slots of V = npad[0] + npad[1] floats
     size_t stride, V;  // slot s: [cloud 0's vector (npad[0]) | cloud 1's (npad[1])]
     int nslots, b;
+    const int *len[2];  // (LEN) the per-sample counts of the two clouds (NULL: all points)
 };
+// Ragged batches (rf_approxmatch_lengths): sample bi uses the first len[bi] points of its cloud; a NULL array means all n, and a
+// device value outside [1, n] is clamped into it (rf_nn_distance_lengths' rule), so no kernel reads past the tensors.
+__device__ __forceinline__ int am_len(const int *__restrict__ len, int bi, int n) {
+    if (!len) return n;
+    const int v = len[bi];
+    return v < 1 ? 1 : (v > n ? n : v);
+}
+// the reference's multipliers (am_multipliers: multiL = am_multi(n, m), multiR = am_multi(m, n)) from a sample's own counts
+__device__ __forceinline__ float am_multi(int self, int other) { return self >= other ? 1.f : (float)(other / self); }
 constexpr int AI_TPB = 1024;
+// LEN: a sample's points beyond its count are padding like the tail behind npts -- zero coordinates in the packed copy and zero
+// in every vector slot -- and its multipliers come from its own counts
+template <bool LEN = false>
 __global__ __launch_bounds__(AI_TPB) void am_init_kernel(AmInit a) {
     const int bi = blockIdx.y, c = blockIdx.z;
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int npts = c ? a.npts[1] : a.npts[0], npad = c ? a.npad[1] : a.npad[0];
+    int nval = npts;  // the points of this sample that are real (LEN: its count)
+    if (LEN) {
+        const int l1 = am_len(a.len[0], bi, a.npts[0]), l2 = am_len(a.len[1], bi, a.npts[1]);
+        a.fill[0] = am_multi(l1, l2), a.fill[1] = am_multi(l2, l1);
+        nval = c ? l2 : l1;
+    }
     if (bi == 0 && c == 0 && j < 64) a.vec[(size_t)a.b * a.stride + j] = 0.f;  // the slack behind the last element's vectors
     if (j >= npad) return;
     float *v = a.vec + (size_t)bi * a.stride + (c ? a.npad[0] : 0) + j;
-    if (j < npts) {
+    if (j < nval) {
         const float *p = (c ? a.xyz[1] : a.xyz[0]) + ((size_t)bi * npts + j) * 3;
         float *q = (c ? a.xyzp[1] : a.xyzp[0]) + (size_t)bi * (c ? a.xyzp_stride[1] : a.xyzp_stride[0]) + (size_t)j * 3;
         q[0] = p[0]; q[1] = p[1]; q[2] = p[2];
@@ -121,7 +140,10 @@ __global__ __launch_bounds__(AI_TPB) void am_init_kernel(AmInit a) {
 // not both exactly 0 (xyz2p / ratioR_prev / remainR then point at that copy, `cstride` floats per sample; counts[bi * 4] = how
 // many, a multiple of 16 with zero-scalar padding).  A column whose scalars are +0 adds fma(e, 0, acc) = acc: leaving it out
 // changes no sum.  The live columns are cut into the workgroup's segments evenly (a device-side count: no host round trip).
-template <bool HAS_P3, int P1, int RPT, int SKIP = 0, int MASK = 0, int CMP = 0>
+// LEN (ragged batches, the dense sweeps only): rows beyond the sample's count len1 are no rows -- a workgroup with none left exits
+// at once, and the rows of the others are read only below the count -- and a segment ends at len2 rounded up to a sub-chunk: the
+// columns behind it are padding with zero scalars (am_init_kernel<true>), whose terms fma(e, +0, acc) = acc change no sum.
+template <bool HAS_P3, int P1, int RPT, int SKIP = 0, int MASK = 0, int CMP = 0, bool LEN = false>
 __global__ __launch_bounds__(1024) void am_rowk_kernel(
     int n, int seglen, const float *__restrict__ xyz1, const float *__restrict__ xyz2p,
     size_t xyz2p_stride, const float *__restrict__ ratioR_prev, const float *__restrict__ remainR,
@@ -129,8 +151,10 @@ __global__ __launch_bounds__(1024) void am_rowk_kernel(
     float *__restrict__ ratioL_out, size_t stride, float c_prev, float c_cur, const int *__restrict__ perm,
     int perm_stride, float tskip, float tskip_prev, const int *__restrict__ guard, int guard_want,
     unsigned short *__restrict__ mask = nullptr, float tmask = 0.f, const int *__restrict__ counts = nullptr,
-    size_t cstride = 0, const float *__restrict__ rowbox = nullptr) {
+    size_t cstride = 0, const float *__restrict__ rowbox = nullptr, const int *__restrict__ len1 = nullptr,
+    const int *__restrict__ len2 = nullptr) {
     static_assert(MASK == 0 || SKIP == 1, "column lists belong to the skipping sweeps");
+    static_assert(!LEN || (SKIP == 0 && CMP == 0), "ragged batches take the dense sweeps");
     static_assert(CMP == 0 || (SKIP == 0 && MASK == 0), "the live-column form is a dense sweep over a shorter column set");
     __shared__ float part3[16][64 * RPT], part1[16][64 * RPT];
     // (guard: an optional device word that switches the launch off -- unused by the current routes)
@@ -143,14 +167,16 @@ __global__ __launch_bounds__(1024) void am_rowk_kernel(
     const int seg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr bool HAS_P1 = P1 != 0;
     const int nseg = blockDim.x >> 6;
+    const int nrow = LEN ? am_len(len1, bi, n) : n;
+    if (LEN && bx * 64 * RPT >= nrow) return;  // (uniform) every row of the workgroup lies beyond the sample's count
     const float *__restrict__ A = xyz1 + (size_t)bi * n * 3;
     float x1[RPT], y1[RPT], z1[RPT], rl[RPT], rem0[RPT], acc3[RPT], acc1[RPT];
     int krow[RPT];  // the lane's rows (original indices; < 0: none)
 #pragma unroll
     for (int r = 0; r < RPT; r++) {
         const int pos = bx * 64 * RPT + r * 64 + lane;
-        krow[r] = SKIP != 0 ? (pos < perm_stride ? perm[(size_t)bi * perm_stride + pos] : -1) : (pos < n ? pos : -1);
-        const int kk = krow[r] >= 0 ? krow[r] : n - 1;
+        krow[r] = SKIP != 0 ? (pos < perm_stride ? perm[(size_t)bi * perm_stride + pos] : -1) : (pos < nrow ? pos : -1);
+        const int kk = krow[r] >= 0 ? krow[r] : nrow - 1;
         x1[r] = A[kk * 3]; y1[r] = A[kk * 3 + 1]; z1[r] = A[kk * 3 + 2];
         if (SKIP != 0 && krow[r] < 0) x1[r] = INFINITY;  // a lane without a row never keeps a column alive (d2 = inf)
         rl[r] = HAS_P3 ? ratioL_prev[(size_t)bi * stride + kk] : 0.f;
@@ -168,6 +194,7 @@ __global__ __launch_bounds__(1024) void am_rowk_kernel(
         c0 = min(seg * slen, cnt);
         c1 = min(c0 + slen, cnt);
     }
+    if (LEN) c1 = min(c1, max(c0, (am_len(len2, bi, nseg * seglen) + SUB - 1) / SUB * SUB));  // (uniform; nseg * seglen = mpad)
     // one column (its coordinates and scalars wave-uniform) against the lane's RPT rows
     // (PK: the lane's two rows as the halves of packed fp32 operations, as in am_rowl_kernel -- bit-identical sums -- together
     // with the column operands through two scalar register sets in turn: the dense fused P3 + P1 sweep 61.8 -> 47.5 us at C4, P3
@@ -437,14 +464,17 @@ __global__ __launch_bounds__(1024) void am_rowk_kernel(
 // exactly 0 (in index order, -1 behind the last; counts[bi * 4 + 1] of them).  A row with remainR = +0 has t = sumr * 0 = 0,
 // cons = min(0 / 1e-9, 1) = 0, ratioR = 0 and stays at 0 whatever its sum: the compaction writes those zeros, this launch skips
 // the rows.  Workgroups beyond the list leave at once.
-template <int RPT, bool ZERO, bool SKIP = false, int MASK = 0, bool LIST = false>
+// LEN: ragged batches, as am_rowk_kernel's (rows beyond len2, columns clipped at len1).
+template <int RPT, bool ZERO, bool SKIP = false, int MASK = 0, bool LIST = false, bool LEN = false>
 __global__ __launch_bounds__(1024) void am_rowl_kernel(
     int m, int seglen, const float *__restrict__ xyz2, const float *__restrict__ xyz1p,
     size_t xyz1p_stride, const float *__restrict__ ratioL, float *__restrict__ remainR,
     float *__restrict__ ratioR_out, size_t stride, float c_cur, const int *__restrict__ perm, int perm_stride,
     float tskip, const int *__restrict__ guard, int guard_want, unsigned short *__restrict__ mask = nullptr,
-    float tmask = 0.f, const int *__restrict__ counts = nullptr, const float *__restrict__ rowbox = nullptr) {
+    float tmask = 0.f, const int *__restrict__ counts = nullptr, const float *__restrict__ rowbox = nullptr,
+    const int *__restrict__ len1 = nullptr, const int *__restrict__ len2 = nullptr) {
     static_assert(MASK == 0 || SKIP, "column lists belong to the skipping sweeps (am_rowk_kernel MASK)");
+    static_assert(!LEN || (!SKIP && !LIST), "ragged batches take the dense sweeps");
     static_assert(!LIST || (!SKIP && MASK == 0), "the live-row form is a dense sweep over fewer rows");
     if (guard && (*guard != 0) != (guard_want != 0)) return;  // (see am_rowk_kernel)
     __shared__ float part[16][64 * RPT];
@@ -455,14 +485,16 @@ __global__ __launch_bounds__(1024) void am_rowl_kernel(
     const int seg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nseg = blockDim.x >> 6;
     if (LIST && bx * 64 * RPT >= ((const __attribute__((address_space(4))) int *)counts)[bi * 4 + 1]) return;  // (uniform)
+    const int nrow = LEN ? am_len(len2, bi, m) : m;
+    if (LEN && bx * 64 * RPT >= nrow) return;  // (uniform)
     const float *__restrict__ B = xyz2 + (size_t)bi * m * 3;
     float x2[RPT], y2[RPT], z2[RPT], rem0[RPT], acc[RPT];
     int lrow[RPT];  // the lane's rows (original indices; < 0: none); SKIP: in the cloud's spatial order (see am_rowk_kernel)
 #pragma unroll
     for (int r = 0; r < RPT; r++) {
         const int pos = bx * 64 * RPT + r * 64 + lane;
-        lrow[r] = (SKIP || LIST) ? (pos < perm_stride ? perm[(size_t)bi * perm_stride + pos] : -1) : (pos < m ? pos : -1);
-        const int ll = lrow[r] >= 0 ? lrow[r] : m - 1;
+        lrow[r] = (SKIP || LIST) ? (pos < perm_stride ? perm[(size_t)bi * perm_stride + pos] : -1) : (pos < nrow ? pos : -1);
+        const int ll = lrow[r] >= 0 ? lrow[r] : nrow - 1;
         x2[r] = B[ll * 3]; y2[r] = B[ll * 3 + 1]; z2[r] = B[ll * 3 + 2];
         if (SKIP && lrow[r] < 0) x2[r] = INFINITY;
         rem0[r] = remainR[(size_t)bi * stride + ll];  // (asked for here, used behind the sweep: am_rowk_kernel)
@@ -470,7 +502,8 @@ __global__ __launch_bounds__(1024) void am_rowl_kernel(
     }
     const float *__restrict__ C = xyz1p + (size_t)bi * xyz1p_stride;
     const float *__restrict__ S = ratioL + (size_t)bi * stride;
-    const int c0 = seg * seglen, c1 = c0 + seglen;
+    const int c0 = seg * seglen;
+    const int c1 = LEN ? min(c0 + seglen, max(c0, (am_len(len1, bi, nseg * seglen) + SUB - 1) / SUB * SUB)) : c0 + seglen;
     // PKL: the lane's two rows as the two halves of packed fp32 operations (v_pk_add / v_pk_mul / v_pk_fma: the same IEEE
     // operations in the same order -- bit-identical sums): 6 instead of 16 vector instructions per column beside the exponentials
     constexpr bool PKL = RPT == 2 && !SKIP;
@@ -1054,12 +1087,17 @@ inline bool quarter_chain(const float *c, int nlv, bool lastzero) {
     return true;
 }
 
-template <int NLV, bool LASTZERO = false, bool SQ = false>
+// LEN (ragged batches): the entries outside a sample's counts are +0, written without reading anything; a workgroup whose
+// entries all lie outside writes its zeros and nothing else.  (Zeros of am_match_kernel and am_match_any_kernel alike.)
+__device__ __forceinline__ void am_match_zeros(float *match, int n, int k, int l0, int lfrom, int lto) {
+    for (int l = lfrom; l < lto; l++) __builtin_nontemporal_store(0.f, &match[(size_t)(l0 + l) * n + k]);
+}
+template <int NLV, bool LASTZERO = false, bool SQ = false, bool LEN = false>
 __global__ __launch_bounds__(AMM_TPB) void am_match_kernel(int n, int m, const float *xyz1,
                                                        const float *xyz2, const float *ratios,
                                                        size_t lv_stride, size_t b_stride, int roff,
                                                        int lv0, int nlv, LevelConsts lc,
-                                                       float *match) {
+                                                       float *match, const int *len1 = nullptr, const int *len2 = nullptr) {
     // ratios: [b][level][ (ratioL: npad) (ratioR: mpad) ]; roff = npad
     __shared__ float cxyz[LSEG][4];
     __shared__ float crr[LSEG][LVG];
@@ -1078,11 +1116,17 @@ __global__ __launch_bounds__(AMM_TPB) void am_match_kernel(int n, int m, const f
     xyz2 += (size_t)bi * m * 3;
     ratios += (size_t)bi * b_stride + (size_t)lv0 * lv_stride;
     match += (size_t)bi * n * m;
+    const int nv = LEN ? am_len(len1, bi, n) : n;                                     // (LEN) valid columns k ...
+    const int lval = LEN ? max(0, min(lcnt, am_len(len2, bi, m) - l0)) : lcnt;  // ... and rows l of this workgroup
+    if (LEN && (bx * AMM_TPB >= nv || lval == 0)) {  // (uniform)
+        if (k < n) am_match_zeros(match, n, k, l0, 0, lcnt);
+        return;
+    }
     for (int i = threadIdx.x; i < lcnt * LVG; i += AMM_TPB) {
         int l = i / LVG, v = i % LVG;
         crr[l][v] = v < nlv ? ratios[(size_t)v * lv_stride + roff + l0 + l] : 0.f;
     }
-    for (int i = threadIdx.x; i < lcnt; i += AMM_TPB) {
+    for (int i = threadIdx.x; i < lval; i += AMM_TPB) {
         cxyz[i][0] = xyz2[(size_t)(l0 + i) * 3 + 0];
         cxyz[i][1] = xyz2[(size_t)(l0 + i) * 3 + 1];
         cxyz[i][2] = xyz2[(size_t)(l0 + i) * 3 + 2];
@@ -1096,6 +1140,11 @@ __global__ __launch_bounds__(AMM_TPB) void am_match_kernel(int n, int m, const f
     }
     __syncthreads();
     if (k >= n) return;
+    if (LEN && k >= nv) {
+        am_match_zeros(match, n, k, l0, 0, lcnt);
+        return;
+    }
+    if (LEN) am_match_zeros(match, n, k, l0, lval, lcnt);
     const float x1 = xyz1[k * 3], y1 = xyz1[k * 3 + 1], z1 = xyz1[k * 3 + 2];
     if (NLV > 0) {
         float rl[NLV > 0 ? NLV : 1], cl[NLV > 0 ? NLV : 1];
@@ -1105,7 +1154,7 @@ __global__ __launch_bounds__(AMM_TPB) void am_match_kernel(int n, int m, const f
             cl[v] = lc.c[v];
         }
         const float t0 = cl[0] < 0.f ? kSkipArg / -cl[0] : INFINITY;  // (uniform)
-        for (int l = 0; l < lcnt; l++) {
+        for (int l = 0; l < lval; l++) {
             const float d2 = rf::d2_fma(cxyz[l][0] - x1, cxyz[l][1] - y1, cxyz[l][2] - z1);
             float e[NLV > 0 ? NLV : 1];
             float acc = 0.f;
@@ -1165,11 +1214,12 @@ __global__ __launch_bounds__(AMM_TPB) void am_match_kernel(int n, int m, const f
 //     the guard is per group of four levels, wave-uniform.
 // REP > 0: a schedule that takes every multiplier REP times in a row (configs[3]: REP = 5) -- one guard, one exponential and REP
 // terms per run instead of a test per level: the branches were what the general form spent its time on (0.40 -> see below).
-template <int NG, int REP = 0>
+template <int NG, int REP = 0, bool LEN = false>
 __global__ __launch_bounds__(AMM_TPB) void am_match_any_kernel(int n, int m, const float *xyz1, const float *xyz2,
                                                                const float *ratios, size_t lv_stride, size_t b_stride,
                                                                int roff, int nlv, LevelConsts lc, unsigned long long fresh,
-                                                               float *match) {
+                                                               float *match, const int *len1 = nullptr,
+                                                               const int *len2 = nullptr) {
     constexpr int NL = LVG * NG;
     __shared__ float cxyz[LSEG][4];
     __shared__ __attribute__((aligned(16))) float crr[LSEG][NL];
@@ -1187,11 +1237,17 @@ __global__ __launch_bounds__(AMM_TPB) void am_match_any_kernel(int n, int m, con
     xyz2 += (size_t)bi * m * 3;
     ratios += (size_t)bi * b_stride;
     match += (size_t)bi * n * m;
+    const int nv = LEN ? am_len(len1, bi, n) : n;  // (LEN: see am_match_kernel)
+    const int lval = LEN ? max(0, min(lcnt, am_len(len2, bi, m) - l0)) : lcnt;
+    if (LEN && (bx * AMM_TPB >= nv || lval == 0)) {  // (uniform)
+        if (k < n) am_match_zeros(match, n, k, l0, 0, lcnt);
+        return;
+    }
     for (int i = threadIdx.x; i < lcnt * NL; i += AMM_TPB) {
         const int l = i / NL, v = i % NL;
         crr[l][v] = v < nlv ? ratios[(size_t)v * lv_stride + roff + l0 + l] : 0.f;
     }
-    for (int i = threadIdx.x; i < lcnt; i += AMM_TPB) {
+    for (int i = threadIdx.x; i < lval; i += AMM_TPB) {
         cxyz[i][0] = xyz2[(size_t)(l0 + i) * 3 + 0];
         cxyz[i][1] = xyz2[(size_t)(l0 + i) * 3 + 1];
         cxyz[i][2] = xyz2[(size_t)(l0 + i) * 3 + 2];
@@ -1204,11 +1260,16 @@ __global__ __launch_bounds__(AMM_TPB) void am_match_any_kernel(int n, int m, con
     }
     __syncthreads();
     if (k >= n) return;
+    if (LEN && k >= nv) {
+        am_match_zeros(match, n, k, l0, 0, lcnt);
+        return;
+    }
+    if (LEN) am_match_zeros(match, n, k, l0, lval, lcnt);
     const float x1 = xyz1[k * 3], y1 = xyz1[k * 3 + 1], z1 = xyz1[k * 3 + 2];
     float rl[NL];
 #pragma unroll
     for (int v = 0; v < NL; v++) rl[v] = v < nlv ? ratios[(size_t)v * lv_stride + k] : 0.f;
-    for (int l = 0; l < lcnt; l++) {
+    for (int l = 0; l < lval; l++) {
         const float d2 = rf::d2_fma(cxyz[l][0] - x1, cxyz[l][1] - y1, cxyz[l][2] - z1);
         const int last = min(cdl[l], nlv - 1);  // (uniform)
         float acc = 0.f, e = 0.f;
@@ -1249,25 +1310,34 @@ __global__ __launch_bounds__(AMM_TPB) void am_match_any_kernel(int n, int m, con
 // the reference's block (tf_approxmatch.cu:13-178) -- and, summing each row strictly in index
 // order, with exactly the reference's summation order.
 constexpr int AM_SMALL = 256;
+// LEN (ragged batches): the schedule runs on the sample's own counts -- the loops end at them, the multipliers come from them --
+// so its sums are those of a call on the unpadded slices, term for term; the entries of `match` outside the counts are +0.
+template <bool LEN = false>
 __global__ __launch_bounds__(AM_SMALL) void am_small_kernel(int n, int m, int nlevels, LevelConsts lc,
                                                             float multiL, float multiR,
                                                             const float *__restrict__ xyz1,
                                                             const float *__restrict__ xyz2,
-                                                            float *__restrict__ match) {
+                                                            float *__restrict__ match, const int *__restrict__ len1 = nullptr,
+                                                            const int *__restrict__ len2 = nullptr) {
     // columns are float4 {x,y,z,scalar}: one broadcast ds_read_b128 per column; the scalar slot is
     // rewritten by the owning thread before each phase (remainR / ratioL / ratioR of the level)
     __shared__ float4 c1[AM_SMALL], c2[AM_SMALL];
     __shared__ float ratL[MAX_LEVELS][AM_SMALL], ratR[MAX_LEVELS][AM_SMALL];  // 128 KiB
     const int bi = blockIdx.x, t = threadIdx.x;
+    const int ns = n, ms = m;  // the tensors' widths (strides)
+    if (LEN) {
+        n = am_len(len1, bi, ns), m = am_len(len2, bi, ms);
+        multiL = am_multi(n, m), multiR = am_multi(m, n);
+    }
     float x1 = 0.f, y1 = 0.f, z1 = 0.f, x2 = 0.f, y2 = 0.f, z2 = 0.f;
     float remL = multiL, remR = multiR;
     if (t < n) {
-        const float *p = xyz1 + ((size_t)bi * n + t) * 3;
+        const float *p = xyz1 + ((size_t)bi * ns + t) * 3;
         x1 = p[0]; y1 = p[1]; z1 = p[2];
         c1[t] = make_float4(x1, y1, z1, 0.f);
     }
     if (t < m) {
-        const float *p = xyz2 + ((size_t)bi * m + t) * 3;
+        const float *p = xyz2 + ((size_t)bi * ms + t) * 3;
         x2 = p[0]; y2 = p[1]; z2 = p[2];
         c2[t] = make_float4(x2, y2, z2, remR);
     }
@@ -1318,23 +1388,31 @@ __global__ __launch_bounds__(AM_SMALL) void am_small_kernel(int n, int m, int nl
         }
     }
     if (t < n) {  // match[l][k] = level-ordered fma chain, as am_match_kernel
-        float *M = match + (size_t)bi * n * m;
+        float *M = match + (size_t)bi * ns * ms;
         for (int l = 0; l < m; l++) {
             const float4 q = c2[l];
             const float d2 = rf::d2_fma(q.x - x1, q.y - y1, q.z - z1);
             float acc = 0.f;
             for (int v = 0; v < nlevels; v++) acc = fmaf(ratL[v][t] * fast_exp2(d2 * lc.c[v]), ratR[v][l], acc);
-            M[(size_t)l * n + t] = acc;
+            M[(size_t)l * ns + t] = acc;
         }
+        if (LEN)
+            for (int l = m; l < ms; l++) M[(size_t)l * ns + t] = 0.f;
+    } else if (LEN && t < ns) {
+        float *M = match + (size_t)bi * ns * ms;
+        for (int l = 0; l < ms; l++) M[(size_t)l * ns + t] = 0.f;
     }
 }
 
 // ---- match_cost: cost[i] = sum_{l,k} match[l][k] * sqrt(d2(k,l)); HBM-bound stream of match.
 // workgroup = 256 k x MC_L l; per-workgroup partial -> workspace; fixed-order final sum.
 constexpr int MC_L = 32;
+// LEN (ragged batches): only the pairs inside the sample's counts are read and summed -- the padding of the clouds and of `match`
+// is never loaded -- and a workgroup without such a pair writes a partial of +0 (mc_final_kernel's sum keeps its bits).
+template <bool LEN = false>
 __global__ __launch_bounds__(TPB) void mc_partial_kernel(int n, int m, const float *xyz1,
                                                          const float *xyz2, const float *match,
-                                                         float *partial) {
+                                                         float *partial, const int *len1 = nullptr, const int *len2 = nullptr) {
     __shared__ float cxyz[MC_L][4];
     __shared__ float wsum[TPB / 64];
     // The batch elements LAST first, and of each its rows last first: match_cost follows approx_match, whose am_match wrote `match`
@@ -1344,7 +1422,13 @@ __global__ __launch_bounds__(TPB) void mc_partial_kernel(int n, int m, const flo
     const int bi = gridDim.z - 1 - blockIdx.z;
     const int l0 = (gridDim.y - 1 - blockIdx.y) * MC_L;
     const int k = blockIdx.x * TPB + threadIdx.x;
-    const int lcnt = min(MC_L, m - l0);
+    const int lcnt0 = min(MC_L, m - l0);
+    const int nv = LEN ? am_len(len1, bi, n) : n;
+    const int lcnt = LEN ? max(0, min(lcnt0, am_len(len2, bi, m) - l0)) : lcnt0;
+    if (LEN && (blockIdx.x * TPB >= nv || lcnt == 0)) {  // (uniform)
+        if (threadIdx.x == 0) partial[((size_t)bi * gridDim.y + l0 / MC_L) * gridDim.x + blockIdx.x] = 0.f;
+        return;
+    }
     xyz1 += (size_t)bi * n * 3;
     xyz2 += (size_t)bi * m * 3;
     match += (size_t)bi * n * m;
@@ -1355,7 +1439,7 @@ __global__ __launch_bounds__(TPB) void mc_partial_kernel(int n, int m, const flo
     }
     __syncthreads();
     float sum = 0.f;
-    if (k < n) {
+    if (k < nv) {
         const float x1 = xyz1[k * 3], y1 = xyz1[k * 3 + 1], z1 = xyz1[k * 3 + 2];
 #pragma unroll 8
         for (int l = 0; l < lcnt; l++) {
@@ -1418,12 +1502,17 @@ __global__ void mc_final_kernel(const float *partial, int per_batch, float *cost
 #define RFA_MG_LOAD(p) __builtin_nontemporal_load(p)  // (`match` is read once: see mr_load_row)
 constexpr int MG_TL = 32;
 constexpr int MG_LSPLIT = RFA_MG_LSPLIT;
+// LEN (ragged batches): the sample's counts stand in for n and m -- the lanes beyond len1 are dead lanes (reading the last valid
+// column of `match`, as the dead lanes beyond n read the last one), the l-range ends at len2 -- so no padded coordinate or entry
+// of `match` is ever loaded; a workgroup entirely beyond a count leaves at once (the outputs are zero-filled first).
+template <bool LEN = false>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4))) void mcg_kernel(int n, int m, int lspan,
                                                   const float *__restrict__ xyz1,
                                                   const float *__restrict__ xyz2,
                                                   const float *__restrict__ match,
                                                   float *__restrict__ grad1,
-                                                  float *__restrict__ grad2) {
+                                                  float *__restrict__ grad2, const int *__restrict__ len1 = nullptr,
+                                                  const int *__restrict__ len2 = nullptr) {
     __shared__ float qs[MG_TL][TPB + 1];
     __shared__ float4 sx1[TPB];
     __shared__ float ps[TPB / MG_TL][MG_TL][3];
@@ -1431,8 +1520,10 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int t = threadIdx.x;
     const int k0 = blockIdx.x * TPB;
     const int k = k0 + t;
-    const bool live = k < n;
-    const int kk = live ? k : n - 1;
+    const int nv = LEN ? am_len(len1, bi, n) : n, mcnt = LEN ? am_len(len2, bi, m) : m;
+    if (LEN && (k0 >= nv || blockIdx.y * lspan >= mcnt)) return;  // (uniform)
+    const bool live = k < nv;
+    const int kk = live ? k : nv - 1;
     const float *__restrict__ A = xyz1 + (size_t)bi * n * 3;
     const float *__restrict__ B = xyz2 + (size_t)bi * m * 3;
     const float *__restrict__ M = match + (size_t)bi * n * m;
@@ -1441,7 +1532,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const float x1a = live ? x1 : INFINITY;  // (phase A only: a dead lane's q = match * rsq(inf) = 0)
     float ax = 0.f, ay = 0.f, az = 0.f;
     const int lbeg = blockIdx.y * lspan;
-    const int lend = min(m, lbeg + lspan);
+    const int lend = min(mcnt, lbeg + lspan);
     const int bl = t & (MG_TL - 1);  // phase-B row (l) of this thread
     const int br = t / MG_TL;        // phase-B k slice: [br*32, br*32+32)
     const unsigned koff = (unsigned)kk * 4u;
@@ -1449,7 +1540,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // flight, as inside the loop -- the wait at the loop head then lets the rows stay in flight)
     float cxv, cyv, czv;
     {
-        const int ll = min(lbeg + (t & (MG_TL - 1)), m - 1);
+        const int ll = min(lbeg + (t & (MG_TL - 1)), mcnt - 1);
         cxv = B[ll * 3];
         cyv = B[ll * 3 + 1];
         czv = B[ll * 3 + 2];
@@ -1464,7 +1555,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         // the next tile's column records first: they are the oldest loads in flight when the next phase A needs them
         float cxn, cyn, czn;
         {
-            const int ll = min(l0 + MG_TL + (t & (MG_TL - 1)), m - 1);
+            const int ll = min(l0 + MG_TL + (t & (MG_TL - 1)), mcnt - 1);
             cxn = B[ll * 3];
             cyn = B[ll * 3 + 1];
             czn = B[ll * 3 + 2];
@@ -1771,16 +1862,19 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // the column operands (x2_l and the 10 ratioR values of l) are wave-uniform and come from one
 // 64-byte record per l by scalar loads.
 constexpr int EF_REC = 16;  // floats per column record: x y z 0 | ratioR[0..NLV) | 0 ..
+// LEN (ragged batches): the columns beyond the sample's count len2 get all-zero records like those beyond m
+template <bool LEN = false>
 __global__ void emd_pack_cols_kernel(int m, int mpad, int nlv, const float *__restrict__ xyz2,
                                      const float *__restrict__ ratios, size_t lv_stride,
-                                     size_t b_stride, int roff, float *__restrict__ rec, int pairs) {
+                                     size_t b_stride, int roff, float *__restrict__ rec, int pairs,
+                                     const int *__restrict__ len2 = nullptr) {
     const int bi = blockIdx.y;
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= mpad) return;
     float r[EF_REC];
 #pragma unroll
     for (int i = 0; i < EF_REC; i++) r[i] = 0.f;
-    if (l < m) {
+    if (l < (LEN ? am_len(len2, bi, m) : m)) {
         const float *p = xyz2 + ((size_t)bi * m + l) * 3;
         r[0] = p[0]; r[1] = p[1]; r[2] = p[2];
         for (int v = 0; v < nlv; v++) r[4 + v] = ratios[(size_t)bi * b_stride + (size_t)v * lv_stride + roff + l];
@@ -1796,7 +1890,10 @@ __global__ void emd_pack_cols_kernel(int m, int mpad, int nlv, const float *__re
     for (int i = 0; i < EF_REC / 4; i++) q[i] = make_float4(r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]);
 }
 
-template <int NLV, bool GRAD, bool LASTZERO, bool SQ>
+// LEN (ragged batches): the lanes beyond the sample's count len1 are dead lanes (ratioL 0: every entry +0), the column range
+// ends at len2 rounded up to a tile (the records behind len2 are all zero: entries +0, terms +0), and a workgroup without a
+// valid pair writes a partial of +0 and leaves; no padded coordinate is read.
+template <int NLV, bool GRAD, bool LASTZERO, bool SQ, bool LEN = false>
 __global__ __launch_bounds__(TPB) void emd_fused_kernel(int n, int m, int mpad, int lspan,
                                                         const float *__restrict__ xyz1,
                                                         const float *__restrict__ rec,
@@ -1804,7 +1901,8 @@ __global__ __launch_bounds__(TPB) void emd_fused_kernel(int n, int m, int mpad, 
                                                         size_t lv_stride, size_t b_stride,
                                                         LevelConsts lc, float *__restrict__ partial,
                                                         float *__restrict__ grad1,
-                                                        float *__restrict__ grad2) {
+                                                        float *__restrict__ grad2, const int *__restrict__ len1 = nullptr,
+                                                        const int *__restrict__ len2 = nullptr) {
     static_assert(NLV + 4 <= EF_REC, "column record too small");
     __shared__ float qs[GRAD ? MG_TL : 1][TPB + 1];
     __shared__ float4 sx1[GRAD ? TPB : 1];
@@ -1818,8 +1916,13 @@ __global__ __launch_bounds__(TPB) void emd_fused_kernel(int n, int m, int mpad, 
     const int by = (lgc_ - bi * per_) / gridDim.x, bx = (lgc_ - bi * per_) - by * gridDim.x;
     const int t = threadIdx.x;
     const int k = bx * TPB + t;
-    const bool live = k < n;
-    const int kk = live ? k : n - 1;
+    const int nv = LEN ? am_len(len1, bi, n) : n, mv = LEN ? am_len(len2, bi, m) : m;
+    if (LEN && (bx * TPB >= nv || by * lspan >= mv)) {  // (uniform)
+        if (t == 0) partial[((size_t)bi * gridDim.y + by) * gridDim.x + bx] = 0.f;
+        return;
+    }
+    const bool live = k < nv;
+    const int kk = live ? k : nv - 1;
     const float *__restrict__ A = xyz1 + (size_t)bi * n * 3;
     const float *__restrict__ R = rec + (size_t)bi * mpad * EF_REC;
     const float x1 = A[kk * 3], y1 = A[kk * 3 + 1], z1 = A[kk * 3 + 2];
@@ -1833,7 +1936,7 @@ __global__ __launch_bounds__(TPB) void emd_fused_kernel(int n, int m, int mpad, 
     if (GRAD) sx1[t] = make_float4(x1, y1, z1, 0.f);
     float ax = 0.f, ay = 0.f, az = 0.f, csum = 0.f;
     const int lbeg = by * lspan;
-    const int lend = min(mpad, lbeg + lspan);  // multiples of MG_TL; records beyond m are zero
+    const int lend = min(LEN ? (mv + MG_TL - 1) / MG_TL * MG_TL : mpad, lbeg + lspan);  // multiples of MG_TL; records beyond m are zero
     const int bl = t & (MG_TL - 1);
     const int br = t / MG_TL;
     if constexpr (!GRAD) {
@@ -1924,7 +2027,7 @@ __global__ __launch_bounds__(TPB) void emd_fused_kernel(int n, int m, int mpad, 
             __syncthreads();
             if (t < MG_TL * 3) {
                 const int l = t / 3, c = t - l * 3;
-                if (l0 + l < m) {
+                if (l0 + l < mv) {
                     float v = 0.f;
 #pragma unroll
                     for (int r = 0; r < TPB / MG_TL; r++) v += ps[r][l][c];
@@ -2297,9 +2400,12 @@ void am_multipliers(int n, int m, float &multiL, float &multiR) {
 // The level pipeline (P1 / P2 / fused P3+P1 launches) of the large-cloud path: fills the
 // workspace's per-level ratio vectors.  Shared by rf_approxmatch_levels (which then materialises
 // match) and rf_earth_mover (which does not).
+// LEN (ragged batches, rf_approxmatch_lengths; the caller pins mode = RF_EMD_SWEPT): the count-aware forms of am_init and of the
+// dense sweeps, which are all that route launches; the multipliers come from each sample's counts on the device.
+template <bool LEN = false>
 int am_run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, int nlevels,
                   const LevelConsts &lc, float multiL, float multiR, void *workspace, hipStream_t s,
-                  int mode = RF_EMD_AUTO) {
+                  int mode = RF_EMD_AUTO, const int *len1 = nullptr, const int *len2 = nullptr) {
     AmLayout L = am_layout(b, n, m, nlevels, mode);
     float *w = (float *)workspace;
     float *remainL = w, *remainR = w + L.npad;          // slot 0 of the vector region
@@ -2323,7 +2429,8 @@ int am_run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, int
         ai.xyz[0] = xyz1, ai.xyz[1] = xyz2, ai.xyzp[0] = x1p, ai.xyzp[1] = x2p;
         ai.xyzp_stride[0] = (size_t)L.npad * 3, ai.xyzp_stride[1] = (size_t)L.mpad * 3;
         ai.vec = w, ai.stride = L.bstride, ai.V = L.V, ai.nslots = 1 + nlevels, ai.b = b;
-        RF_LAUNCH("am_init", am_init_kernel, dim3(rf::ceil_div(max(L.npad, L.mpad), AI_TPB), b, 2), dim3(AI_TPB), 0, s, ai);
+        ai.len[0] = len1, ai.len[1] = len2;
+        RF_LAUNCH("am_init", am_init_kernel<LEN>, dim3(rf::ceil_div(max(L.npad, L.mpad), AI_TPB), b, 2), dim3(AI_TPB), 0, s, ai);
     }
 
     // the sharp levels that stay on the dense sweeps: rows in the clouds' spatial order, columns with all-zero weights skipped
@@ -2422,26 +2529,28 @@ int am_run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, int
             const float *pL = ratios + (size_t)(v - 1) * L.V, *pR = pL + L.npad;
             RF_LAUNCH("am_p3p1", (am_rowk_kernel<true, 1, RPT, 1>), gks, dim3(64 * segk), 0, s,
                       AM_ROWK_ARGS(pR, pL, lc.c[v - 1]));
-        } else if (v == 0) {
+        } else if (v == 0) {  // (the dense sweeps: LEN takes their count-aware forms, AM_ROWK_LEN their counts)
+#define AM_ROWK_LEN (unsigned short *)nullptr, 0.f, (const int *)nullptr, (size_t)0, (const float *)nullptr, len1, len2
             if (zero) {
-                RF_LAUNCH("am_p1", (am_rowk_kernel<false, 2, RPT>), gk, dim3(64 * segk), 0, s,
-                          AM_ROWK_ARGS((const float *)remainR, (const float *)remainL, 0.f));
+                RF_LAUNCH("am_p1", (am_rowk_kernel<false, 2, RPT, 0, 0, 0, LEN>), gk, dim3(64 * segk), 0, s,
+                          AM_ROWK_ARGS((const float *)remainR, (const float *)remainL, 0.f), AM_ROWK_LEN);
             } else {
-                RF_LAUNCH("am_p1", (am_rowk_kernel<false, 1, RPT>), gk, dim3(64 * segk), 0, s,
-                          AM_ROWK_ARGS((const float *)remainR, (const float *)remainL, 0.f));
+                RF_LAUNCH("am_p1", (am_rowk_kernel<false, 1, RPT, 0, 0, 0, LEN>), gk, dim3(64 * segk), 0, s,
+                          AM_ROWK_ARGS((const float *)remainR, (const float *)remainL, 0.f), AM_ROWK_LEN);
             }
         } else {
             const float *pL = ratios + (size_t)(v - 1) * L.V, *pR = pL + L.npad;
             if (zero) {
-                RF_LAUNCH("am_p3p1", (am_rowk_kernel<true, 2, RPT>), gk, dim3(64 * segk), 0, s,
-                          AM_ROWK_ARGS(pR, pL, lc.c[v - 1]));
+                RF_LAUNCH("am_p3p1", (am_rowk_kernel<true, 2, RPT, 0, 0, 0, LEN>), gk, dim3(64 * segk), 0, s,
+                          AM_ROWK_ARGS(pR, pL, lc.c[v - 1]), AM_ROWK_LEN);
             } else if (lc.c[v - 1] == lc.c[v]) {
-                RF_LAUNCH("am_p3p1", (am_rowk_kernel<true, 3, RPT>), gk, dim3(64 * segk), 0, s,
-                          AM_ROWK_ARGS(pR, pL, lc.c[v - 1]));
+                RF_LAUNCH("am_p3p1", (am_rowk_kernel<true, 3, RPT, 0, 0, 0, LEN>), gk, dim3(64 * segk), 0, s,
+                          AM_ROWK_ARGS(pR, pL, lc.c[v - 1]), AM_ROWK_LEN);
             } else {
-                RF_LAUNCH("am_p3p1", (am_rowk_kernel<true, 1, RPT>), gk, dim3(64 * segk), 0, s,
-                          AM_ROWK_ARGS(pR, pL, lc.c[v - 1]));
+                RF_LAUNCH("am_p3p1", (am_rowk_kernel<true, 1, RPT, 0, 0, 0, LEN>), gk, dim3(64 * segk), 0, s,
+                          AM_ROWK_ARGS(pR, pL, lc.c[v - 1]), AM_ROWK_LEN);
             }
+#undef AM_ROWK_LEN
         }
 #undef AM_ROWK_ARGS
         if (live) {
@@ -2463,9 +2572,10 @@ int am_run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, int
 #undef AM_P2_LIVE
         } else
         if (zero) {
-            RF_LAUNCH("am_p2", (am_rowl_kernel<RPT, true>), gl, dim3(64 * segl), 0, s, m, L.npad / segl, xyz2,
+            RF_LAUNCH("am_p2", (am_rowl_kernel<RPT, true, false, 0, false, LEN>), gl, dim3(64 * segl), 0, s, m, L.npad / segl, xyz2,
                       (const float *)x1p, (size_t)L.npad * 3, (const float *)ratioL, remainR, ratioR,
-                      L.bstride, lc.c[v], permB, L.nsb, tsk, gptr, 1);
+                      L.bstride, lc.c[v], permB, L.nsb, tsk, gptr, 1, (unsigned short *)nullptr, 0.f, (const int *)nullptr,
+                      (const float *)nullptr, len1, len2);
         } else if (permB && tsk <= kSkipMaxT && masked && v < vE) {
             if (v == 0) {
                 RF_LAUNCH("am_p2", (am_rowl_kernel<RPT, false, true, 1>), gls, dim3(64 * segl), 0, s, m, L.npad / segl, xyz2,
@@ -2481,12 +2591,77 @@ int am_run_levels(int b, int n, int m, const float *xyz1, const float *xyz2, int
                       (const float *)x1p, (size_t)L.npad * 3, (const float *)ratioL, remainR, ratioR,
                       L.bstride, lc.c[v], permB, L.nsb, tsk, gptr, 1);
         } else {
-            RF_LAUNCH("am_p2", (am_rowl_kernel<RPT, false>), gl, dim3(64 * segl), 0, s, m, L.npad / segl, xyz2,
+            RF_LAUNCH("am_p2", (am_rowl_kernel<RPT, false, false, 0, false, LEN>), gl, dim3(64 * segl), 0, s, m, L.npad / segl, xyz2,
                       (const float *)x1p, (size_t)L.npad * 3, (const float *)ratioL, remainR, ratioR,
-                      L.bstride, lc.c[v], permB, L.nsb, tsk, gptr, 1);
+                      L.bstride, lc.c[v], permB, L.nsb, tsk, gptr, 1, (unsigned short *)nullptr, 0.f, (const int *)nullptr,
+                      (const float *)nullptr, len1, len2);
         }
         if (compact && v + 1 == vC)  // the first two packed sets (from here on every P2 packs the next one itself)
             if (int e = pack_live(v, ratioR)) return e;
+    }
+    return RF_OK;
+}
+
+// approx_match after its argument checks: the small-cloud kernel or the level pipeline, then `match`.  LEN: the ragged form
+// (rf_approxmatch_lengths, mode = RF_EMD_SWEPT): the count-aware instantiations of the same launches.
+template <bool LEN>
+int am_approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match, const float *levels_host,
+                   int nlevels, void *workspace, hipStream_t s, int mode, const int *len1, const int *len2) {
+    float multiL, multiR;  // (LEN: per sample, from the counts, on the device)
+    am_multipliers(n, m, multiL, multiR);
+
+    if (n <= AM_SMALL && m <= AM_SMALL) {
+        LevelConsts lcs;
+        for (int v = 0; v < MAX_LEVELS; v++) lcs.c[v] = v < nlevels ? levels_host[v] * kLog2e : 0.f;
+        RF_LAUNCH("am_small", am_small_kernel<LEN>, dim3(b), dim3(AM_SMALL), 0, s, n, m, nlevels, lcs, multiL,
+                  multiR, xyz1, xyz2, match, len1, len2);
+        return RF_OK;
+    }
+    LevelConsts lc;
+    for (int v = 0; v < MAX_LEVELS; v++) lc.c[v] = v < nlevels ? levels_host[v] * kLog2e : 0.f;
+    {
+        const int st = am_run_levels<LEN>(b, n, m, xyz1, xyz2, nlevels, lc, multiL, multiR, workspace, s, mode, len1, len2);
+        if (st != RF_OK) return st;
+    }
+    const AmLayout L = am_layout(b, n, m, nlevels, mode);
+    const float *ratios = (const float *)workspace + L.V;
+    // P3 of the last level only updates remainL, which nothing reads afterwards: not launched.
+    const dim3 gm(rf::ceil_div(n, AMM_TPB), rf::ceil_div(m, LSEG), b);
+    if (nlevels == 10 && lc.c[9] == 0.0f && quarter_chain(lc.c, 10, true)) {  // the reference schedule
+        RF_LAUNCH("am_match", (am_match_kernel<10, true, true, LEN>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2,
+                  (const float *)ratios, L.V, L.bstride, L.npad, 0, 10, lc, match, len1, len2);
+    } else if (nlevels == 10 && lc.c[9] == 0.0f) {
+        RF_LAUNCH("am_match", (am_match_kernel<10, true, false, LEN>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2,
+                  (const float *)ratios, L.V, L.bstride, L.npad, 0, 10, lc, match, len1, len2);
+    } else if (nlevels == 10) {
+        RF_LAUNCH("am_match", (am_match_kernel<10, false, false, LEN>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2,
+                  (const float *)ratios, L.V, L.bstride, L.npad, 0, 10, lc, match, len1, len2);
+    } else {  // any other schedule: every level in one pass (am_match_any_kernel)
+#define AM_MATCH_ANY(NG)                                                                                              \
+    RF_LAUNCH("am_match", (am_match_any_kernel<NG, 0, LEN>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2, (const float *)ratios, \
+              L.V, L.bstride, L.npad, nlevels, lc, fresh, match, len1, len2)
+        unsigned long long fresh = 1ull;  // bit v: level v's multiplier differs from level v - 1's (a new exponential)
+        for (int v = 1; v < nlevels; v++) fresh |= (lc.c[v] != lc.c[v - 1]) ? 1ull << v : 0ull;
+        static_assert(MAX_LEVELS == 4 * LVG, "the four instantiations below cover every admissible schedule");
+        int rep = 0;  // every multiplier exactly `rep` times in a row?
+        for (int r = 2; r <= 8 && !rep; r++) {
+            bool ok = nlevels % r == 0;
+            for (int v = 0; ok && v < nlevels; v++) ok = ((fresh >> v & 1ull) != 0ull) == (v % r == 0);
+            if (ok) rep = r;
+        }
+        if (rep == 5 && nlevels <= 60) {  // (BASELINE configs[3])
+            RF_LAUNCH("am_match", (am_match_any_kernel<4, 5, LEN>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2, (const float *)ratios,
+                      L.V, L.bstride, L.npad, nlevels, lc, fresh, match, len1, len2);
+        } else if (nlevels <= LVG) {
+            AM_MATCH_ANY(1);
+        } else if (nlevels <= 2 * LVG) {
+            AM_MATCH_ANY(2);
+        } else if (nlevels <= 3 * LVG) {
+            AM_MATCH_ANY(3);
+        } else {
+            AM_MATCH_ANY(4);
+        }
+#undef AM_MATCH_ANY
     }
     return RF_OK;
 }
@@ -2534,64 +2709,8 @@ int rf_approxmatch_mode(int b, int n, int m, const float *xyz1, const float *xyz
     if (b == 0 || n == 0 || m == 0) return RF_OK;
     if (!xyz1 || !xyz2 || !match || !workspace || !rf::aligned16(workspace)) return RF_EINVAL;
     if (workspace_bytes < rf_approxmatch_mode_workspace_bytes(b, n, m, nlevels, mode)) return RF_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float multiL, multiR;
-    am_multipliers(n, m, multiL, multiR);
-
-    if (n <= AM_SMALL && m <= AM_SMALL) {
-        LevelConsts lcs;
-        for (int v = 0; v < MAX_LEVELS; v++) lcs.c[v] = v < nlevels ? levels_host[v] * kLog2e : 0.f;
-        RF_LAUNCH("am_small", am_small_kernel, dim3(b), dim3(AM_SMALL), 0, s, n, m, nlevels, lcs, multiL,
-                  multiR, xyz1, xyz2, match);
-        return RF_OK;
-    }
-    LevelConsts lc;
-    for (int v = 0; v < MAX_LEVELS; v++) lc.c[v] = v < nlevels ? levels_host[v] * kLog2e : 0.f;
-    {
-        const int st = am_run_levels(b, n, m, xyz1, xyz2, nlevels, lc, multiL, multiR, workspace, s, mode);
-        if (st != RF_OK) return st;
-    }
-    const AmLayout L = am_layout(b, n, m, nlevels, mode);
-    const float *ratios = (const float *)workspace + L.V;
-    // P3 of the last level only updates remainL, which nothing reads afterwards: not launched.
-    const dim3 gm(rf::ceil_div(n, AMM_TPB), rf::ceil_div(m, LSEG), b);
-    if (nlevels == 10 && lc.c[9] == 0.0f && quarter_chain(lc.c, 10, true)) {  // the reference schedule
-        RF_LAUNCH("am_match", (am_match_kernel<10, true, true>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2,
-                  (const float *)ratios, L.V, L.bstride, L.npad, 0, 10, lc, match);
-    } else if (nlevels == 10 && lc.c[9] == 0.0f) {
-        RF_LAUNCH("am_match", (am_match_kernel<10, true>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2,
-                  (const float *)ratios, L.V, L.bstride, L.npad, 0, 10, lc, match);
-    } else if (nlevels == 10) {
-        RF_LAUNCH("am_match", (am_match_kernel<10, false>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2,
-                  (const float *)ratios, L.V, L.bstride, L.npad, 0, 10, lc, match);
-    } else {  // any other schedule: every level in one pass (am_match_any_kernel)
-#define AM_MATCH_ANY(NG)                                                                                              \
-    RF_LAUNCH("am_match", (am_match_any_kernel<NG>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2, (const float *)ratios, \
-              L.V, L.bstride, L.npad, nlevels, lc, fresh, match)
-        unsigned long long fresh = 1ull;  // bit v: level v's multiplier differs from level v - 1's (a new exponential)
-        for (int v = 1; v < nlevels; v++) fresh |= (lc.c[v] != lc.c[v - 1]) ? 1ull << v : 0ull;
-        static_assert(MAX_LEVELS == 4 * LVG, "the four instantiations below cover every admissible schedule");
-        int rep = 0;  // every multiplier exactly `rep` times in a row?
-        for (int r = 2; r <= 8 && !rep; r++) {
-            bool ok = nlevels % r == 0;
-            for (int v = 0; ok && v < nlevels; v++) ok = ((fresh >> v & 1ull) != 0ull) == (v % r == 0);
-            if (ok) rep = r;
-        }
-        if (rep == 5 && nlevels <= 60) {  // (BASELINE configs[3])
-            RF_LAUNCH("am_match", (am_match_any_kernel<4, 5>), gm, dim3(AMM_TPB), 0, s, n, m, xyz1, xyz2, (const float *)ratios,
-                      L.V, L.bstride, L.npad, nlevels, lc, fresh, match);
-        } else if (nlevels <= LVG) {
-            AM_MATCH_ANY(1);
-        } else if (nlevels <= 2 * LVG) {
-            AM_MATCH_ANY(2);
-        } else if (nlevels <= 3 * LVG) {
-            AM_MATCH_ANY(3);
-        } else {
-            AM_MATCH_ANY(4);
-        }
-#undef AM_MATCH_ANY
-    }
-    return RF_OK;
+    return am_approxmatch<false>(b, n, m, xyz1, xyz2, match, levels_host, nlevels, workspace, (hipStream_t)stream, mode, nullptr,
+                                 nullptr);
 }
 
 int rf_approxmatch(int b, int n, int m, const float *xyz1, const float *xyz2, float *match,
@@ -2607,6 +2726,38 @@ size_t rf_matchcost_workspace_bytes(int b, int n, int m) {
     return (size_t)b * rf::ceil_div(n, TPB) * rf::ceil_div(m, MC_L) * sizeof(float);
 }
 
+}  // extern "C"
+
+namespace {
+// match_cost's two launches; LEN: the count-aware partial sums (mc_partial_kernel<true>) -- mc_final_kernel sums the partials of
+// every workgroup either way, and those of workgroups outside the counts are +0
+template <bool LEN>
+int mc_launch(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *cost, void *workspace,
+              hipStream_t s, const int *len1, const int *len2) {
+    dim3 g(rf::ceil_div(n, TPB), rf::ceil_div(m, MC_L), b);
+    RF_LAUNCH("mc_partial", mc_partial_kernel<LEN>, g, dim3(TPB), 0, s, n, m, xyz1, xyz2, match, (float *)workspace, len1, len2);
+    RF_LAUNCH("mc_final", mc_final_kernel, dim3(b), dim3(256), 0, s, (const float *)workspace, (int)(g.x * g.y), cost);
+    return RF_OK;
+}
+
+// the tile form of the gradient pass (mcg_kernel; outputs zero-filled by the caller).  LEN: its count-aware form, which every
+// ragged call takes (the whole-row mcg_rows_kernel stays count-unaware)
+template <bool LEN>
+int mcg_tile_launch(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match, float *grad1, float *grad2,
+                    hipStream_t s, const int *len1, const int *len2) {
+    int lsplit = MG_LSPLIT;
+    while (lsplit > 1 && m / lsplit < MG_TL) lsplit /= 2;
+    const int lspan = rf::ceil_div(rf::ceil_div(m, lsplit), MG_TL) * MG_TL;
+    dim3 g(rf::ceil_div(n, TPB), rf::ceil_div(m, lspan), b);
+    RF_LAUNCH("mc_grad", mcg_kernel<LEN>, g, dim3(TPB), 0, s, n, m, lspan, xyz1, xyz2, match, grad1, grad2, len1, len2);
+    return RF_OK;
+}
+
+bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+}  // namespace
+
+extern "C" {
+
 int rf_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, const float *match,
                  float *cost, void *workspace, size_t workspace_bytes, rf_stream_t stream) {
     if (b < 0 || b > MAX_BATCH || n < 0 || m < 0) return RF_EINVAL;
@@ -2618,12 +2769,7 @@ int rf_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, cons
     }
     if (!xyz1 || !xyz2 || !match || !cost || !workspace) return RF_EINVAL;
     if (workspace_bytes < rf_matchcost_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
-    dim3 g(rf::ceil_div(n, TPB), rf::ceil_div(m, MC_L), b);
-    RF_LAUNCH("mc_partial", mc_partial_kernel, g, dim3(TPB), 0, s, n, m, xyz1, xyz2, match,
-              (float *)workspace);
-    RF_LAUNCH("mc_final", mc_final_kernel, dim3(b), dim3(256), 0, s, (const float *)workspace,
-              (int)(g.x * g.y), cost);
-    return RF_OK;
+    return mc_launch<false>(b, n, m, xyz1, xyz2, match, cost, workspace, s, nullptr, nullptr);
 }
 
 // The gradient pass over `match` (outputs zero-filled by the caller): whole rows per workgroup where the layout allows it.
@@ -2647,12 +2793,7 @@ static int mcg_launch(int b, int n, int m, const float *xyz1, const float *xyz2,
         }
         return RF_OK;
     }
-    int lsplit = MG_LSPLIT;
-    while (lsplit > 1 && m / lsplit < MG_TL) lsplit /= 2;
-    const int lspan = rf::ceil_div(rf::ceil_div(m, lsplit), MG_TL) * MG_TL;
-    dim3 g(rf::ceil_div(n, TPB), rf::ceil_div(m, lspan), b);
-    RF_LAUNCH("mc_grad", mcg_kernel, g, dim3(TPB), 0, s, n, m, lspan, xyz1, xyz2, match, grad1, grad2);
-    return RF_OK;
+    return mcg_tile_launch<false>(b, n, m, xyz1, xyz2, match, grad1, grad2, s, nullptr, nullptr);
 }
 
 int rf_matchcost_grad(int b, int n, int m, const float *xyz1, const float *xyz2,
@@ -2664,6 +2805,61 @@ int rf_matchcost_grad(int b, int n, int m, const float *xyz1, const float *xyz2,
     if (b == 0 || n == 0 || m == 0) return RF_OK;
     return mcg_launch(b, n, m, xyz1, xyz2, match, grad1, grad2, s);
 }
+
+// ---- ragged batches (include/rfops.h): approx_match, match_cost, match_cost_grad with per-sample counts ----------------
+size_t rf_approxmatch_lengths_workspace_bytes(int b, int n, int m, int nlevels) {
+    if (nlevels < 0 || nlevels > MAX_LEVELS) return 0;
+    return rf_approxmatch_mode_workspace_bytes(b, n, m, nlevels, RF_EMD_SWEPT);
+}
+
+int rf_approxmatch_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                           float *match, const float *levels_host, int nlevels, void *workspace, size_t workspace_bytes,
+                           rf_stream_t stream) {
+    float lv_default[16];
+    if (!levels_host && nlevels == 0) {  // the reference schedule
+        nlevels = default_levels(lv_default);
+        levels_host = lv_default;
+    }
+    if (b < 0 || b > MAX_BATCH || n < 0 || m < 0 || nlevels <= 0 || nlevels > MAX_LEVELS || !levels_host) return RF_EINVAL;
+    // (every multiplier <= 0 and finite: the weights are then in [0, 1] and the padding's terms are exactly +0 -- ADVICE.md,
+    // am_match_any_kernel's guarded sums)
+    for (int v = 0; v < nlevels; v++)
+        if (!(levels_host[v] <= 0.f) || !isfinite(levels_host[v])) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
+    if (!xyz1 || !xyz2 || !match || !workspace || !rf::aligned16(workspace) || !aligned4(len1) || !aligned4(len2))
+        return RF_EINVAL;
+    if (workspace_bytes < rf_approxmatch_lengths_workspace_bytes(b, n, m, nlevels)) return RF_EWORKSPACE;
+    return am_approxmatch<true>(b, n, m, xyz1, xyz2, match, levels_host, nlevels, workspace, (hipStream_t)stream, RF_EMD_SWEPT,
+                                len1, len2);
+}
+
+size_t rf_matchcost_lengths_workspace_bytes(int b, int n, int m) { return rf_matchcost_workspace_bytes(b, n, m); }
+
+int rf_matchcost_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                         const float *match, float *cost, void *workspace, size_t workspace_bytes, rf_stream_t stream) {
+    if (b < 0 || b > MAX_BATCH || n < 0 || m < 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0) return RF_EINVAL;
+    if (!xyz1 || !xyz2 || !match || !cost || !workspace || !rf::aligned16(workspace) || !aligned4(len1) || !aligned4(len2))
+        return RF_EINVAL;
+    if (workspace_bytes < rf_matchcost_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
+    return mc_launch<true>(b, n, m, xyz1, xyz2, match, cost, workspace, (hipStream_t)stream, len1, len2);
+}
+
+int rf_matchcost_grad_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                              const float *match, float *grad1, float *grad2, rf_stream_t stream) {
+    if (b < 0 || b > MAX_BATCH || n < 0 || m < 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0) return RF_EINVAL;
+    if (!xyz1 || !xyz2 || !match || !grad1 || !grad2 || !aligned4(len1) || !aligned4(len2)) return RF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    RF_ZERO(grad1, sizeof(float) * 3 * (size_t)b * n, s);
+    RF_ZERO(grad2, sizeof(float) * 3 * (size_t)b * m, s);
+    return mcg_tile_launch<true>(b, n, m, xyz1, xyz2, match, grad1, grad2, s, len1, len2);
+}
+
+}  // extern "C"
 
 // ---- row f1: earth_mover fused ------------------------------------------------------------
 namespace {
@@ -2702,7 +2898,81 @@ EmdLayout emd_layout(int b, int n, int m, int mode = RF_EMD_AUTO) {
     E.off_match = E.off_mc = 0;
     return E;
 }
+
+// earth_mover after its argument checks (gradients zero-filled by the caller).  LEN: the ragged form (rf_earth_mover_lengths,
+// mode = RF_EMD_SWEPT) -- the count-aware instantiations of the same launches, and for the cost alone the plain fused kernel.
+template <bool LEN>
+int emd_run(int b, int n, int m, const float *xyz1, const float *xyz2, float *cost, float *grad1, float *grad2, void *workspace,
+            hipStream_t s, int mode, const int *len1, const int *len2) {
+    const bool want_grad = grad1 != nullptr;
+    const EmdLayout E = emd_layout(b, n, m, mode);
+    float *w = (float *)workspace;
+    float lv[16];
+    const int nl = default_levels(lv);
+    LevelConsts lc;
+    for (int v = 0; v < MAX_LEVELS; v++) lc.c[v] = v < nl ? lv[v] * kLog2e : 0.f;
+    float multiL, multiR;
+    am_multipliers(n, m, multiL, multiR);
+    if (E.small) {
+        // launch-bound sizes: one workgroup per sample builds match (<= 256 KiB) in the workspace,
+        // then the ordinary match_cost(+grad) kernels read it back out of L2
+        float *match = w + E.off_match;
+        RF_LAUNCH("am_small", am_small_kernel<LEN>, dim3(b), dim3(AM_SMALL), 0, s, n, m, nl, lc, multiL, multiR,
+                  xyz1, xyz2, match, len1, len2);
+        if (int st = mc_launch<LEN>(b, n, m, xyz1, xyz2, match, cost, w + E.off_mc, s, len1, len2)) return st;
+        if (want_grad) return mcg_tile_launch<LEN>(b, n, m, xyz1, xyz2, (const float *)match, grad1, grad2, s, len1, len2);
+        return RF_OK;
+    }
+    {
+        const int st = am_run_levels<LEN>(b, n, m, xyz1, xyz2, nl, lc, multiL, multiR, workspace, s, mode, len1, len2);
+        if (st != RF_OK) return st;
+    }
+    const AmLayout L = am_layout(b, n, m, nl, mode);
+    const float *ratios = w + L.V;
+    float *rec = w + E.off_rec, *partial = w + E.off_partial;
+    const dim3 g(rf::ceil_div(n, TPB), E.lsplit, b);
+    const bool sq = quarter_chain(lc.c, 10, true);
+    if (!LEN && !want_grad && sq) {  // the cost alone: the columns by the class of their last live level (emd_fused_cls_kernel)
+        int *coff = (int *)(w + E.off_coff);
+        int *wgcnt = coff + (size_t)b * 8;
+        const dim3 gp(rf::ceil_div(L.mpad, EP_TPB), b);
+        RF_LAUNCH("emd_pack_cols", emd_class_count_kernel, gp, dim3(EP_TPB), 0, s, m, L.mpad, ratios, L.V, L.bstride, L.npad, wgcnt);
+        RF_LAUNCH("emd_pack_cols", emd_pack_cols_sorted_kernel, gp, dim3(EP_TPB), 0, s, m, L.mpad, xyz2, ratios, L.V, L.bstride,
+                  L.npad, (const int *)wgcnt, rec, E.rstride, coff);
+        const dim3 gc(rf::ceil_div(n, TPB), E.lsplit, b);
+        RF_LAUNCH("emd_fused", emd_fused_cls_kernel, gc, dim3(TPB), 0, s, n, E.lspan, xyz1, (const float *)rec, E.rstride,
+                  (const int *)coff, ratios, L.V, L.bstride, lc, partial);
+        RF_LAUNCH("mc_final", mc_final_kernel, dim3(b), dim3(256), 0, s, (const float *)partial, (int)(gc.x * gc.y), cost);
+        return RF_OK;
+    } else {
+        RF_LAUNCH("emd_pack_cols", emd_pack_cols_kernel<LEN>, dim3(rf::ceil_div(L.mpad, 256), b), dim3(256), 0, s, m,
+                  L.mpad, nl, xyz2, ratios, L.V, L.bstride, L.npad, rec, want_grad ? 0 : 1, len2);
+        if (want_grad && sq) {
+            RF_LAUNCH("emd_fused_grad", (emd_fused_kernel<10, true, true, true, LEN>), g, dim3(TPB), 0, s, n, m, L.mpad, E.lspan,
+                      xyz1, (const float *)rec, ratios, L.V, L.bstride, lc, partial, grad1, grad2, len1, len2);
+        } else if (want_grad) {
+            RF_LAUNCH("emd_fused_grad", (emd_fused_kernel<10, true, true, false, LEN>), g, dim3(TPB), 0, s, n, m, L.mpad, E.lspan,
+                      xyz1, (const float *)rec, ratios, L.V, L.bstride, lc, partial, grad1, grad2, len1, len2);
+        } else if constexpr (LEN) {  // (ragged, the cost alone: the plain fused kernel -- the class-sorted one is count-unaware)
+            if (sq) {
+                RF_LAUNCH("emd_fused", (emd_fused_kernel<10, false, true, true, true>), g, dim3(TPB), 0, s, n, m, L.mpad, E.lspan,
+                          xyz1, (const float *)rec, ratios, L.V, L.bstride, lc, partial, grad1, grad2, len1, len2);
+            } else {
+                RF_LAUNCH("emd_fused", (emd_fused_kernel<10, false, true, false, true>), g, dim3(TPB), 0, s, n, m, L.mpad, E.lspan,
+                          xyz1, (const float *)rec, ratios, L.V, L.bstride, lc, partial, grad1, grad2, len1, len2);
+            }
+        } else {
+            RF_LAUNCH("emd_fused", (emd_fused_kernel<10, false, true, false>), g, dim3(TPB), 0, s, n, m, L.mpad, E.lspan, xyz1,
+                      (const float *)rec, ratios, L.V, L.bstride, lc, partial, grad1, grad2);
+        }
+    }
+    RF_LAUNCH("mc_final", mc_final_kernel, dim3(b), dim3(256), 0, s, (const float *)partial,
+              (int)(g.x * g.y), cost);
+    return RF_OK;
+}
 }  // namespace
+
+extern "C" {
 
 size_t rf_earth_mover_workspace_bytes(int b, int n, int m) { return rf_earth_mover_mode_workspace_bytes(b, n, m, RF_EMD_AUTO); }
 
@@ -2736,71 +3006,27 @@ int rf_earth_mover_mode(int b, int n, int m, const float *xyz1, const float *xyz
     }
     if (!xyz1 || !xyz2 || !workspace || !rf::aligned16(workspace)) return RF_EINVAL;
     if (workspace_bytes < rf_earth_mover_mode_workspace_bytes(b, n, m, mode)) return RF_EWORKSPACE;
-    const EmdLayout E = emd_layout(b, n, m, mode);
-    float *w = (float *)workspace;
-    float lv[16];
-    const int nl = default_levels(lv);
-    LevelConsts lc;
-    for (int v = 0; v < MAX_LEVELS; v++) lc.c[v] = v < nl ? lv[v] * kLog2e : 0.f;
-    float multiL, multiR;
-    am_multipliers(n, m, multiL, multiR);
-    if (E.small) {
-        // launch-bound sizes: one workgroup per sample builds match (<= 256 KiB) in the workspace,
-        // then the ordinary match_cost(+grad) kernels read it back out of L2
-        float *match = w + E.off_match;
-        RF_LAUNCH("am_small", am_small_kernel, dim3(b), dim3(AM_SMALL), 0, s, n, m, nl, lc, multiL, multiR,
-                  xyz1, xyz2, match);
-        int st = rf_matchcost(b, n, m, xyz1, xyz2, match, cost, w + E.off_mc,
-                              rf_matchcost_workspace_bytes(b, n, m), stream);
-        if (st != RF_OK) return st;
-        if (want_grad) {
-            int lsplit = MG_LSPLIT;
-            while (lsplit > 1 && m / lsplit < MG_TL) lsplit /= 2;
-            const int lspan = rf::ceil_div(rf::ceil_div(m, lsplit), MG_TL) * MG_TL;
-            dim3 g(rf::ceil_div(n, TPB), rf::ceil_div(m, lspan), b);
-            RF_LAUNCH("mc_grad", mcg_kernel, g, dim3(TPB), 0, s, n, m, lspan, xyz1, xyz2,
-                      (const float *)match, grad1, grad2);
-        }
-        return RF_OK;
+    return emd_run<false>(b, n, m, xyz1, xyz2, cost, grad1, grad2, workspace, s, mode, nullptr, nullptr);
+}
+
+size_t rf_earth_mover_lengths_workspace_bytes(int b, int n, int m) { return rf_earth_mover_mode_workspace_bytes(b, n, m, RF_EMD_SWEPT); }
+
+int rf_earth_mover_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                           float *cost, float *grad1, float *grad2, void *workspace, size_t workspace_bytes,
+                           rf_stream_t stream) {
+    if (b < 0 || b > MAX_BATCH || n < 0 || m < 0) return RF_EINVAL;
+    if ((grad1 == nullptr) != (grad2 == nullptr)) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
+    if (!xyz1 || !xyz2 || !cost || !workspace || !rf::aligned16(workspace) || !aligned4(len1) || !aligned4(len2))
+        return RF_EINVAL;
+    if (workspace_bytes < rf_earth_mover_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    if (grad1) {
+        RF_ZERO(grad1, sizeof(float) * 3 * (size_t)b * n, s);
+        RF_ZERO(grad2, sizeof(float) * 3 * (size_t)b * m, s);
     }
-    {
-        const int st = am_run_levels(b, n, m, xyz1, xyz2, nl, lc, multiL, multiR, workspace, s, mode);
-        if (st != RF_OK) return st;
-    }
-    const AmLayout L = am_layout(b, n, m, nl, mode);
-    const float *ratios = w + L.V;
-    float *rec = w + E.off_rec, *partial = w + E.off_partial;
-    const dim3 g(rf::ceil_div(n, TPB), E.lsplit, b);
-    const bool sq = quarter_chain(lc.c, 10, true);
-    if (!want_grad && sq) {  // the cost alone: the columns by the class of their last live level (emd_fused_cls_kernel)
-        int *coff = (int *)(w + E.off_coff);
-        int *wgcnt = coff + (size_t)b * 8;
-        const dim3 gp(rf::ceil_div(L.mpad, EP_TPB), b);
-        RF_LAUNCH("emd_pack_cols", emd_class_count_kernel, gp, dim3(EP_TPB), 0, s, m, L.mpad, ratios, L.V, L.bstride, L.npad, wgcnt);
-        RF_LAUNCH("emd_pack_cols", emd_pack_cols_sorted_kernel, gp, dim3(EP_TPB), 0, s, m, L.mpad, xyz2, ratios, L.V, L.bstride,
-                  L.npad, (const int *)wgcnt, rec, E.rstride, coff);
-        const dim3 gc(rf::ceil_div(n, TPB), E.lsplit, b);
-        RF_LAUNCH("emd_fused", emd_fused_cls_kernel, gc, dim3(TPB), 0, s, n, E.lspan, xyz1, (const float *)rec, E.rstride,
-                  (const int *)coff, ratios, L.V, L.bstride, lc, partial);
-        RF_LAUNCH("mc_final", mc_final_kernel, dim3(b), dim3(256), 0, s, (const float *)partial, (int)(gc.x * gc.y), cost);
-        return RF_OK;
-    } else {
-        RF_LAUNCH("emd_pack_cols", emd_pack_cols_kernel, dim3(rf::ceil_div(L.mpad, 256), b), dim3(256), 0, s, m,
-                  L.mpad, nl, xyz2, ratios, L.V, L.bstride, L.npad, rec, want_grad ? 0 : 1);
-        if (want_grad && sq) {
-            RF_LAUNCH("emd_fused_grad", (emd_fused_kernel<10, true, true, true>), g, dim3(TPB), 0, s, n, m, L.mpad, E.lspan,
-                      xyz1, (const float *)rec, ratios, L.V, L.bstride, lc, partial, grad1, grad2);
-        } else if (want_grad) {
-            RF_LAUNCH("emd_fused_grad", (emd_fused_kernel<10, true, true, false>), g, dim3(TPB), 0, s, n, m, L.mpad, E.lspan,
-                      xyz1, (const float *)rec, ratios, L.V, L.bstride, lc, partial, grad1, grad2);
-        } else {
-            RF_LAUNCH("emd_fused", (emd_fused_kernel<10, false, true, false>), g, dim3(TPB), 0, s, n, m, L.mpad, E.lspan, xyz1,
-                      (const float *)rec, ratios, L.V, L.bstride, lc, partial, grad1, grad2);
-        }
-    }
-    RF_LAUNCH("mc_final", mc_final_kernel, dim3(b), dim3(256), 0, s, (const float *)partial,
-              (int)(g.x * g.y), cost);
-    return RF_OK;
+    return emd_run<true>(b, n, m, xyz1, xyz2, cost, grad1, grad2, workspace, s, RF_EMD_SWEPT, len1, len2);
 }
 
 }  // extern "C"

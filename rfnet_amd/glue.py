@@ -159,10 +159,21 @@ def fidelity_loss(pcd1, pcd2, sorted1=None, sorted2=None, lengths1=None, lengths
     return loss[:, 0].mean()
 
 
-def earth_mover(pcd1, pcd2):
-    assert pcd1.shape[1] == pcd2.shape[1]
-    cost = earth_mover_cost(pcd1, pcd2)  # approx_match -> match_cost fused: match never hits HBM
-    return (cost / float(pcd1.shape[1])).mean()
+def earth_mover(pcd1, pcd2, lengths1=None, lengths2=None):
+    """mean over the batch of cost_i / #points (vv_recon.py:392-399).  lengths1 / lengths2: per-sample point counts of a
+    ragged batch (rf_earth_mover_lengths): the mean of cost_i / lengths1[i], the ragged form of the division by
+    pcd1.shape[1]; padded rows get a zero gradient."""
+    if lengths1 is None and lengths2 is None:
+        assert pcd1.shape[1] == pcd2.shape[1]
+        cost = earth_mover_cost(pcd1, pcd2)  # approx_match -> match_cost fused: match never hits HBM
+        return (cost / float(pcd1.shape[1])).mean()
+    cost = earth_mover_cost(pcd1, pcd2, lengths1=lengths1, lengths2=lengths2)
+    b, n = pcd1.shape[0], pcd1.shape[1]
+    l1 = _raw._check_lengths(lengths1, b, n, "lengths1")
+    if l1 is None:
+        return (cost / float(n)).mean()
+    # (device counts as the kernels read them: clamped into [1, n])
+    return (cost / l1.to(device=cost.device, dtype=cost.dtype).clamp(1, n)).mean()
 
 
 def re_chamfer(gt, pred, part=8):

@@ -60,9 +60,9 @@ def match_cost_grad(xyz1, xyz2, match):
 
 class _EarthMoverCost(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xyz1, xyz2, mode):
+    def forward(ctx, xyz1, xyz2, mode, lengths1=None, lengths2=None):
         # one launch sequence yields the cost and MatchCostGrad's outputs; the backward only scales
-        cost, g1, g2 = _raw.earth_mover(xyz1, xyz2, with_grad=True, mode=mode)
+        cost, g1, g2 = _raw.earth_mover(xyz1, xyz2, with_grad=True, mode=mode, lengths1=lengths1, lengths2=lengths2)
         ctx.save_for_backward(g1, g2)
         return cost
 
@@ -70,16 +70,18 @@ class _EarthMoverCost(torch.autograd.Function):
     def backward(ctx, grad_cost):
         g1, g2 = ctx.saved_tensors
         s = grad_cost.reshape(-1, 1, 1)
-        return g1 * s, g2 * s, None
+        return g1 * s, g2 * s, None, None, None
 
 
-def earth_mover_cost(xyz1, xyz2, mode="auto"):
+def earth_mover_cost(xyz1, xyz2, mode="auto", lengths1=None, lengths2=None):
     """match_cost(xyz1, xyz2, approx_match(xyz1, xyz2)) as ONE fused op: cost (batch_size), with the
     reference's gradient (MatchCostGrad scaled by grad_cost, match held constant) -- but the
     (batch, #query, #dataset) match tensor is never written.  Extension for the loss glue
     (`earth_mover`, vv_recon.py:392-399); the two-op chain above stays available unchanged.
-    mode="swept" pins the route so that cost[i] does not depend on the batch around sample i (include/rfops.h, RF_EMD_SWEPT)."""
+    mode="swept" pins the route so that cost[i] does not depend on the batch around sample i (include/rfops.h, RF_EMD_SWEPT).
+    `lengths1` / `lengths2`: per-sample point counts of a ragged batch (rf_earth_mover_lengths, always the pinned route):
+    sample i is xyz1[i, :lengths1[i]] against xyz2[i, :lengths2[i]], and the padded rows' gradients are 0."""
     if all(isinstance(t, torch.Tensor) for t in (xyz1, xyz2)) and (
             xyz1.requires_grad or xyz2.requires_grad):
-        return _EarthMoverCost.apply(xyz1, xyz2, mode)
-    return _raw.earth_mover(xyz1, xyz2, mode=mode)
+        return _EarthMoverCost.apply(xyz1, xyz2, mode, lengths1, lengths2)
+    return _raw.earth_mover(xyz1, xyz2, mode=mode, lengths1=lengths1, lengths2=lengths2)
