@@ -202,16 +202,7 @@ int run_forward(int b, int n, int m, const float *xyz1, const float *xyz2, const
                                       workspace_bytes - p.off_dense, s, dirs);
     const rfp::Sorted s1 = rfp::sorted_view(b, n, sorted1 ? sorted1 : w + p.off_s1);
     const rfp::Sorted s2 = rfp::sorted_view(b, m, sorted2 ? sorted2 : w + p.off_s2);
-    if (!sorted1 && !sorted2) {
-        const int nn[2] = {n, m};
-        const float *src[2] = {xyz1, xyz2};
-        const rfp::Sorted so[2] = {s1, s2};
-        if (int e = rfp::sort_sets(b, 2, nn, src, so, s, nullptr)) return e;
-    } else if (!sorted1) {
-        if (int e = rfp::sort_sets(b, 1, &n, &xyz1, &s1, s, nullptr)) return e;
-    } else if (!sorted2) {
-        if (int e = rfp::sort_sets(b, 1, &m, &xyz2, &s2, s, nullptr)) return e;
-    }
+    if (int e = rfp::sort_missing(b, n, m, xyz1, xyz2, s1, s2, sorted1 != nullptr, sorted2 != nullptr, s)) return e;
     return rfp::sweep_sorted(b, n, m, s1, s2, dist1, idx1, dist2, idx2, dirs, s, nullptr);
 }
 

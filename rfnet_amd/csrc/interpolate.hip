@@ -7,20 +7,17 @@
 // rounded.  This file is compiled with -ffp-contract=off and uses no fmaf(), so dist / idx /
 // out are bit-exact with oracle/rfops_oracle.c (and with the reference CPU bodies).
 //
-// three_nn: one lane per unknown point; the known set is wave-uniform, so it is streamed through
-// SGPRs by scalar loads (two register sets used alternately, as query_ball_lanes_kernel) and the
-// VALU ops take the SGPR operands directly -- no LDS tile, no barrier.  A candidate enters the
-// lane's sorted triple only if d < b3; that test is one compare, and the insertion chain sits
-// behind a wave-uniform branch (taken for ~half of the candidates at m = 1024, ever more rarely as
-// m grows), instead of being predicated over every pair.
+// three_nn: one lane per unknown point; the known set is wave-uniform and streamed through SGPRs
+// (box_bound.hpp ts_stream, shared with knn_scan_kernel).  A candidate enters the lane's sorted
+// triple only if d < b3; that test is one compare, and the insertion chain sits behind a
+// wave-uniform branch (taken for ~half of the candidates at m = 1024, ever more rarely as m
+// grows), instead of being predicated over every pair.
 //
-// three_nn over SORTED clouds (three_nn_boxes_kernel, rf_threenn_boxes): both sets in the spatial order of the Chamfer sweep's
-// sort (nn_pruned.hip: 64-record superblocks and 16-record blocks with their boxes).  A wave takes 64 consecutive sorted
-// unknown points -- a compact cell -- and visits only the candidate blocks whose box can still hold a point at or inside some
-// lane's third-best distance.  The bound is the SAME unfused fp32 expression evaluated on the per-axis gaps to the box: rounding
-// is monotone, so bound <= distance holds in fp32 exactly and nothing that the full scan would insert is skipped.  The scan
-// visits candidates in index order and inserts on strict '<': its result is the three smallest by (distance, index); the boxed
-// form visits them in any order and inserts by that pair -- the same triple, ties included.
+// three_nn over SORTED clouds (three_nn_boxes_kernel, rf_threenn_boxes): the boxed walk of box_bound.hpp (tb_walk, shared with
+// knn_boxes_kernel) with three_nn's list, TnList.  A wave takes 64 consecutive sorted unknown points and visits only the
+// candidate blocks whose box can still hold a point at or inside some lane's third-best distance.  The scan visits candidates in
+// index order and inserts on strict '<': its result is the three smallest by (distance, index); the boxed form visits them in
+// any order and inserts by that pair -- the same triple, ties included.
 #include "common.hpp"
 #include "scatter_rows.hpp"
 #include "nn_pruned.hpp"
@@ -29,7 +26,6 @@
 namespace {
 
 constexpr int TN_TPB = 256;
-constexpr int TN_SUB = 8;  // known points per scalar-load sub-chunk
 
 __global__ __launch_bounds__(TN_TPB) void three_nn_kernel(int n, int m,
                                                           const float *__restrict__ xyz1,
@@ -44,58 +40,27 @@ __global__ __launch_bounds__(TN_TPB) void three_nn_kernel(int n, int m,
     const float x1 = U[jj * 3], y1 = U[jj * 3 + 1], z1 = U[jj * 3 + 2];
     float b1 = INFINITY, b2 = INFINITY, b3 = INFINITY;
     int i1 = 0, i2 = 0, i3 = 0;
-    // One candidate.  A macro, not a lambda: with the triple captured by reference the compiler
-    // kept the indices in scratch memory.  The insertion is select-only (2 compares, 10 selects):
-    // strict '<' everywhere, so an earlier index keeps its place on ties, exactly the reference's
-    // if / else-if chain (tf_interpolate.cpp:78-93).
-#define TN_CONSIDER(cx, cy, cz, kk)                                                           \
-    {                                                                                         \
-        const float dx_ = (cx) - x1, dy_ = (cy) - y1, dz_ = (cz) - z1;                         \
-        const float xx_ = dx_ * dx_, yy_ = dy_ * dy_, zz_ = dz_ * dz_;                         \
-        const float d_ = (xx_ + yy_) + zz_;                                                    \
-        const bool in_ = d_ < b3;                                                              \
-        if (__ballot(in_) != 0ull) { /* wave-uniform */                                        \
-            asm volatile("; some lane inserts"); /* keeps this a real branch (grouping.hip) */ \
-            if (in_) {                                                                         \
-                const bool c1_ = d_ < b1, c2_ = d_ < b2;                                       \
-                b3 = c2_ ? b2 : d_;                                                            \
-                i3 = c2_ ? i2 : (kk);                                                          \
-                b2 = c1_ ? b1 : (c2_ ? d_ : b2);                                               \
-                i2 = c1_ ? i1 : (c2_ ? (kk) : i2);                                             \
-                b1 = c1_ ? d_ : b1;                                                            \
-                i1 = c1_ ? (kk) : i1;                                                          \
-            }                                                                                  \
-        }                                                                                      \
-    }
-    const int m_full = (m / TN_SUB) * TN_SUB;
-    if (m_full > 0) {
-        float pa[3 * TN_SUB], pb[3 * TN_SUB];
-        auto fetch = [&](float (&dst)[3 * TN_SUB], int k) {
-            const float *cp = K + (size_t)min(k, m - TN_SUB) * 3;  // uniform -> s_load; clamped in bounds
-#pragma unroll
-            for (int i = 0; i < 3 * TN_SUB; i++) dst[i] = cp[i];
-        };
-#define TN_SCAN8(c, k0)                  \
-    _Pragma("unroll") for (int u = 0; u < TN_SUB; u++) TN_CONSIDER(c[u * 3], c[u * 3 + 1], c[u * 3 + 2], (k0) + u)
-        fetch(pa, 0);
-        for (int k0 = 0; k0 < m_full; k0 += 2 * TN_SUB) {
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): pa has arrived
-            __builtin_amdgcn_sched_barrier(0);
-            fetch(pb, k0 + TN_SUB);
-            __builtin_amdgcn_sched_barrier(0);
-            TN_SCAN8(pa, k0);
-            if (k0 + TN_SUB >= m_full) break;
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // pb has arrived
-            __builtin_amdgcn_sched_barrier(0);
-            fetch(pa, k0 + 2 * TN_SUB);
-            __builtin_amdgcn_sched_barrier(0);
-            TN_SCAN8(pb, k0 + TN_SUB);
+    // One candidate.  The insertion is select-only (2 compares, 10 selects): strict '<' everywhere, so an earlier index keeps
+    // its place on ties, exactly the reference's if / else-if chain (tf_interpolate.cpp:78-93).
+    auto consider = [&](float cx, float cy, float cz, int kk) __attribute__((always_inline)) {
+        const float dx = cx - x1, dy = cy - y1, dz = cz - z1;
+        const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+        const float d = (xx + yy) + zz;
+        const bool in = d < b3;
+        if (__ballot(in) != 0ull) {  // wave-uniform
+            asm volatile("; some lane inserts");  // keeps this a real branch (grouping.hip)
+            if (in) {
+                const bool c1 = d < b1, c2 = d < b2;
+                b3 = c2 ? b2 : d;
+                i3 = c2 ? i2 : kk;
+                b2 = c1 ? b1 : (c2 ? d : b2);
+                i2 = c1 ? i1 : (c2 ? kk : i2);
+                b1 = c1 ? d : b1;
+                i1 = c1 ? kk : i1;
+            }
         }
-    }
-#pragma unroll 1
-    for (int k = m_full; k < m; k++) TN_CONSIDER(K[k * 3], K[k * 3 + 1], K[k * 3 + 2], k);
-#undef TN_SCAN8
-#undef TN_CONSIDER
+    };
+    ts_stream(K, m, consider);
     if (j < n) {
         size_t o = ((size_t)bi * n + j) * 3;
         dist[o] = b1; dist[o + 1] = b2; dist[o + 2] = b3;
@@ -104,187 +69,68 @@ __global__ __launch_bounds__(TN_TPB) void three_nn_kernel(int n, int m,
 }
 
 
-// ---- three_nn over sorted clouds ----------------------------------------------------------------------------------------
-#ifndef RFI_TB_WAVES
-#define RFI_TB_WAVES 4
-#endif
-constexpr int TB_WAVES = RFI_TB_WAVES;  // waves per workgroup, each on its own (no barrier)
+// ---- three_nn over sorted clouds: the walk of box_bound.hpp with three_nn's list --------------------------------------------
+// The three best as 64-bit keys (distance bits, index): a squared distance is never negative, so its bit pattern orders as the
+// float does, a NaN above +inf; "smaller key" is then the scan's strict '<' in index order, ties included, in ONE comparison.
+// Unfilled slots are (+inf, 0) as the op leaves them.
+struct TnList {
+    typedef unsigned long long u64;
+    static constexpr u64 kInf = (u64)0x7f800000u << 32;
+    // a key must be below (+inf, 0) to enter, so a non-finite distance never does (tf_interpolate.cpp:78-93: every comparison
+    // fails): no superblock at +inf is visited, and there is no untested walk
+    static constexpr bool kNonFinite = false;
+    u64 k1, k2, k3;
+    // a lane that does not search holds zeros -- no key is below them -- until the end
+    __device__ __forceinline__ explicit TnList(bool search) : k1(search ? kInf : 0ull), k2(k1), k3(k1) {}
+    // the third-best distance (0 in a lane that does not search: its point is padding or non-finite, at +inf from every box)
+    __device__ __forceinline__ float prune() const { return __uint_as_float((unsigned)(k3 >> 32)); }
+    __device__ __forceinline__ bool admit(float d) const { return d <= prune(); }
+    // by the keys alone, in every lane (one whose pre-test failed has a key that is not below k3; a padding record, index -1 =
+    // the largest unsigned, coordinates +inf, is not below (+inf, 0))
+    __device__ __forceinline__ void insert(float d, int oi, bool) {
+        const u64 key = ((u64)__float_as_uint(d) << 32) | (u64)(unsigned)oi;
+        const bool c3 = key < k3, c2 = key < k2, c1 = key < k1;
+        k3 = c3 ? (c2 ? k2 : key) : k3;
+        k2 = c2 ? (c1 ? k1 : key) : k2;
+        k1 = c1 ? key : k1;
+    }
+};
 
 __global__ __launch_bounds__(64 * TB_WAVES) void three_nn_boxes_kernel(
     int n, int npq, int npc, const float *__restrict__ qxyz, const int *__restrict__ qorig, const float *__restrict__ qb64,
     const float *__restrict__ cxyz, const int *__restrict__ corig, const float *__restrict__ cb16,
     const float *__restrict__ cb64, float *__restrict__ dist, int *__restrict__ idx) {
-    const int lane = threadIdx.x & 63;
-    // a sample's workgroups on the XCD that sorted it (rf::xcd_contiguous, as nnp_sort): its records are still in that L2
-    const int bpb = ((npq >> 6) + TB_WAVES - 1) / TB_WAVES;  // workgroups per sample
-    const unsigned logical = rf::xcd_contiguous(blockIdx.x, gridDim.x);  // a sample's workgroups on one XCD
-    const int bi = logical / bpb;
-    const int group = (logical - bi * bpb) * TB_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (group * 64 >= npq) return;  // (uniform)
-    const int p = group * 64 + lane;
+    const TbPlace w = tb_place(npq);
+    if (w.group * 64 >= npq) return;  // (uniform)
+    const int bi = w.bi;
+    const int p = w.group * 64 + (threadIdx.x & 63);
     const float *__restrict__ Q = qxyz + ((size_t)bi * npq + p) * 3;
-    const float x1 = Q[0], y1 = Q[1], z1 = Q[2];
+    TbQuery q;
+    q.x = Q[0], q.y = Q[1], q.z = Q[2];
     const int oq = qorig[(size_t)bi * npq + p];
     // a point with a NaN or infinite coordinate is at a NaN or infinite distance from everything: nothing is ever inserted
     // (tf_interpolate.cpp:78-93: every comparison fails) and it takes no part in the search
-    const bool search = oq >= 0 && isfinite(x1) && isfinite(y1) && isfinite(z1);
-    // the lane's three best as 64-bit keys (distance bits, index): a squared distance is never negative, so its bit pattern orders
-    // as the float does, a NaN above +inf; "smaller key" is then the scan's strict '<' in index order, ties included, in ONE
-    // comparison.  Unfilled slots are (+inf, 0) as the op leaves them; a lane that does not search holds zeros -- nothing is
-    // below them -- until the end.
-    typedef unsigned long long u64;
-    const u64 kInf = (u64)0x7f800000u << 32;
-    u64 k1 = search ? kInf : 0ull, k2 = k1, k3 = k1;
-    const float *__restrict__ CX = cxyz + (size_t)bi * npc * 3;
-    const int *__restrict__ CO = corig + (size_t)bi * npc;
+    q.search = oq >= 0 && isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
+    q.full = false;
+    q.qb = qb64 + ((size_t)bi * (npq >> 6) + w.group) * 8;
     const int nsb = npc >> 6;
-    const float *__restrict__ B16 = cb16 + (size_t)bi * nsb * 24;
-    const float *__restrict__ B64 = cb64 + (size_t)bi * nsb * 8;
-#define TB_B3 __uint_as_float((unsigned)(k3 >> 32))
-
-    // One candidate (uniform coordinates and original index, through scalar registers).  A padding record (index -1 = the largest
-    // unsigned, coordinates +inf) never enters: its key is not below (+inf, 0).
-#define TB_CONSIDER(cx, cy, cz, oi)                                                                         \
-    {                                                                                                       \
-        const float dx_ = (cx) - x1, dy_ = (cy) - y1, dz_ = (cz) - z1;                                       \
-        const float xx_ = dx_ * dx_, yy_ = dy_ * dy_, zz_ = dz_ * dz_;                                       \
-        const float d_ = (xx_ + yy_) + zz_;                                                                  \
-        if (__ballot(d_ <= TB_B3) != 0ull) { /* wave-uniform */                                              \
-            asm volatile("; some lane may insert");                                                          \
-            const u64 key_ = ((u64)__float_as_uint(d_) << 32) | (u64)(unsigned)(oi);                         \
-            const bool c3_ = key_ < k3, c2_ = key_ < k2, c1_ = key_ < k1;                                    \
-            k3 = c3_ ? (c2_ ? k2 : key_) : k3;                                                               \
-            k2 = c2_ ? (c1_ ? k1 : key_) : k2;                                                               \
-            k1 = c1_ ? key_ : k1;                                                                            \
-        }                                                                                                   \
-    }
-#ifdef TB_STATS
-    int nblk = 0, nsbv = 0;  // (uniform) block scans, superblock visits
-#endif
-    // one superblock: per 16-record block the lanes' bounds against their third-best (TEST), then the records of the blocks
-    // some lane needs, eight at a time through two scalar register sets in turn (the next eight are on their way while
-    // these are compared)
-    auto visit = [&](int sb, bool test) {
-#ifdef TB_STATS
-        nsbv++;
-#endif
-        unsigned hm = 0xFFu;  // the half-blocks to scan
-        if (test) {
-            const float *bx = B16 + (size_t)sb * 24;  // (uniform -> scalar loads)
-            float bb[24];
-#pragma unroll
-            for (int i = 0; i < 24; i++) bb[i] = bx[i];
-            hm = 0u;
-#pragma unroll
-            for (int blk = 0; blk < 4; blk++) {
-                const float lb = tb_bound(bb[blk * 6], bb[blk * 6 + 1], bb[blk * 6 + 2], bb[blk * 6 + 3], bb[blk * 6 + 4],
-                                          bb[blk * 6 + 5], x1, y1, z1, x1, y1, z1);
-                if (__ballot(lb <= TB_B3) != 0ull) hm |= 3u << (2 * blk);  // (uniform)
-            }
-            if (hm == 0u) return;
-        }
-#ifdef TB_STATS
-        nblk += __builtin_popcount(hm) >> 1;
-#endif
-        const float *cb = CX + (size_t)sb * 192;
-        const int *ob = CO + sb * 64;
-        float ca[24], cc[24];
-        int oa[8], oc[8];
-#define TB_FETCH(C, O, H)                                           \
-    {                                                               \
-        const float *cp_ = cb + (H) * 24;                           \
-        const int *op_ = ob + (H) * 8;                              \
-        _Pragma("unroll") for (int i = 0; i < 24; i++) C[i] = cp_[i]; \
-        _Pragma("unroll") for (int i = 0; i < 8; i++) O[i] = op_[i];  \
-    }
-#define TB_SCAN8(C, O) _Pragma("unroll") for (int u = 0; u < 8; u++) TB_CONSIDER(C[u * 3], C[u * 3 + 1], C[u * 3 + 2], O[u])
-        int h = __builtin_ctz(hm);
-        hm &= hm - 1u;
-        TB_FETCH(ca, oa, h);
-        for (;;) {
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): set a has arrived
-            __builtin_amdgcn_sched_barrier(0);
-            const bool more_b = hm != 0u;
-            if (more_b) {
-                h = __builtin_ctz(hm);
-                hm &= hm - 1u;
-                TB_FETCH(cc, oc, h);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            TB_SCAN8(ca, oa);
-            if (!more_b) break;
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // set c has arrived
-            __builtin_amdgcn_sched_barrier(0);
-            const bool more_a = hm != 0u;
-            if (more_a) {
-                h = __builtin_ctz(hm);
-                hm &= hm - 1u;
-                TB_FETCH(ca, oa, h);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            TB_SCAN8(cc, oc);
-            if (!more_a) break;
-        }
-#undef TB_SCAN8
-#undef TB_FETCH
-    };
-
-    // the wave's own box (its 64 unknown points are one superblock of their sorted set); without a point to search for, no search
-    const float *qb = qb64 + ((size_t)bi * (npq >> 6) + group) * 8;
-    const float qlx = qb[0], qly = qb[1], qlz = qb[2], qhx = qb[4], qhy = qb[5], qhz = qb[6];
-    if (__ballot(search) != 0ull) {
-        // 1. lanes <-> candidate superblocks: the one nearest to the wave's box goes first and sets the third-bests
-        float best = INFINITY;
-        int arg = 0;
-        for (int r0 = 0; r0 < nsb; r0 += 64) {
-            const int g = r0 + lane;
-            float lb = INFINITY;
-            if (g < nsb) {
-                const float4 lo = *(const float4 *)(B64 + (size_t)g * 8), hi = *(const float4 *)(B64 + (size_t)g * 8 + 4);
-                lb = tb_bound(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, qlx, qly, qlz, qhx, qhy, qhz);
-            }
-            if (lb < best) best = lb, arg = g;
-        }
-        const float wmin = tb_wave_min(best);
-        const unsigned long long at = __ballot(best == wmin);
-        const int seed = at != 0ull ? __builtin_amdgcn_readlane(arg, __builtin_ctzll(at)) : 0;
-        visit(seed, false);
-        // 2. every other superblock whose box is not beyond the wave's largest third-best (which shrinks as the visits go),
-        //    64 superblocks at a time
-        float w3 = tb_wave_max(TB_B3);  // (a lane that does not search holds 0)
-        for (int r0 = 0; r0 < nsb; r0 += 64) {
-            const int g = r0 + lane;
-            float lb = INFINITY;
-            if (g < nsb && g != seed) {
-                const float4 lo = *(const float4 *)(B64 + (size_t)g * 8), hi = *(const float4 *)(B64 + (size_t)g * 8 + 4);
-                lb = tb_bound(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, qlx, qly, qlz, qhx, qhy, qhz);
-            }
-            // nearest box first: the third-bests shrink fastest that way, and the first box beyond the wave's largest ends the round
-            bool pend = lb <= w3 && lb != INFINITY;
-            while (__ballot(pend) != 0ull) {  // (uniform)
-                const float wmin = tb_wave_min(pend ? lb : INFINITY);
-                if (!(wmin <= w3)) break;
-                const int j = __builtin_ctzll(__ballot(pend && lb == wmin));
-                pend = pend && lane != j;
-                visit(r0 + j, true);
-                w3 = tb_wave_max(TB_B3);
-            }
-        }
-    }
-#undef TB_CONSIDER
-#undef TB_B3
+    const TbCands c = {cxyz + (size_t)bi * npc * 3, corig + (size_t)bi * npc, cb16 + (size_t)bi * nsb * 24,
+                       cb64 + (size_t)bi * nsb * 8, nsb};
+    TnList L(q.search);
+    TbStats st;
+    tb_walk(L, q, c, st);
     if (oq >= 0) {
-        if (!search) k1 = k2 = k3 = kInf;
+        if (!q.search) L.k1 = L.k2 = L.k3 = TnList::kInf;
         const size_t o = ((size_t)bi * n + oq) * 3;
-        dist[o] = __uint_as_float((unsigned)(k1 >> 32));
-        dist[o + 1] = __uint_as_float((unsigned)(k2 >> 32));
-        dist[o + 2] = __uint_as_float((unsigned)(k3 >> 32));
-        idx[o] = (int)(unsigned)k1;
+        dist[o] = __uint_as_float((unsigned)(L.k1 >> 32));
+        dist[o + 1] = __uint_as_float((unsigned)(L.k2 >> 32));
+        dist[o + 2] = __uint_as_float((unsigned)(L.k3 >> 32));
+        idx[o] = (int)(unsigned)L.k1;
 #ifdef TB_STATS
-        idx[o + 1] = nsbv, idx[o + 2] = nblk;
+        idx[o + 1] = st.visits, idx[o + 2] = st.scans;
 #else
-        idx[o + 1] = (int)(unsigned)k2;
-        idx[o + 2] = (int)(unsigned)k3;
+        idx[o + 1] = (int)(unsigned)L.k2;
+        idx[o + 2] = (int)(unsigned)L.k3;
 #endif
     }
 }
@@ -530,16 +376,7 @@ int rf_threenn_boxes(int b, int n, int m, const float *xyz1, const float *xyz2, 
     rfp::Sorted sv[2];
     sv[0] = rfp::sorted_view(b, n, sorted1 ? sorted1 : workspace);
     sv[1] = rfp::sorted_view(b, m, sorted2 ? sorted2 : (const char *)workspace + rfp::sorted_bytes(b, n));
-    {  // the sets that came without a handle, in one launch
-        int nn[2];
-        const float *src[2];
-        rfp::Sorted out[2];
-        int k = 0;
-        if (!sorted1) nn[k] = n, src[k] = xyz1, out[k] = sv[0], k++;
-        if (!sorted2) nn[k] = m, src[k] = xyz2, out[k] = sv[1], k++;
-        if (k > 0)
-            if (int e = rfp::sort_sets(b, k, nn, src, out, s, nullptr)) return e;
-    }
+    if (int e = rfp::sort_missing(b, n, m, xyz1, xyz2, sv[0], sv[1], sorted1 != nullptr, sorted2 != nullptr, s)) return e;
     RF_LAUNCH("three_nn_boxes", three_nn_boxes_kernel, dim3(rf::ceil_div(sv[0].npad / 64, TB_WAVES) * b), dim3(64 * TB_WAVES), 0, s,
               n, sv[0].npad, sv[1].npad, sv[0].xyz, sv[0].orig, sv[0].box64, sv[1].xyz, sv[1].orig, sv[1].box16, sv[1].box64,
               dist, idx);

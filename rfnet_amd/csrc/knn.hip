@@ -16,16 +16,16 @@
 // candidate passes), -inf once it is full of NaN distances (only NaNs pass) -- behind a wave-uniform __ballot branch, and only
 // then keyed and inserted by exact 64-bit comparisons (KB compares, 4 KB selects); the scan first buffers what passes (below).
 //
-// knn_scan_kernel (rf_knn): one lane per query, the candidates wave-uniform through SGPRs in index order, as three_nn_kernel.
-// In index order a tie never displaces the earlier index, so the float pre-test is strict ('d < thr').
+// knn_scan_kernel (rf_knn): one lane per query, the candidates wave-uniform through SGPRs in index order (box_bound.hpp
+// ts_stream, shared with three_nn_kernel).  In index order a tie never displaces the earlier index, so the float pre-test is
+// strict ('d < thr').
 //
-// knn_boxes_kernel (rf_knn_boxes): both sets in rf_nn_sort order, as three_nn_boxes_kernel: a wave of 64 neighbouring queries
-// visits the 16-record candidate blocks whose box bound is <= some lane's k-th distance, nearest superblock first.  Visits go
-// in any order, so the pre-test admits ties ('d <= thr') and the keys settle them.  The bound is the same unfused expression
-// on the per-axis gaps (box_bound.hpp), so it never exceeds a distance inside the box: the result is the scan's, bit for bit.
-// Non-finite values break the bounds (the sort leaves such points out of the boxes, and a NaN distance ranks FIRST): a wave
-// with a non-finite query, or a sample whose candidate set holds a non-finite coordinate (the sort's flag), visits every
-// superblock without a test -- still the same keys, so still the scan's result.
+// knn_boxes_kernel (rf_knn_boxes): the boxed walk of box_bound.hpp (tb_walk, shared with three_nn_boxes_kernel) with knn's list,
+// KnList: a wave of 64 neighbouring sorted queries visits the candidate blocks whose box bound is <= some lane's k-th distance,
+// nearest superblock first.  Visits go in any order, so the pre-test admits ties ('d <= thr') and the keys settle them: the
+// result is the scan's, bit for bit.  Non-finite values break the bounds (the sort leaves such points out of the boxes, and a
+// NaN distance ranks FIRST): a wave with a non-finite query, or a sample whose candidate set holds a non-finite coordinate (the
+// sort's flag), visits every superblock without a test -- still the same keys, so still the scan's result.
 //
 // The gradient (rf_knn_grad): term(j, t) = 2 g[j, t] (x1[i] - x2[j]), i = idx[j, t]; grad_xyz2[j] = sum_t term, one lane per
 // query; grad_xyz1[i] = -sum of the terms that name i, a scatter done as group_point's (scatter_rows.hip): the m k slots
@@ -42,7 +42,6 @@ typedef unsigned long long u64;
 
 constexpr int KN_MAXK = 64;
 constexpr int KN_TPB = 256;
-constexpr int KN_SUB = 8;  // candidates per scalar-load sub-chunk
 
 __device__ __forceinline__ u64 kn_key(float d, unsigned i) {
     const unsigned r = d != d ? 0u : __float_as_uint(d) + 1u;
@@ -84,11 +83,12 @@ __device__ __forceinline__ void kn_write(const u64 (&L)[KB], int k, float *__res
 // the KB-slot insertion whenever ANY of its 64 lanes admits a candidate -- nearly every candidate of the first 64 k -- while a
 // flush costs as many insertions as the fullest buffer holds: the wave's insertions fall from ~ the union of its lanes' to ~ the
 // largest lane's.  The threshold a lane tests against is then that of its last flush, never below the true one: nothing that
-// belongs in the list is missed, and the exact keys decide.
+// belongs in the list is missed, and the exact keys decide.  The flush loop is unrolled for lists of up to 8 slots only
+// (kn_flush_unroll, in the kernel): unrolled at every candidate, a 16-slot list's flush makes the kernel ten times longer.
 constexpr int KN_BUF = 16;  // entries per lane
 #define KN_FLUSH(BD, BI, TID)                                                                                        \
     {                                                                                                                \
-        for (int f_ = 0; f_ < KN_BUF; f_++) {                                                                        \
+        _Pragma("unroll kn_flush_unroll") for (int f_ = 0; f_ < KN_BUF; f_++) {                                      \
             if (__ballot(f_ < cnt) == 0ull) break; /* wave-uniform */                                                \
             const unsigned i_ = f_ < cnt ? BI[f_][TID] : 0xFFFFFFFFu;                                                \
             kn_insert<KB>(L, i_ == 0xFFFFFFFFu ? ~0ull : kn_key(BD[f_][TID], i_));                                   \
@@ -97,7 +97,7 @@ constexpr int KN_BUF = 16;  // entries per lane
         thr = kn_thr(L[KB - 1]);                                                                                     \
     }
 
-// ---- scan: one lane per query, every candidate ----------------------------------------------------------------------------
+// ---- scan: one lane per query, every candidate (box_bound.hpp ts_stream) ----------------------------------------------------
 template <int KB>
 __global__ __launch_bounds__(KN_TPB) void knn_scan_kernel(int n, int m, int k, const float *__restrict__ xyz1,
                                                           const float *__restrict__ xyz2, float *__restrict__ val,
@@ -116,225 +116,85 @@ __global__ __launch_bounds__(KN_TPB) void knn_scan_kernel(int n, int m, int k, c
     __shared__ unsigned bx[KN_BUF][KN_TPB];
     const int tid = threadIdx.x;
     int cnt = 0;
-    // (a macro, as TN_CONSIDER: the candidate's coordinates and index stay scalar operands)
-#define KN_CONSIDER(cx, cy, cz, ci)                                                    \
-    {                                                                                  \
-        const float dx_ = (cx) - x2, dy_ = (cy) - y2, dz_ = (cz) - z2;                  \
-        const float xx_ = dx_ * dx_, yy_ = dy_ * dy_, zz_ = dz_ * dz_;                  \
-        const float d_ = (xx_ + yy_) + zz_;                                             \
-        const bool in_ = !(d_ >= thr);                                                  \
-        if (__ballot(in_) != 0ull) { /* wave-uniform */                                 \
-            asm volatile("; some lane admits");                                         \
-            if (in_) {                                                                  \
-                bd[cnt][tid] = d_;                                                      \
-                bx[cnt][tid] = (unsigned)(ci);                                          \
-                cnt++;                                                                  \
-            }                                                                           \
-            if (__ballot(cnt == KN_BUF) != 0ull) KN_FLUSH(bd, bx, tid);                 \
-        }                                                                               \
-    }
-    const int n_full = (n / KN_SUB) * KN_SUB;
-    if (n_full > 0) {
-        float pa[3 * KN_SUB], pb[3 * KN_SUB];
-        auto fetch = [&](float (&dst)[3 * KN_SUB], int c0) {
-            const float *cp = C + (size_t)min(c0, n - KN_SUB) * 3;  // uniform -> s_load; clamped in bounds
-#pragma unroll
-            for (int i = 0; i < 3 * KN_SUB; i++) dst[i] = cp[i];
-        };
-#define KN_SCAN8(c, c0) \
-    _Pragma("unroll") for (int u = 0; u < KN_SUB; u++) KN_CONSIDER(c[u * 3], c[u * 3 + 1], c[u * 3 + 2], (c0) + u)
-        fetch(pa, 0);
-        for (int c0 = 0; c0 < n_full; c0 += 2 * KN_SUB) {
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): pa has arrived
-            __builtin_amdgcn_sched_barrier(0);
-            fetch(pb, c0 + KN_SUB);
-            __builtin_amdgcn_sched_barrier(0);
-            KN_SCAN8(pa, c0);
-            if (c0 + KN_SUB >= n_full) break;
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // pb has arrived
-            __builtin_amdgcn_sched_barrier(0);
-            fetch(pa, c0 + 2 * KN_SUB);
-            __builtin_amdgcn_sched_barrier(0);
-            KN_SCAN8(pb, c0 + KN_SUB);
+    constexpr int kn_flush_unroll = KB <= 8 ? KN_BUF : 1;
+    auto consider = [&](float cx, float cy, float cz, int ci) __attribute__((always_inline)) {
+        const float dx = cx - x2, dy = cy - y2, dz = cz - z2;
+        const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
+        const float d = (xx + yy) + zz;
+        const bool in = !(d >= thr);
+        if (__ballot(in) != 0ull) {  // wave-uniform
+            asm volatile("; some lane admits");
+            if (in) {
+                bd[cnt][tid] = d;
+                bx[cnt][tid] = (unsigned)ci;
+                cnt++;
+            }
+            if (__ballot(cnt == KN_BUF) != 0ull) KN_FLUSH(bd, bx, tid);
         }
-#undef KN_SCAN8
-    }
-#pragma unroll 1
-    for (int c = n_full; c < n; c++) KN_CONSIDER(C[c * 3], C[c * 3 + 1], C[c * 3 + 2], c);
-#undef KN_CONSIDER
+    };
+    ts_stream(C, n, consider);
     KN_FLUSH(bd, bx, tid);
     if (j < m) kn_write<KB>(L, k, val + ((size_t)bi * m + j) * k, idx + ((size_t)bi * m + j) * k);
 }
 
-// ---- boxed: a wave of 64 sorted queries, the candidate blocks that can still matter -----------------------------------------
-constexpr int KB_WAVES = 4;  // waves per workgroup, each on its own (no barrier)
+// ---- boxed: the walk of box_bound.hpp with knn's list ----------------------------------------------------------------------
+template <int KB>
+struct KnList {
+    // NaN ranks first and +inf is admitted while a list is not full: superblocks at +inf are visited, and a wave with a
+    // non-finite query or candidate set (whose points the boxes leave out) walks every superblock untested
+    static constexpr bool kNonFinite = true;
+    u64 L[KB];
+    float thr;
+    bool search;
+    __device__ __forceinline__ KnList(bool search_, int k) : search(search_) {
+#pragma unroll
+        for (int t = 0; t < KB; t++) L[t] = (search && t >= KB - k) ? ~0ull : 0ull;
+        thr = search ? __uint_as_float(0x7FC00000u) : -INFINITY;
+    }
+    // +inf while the list is not full (thr NaN; only in a finite wave, where thr is never -inf); -inf in a lane that does not
+    // search, which no bound is <=
+    __device__ __forceinline__ float prune() const { return thr != thr ? INFINITY : thr; }
+    // ties pass: visits go in any order and the keys settle them.  A lane that does not search admits nothing.
+    __device__ __forceinline__ bool admit(float d) const { return !(d > thr) && search; }
+    // at once (a buffer as the scan's, flushed inside the visits, pushed this kernel into scratch; the nearest-first order fills
+    // the lists early anyway).  A padding record (index -1) is keyed above everything.
+    __device__ __forceinline__ void insert(float d, int oi, bool in) {
+        if (in) {
+            kn_insert<KB>(L, oi < 0 ? ~0ull : kn_key(d, (unsigned)oi));
+            thr = kn_thr(L[KB - 1]);
+        }
+    }
+};
 
 template <int KB>
-__global__ __launch_bounds__(64 * KB_WAVES) void knn_boxes_kernel(
+__global__ __launch_bounds__(64 * TB_WAVES) void knn_boxes_kernel(
     int b, int m, int k, int npq, int npc, const float *__restrict__ qxyz, const int *__restrict__ qorig,
     const float *__restrict__ qb64, const float *__restrict__ cxyz, const int *__restrict__ corig,
     const float *__restrict__ cb16, const float *__restrict__ cb64, const int *__restrict__ cflags,
     float *__restrict__ val, int *__restrict__ idx) {
-    const int lane = threadIdx.x & 63;
-    const int bpb = ((npq >> 6) + KB_WAVES - 1) / KB_WAVES;  // workgroups per sample
-    const unsigned logical = rf::xcd_contiguous(blockIdx.x, gridDim.x);  // a sample's workgroups on one XCD
-    const int bi = logical / bpb;
-    const int group = (logical - bi * bpb) * KB_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (group * 64 >= npq) return;  // (uniform)
-    const int p = group * 64 + lane;
+    const TbPlace w = tb_place(npq);
+    if (w.group * 64 >= npq) return;  // (uniform)
+    const int bi = w.bi;
+    const int p = w.group * 64 + (threadIdx.x & 63);
     const float *__restrict__ Q = qxyz + ((size_t)bi * npq + p) * 3;
-    const float x2 = Q[0], y2 = Q[1], z2 = Q[2];
+    TbQuery q;
+    q.x = Q[0], q.y = Q[1], q.z = Q[2];
     const int oq = qorig[(size_t)bi * npq + p];
-    const bool search = oq >= 0;  // (a padding record searches nothing)
-    const u64 smask = __ballot(search);
+    q.search = oq >= 0;  // (a padding record searches nothing)
     // every superblock, untested: a non-finite query in the wave, or one in the candidate set (the sort's flag, behind pos0)
-    const bool full = __ballot(search && !(isfinite(x2) && isfinite(y2) && isfinite(z2))) != 0ull || cflags[2 * b + bi] != 0;
-    u64 L[KB];
-#pragma unroll
-    for (int t = 0; t < KB; t++) L[t] = (search && t >= KB - k) ? ~0ull : 0ull;
-    float thr = search ? __uint_as_float(0x7FC00000u) : -INFINITY;
-    const float *__restrict__ CX = cxyz + (size_t)bi * npc * 3;
-    const int *__restrict__ CO = corig + (size_t)bi * npc;
+    q.full = __ballot(q.search && !(isfinite(q.x) && isfinite(q.y) && isfinite(q.z))) != 0ull || cflags[2 * b + bi] != 0;
+    q.qb = qb64 + ((size_t)bi * (npq >> 6) + w.group) * 8;
     const int nsb = npc >> 6;
-    const float *__restrict__ B16 = cb16 + (size_t)bi * nsb * 24;
-    const float *__restrict__ B64 = cb64 + (size_t)bi * nsb * 8;
-    // the lane's pruning distance: +inf while its list is not full (only in a finite wave: thr is then never -inf)
-#define KB_PRUNE (thr != thr ? INFINITY : thr)
-
-    // One candidate, inserted at once (a buffer as the scan's, flushed inside the visits, pushed this kernel into scratch; its
-    // nearest-first order fills the lists early anyway).  A padding record (index -1, coordinates +inf) is keyed above everything
-    // and never enters.  A lane that does not search admits nothing.
-#define KB_CONSIDER(cx, cy, cz, oi)                                                               \
-    {                                                                                             \
-        const float dx_ = (cx) - x2, dy_ = (cy) - y2, dz_ = (cz) - z2;                             \
-        const float xx_ = dx_ * dx_, yy_ = dy_ * dy_, zz_ = dz_ * dz_;                             \
-        const float d_ = (xx_ + yy_) + zz_;                                                        \
-        const bool in_ = !(d_ > thr) && search;                                                    \
-        if (__ballot(in_) != 0ull) { /* wave-uniform */                                            \
-            asm volatile("; some lane may insert");                                                \
-            if (in_) {                                                                             \
-                kn_insert<KB>(L, (oi) < 0 ? ~0ull : kn_key(d_, (unsigned)(oi)));                   \
-                thr = kn_thr(L[KB - 1]);                                                           \
-            }                                                                                      \
-        }                                                                                         \
-    }
-#ifdef KB_STATS
-    int nblk = 0;  // (uniform) 16-record block scans
-#endif
-    auto visit = [&](int sb, bool test) {
-        unsigned hm = 0xFFu;  // the half-blocks to scan
-        if (test) {
-            const float *bx = B16 + (size_t)sb * 24;  // (uniform -> scalar loads)
-            float bb[24];
-#pragma unroll
-            for (int i = 0; i < 24; i++) bb[i] = bx[i];
-            hm = 0u;
-            const float pr = KB_PRUNE;
-#pragma unroll
-            for (int blk = 0; blk < 4; blk++) {
-                const float lb = tb_bound(bb[blk * 6], bb[blk * 6 + 1], bb[blk * 6 + 2], bb[blk * 6 + 3], bb[blk * 6 + 4],
-                                          bb[blk * 6 + 5], x2, y2, z2, x2, y2, z2);
-                if ((__ballot(lb <= pr) & smask) != 0ull) hm |= 3u << (2 * blk);  // (uniform)
-            }
-            if (hm == 0u) return;
-        }
-#ifdef KB_STATS
-        nblk += __builtin_popcount(hm) >> 1;
-#endif
-        const float *cb = CX + (size_t)sb * 192;
-        const int *ob = CO + sb * 64;
-        float ca[24], cc[24];
-        int oa[8], oc[8];
-#define KB_FETCH(CC, O, H)                                              \
-    {                                                                   \
-        const float *cp_ = cb + (H) * 24;                               \
-        const int *op_ = ob + (H) * 8;                                  \
-        _Pragma("unroll") for (int i = 0; i < 24; i++) CC[i] = cp_[i];  \
-        _Pragma("unroll") for (int i = 0; i < 8; i++) O[i] = op_[i];    \
-    }
-#define KB_SCAN8(CC, O) _Pragma("unroll") for (int u = 0; u < 8; u++) KB_CONSIDER(CC[u * 3], CC[u * 3 + 1], CC[u * 3 + 2], O[u])
-        int h = __builtin_ctz(hm);
-        hm &= hm - 1u;
-        KB_FETCH(ca, oa, h);
-        for (;;) {
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): set a has arrived
-            __builtin_amdgcn_sched_barrier(0);
-            const bool more_b = hm != 0u;
-            if (more_b) {
-                h = __builtin_ctz(hm);
-                hm &= hm - 1u;
-                KB_FETCH(cc, oc, h);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            KB_SCAN8(ca, oa);
-            if (!more_b) break;
-            __builtin_amdgcn_s_waitcnt(0xC07F);  // set c has arrived
-            __builtin_amdgcn_sched_barrier(0);
-            const bool more_a = hm != 0u;
-            if (more_a) {
-                h = __builtin_ctz(hm);
-                hm &= hm - 1u;
-                KB_FETCH(ca, oa, h);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            KB_SCAN8(cc, oc);
-            if (!more_a) break;
-        }
-#undef KB_SCAN8
-#undef KB_FETCH
-    };
-
-    if (full) {
-        for (int sb = 0; sb < nsb; sb++) visit(sb, false);
-    } else {
-        // the wave's own box (its 64 queries are one superblock of their sorted set)
-        const float *qb = qb64 + ((size_t)bi * (npq >> 6) + group) * 8;
-        const float qlx = qb[0], qly = qb[1], qlz = qb[2], qhx = qb[4], qhy = qb[5], qhz = qb[6];
-        // 1. the candidate superblock nearest to the wave's box goes first
-        float best = INFINITY;
-        int arg = 0;
-        for (int r0 = 0; r0 < nsb; r0 += 64) {
-            const int g = r0 + lane;
-            float lb = INFINITY;
-            if (g < nsb) {
-                const float4 lo = *(const float4 *)(B64 + (size_t)g * 8), hi = *(const float4 *)(B64 + (size_t)g * 8 + 4);
-                lb = tb_bound(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, qlx, qly, qlz, qhx, qhy, qhz);
-            }
-            if (lb < best) best = lb, arg = g;
-        }
-        const float wmin = tb_wave_min(best);
-        const u64 at = __ballot(best == wmin);
-        const int seed = at != 0ull ? __builtin_amdgcn_readlane(arg, __builtin_ctzll(at)) : 0;
-        visit(seed, false);
-        // 2. every other superblock whose box is not beyond the wave's largest k-th distance (which shrinks as the visits go),
-        //    nearest first, 64 superblocks at a time.  (No finite bound is skipped while a lane's list is not full: its
-        //    pruning distance is +inf then.)
-        float wk = tb_wave_max(search ? KB_PRUNE : -INFINITY);
-        for (int r0 = 0; r0 < nsb; r0 += 64) {
-            const int g = r0 + lane;
-            float lb = INFINITY;
-            if (g < nsb && g != seed) {
-                const float4 lo = *(const float4 *)(B64 + (size_t)g * 8), hi = *(const float4 *)(B64 + (size_t)g * 8 + 4);
-                lb = tb_bound(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, qlx, qly, qlz, qhx, qhy, qhz);
-            }
-            bool pend = g < nsb && g != seed && lb <= wk;
-            while (__ballot(pend) != 0ull) {  // (uniform)
-                const float wmin2 = tb_wave_min(pend ? lb : INFINITY);
-                if (!(wmin2 <= wk)) break;
-                const int jn = __builtin_ctzll(__ballot(pend && lb == wmin2));
-                pend = pend && lane != jn;
-                visit(r0 + jn, true);
-                wk = tb_wave_max(search ? KB_PRUNE : -INFINITY);
-            }
-        }
-    }
-#undef KB_CONSIDER
-#undef KB_PRUNE
-    if (search) {
+    const TbCands c = {cxyz + (size_t)bi * npc * 3, corig + (size_t)bi * npc, cb16 + (size_t)bi * nsb * 24,
+                       cb64 + (size_t)bi * nsb * 8, nsb};
+    KnList<KB> L(q.search, k);
+    TbStats st;
+    tb_walk(L, q, c, st);
+    if (q.search) {
         const size_t o = ((size_t)bi * m + oq) * k;
-        kn_write<KB>(L, k, val + o, idx + o);
-#ifdef KB_STATS
-        idx[o] = nblk;
+        kn_write<KB>(L.L, k, val + o, idx + o);
+#ifdef TB_STATS
+        idx[o] = st.scans;
 #endif
     }
 }
@@ -442,19 +302,10 @@ int rf_knn_boxes(int b, int n, int m, int k, const float *xyz1, const float *xyz
     rfp::Sorted sv[2];
     sv[0] = rfp::sorted_view(b, n, sorted1 ? sorted1 : workspace);
     sv[1] = rfp::sorted_view(b, m, sorted2 ? sorted2 : (const char *)workspace + rfp::sorted_bytes(b, n));
-    {  // the sets that came without a handle, in one launch
-        int nn[2];
-        const float *src[2];
-        rfp::Sorted out[2];
-        int c = 0;
-        if (!sorted1) nn[c] = n, src[c] = xyz1, out[c] = sv[0], c++;
-        if (!sorted2) nn[c] = m, src[c] = xyz2, out[c] = sv[1], c++;
-        if (c > 0)
-            if (int e = rfp::sort_sets(b, c, nn, src, out, s, nullptr)) return e;
-    }
-    const dim3 grid(rf::ceil_div(sv[1].npad / 64, KB_WAVES) * b);
+    if (int e = rfp::sort_missing(b, n, m, xyz1, xyz2, sv[0], sv[1], sorted1 != nullptr, sorted2 != nullptr, s)) return e;
+    const dim3 grid(rf::ceil_div(sv[1].npad / 64, TB_WAVES) * b);
 #define KB_GO(KB)                                                                                                              \
-    RF_LAUNCH("knn_boxes", knn_boxes_kernel<KB>, grid, dim3(64 * KB_WAVES), 0, s, b, m, k, sv[1].npad, sv[0].npad, sv[1].xyz, \
+    RF_LAUNCH("knn_boxes", knn_boxes_kernel<KB>, grid, dim3(64 * TB_WAVES), 0, s, b, m, k, sv[1].npad, sv[0].npad, sv[1].xyz, \
               sv[1].orig, sv[1].box64, sv[0].xyz, sv[0].orig, sv[0].box16, sv[0].box64, sv[0].pos0, val, idx)
     KN_DISPATCH(k, KB_GO);
 #undef KB_GO

@@ -2307,6 +2307,17 @@ int sort_sets(int b, int nsets, const int *n, const float *const *src, const Sor
     return RF_OK;
 }
 
+int sort_missing(int b, int n, int m, const float *xyz1, const float *xyz2, const Sorted &s1, const Sorted &s2, bool have1,
+                 bool have2, hipStream_t s) {
+    int nn[2];
+    const float *src[2];
+    Sorted out[2];
+    int c = 0;
+    if (!have1) nn[c] = n, src[c] = xyz1, out[c] = s1, c++;
+    if (!have2) nn[c] = m, src[c] = xyz2, out[c] = s2, c++;
+    return c > 0 ? sort_sets(b, c, nn, src, out, s, nullptr) : RF_OK;
+}
+
 // The sweep over two sorted sets.  dirs bit 0: nearest neighbour of every point of set 0 in set 1
 // (-> dist1/idx1), bit 1: the opposite (-> dist2/idx2).  A direction that is not asked for costs
 // nothing: its workgroups are not launched.

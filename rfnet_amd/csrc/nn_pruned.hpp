@@ -43,6 +43,10 @@ size_t sorted_bytes(int b, int n);
 Sorted sorted_view(int b, int n, const void *buf);
 int sort_sets(int b, int nsets, const int *n, const float *const *src, const Sorted *out, hipStream_t s,
               unsigned long long *dbg, const int *const *lens = nullptr);
+// Sort the sets of a pair (xyz1 -> s1, xyz2 -> s2) that did not come from the caller as handles (have1 / have2), in one
+// sort_sets launch; nothing when both did.
+int sort_missing(int b, int n, int m, const float *xyz1, const float *xyz2, const Sorted &s1, const Sorted &s2, bool have1,
+                 bool have2, hipStream_t s);
 int sweep_sorted(int b, int n, int m, const Sorted &s0, const Sorted &s1, float *dist1, int *idx1, float *dist2,
                  int *idx2, int dirs, hipStream_t s, unsigned long long *stats_dev);
 

@@ -2,8 +2,8 @@
 """knn_point on one MI355X: the scan kernel (rf_knn), the boxed kernel with its own sort and on caller sort handles
 (rf_knn_boxes), and the tensor expression it replaces (tf_grouping.py:64-73: the (b, m, n, 3) difference, sum, topk) -- same
 process, same seeded inputs, alternated, device events after warm-up; torch.cuda.max_memory_allocated per path; the boxed
-kernel's evaluated-pair fraction with --stats (a build with -DKB_STATS: knn_boxes_kernel then writes its 16-record block scans
-per wave into idx[..., 0]; python tools/build_variant.py kbstats -DKB_STATS, RFOPS_LIB=rfnet_amd/variants/librfops_kbstats.so).
+kernel's evaluated-pair fraction with --stats (a build with -DTB_STATS: knn_boxes_kernel then writes its 16-record block scans
+per wave into idx[..., 0]; python tools/build_variant.py tbstats -DTB_STATS, RFOPS_LIB=rfnet_amd/variants/librfops_tbstats.so).
 usage: python tools/ab_knn.py [--reps R] [--stats] [--out FILE]"""
 import argparse
 import json
