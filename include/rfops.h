@@ -244,6 +244,31 @@ size_t rf_farthestpointsampling_sorted_workspace_bytes(int b, int n);
 int rf_farthestpointsampling_sorted(int b, int n, int m, int form, const float *inp, void *workspace,
                                     size_t workspace_bytes, int *out, float *new_xyz, rf_stream_t stream);
 
+/* ---- ragged batches: per-sample point counts (sampling, grouping, neighbour search) --------
+ * The conventions of rf_nn_distance_lengths, for the ops that run BEFORE the losses on the same padded clouds.  A count argument
+ * (len, len1, len2, len_out) is a DEVICE int32 array of b values or NULL ("all"), 4-byte aligned; the kernels read it themselves
+ * (no host synchronisation: every call captures into a HIP graph and a replay sees new counts) and CLAMP a value outside its
+ * domain into [1, n] (resp. [1, m]), so a bad count can never make a kernel read or write outside the tensors.
+ *   - Valid slots are bit for bit what the plain entry point returns when called on that sample's unpadded slices alone (ties,
+ *     non-finite inputs and every documented quirk of the plain op included).
+ *   - Nothing in the padding reaches a result, whatever it holds (NaN, inf, 1e30, copies of valid points).
+ *   - PADDED OUTPUT SLOTS ARE ZEROS: index outputs 0, counts 0, floats +0.0f.  Deliberately not Chamfer's idx = -1: the index
+ *     outputs of this family feed gathers that do not range-check (rf_grouppoint, rf_gatherpoint, rf_threeinterpolate), and the
+ *     library already writes 0 for a row without a result (rf_sample_and_group's empty balls).  The counts say what is valid.
+ *   - The work shrinks with the counts; with all counts NULL or full the results equal the plain op's.
+ *   - Before any HIP call: RF_EINVAL for a negative or zero size (b == 0 is RF_OK), a NULL tensor, a misaligned count array,
+ *     tensor (4 bytes) or workspace (16 bytes); RF_EWORKSPACE for a workspace smaller than the matching _workspace_bytes.
+ *
+ * rf_farthestpointsampling_lengths: len = valid points per cloud; len_out (may be NULL) = how many samples each cloud wants,
+ * clamped into [1, m]: the cloud's chain of dependent iterations stops there (this is where ragged FPS saves time) and the tail
+ * of its row is zeros.  FPS is prefix-stable, so out[i, :len_out[i]] are the first len_out[i] samples of rf_farthestpointsampling
+ * on inp[i, :len[i]]; m > len[i] is legal and gives what the plain op gives there (point 0 repeated once every point is taken).
+ * new_xyz (b, m, 3) or NULL: the samples' coordinates (zeros behind len_out).  Kernels and workspace are chosen by the padded
+ * (n, m) exactly as rf_farthestpointsampling_ws chooses them; workspace may be NULL when the size query returns 0. */
+size_t rf_farthestpointsampling_lengths_workspace_bytes(int b, int n, int m);
+int rf_farthestpointsampling_lengths(int b, int n, int m, const float *inp, const int *len, const int *len_out,
+                                     void *workspace, size_t workspace_bytes, int *out, float *new_xyz, rf_stream_t stream);
+
 /* Replaces gatherpointLauncher (tf_sampling.cpp:125, tf_sampling_g.cu:206-208). */
 int rf_gatherpoint(int b, int n, int m, const float *inp, const int *idx, float *out,
                    rf_stream_t stream);
@@ -280,6 +305,22 @@ int rf_queryballpoint_boxes(int b, int n, int m, float radius, const float *radi
                             const float *xyz1, const float *xyz2, const void *sorted1, int *idx, int *pts_cnt,
                             void *workspace, size_t workspace_bytes, rf_stream_t stream);
 
+/* query_ball_point over a ragged batch (the conventions of the "ragged batches" block of the sampling section): len1 = points per
+ * dataset, len2 = queries per sample.  idx / pts_cnt on the valid queries are rf_queryballpoint's on xyz1[i, :len1[i]] and
+ * xyz2[i, :len2[i]] -- except that, unlike rf_queryballpoint, EVERY row is written: an empty ball and a padded query are
+ * idx = 0 ..., pts_cnt = 0.  radius_dev: NULL (use `radius`) or the reference's device scalar.  form: RF_GROUP_AUTO (the boxed
+ * kernel for padded datasets of 2048 points and more inside its domain, what the Python wrapper applies to the plain op),
+ * RF_GROUP_SCAN (every size; no workspace) or RF_GROUP_BOXES (64 <= n <= 65536, nsample <= 64, b <= 65535 on the PADDED sizes,
+ * else RF_EINVAL; a count below 64 is fine); same results.  workspace: rf_queryballpoint_lengths_workspace_bytes(b, n, m,
+ * nsample, form) bytes (0: may be NULL).  No sorted handle: a handle was sorted without counts. */
+#define RF_GROUP_AUTO 0
+#define RF_GROUP_SCAN 1
+#define RF_GROUP_BOXES 2
+size_t rf_queryballpoint_lengths_workspace_bytes(int b, int n, int m, int nsample, int form);
+int rf_queryballpoint_lengths(int b, int n, int m, float radius, const float *radius_dev, int nsample, const float *xyz1,
+                              const float *xyz2, const int *len1, const int *len2, int *idx, int *pts_cnt, void *workspace,
+                              size_t workspace_bytes, rf_stream_t stream, int form);
+
 /* The set-abstraction chain of BASELINE.json configs[2] as ONE call on caller buffers:
  *     fps_idx = farthest_point_sample(npoint, xyz)          (tf_sampling_g.cu:105-170)
  *     new_xyz = gather_point(xyz, fps_idx)                  (tf_sampling_g.cu:172-181)
@@ -297,6 +338,17 @@ size_t rf_sample_and_group_workspace_bytes(int b, int n);
 int rf_sample_and_group(int b, int n, int npoint, float radius, const float *radius_dev, int nsample, const float *xyz,
                         int *fps_idx, float *new_xyz, int *idx, int *pts_cnt, float *grouped_xyz, void *workspace,
                         size_t workspace_bytes, rf_stream_t stream, rf_stream_t aux_stream);
+
+/* rf_sample_and_group over a ragged batch: rf_farthestpointsampling_lengths (len, len_out) and rf_queryballpoint_lengths (boxed
+ * form, len1 = len, len2 = len_out) chained exactly as rf_sample_and_group chains the plain ops -- FPS writes new_xyz, the boxed
+ * query writes grouped_xyz, one sort shared by both or beside FPS on aux_stream, graph-capturable; same domain on the PADDED
+ * sizes (64 <= n <= 65536, nsample <= 64, b <= 65535).  Results: those of the two ragged entries called separately, bit for bit;
+ * rows of samples behind len_out[i] are zeros in all five outputs (grouped_xyz +0.0f). */
+size_t rf_sample_and_group_lengths_workspace_bytes(int b, int n);
+int rf_sample_and_group_lengths(int b, int n, int npoint, float radius, const float *radius_dev, int nsample, const float *xyz,
+                                const int *len, const int *len_out, int *fps_idx, float *new_xyz, int *idx, int *pts_cnt,
+                                float *grouped_xyz, void *workspace, size_t workspace_bytes, rf_stream_t stream,
+                                rf_stream_t aux_stream);
 
 /* Replaces groupPointLauncher / groupPointGradLauncher (tf_grouping.cpp:146,177,208).
  * points (b,n,c); idx (b,m,nsample); out / grad_out (b,m,nsample,c); grad_points (b,n,c)
@@ -342,6 +394,22 @@ size_t rf_knn_grad_workspace_bytes(int b, int n, int m, int k);
 int rf_knn_grad(int b, int n, int m, int k, const float *xyz1, const float *xyz2, const int *idx, const float *grad_val,
                 float *grad_xyz1, float *grad_xyz2, void *workspace, size_t workspace_bytes, rf_stream_t stream);
 
+/* knn_point over a ragged batch (the conventions of the "ragged batches" block of the sampling section; RF_GROUP_* forms as
+ * rf_queryballpoint_lengths, RF_GROUP_AUTO by the Python wrapper's thresholds on the padded sizes): len1 = candidates per
+ * sample, len2 = queries.  k <= min(n, 64) is checked on the host against the PADDED n; a sample with len1[i] < k (only the
+ * device knows) gets its len1[i] neighbours in slots [0, len1[i]) of every valid row, identical to rf_knn called with
+ * k = len1[i] on the slices, and zeros behind; rows of padded queries are zeros (val +0.0f, idx 0).  rf_knn_grad_lengths: the
+ * slots of padded queries, the slots t >= len1[i] and slots naming a candidate behind len1[i] contribute nothing, whatever idx
+ * and grad_val hold there; rows of padded candidates and padded queries are exactly +0.0f; valid rows are rf_knn_grad's on the
+ * slices (fp32 rounding of sums in double).  b == 0 is RF_OK. */
+size_t rf_knn_lengths_workspace_bytes(int b, int n, int m, int k, int form);
+int rf_knn_lengths(int b, int n, int m, int k, const float *xyz1, const float *xyz2, const int *len1, const int *len2, float *val,
+                   int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream, int form);
+size_t rf_knn_grad_lengths_workspace_bytes(int b, int n, int m, int k);
+int rf_knn_grad_lengths(int b, int n, int m, int k, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                        const int *idx, const float *grad_val, float *grad_xyz1, float *grad_xyz2, void *workspace,
+                        size_t workspace_bytes, rf_stream_t stream);
+
 /* -------------------------------------------------- interpolation (tf_ops/interpolation) - */
 /* Replace threenn_cpu / threeinterpolate_cpu / threeinterpolate_grad_cpu
  * (tf_interpolate.cpp:60-153; CPU-only ops in the reference).  xyz1 (b,n,3) unknown,
@@ -360,6 +428,16 @@ size_t rf_threenn_boxes_workspace_bytes(int b, int n, int m);
 int rf_threenn_boxes(int b, int n, int m, const float *xyz1, const float *xyz2, const void *sorted1,
                      const void *sorted2, float *dist, int *idx, void *workspace, size_t workspace_bytes,
                      rf_stream_t stream);
+/* three_nn over a ragged batch (the conventions of the "ragged batches" block of the sampling section; RF_GROUP_* forms as
+ * rf_queryballpoint_lengths): len1 = unknown points per sample, len2 = known points.  Rows [0, len1[i]) are rf_threenn's on
+ * the slices -- with len2[i] < 3 what rf_threenn gives for m < 3, (+inf, 0) in the slots without a neighbour -- and the rows
+ * behind len1[i] are zeros.  RF_GROUP_AUTO takes the boxed form where the Python wrapper takes it for the plain op, by the
+ * padded sizes; RF_GROUP_BOXES outside rf_threenn_boxes' domain is RF_EINVAL.  rf_threeinterpolate and its gradient take the
+ * result as it is: the zero-filled indices of padded rows are in range (they interpolate known point 0 with weight rows the
+ * caller left there; the counts say which rows mean something). */
+size_t rf_threenn_lengths_workspace_bytes(int b, int n, int m, int form);
+int rf_threenn_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2, float *dist,
+                       int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream, int form);
 int rf_threeinterpolate(int b, int m, int c, int n, const float *points, const int *idx,
                         const float *weight, float *out, rf_stream_t stream);
 int rf_threeinterpolate_grad(int b, int n, int c, int m, const float *grad_out, const int *idx,

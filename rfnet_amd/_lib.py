@@ -72,12 +72,18 @@ SIGNATURES = {
     "rf_farthestpointsampling_ws": (_i, [_i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
     "rf_farthestpointsampling_sorted_workspace_bytes": (_sz, [_i, _i]),
     "rf_farthestpointsampling_sorted": (_i, [_i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "rf_farthestpointsampling_lengths_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_farthestpointsampling_lengths": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "rf_gatherpoint": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "rf_scatteraddpoint": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "rf_queryballpoint": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_queryballpoint_dev": (_i, [_i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_queryballpoint_boxes_workspace_bytes": (_sz, [_i, _i]),
     "rf_queryballpoint_boxes": (_i, [_i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rf_queryballpoint_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "rf_queryballpoint_lengths": (_i, [_i, _i, _i, _f, _vp, _i] + [_vp] * 7 + [_sz, _vp, _i]),
+    "rf_sample_and_group_lengths_workspace_bytes": (_sz, [_i, _i]),
+    "rf_sample_and_group_lengths": (_i, [_i, _i, _i, _f, _vp, _i] + [_vp] * 9 + [_sz, _vp, _vp]),
     "rf_sample_and_group_workspace_bytes": (_sz, [_i, _i]),
     "rf_sample_and_group": (_i, [_i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "rf_grouppoint": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -87,9 +93,15 @@ SIGNATURES = {
     "rf_knn": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_knn_boxes_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_knn_boxes": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
+    "rf_knn_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "rf_knn_lengths": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp, _i]),
+    "rf_knn_grad_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "rf_knn_grad_lengths": (_i, [_i, _i, _i, _i] + [_vp] * 9 + [_sz, _vp]),
     "rf_knn_grad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_knn_grad": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_threenn": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "rf_threenn_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "rf_threenn_lengths": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp, _i]),
     "rf_threenn_boxes_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_threenn_boxes": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rf_threeinterpolate": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -574,8 +574,12 @@ def earth_mover(xyz1, xyz2, with_grad=False, mode="auto", lengths1=None, lengths
 
 # ------------------------------------------------------------------ sampling ---------------
 @H.on_input_device
-def farthest_point_sample(npoint, inp, _pin_reg=False):
+def farthest_point_sample(npoint, inp, lengths=None, npoints=None, with_xyz=False, _pin_reg=False):
     """FarthestPointSampleGpuOp, tf_ops/sampling/tf_sampling.cpp:95-123 -> (b,npoint) int32.
+
+    lengths / npoints: a ragged batch (rf_farthestpointsampling_lengths) -- lengths[i] valid points in cloud i, npoints[i]
+    samples wanted from it (at most npoint); row i holds the samples of inp[i, :lengths[i]] and zeros behind npoints[i].
+    with_xyz (ragged form only): also the samples' coordinates (b,npoint,3), zeros behind npoints[i].
     (_pin_reg: the kernels of the unsorted cloud whatever the size -- rf_farthestpointsampling; a measurement aid.)"""
     npoint = int(npoint)
     if npoint <= 0:
@@ -585,6 +589,23 @@ def farthest_point_sample(npoint, inp, _pin_reg=False):
     if not _shape3(p, 3):
         raise H.invalid("FarthestPointSample expects (batch_size,num_points,3) inp shape")
     b, n = p.shape[0], p.shape[1]
+    if lengths is not None or npoints is not None:
+        if _pin_reg:
+            raise H.invalid("FarthestPointSample: _pin_reg is a measurement aid of the plain op")
+        if n == 0:
+            raise H.invalid("FarthestPointSample: a ragged batch needs at least one point per cloud")
+        ln, lo = _check_lengths(lengths, b, n, "lengths"), _check_lengths(npoints, b, npoint, "npoints")
+        dev = st.device_()
+        p, = st.up(p)
+        ln, lo = _lengths_up(ln, dev, n), _lengths_up(lo, dev, npoint)
+        out = H.empty((b, npoint), I32, dev)
+        nx = H.empty((b, npoint, 3), F32, dev) if with_xyz else None
+        ws, wsz = H.workspace(lib.rf_farthestpointsampling_lengths_workspace_bytes(b, n, npoint), dev, "fps")
+        check(lib.rf_farthestpointsampling_lengths(b, n, npoint, H.ptr(p), H.ptr(ln), H.ptr(lo), H.ptr(ws), wsz, H.ptr(out),
+                                                   H.ptr(nx), H.stream(dev)), "rf_farthestpointsampling_lengths")
+        return (st.give(out), st.give(nx)) if with_xyz else st.give(out)
+    if with_xyz:
+        raise H.invalid("FarthestPointSample: with_xyz belongs to the ragged form (farthest_point_sample_sorted has its own)")
     dev = st.device_()
     p, = st.up(p)
     out = H.empty((b, npoint), I32, dev)
@@ -669,20 +690,36 @@ def gather_point_grad(inp, idx, out_g):
 
 # ------------------------------------------------------------------ grouping ---------------
 QB_BOXES_MIN_N = 2048  # datasets from this size on take the boxed kernel (its sort costs ~20 us whatever the size)
+GROUP_FORMS = {"auto": 0, "scan": 1, "boxes": 2}  # RF_GROUP_* (include/rfops.h): the `form` of the ragged entries
+
+
+def _radius_arg(radius, dev):
+    """-> (value, device tensor or None): a CUDA radius tensor is the reference's op input (tf_grouping.cpp:18,93-95)."""
+    if isinstance(radius, torch.Tensor) and radius.is_cuda:
+        if radius.device != dev:
+            raise ValueError(f"all GPU inputs of one op must live on the same device: got {dev} and {radius.device}")
+        return 0.0, radius.detach().reshape(-1)[:1].to(F32).contiguous()
+    return float(np.float32(float(radius))), None
 
 
 @H.on_input_device
-def query_ball_point(radius, nsample, xyz1, xyz2, sorted1=None, form="auto"):
+def query_ball_point(radius, nsample, xyz1, xyz2, sorted1=None, form="auto", lengths1=None, lengths2=None):
     """QueryBallPointGpuOp, tf_ops/grouping/tf_grouping.cpp:68-110 -> idx (b,m,nsample), pts_cnt (b,m).
 
     Rows whose ball is empty are not written by the kernel (as in the reference, whose output
     buffer is then uninitialised); this wrapper allocates idx zero-filled so they read 0.
     form: "auto" (the boxed kernel for datasets of QB_BOXES_MIN_N points and more, the scan below that), "boxes",
     "scan" -- same results; sorted1: an rf_nn_sort handle of xyz1 (nn_sort), skips the boxed form's own sort.
+    lengths1 / lengths2: a ragged batch (rf_queryballpoint_lengths) -- points per dataset, queries per sample; EVERY row is
+    then written by the kernel: an empty ball and a padded query read idx 0, pts_cnt 0.  Not together with sorted1 (a handle
+    was sorted without counts).
     """
     nsample = int(nsample)
     if nsample <= 0:
         raise H.invalid("QueryBallPoint expects positive nsample")
+    ragged = lengths1 is not None or lengths2 is not None
+    if ragged and sorted1 is not None:
+        raise H.invalid("QueryBallPoint: lengths cannot be combined with a sorted handle (it was sorted without counts)")
     st = H.Staged()
     d, q = st.take(xyz1, F32), st.take(xyz2, F32)
     if not _shape3(d, 3):
@@ -690,6 +727,26 @@ def query_ball_point(radius, nsample, xyz1, xyz2, sorted1=None, form="auto"):
     if not _shape3(q, 3):
         raise H.invalid("QueryBallPoint expects (batch_size, npoint, 3) xyz2 shape.")
     b, n, m = d.shape[0], d.shape[1], q.shape[1]
+    if ragged:
+        if form not in GROUP_FORMS:
+            raise H.invalid(f"QueryBallPoint: form must be one of {sorted(GROUP_FORMS)}")
+        if q.shape[0] != b or n == 0 or m == 0:
+            raise H.invalid("QueryBallPoint: a ragged batch needs one non-empty dataset and query set per sample")
+        l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+        dev = st.device_()
+        d, q = st.up(d, q)
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        r, rt = _radius_arg(radius, dev)
+        f = GROUP_FORMS[form]
+        wsz = lib.rf_queryballpoint_lengths_workspace_bytes(b, n, m, nsample, f)
+        if form == "boxes" and not wsz:
+            raise H.invalid("QueryBallPoint: the boxed form takes datasets of 64..65536 points and nsample <= 64")
+        idx, cnt = H.empty((b, m, nsample), I32, dev), H.empty((b, m), I32, dev)
+        ws = H.empty((wsz // 4,), F32, dev) if wsz else None
+        check(lib.rf_queryballpoint_lengths(b, n, m, r, H.ptr(rt), nsample, H.ptr(d), H.ptr(q), H.ptr(l1), H.ptr(l2),
+                                            H.ptr(idx), H.ptr(cnt), H.ptr(ws), wsz, H.stream(dev), f),
+              "rf_queryballpoint_lengths")
+        return st.give(idx), st.give(cnt)
     dev = st.device_()
     d, q = st.up(d, q)
     idx = H.zeros((b, m, nsample), I32, dev)
@@ -722,10 +779,12 @@ def query_ball_point(radius, nsample, xyz1, xyz2, sorted1=None, form="auto"):
 
 
 @H.on_input_device
-def sample_and_group(npoint, radius, nsample, xyz, aux_stream=None):
+def sample_and_group(npoint, radius, nsample, xyz, aux_stream=None, lengths=None, npoints=None):
     """rf_sample_and_group: farthest_point_sample -> gather_point -> query_ball_point -> group_point(xyz) as one call
     -> (fps_idx (b,npoint), new_xyz (b,npoint,3), idx (b,npoint,nsample), pts_cnt (b,npoint), grouped_xyz (b,npoint,nsample,3)),
-    bit-identical to the four ops.  aux_stream: a torch.cuda.Stream on which the dataset's sort runs beside FPS."""
+    bit-identical to the four ops.  aux_stream: a torch.cuda.Stream on which the dataset's sort runs beside FPS.
+    lengths / npoints: a ragged batch (rf_sample_and_group_lengths) -- points per cloud, samples wanted per cloud; the rows of
+    samples behind npoints[i] are zeros in all five outputs."""
     npoint, nsample = int(npoint), int(nsample)
     if npoint <= 0:
         raise H.invalid("FarthestPointSample expects positive npoint")
@@ -736,8 +795,11 @@ def sample_and_group(npoint, radius, nsample, xyz, aux_stream=None):
     if not _shape3(p, 3):
         raise H.invalid("FarthestPointSample expects (batch_size,num_points,3) inp shape")
     b, n = p.shape[0], p.shape[1]
+    ragged = lengths is not None or npoints is not None
+    ln, lo = _check_lengths(lengths, b, n, "lengths"), _check_lengths(npoints, b, npoint, "npoints")
     dev = st.device_()
     p, = st.up(p)
+    ln, lo = _lengths_up(ln, dev, n), _lengths_up(lo, dev, npoint)
     wsz = lib.rf_sample_and_group_workspace_bytes(b, n) if nsample <= 64 and b <= 65535 else 0
     if not wsz:
         raise H.invalid("sample_and_group takes clouds of 64..65536 points and nsample <= 64")
@@ -753,9 +815,14 @@ def sample_and_group(npoint, radius, nsample, xyz, aux_stream=None):
     cnt = H.empty((b, npoint), I32, dev)
     gx = H.empty((b, npoint, nsample, 3), F32, dev)
     ws = H.empty((wsz // 4,), F32, dev)
-    check(lib.rf_sample_and_group(b, n, npoint, r, H.ptr(rt), nsample, H.ptr(p), H.ptr(fi), H.ptr(nx), H.ptr(gi), H.ptr(cnt),
-                                  H.ptr(gx), H.ptr(ws), wsz, H.stream(dev),
-                                  aux_stream.cuda_stream if aux_stream is not None else None), "rf_sample_and_group")
+    aux = aux_stream.cuda_stream if aux_stream is not None else None
+    if ragged:
+        check(lib.rf_sample_and_group_lengths(b, n, npoint, r, H.ptr(rt), nsample, H.ptr(p), H.ptr(ln), H.ptr(lo), H.ptr(fi),
+                                              H.ptr(nx), H.ptr(gi), H.ptr(cnt), H.ptr(gx), H.ptr(ws), wsz, H.stream(dev), aux),
+              "rf_sample_and_group_lengths")
+    else:
+        check(lib.rf_sample_and_group(b, n, npoint, r, H.ptr(rt), nsample, H.ptr(p), H.ptr(fi), H.ptr(nx), H.ptr(gi),
+                                      H.ptr(cnt), H.ptr(gx), H.ptr(ws), wsz, H.stream(dev), aux), "rf_sample_and_group")
     if aux_stream is not None:
         ws.record_stream(aux_stream)  # the sort wrote the workspace on that stream
     return st.give(fi), st.give(nx), st.give(gi), st.give(cnt), st.give(gx)
@@ -816,12 +883,17 @@ TN_BOXES_MIN_KNOWN = 512  # fewer known points: a handful of blocks, nothing to 
 
 
 @H.on_input_device
-def three_nn(xyz1, xyz2, form="auto", sorted1=None, sorted2=None):
+def three_nn(xyz1, xyz2, form="auto", sorted1=None, sorted2=None, lengths1=None, lengths2=None):
     """ThreeNNOp, tf_ops/interpolation/tf_interpolate.cpp:157-187 -> dist (b,n,3), idx (b,n,3).
 
     form: "auto" (the boxed kernel over sorted copies of the two sets from TN_BOXES_MIN_PAIRS pairs per call on, the scan
     below that), "boxes", "scan" -- same results, ties included; sorted1 / sorted2: rf_nn_sort handles of xyz1 / xyz2
-    (nn_sort), which skip the boxed form's own sort of that set."""
+    (nn_sort), which skip the boxed form's own sort of that set.
+    lengths1 / lengths2: a ragged batch (rf_threenn_lengths) -- unknown / known points per sample; rows behind lengths1[i] come
+    back as zeros.  Not together with sorted handles (they were sorted without counts)."""
+    ragged = lengths1 is not None or lengths2 is not None
+    if ragged and (sorted1 is not None or sorted2 is not None):
+        raise H.invalid("ThreeNN: lengths cannot be combined with sorted handles (they were sorted without counts)")
     st = H.Staged()
     u, k = st.take(xyz1, F32), st.take(xyz2, F32)
     if not _shape3(u, 3):
@@ -829,6 +901,24 @@ def three_nn(xyz1, xyz2, form="auto", sorted1=None, sorted2=None):
     if not _shape3(k, 3):
         raise H.invalid("ThreeNN expects (b,m,3) xyz2 shape.")
     b, n, m = u.shape[0], u.shape[1], k.shape[1]
+    if ragged:
+        if form not in GROUP_FORMS:
+            raise H.invalid(f"ThreeNN: form must be one of {sorted(GROUP_FORMS)}")
+        if k.shape[0] != b or n == 0 or m == 0 or b > 65535:
+            raise H.invalid("ThreeNN: a ragged batch needs one non-empty set of each kind per sample (b <= 65535)")
+        l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+        dev = st.device_()
+        u, k = st.up(u, k)
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        f = GROUP_FORMS[form]
+        wsz = lib.rf_threenn_lengths_workspace_bytes(b, n, m, f)
+        if form == "boxes" and not wsz:
+            raise H.invalid("ThreeNN: the boxed form takes sets of 1..65536 points")
+        dist, idx = H.empty((b, n, 3), F32, dev), H.empty((b, n, 3), I32, dev)
+        ws = H.empty((wsz // 4,), F32, dev) if wsz else None
+        check(lib.rf_threenn_lengths(b, n, m, H.ptr(u), H.ptr(k), H.ptr(l1), H.ptr(l2), H.ptr(dist), H.ptr(idx), H.ptr(ws),
+                                     wsz, H.stream(dev), f), "rf_threenn_lengths")
+        return st.give(dist), st.give(idx)
     dev = st.device_()
     u, k = st.up(u, k)
     dist, idx = H.empty((b, n, 3), F32, dev), H.empty((b, n, 3), I32, dev)
@@ -892,21 +982,36 @@ def knn_auto_boxes(k, n, m):
 
 
 @H.on_input_device
-def knn_point(k, xyz1, xyz2, form="auto", sorted1=None, sorted2=None):
+def knn_point(k, xyz1, xyz2, form="auto", sorted1=None, sorted2=None, lengths1=None, lengths2=None):
     """knn_point (tf_ops/grouping/tf_grouping.py:48-73) on the GPU -> val (b,m,k) = -d, idx (b,m,k) int32: per query of xyz2 the
     k points of xyz1 of smallest squared distance, ascending, ties to the lower index (tf.nn.top_k's rule).
 
     form: "auto" (the boxed kernel over sorted copies of the two sets where it measured faster -- m >= KNN_BOXES_MIN_QUERIES,
     n >= KNN_BOXES_MIN_CANDIDATES, k <= KNN_BOXES_MAX_K -- the scan elsewhere), "boxes", "scan" -- same results, bit for bit; sorted1 / sorted2: rf_nn_sort handles (nn_sort(...).buf) of
-    xyz1 / xyz2, which skip the boxed form's own sort of that set."""
+    xyz1 / xyz2, which skip the boxed form's own sort of that set.
+    lengths1 / lengths2: a ragged batch (rf_knn_lengths) -- candidates / queries per sample.  Rows of padded queries come back
+    as zeros; a sample with fewer candidates than k gets its lengths1[i] neighbours and zeros behind them.  Not together with
+    sorted handles (they were sorted without counts)."""
     if form not in ("auto", "scan", "boxes"):
         raise H.invalid("knn_point: form must be one of auto, scan, boxes")
+    ragged = lengths1 is not None or lengths2 is not None
+    if ragged and (sorted1 is not None or sorted2 is not None):
+        raise H.invalid("knn_point: lengths cannot be combined with sorted handles (they were sorted without counts)")
     k = int(k)
     st = H.Staged()
     a, q, b, n, m = _knn_inputs(st, xyz1, xyz2, k, "KnnPoint")
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
     dev = st.device_()
     a, q = st.up(a, q)
     val, idx = H.empty((b, m, k), F32, dev), H.empty((b, m, k), I32, dev)
+    if ragged:
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        f = GROUP_FORMS[form]
+        wsz = int(lib.rf_knn_lengths_workspace_bytes(b, n, m, k, f))
+        ws = H.empty((wsz // 4,), F32, dev) if wsz else None
+        check(lib.rf_knn_lengths(b, n, m, k, H.ptr(a), H.ptr(q), H.ptr(l1), H.ptr(l2), H.ptr(val), H.ptr(idx), H.ptr(ws), wsz,
+                                 H.stream(dev), f), "rf_knn_lengths")
+        return st.give(val), st.give(idx)
     boxes = form == "boxes" or (form == "auto" and knn_auto_boxes(k, n, m))
     if boxes:
         wsz = int(lib.rf_knn_boxes_workspace_bytes(b, n, m))
@@ -919,8 +1024,9 @@ def knn_point(k, xyz1, xyz2, form="auto", sorted1=None, sorted2=None):
 
 
 @H.on_input_device
-def knn_point_grad(xyz1, xyz2, idx, grad_val):
-    """The gradient of knn_point's val -> (grad_xyz1 (b,n,3), grad_xyz2 (b,m,3)) (rf_knn_grad)."""
+def knn_point_grad(xyz1, xyz2, idx, grad_val, lengths1=None, lengths2=None):
+    """The gradient of knn_point's val -> (grad_xyz1 (b,n,3), grad_xyz2 (b,m,3)) (rf_knn_grad).  lengths1 / lengths2: the counts
+    of the ragged forward (rf_knn_grad_lengths): padded slots add nothing whatever they hold, padded rows are exactly 0."""
     st = H.Staged()
     ix, g = st.take(idx, I32), st.take(grad_val, F32)
     if ix.dim() != 3:
@@ -929,10 +1035,16 @@ def knn_point_grad(xyz1, xyz2, idx, grad_val):
     k = int(ix.shape[2])
     if tuple(ix.shape) != (b, m, k) or tuple(g.shape) != (b, m, k):
         raise H.invalid("KnnPointGrad expects (b,m,k) idx and grad_val shapes")
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
     dev = st.device_()
     a, q, ix, g = st.up(a, q, ix, g)
     g1, g2 = H.empty((b, n, 3), F32, dev), H.empty((b, m, 3), F32, dev)
     ws, wsz = H.workspace(lib.rf_knn_grad_workspace_bytes(b, n, m, k), dev, "knng")
+    if l1 is not None or l2 is not None:
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+        check(lib.rf_knn_grad_lengths(b, n, m, k, H.ptr(a), H.ptr(q), H.ptr(l1), H.ptr(l2), H.ptr(ix), H.ptr(g), H.ptr(g1),
+                                      H.ptr(g2), H.ptr(ws), wsz, H.stream(dev)), "rf_knn_grad_lengths")
+        return st.give(g1), st.give(g2)
     check(lib.rf_knn_grad(b, n, m, k, H.ptr(a), H.ptr(q), H.ptr(ix), H.ptr(g), H.ptr(g1), H.ptr(g2), H.ptr(ws), wsz,
                           H.stream(dev)), "rf_knn_grad")
     return st.give(g1), st.give(g2)

@@ -68,14 +68,17 @@ constexpr int QB_NS = 64;    // nsample up to which the hit lists are staged in 
 // half of the queries, so nearly every wave scans all n points; the loop issues 74 VALU + 49 SALU
 // instructions per 64-point step and is bound by the per-SIMD issue rate (~2.3 cycles per
 // instruction of either kind), not by memory (SQ_WAIT_INST_ANY = 20 % of wave cycles).
-template <bool STAGE>
+// RAGGED (rf_queryballpoint_lengths; the counts arrive as rfi::Counts, group_internal.hpp): the dataset is its first nv points,
+// the queries of the cloud its first mv; the wave's queries behind mv start "done" like the absent ones, every row of the
+// wave is written -- an empty ball and a padded query as index 0 and count 0 -- and a wave without a valid query scans nothing.
+template <bool STAGE, bool RAGGED = false>
 __global__ __launch_bounds__(QB_TPB) void query_ball_kernel(int n, int m, int nwaves_per_batch, int b,
                                                             float thresh, const float *__restrict__ radius_dev,
                                                             int nsample,
                                                             const float *__restrict__ xyz1,
                                                             const float *__restrict__ xyz2,
                                                             int *__restrict__ idx,
-                                                            int *__restrict__ pts_cnt) {
+                                                            int *__restrict__ pts_cnt, rfi::Counts<RAGGED> lens) {
     __shared__ int stage[STAGE ? QB_TPB / 64 : 1][QPW][STAGE ? QB_NS : 1];
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -83,9 +86,11 @@ __global__ __launch_bounds__(QB_TPB) void query_ball_kernel(int n, int m, int nw
     const int bi = w / nwaves_per_batch;
     if (bi >= b) return;
     if (radius_dev) thresh = ball_threshold_dev(radius_dev[0]);  // uniform
-    const int n_scan = thresh > 0.f ? n : 0;  // radius within the 1e-20 clamp: nothing is ever inside
+    const int nv = rfi::count1(lens, bi, n);
+    const int n_scan = thresh > 0.f ? nv : 0;  // radius within the 1e-20 clamp: nothing is ever inside
     const int q0 = (w - bi * nwaves_per_batch) * QPW;  // first query of this wave (within the cloud)
     const int nq = min(QPW, m - q0);
+    const int nqv = RAGGED ? max(0, min(nq, rfi::count2(lens, bi, m) - q0)) : nq;  // ... of which valid
     const float *__restrict__ D = xyz1 + (size_t)bi * n * 3;
     const float *__restrict__ Q = xyz2 + ((size_t)bi * m + q0) * 3;
     int *__restrict__ I = idx + ((size_t)bi * m + q0) * nsample;
@@ -98,14 +103,14 @@ __global__ __launch_bounds__(QB_TPB) void query_ball_kernel(int n, int m, int nw
         qx[i] = Q[ii * 3 + 0];
         qy[i] = Q[ii * 3 + 1];
         qz[i] = Q[ii * 3 + 2];
-        cnt[i] = i < nq ? 0 : nsample;  // absent queries are "done"
+        cnt[i] = i < nqv ? 0 : nsample;  // absent queries are "done"
         first[i] = -1;
     }
     // dataset points are fetched one step ahead of the tests (the early-exit loop would otherwise
     // expose the full L2 latency on every step)
     float nx, ny, nz;
     {
-        const int kk = min(lane, n - 1);
+        const int kk = min(lane, nv - 1);
         nx = D[kk * 3 + 0]; ny = D[kk * 3 + 1]; nz = D[kk * 3 + 2];
     }
     for (int k0 = 0; k0 < n_scan; k0 += 64) {
@@ -116,10 +121,10 @@ __global__ __launch_bounds__(QB_TPB) void query_ball_kernel(int n, int m, int nw
         const int k = k0 + lane;
         const float x1 = nx, y1 = ny, z1 = nz;
         {
-            const int kk = min(k + 64, n - 1);
+            const int kk = min(k + 64, nv - 1);
             nx = D[kk * 3 + 0]; ny = D[kk * 3 + 1]; nz = D[kk * 3 + 2];
         }
-        const unsigned long long valid = __ballot(k < n);
+        const unsigned long long valid = __ballot(k < nv);
         // all QPW tests first (independent VALU work), the scalar bookkeeping afterwards
         unsigned long long mask[QPW], any = 0ull;
 #pragma unroll
@@ -146,6 +151,11 @@ __global__ __launch_bounds__(QB_TPB) void query_ball_kernel(int n, int m, int nw
     // the wave's own LDS writes are visible to it without a barrier (in-order LDS queue)
 #pragma unroll
     for (int i = 0; i < QPW; i++) {
+        if (RAGGED && i < nq && (i >= nqv || cnt[i] == 0)) {  // a padded query, an empty ball: a defined row
+            for (int l = lane; l < nsample; l += 64) I[(size_t)i * nsample + l] = 0;
+            if (lane == 0) pts_cnt[(size_t)bi * m + q0 + i] = 0;
+            continue;
+        }
         if (i < nq) {
             if (cnt[i] > 0) {
                 if (STAGE) {
@@ -170,7 +180,10 @@ __global__ __launch_bounds__(QB_TPB) void query_ball_kernel(int n, int m, int nw
 // workgroup for the same 64 queries; each keeps the first `nsample` hits of its segment in LDS and
 // the workgroup concatenates the segments in order at the end (no global scratch, no second launch).
 constexpr int QL_SUB = 8;  // dataset points per scalar-load sub-chunk
-template <int QS, int NSMAX>
+// RAGGED: the QS segments cut the cloud's first nv points (so the work shrinks with the count; the result does not depend on
+// the cut), lanes whose query lies behind mv never append and report no hits, a workgroup of padded queries scans nothing, and
+// rows without a hit are written as index 0.
+template <int QS, int NSMAX, bool RAGGED = false>
 __global__ __launch_bounds__(64 * QS) void query_ball_lanes_kernel(int n, int m, int n_pad, int seg,
                                                                    float thresh,
                                                                    const float *__restrict__ radius_dev,
@@ -178,7 +191,7 @@ __global__ __launch_bounds__(64 * QS) void query_ball_lanes_kernel(int n, int m,
                                                                    const float *__restrict__ xyz1,
                                                                    const float *__restrict__ xyz2,
                                                                    int *__restrict__ idx,
-                                                                   int *__restrict__ pts_cnt) {
+                                                                   int *__restrict__ pts_cnt, rfi::Counts<RAGGED> lens) {
     __shared__ int list[QS][NSMAX][64];  // [segment][slot][query lane]
     __shared__ int segcnt[QS][64];
     const int lane = threadIdx.x & 63;
@@ -191,8 +204,14 @@ __global__ __launch_bounds__(64 * QS) void query_ball_lanes_kernel(int n, int m,
     const float qx = Q[0], qy = Q[1], qz = Q[2];
     int cnt = 0;
     if (radius_dev) thresh = ball_threshold_dev(radius_dev[0]);  // uniform
+    const int nv = rfi::count1(lens, bi, n), mv = rfi::count2(lens, bi, m);
+    if (RAGGED) {
+        seg = ((nv + QS - 1) / QS + QL_SUB - 1) / QL_SUB * QL_SUB;
+        if (q >= mv) cnt = nsample;  // a padded query: full from the start
+        if ((int)blockIdx.x * 64 >= mv) thresh = 0.f;  // (uniform) no valid query here
+    }
     // threshold 0: the radius does not exceed the 1e-20 clamp, nothing is ever inside (not even a NaN)
-    const int k_begin = sg * seg, k_end = thresh > 0.f ? min(n, k_begin + seg) : k_begin;
+    const int k_begin = sg * seg, k_end = thresh > 0.f ? min(nv, k_begin + seg) : k_begin;
     // Whole sub-chunks of 8 points: scalar prefetch one sub-chunk ahead, no per-point range test.
     // The hit path sits behind a wave-uniform branch on the compare mask (without it the compiler
     // predicates the 5 append instructions and issues them for every point).
@@ -240,18 +259,19 @@ __global__ __launch_bounds__(64 * QS) void query_ball_lanes_kernel(int n, int m,
     }
     // ragged tail of the cloud (n not a multiple of 8): the last 8 points, those below k_full skipped
     if (k_full < k_end) {
-        const int ks = n - QL_SUB;
+        const int ks = RAGGED ? k_end - QL_SUB : n - QL_SUB;  // (RAGGED: an index below 0 is clamped for the load and fails k >= k_full)
 #pragma unroll 1
         for (int u = 0; u < QL_SUB; u++) {
             const int k = ks + u;
-            const float d2 = rf::d2_fma(qx - D[k * 3], qy - D[k * 3 + 1], qz - D[k * 3 + 2]);
+            const int kl = RAGGED ? max(k, 0) : k;
+            const float d2 = rf::d2_fma(qx - D[kl * 3], qy - D[kl * 3 + 1], qz - D[kl * 3 + 2]);
             if (!(d2 >= thresh) && k >= k_full && k < k_end && cnt < nsample) {
                 list[sg][cnt][lane] = k;
                 cnt++;
             }
         }
     }
-    segcnt[sg][lane] = cnt;
+    segcnt[sg][lane] = (RAGGED && q >= mv) ? 0 : cnt;
     __syncthreads();
     // concatenate: query `ql`, output slot j <- the j-th hit over the segments in order
     int *__restrict__ I = idx + ((size_t)bi * m + (size_t)blockIdx.x * 64) * nsample;
@@ -267,6 +287,7 @@ __global__ __launch_bounds__(64 * QS) void query_ball_lanes_kernel(int n, int m,
             total += c;
         }
         if (total > 0) I[e] = val >= 0 ? val : first;  // empty balls are left untouched
+        else if (RAGGED) I[e] = 0;                     // ... RAGGED: written as index 0, like the rows of padded queries
     }
     if (threadIdx.x < nq) {
         int total = 0;
@@ -334,12 +355,17 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
 // consecutive dwords, conflict-free), staged ONCE per workgroup -- with every wave reading its 8 KB of boxes from global
 // memory the box phase alone was 20 of the launch's 36 us at C3 (the vector L1's 64 B/clk) -- then per wave its bitmap,
 // survivor list and output row.
+// RAGGED: the dataset was sorted WITH its counts (rfp::sort_sets' lens), so the records, the boxes and the non-finite flag are
+// those of its first nv points; the walk in index order stops at nv; the wave of a query behind mv writes the zeros of its row
+// (index 0, count 0, grouped +0) itself.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(1024) void query_ball_boxes_kernel(
     int n, int m, int npad, int words /* bitmap words per wave, a multiple of 128 */, float thresh,
     const float *__restrict__ radius_dev, int nsample, const float *__restrict__ xyz1,
     const float *__restrict__ xyz2, const float *__restrict__ sxyz, const int *__restrict__ sorig,
     const float *__restrict__ box64, const int *__restrict__ nonfinite, int *__restrict__ idx,
-    int *__restrict__ pts_cnt, float *__restrict__ grouped /* (b, m, nsample, 3) or NULL */, int zero_empty) {
+    int *__restrict__ pts_cnt, float *__restrict__ grouped /* (b, m, nsample, 3) or NULL */, int zero_empty,
+    rfi::Counts<RAGGED> lens) {
     extern __shared__ __attribute__((aligned(16))) unsigned qx_lds[];
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -372,6 +398,16 @@ __global__ __launch_bounds__(1024) void query_ball_boxes_kernel(
     const float *__restrict__ Q = xyz2 + ((size_t)bi * m + q) * 3;
     const float qx = Q[0], qy = Q[1], qz = Q[2];
     int *__restrict__ I = idx + ((size_t)bi * m + q) * nsample;
+    const int nv = rfi::count1(lens, bi, n);
+    if (RAGGED && q >= rfi::count2(lens, bi, m)) {  // (uniform) a padded query
+        if (lane == 0) pts_cnt[(size_t)bi * m + q] = 0;
+        QxP3 *__restrict__ GR = grouped ? (QxP3 *)grouped + ((size_t)bi * m + q) * nsample : nullptr;
+        for (int l = lane; l < nsample; l += 64) {
+            I[l] = 0;
+            if (GR) GR[l] = QxP3{0.f, 0.f, 0.f};
+        }
+        return;
+    }
     const float *__restrict__ SX = sxyz + (size_t)bi * npad * 3;
     const int *__restrict__ SO = sorig + (size_t)bi * npad;
     // The row leaves through here.  An EMPTY ball: pts_cnt = 0 and the row is left untouched, as the reference leaves it
@@ -469,11 +505,11 @@ __global__ __launch_bounds__(1024) void query_ball_boxes_kernel(
     } else {
         // the cloud in index order, 64 points per step, until nsample hits
         const float *__restrict__ D = xyz1 + (size_t)bi * n * 3;
-        for (int k0 = 0; k0 < n && total < nsample; k0 += 64) {
+        for (int k0 = 0; k0 < nv && total < nsample; k0 += 64) {
             const int k = k0 + lane;
-            const int kk = min(k, n - 1);
+            const int kk = min(k, nv - 1);
             const float d2 = rf::d2_fma(qx - D[(size_t)kk * 3], qy - D[(size_t)kk * 3 + 1], qz - D[(size_t)kk * 3 + 2]);
-            const bool hit = !(d2 >= thresh) && k < n;
+            const bool hit = !(d2 >= thresh) && k < nv;
             const unsigned long long mask = __ballot(hit);
             if (mask == 0ull) continue;
             const int pos = total + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
@@ -619,7 +655,8 @@ static float ball_threshold(float radius) {
 namespace rfi {
 // the boxed ball query on a sorted dataset (group_internal.hpp); the domain is the caller's to check
 int ball_boxes(int b, int n, int m, float radius, const float *radius_dev, int nsample, const float *xyz1, const float *xyz2,
-               const rfp::Sorted &so, int *idx, int *pts_cnt, float *grouped_xyz, int zero_empty, hipStream_t s) {
+               const rfp::Sorted &so, int *idx, int *pts_cnt, float *grouped_xyz, int zero_empty, hipStream_t s, bool ragged,
+               const int *len1, const int *len2) {
     const float thresh = radius_dev ? 1.f : ball_threshold(radius);
     const int words = ((n + 31) / 32 + 127) / 128 * 128;
     const int gpad = (so.npad / 64 + 63) & ~63;
@@ -627,17 +664,24 @@ int ball_boxes(int b, int n, int m, float radius, const float *radius_dev, int n
     // (C3, same device: 4 / 8 / 16 queries per workgroup 33.1 / 31.9 / 34.0 us)
     const int wpb = n <= 32768 ? 8 : 4;
     const size_t shmem = sizeof(unsigned) * ((size_t)6 * gpad + (size_t)wpb * (words + QX_LIST + QX_STAGE));
-    RF_LAUNCH("query_ball_boxes", query_ball_boxes_kernel, dim3(rf::ceil_div(m, wpb) * b), dim3(64 * wpb), shmem, s, n, m,
+    if (ragged) {
+        RF_LAUNCH("query_ball_boxes_lengths", query_ball_boxes_kernel<true>, dim3(rf::ceil_div(m, wpb) * b), dim3(64 * wpb), shmem,
+                  s, n, m, so.npad, words, thresh, radius_dev, nsample, xyz1, xyz2, so.xyz, so.orig, so.box64, so.pos0 + 2 * b, idx,
+                  pts_cnt, grouped_xyz, 1, rfi::Counts<true>{len1, len2});
+        return RF_OK;
+    }
+    RF_LAUNCH("query_ball_boxes", query_ball_boxes_kernel<false>, dim3(rf::ceil_div(m, wpb) * b), dim3(64 * wpb), shmem, s, n, m,
               so.npad, words, thresh, radius_dev, nsample, xyz1, xyz2, so.xyz, so.orig, so.box64, so.pos0 + 2 * b, idx, pts_cnt,
-              grouped_xyz, zero_empty);
+              grouped_xyz, zero_empty, rfi::Counts<false>{});
     return RF_OK;
 }
 }  // namespace rfi
 
-extern "C" {
+static bool qb_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
-static int queryball_impl(int b, int n, int m, float radius, const float *radius_dev, int nsample,
-                          const float *xyz1, const float *xyz2, int *idx, int *pts_cnt, rf_stream_t stream) {
+template <bool RAGGED>
+static int queryball_impl(int b, int n, int m, float radius, const float *radius_dev, int nsample, const float *xyz1,
+                          const float *xyz2, int *idx, int *pts_cnt, rf_stream_t stream, rfi::Counts<RAGGED> lens) {
     if (b < 0 || n < 0 || m < 0 || nsample <= 0) return RF_EINVAL;
     long nquery = (long)b * m;
     if (nquery == 0) return RF_OK;
@@ -657,35 +701,39 @@ static int queryball_impl(int b, int n, int m, float radius, const float *radius
         if (nsample <= 32) {
             constexpr int QS = 8;
             const int seg = rf::ceil_div(rf::ceil_div(n, QS), QL_SUB) * QL_SUB;
-            RF_LAUNCH("query_ball_point", (query_ball_lanes_kernel<QS, 32>), g, dim3(64 * QS), 0, s, n, m, n_pad,
-                      seg, thresh, radius_dev, nsample, xyz1, xyz2, idx, pts_cnt);
+            RF_LAUNCH(RAGGED ? "query_ball_point_lengths" : "query_ball_point", (query_ball_lanes_kernel<QS, 32, RAGGED>), g,
+                      dim3(64 * QS), 0, s, n, m, n_pad, seg, thresh, radius_dev, nsample, xyz1, xyz2, idx, pts_cnt, lens);
         } else {
             constexpr int QS = 4;
             const int seg = rf::ceil_div(rf::ceil_div(n, QS), QL_SUB) * QL_SUB;
-            RF_LAUNCH("query_ball_point", (query_ball_lanes_kernel<QS, 64>), g, dim3(64 * QS), 0, s, n, m, n_pad,
-                      seg, thresh, radius_dev, nsample, xyz1, xyz2, idx, pts_cnt);
+            RF_LAUNCH(RAGGED ? "query_ball_point_lengths" : "query_ball_point", (query_ball_lanes_kernel<QS, 64, RAGGED>), g,
+                      dim3(64 * QS), 0, s, n, m, n_pad, seg, thresh, radius_dev, nsample, xyz1, xyz2, idx, pts_cnt, lens);
         }
         return RF_OK;
     }
     if (nsample <= QB_NS) {
-        RF_LAUNCH("query_ball_point", query_ball_kernel<true>, dim3(rf::ceil_div(waves, QB_TPB / 64)),
-                  dim3(QB_TPB), 0, s, n, m, wpb, b, thresh, radius_dev, nsample, xyz1, xyz2, idx, pts_cnt);
+        RF_LAUNCH(RAGGED ? "query_ball_point_lengths" : "query_ball_point", (query_ball_kernel<true, RAGGED>),
+                  dim3(rf::ceil_div(waves, QB_TPB / 64)), dim3(QB_TPB), 0, s, n, m, wpb, b, thresh, radius_dev, nsample, xyz1, xyz2,
+                  idx, pts_cnt, lens);
     } else {
-        RF_LAUNCH("query_ball_point", query_ball_kernel<false>, dim3(rf::ceil_div(waves, QB_TPB / 64)),
-                  dim3(QB_TPB), 0, s, n, m, wpb, b, thresh, radius_dev, nsample, xyz1, xyz2, idx, pts_cnt);
+        RF_LAUNCH(RAGGED ? "query_ball_point_lengths" : "query_ball_point", (query_ball_kernel<false, RAGGED>),
+                  dim3(rf::ceil_div(waves, QB_TPB / 64)), dim3(QB_TPB), 0, s, n, m, wpb, b, thresh, radius_dev, nsample, xyz1, xyz2,
+                  idx, pts_cnt, lens);
     }
     return RF_OK;
 }
 
+extern "C" {
+
 int rf_queryballpoint(int b, int n, int m, float radius, int nsample, const float *xyz1,
                       const float *xyz2, int *idx, int *pts_cnt, rf_stream_t stream) {
-    return queryball_impl(b, n, m, radius, nullptr, nsample, xyz1, xyz2, idx, pts_cnt, stream);
+    return queryball_impl<false>(b, n, m, radius, nullptr, nsample, xyz1, xyz2, idx, pts_cnt, stream, {});
 }
 
 int rf_queryballpoint_dev(int b, int n, int m, const float *radius_dev, int nsample, const float *xyz1,
                           const float *xyz2, int *idx, int *pts_cnt, rf_stream_t stream) {
     if (!radius_dev) return RF_EINVAL;
-    return queryball_impl(b, n, m, 0.f, radius_dev, nsample, xyz1, xyz2, idx, pts_cnt, stream);
+    return queryball_impl<false>(b, n, m, 0.f, radius_dev, nsample, xyz1, xyz2, idx, pts_cnt, stream, {});
 }
 
 
@@ -715,6 +763,47 @@ int rf_queryballpoint_boxes(int b, int n, int m, float radius, const float *radi
         if (int e = rfp::sort_sets(b, 1, nn, src, &so, s, nullptr)) return e;
     }
     return rfi::ball_boxes(b, n, m, radius, radius_dev, nsample, xyz1, xyz2, so, idx, pts_cnt, nullptr, 0, s);
+}
+
+// ---- ragged batches (include/rfops.h).  auto: the boxed form from QB_BOXES_MIN_N dataset points on, inside its domain -- the
+// threshold the Python wrapper applies to the plain op -- by the PADDED sizes.
+constexpr int QB_BOXES_MIN_N = 2048;
+static bool qb_boxes_domain(int b, int n, int nsample) {
+    return n >= 64 && nsample <= 64 && b <= 65535 && rfp::pruned_supported(b, n, n);
+}
+static int qb_lengths_form(int b, int n, int nsample, int form) {  // -> RF_GROUP_SCAN / RF_GROUP_BOXES, or -1
+    if (form == RF_GROUP_SCAN) return RF_GROUP_SCAN;
+    if (form == RF_GROUP_BOXES) return qb_boxes_domain(b, n, nsample) ? RF_GROUP_BOXES : -1;
+    if (form != RF_GROUP_AUTO) return -1;
+    return n >= QB_BOXES_MIN_N && qb_boxes_domain(b, n, nsample) ? RF_GROUP_BOXES : RF_GROUP_SCAN;
+}
+
+size_t rf_queryballpoint_lengths_workspace_bytes(int b, int n, int m, int nsample, int form) {
+    if (b <= 0 || n <= 0 || m <= 0 || nsample <= 0) return 0;
+    return qb_lengths_form(b, n, nsample, form) == RF_GROUP_BOXES ? rfp::sorted_bytes(b, n) : 0;
+}
+
+int rf_queryballpoint_lengths(int b, int n, int m, float radius, const float *radius_dev, int nsample, const float *xyz1,
+                              const float *xyz2, const int *len1, const int *len2, int *idx, int *pts_cnt, void *workspace,
+                              size_t workspace_bytes, rf_stream_t stream, int form) {
+    if (b < 0 || n < 0 || m < 0 || nsample <= 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
+    if (!xyz1 || !xyz2 || !idx || !pts_cnt) return RF_EINVAL;
+    if (!qb_aligned4(xyz1) || !qb_aligned4(xyz2) || !qb_aligned4(len1) || !qb_aligned4(len2) || !qb_aligned4(idx) ||
+        !qb_aligned4(pts_cnt) || !qb_aligned4(radius_dev) || !rf::aligned16(workspace))
+        return RF_EINVAL;
+    const int route = qb_lengths_form(b, n, nsample, form);
+    if (route < 0) return RF_EINVAL;
+    if (route == RF_GROUP_SCAN)
+        return queryball_impl<true>(b, n, m, radius, radius_dev, nsample, xyz1, xyz2, idx, pts_cnt, stream, {len1, len2});
+    if (!workspace) return RF_EINVAL;
+    if (workspace_bytes < rfp::sorted_bytes(b, n)) return RF_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const rfp::Sorted so = rfp::sorted_view(b, n, workspace);
+    const int *lens[1] = {len1};
+    if (int e = rfp::sort_sets(b, 1, &n, &xyz1, &so, s, nullptr, len1 ? lens : nullptr)) return e;
+    return rfi::ball_boxes(b, n, m, radius, radius_dev, nsample, xyz1, xyz2, so, idx, pts_cnt, nullptr, 1, s, true, len1, len2);
 }
 
 int rf_grouppoint(int b, int n, int c, int m, int nsample, const float *points, const int *idx,

@@ -22,18 +22,32 @@
 #include "scatter_rows.hpp"
 #include "nn_pruned.hpp"
 #include "box_bound.hpp"
+#include "group_internal.hpp"
 
 namespace {
 
 constexpr int TN_TPB = 256;
 
+// RAGGED (rf_threenn_lengths; the counts arrive as rfi::Counts, group_internal.hpp): the unknown points are the sample's first
+// nv, the known ones its first mv -- the stream ends there -- and the rows behind nv are written as zeros; a wave of padded
+// rows writes them and leaves.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(TN_TPB) void three_nn_kernel(int n, int m,
                                                           const float *__restrict__ xyz1,
                                                           const float *__restrict__ xyz2,
                                                           float *__restrict__ dist,
-                                                          int *__restrict__ idx) {
+                                                          int *__restrict__ idx, rfi::Counts<RAGGED> lens) {
     const int bi = blockIdx.y;
     const int j = blockIdx.x * TN_TPB + threadIdx.x;
+    const int nv = rfi::count1(lens, bi, n), mv = rfi::count2(lens, bi, m);
+    if (RAGGED && (int)(blockIdx.x * TN_TPB + (threadIdx.x & ~63u)) >= nv) {  // (uniform) a wave of padded rows
+        if (j < n) {
+            const size_t o = ((size_t)bi * n + j) * 3;
+            dist[o] = dist[o + 1] = dist[o + 2] = 0.f;
+            idx[o] = idx[o + 1] = idx[o + 2] = 0;
+        }
+        return;
+    }
     const float *__restrict__ U = xyz1 + (size_t)bi * n * 3;
     const float *__restrict__ K = xyz2 + (size_t)bi * m * 3;
     const int jj = min(j, n - 1);
@@ -60,11 +74,15 @@ __global__ __launch_bounds__(TN_TPB) void three_nn_kernel(int n, int m,
             }
         }
     };
-    ts_stream(K, m, consider);
-    if (j < n) {
+    ts_stream(K, mv, consider);
+    if (j < nv) {
         size_t o = ((size_t)bi * n + j) * 3;
         dist[o] = b1; dist[o + 1] = b2; dist[o + 2] = b3;
         idx[o] = i1;  idx[o + 1] = i2;  idx[o + 2] = i3;
+    } else if (RAGGED && j < n) {
+        const size_t o = ((size_t)bi * n + j) * 3;
+        dist[o] = dist[o + 1] = dist[o + 2] = 0.f;
+        idx[o] = idx[o + 1] = idx[o + 2] = 0;
     }
 }
 
@@ -96,14 +114,23 @@ struct TnList {
     }
 };
 
+// RAGGED: both sets were sorted WITH their counts, so the records and boxes are those of the valid points and the walk needs
+// nothing more.  The rows of padded unknown points belong to no record: the lane at sorted position p writes the zeros of row p
+// where nv <= p < n (npq >= n: every such row has its lane) -- in this launch, before the walk, no fill pass.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(64 * TB_WAVES) void three_nn_boxes_kernel(
     int n, int npq, int npc, const float *__restrict__ qxyz, const int *__restrict__ qorig, const float *__restrict__ qb64,
     const float *__restrict__ cxyz, const int *__restrict__ corig, const float *__restrict__ cb16,
-    const float *__restrict__ cb64, float *__restrict__ dist, int *__restrict__ idx) {
+    const float *__restrict__ cb64, float *__restrict__ dist, int *__restrict__ idx, rfi::Counts<RAGGED> lens) {
     const TbPlace w = tb_place(npq);
     if (w.group * 64 >= npq) return;  // (uniform)
     const int bi = w.bi;
     const int p = w.group * 64 + (threadIdx.x & 63);
+    if (RAGGED && p >= rfi::count1(lens, bi, n) && p < n) {
+        const size_t o = ((size_t)bi * n + p) * 3;
+        dist[o] = dist[o + 1] = dist[o + 2] = 0.f;
+        idx[o] = idx[o + 1] = idx[o + 2] = 0;
+    }
     const float *__restrict__ Q = qxyz + ((size_t)bi * npq + p) * 3;
     TbQuery q;
     q.x = Q[0], q.y = Q[1], q.z = Q[2];
@@ -353,8 +380,8 @@ int rf_threenn(int b, int n, int m, const float *xyz1, const float *xyz2, float 
     if (b < 0 || b > 65535 || n < 0 || m < 0) return RF_EINVAL;  // the batch is grid.y
     if (b == 0 || n == 0) return RF_OK;
     if (!xyz1 || !dist || !idx || (m > 0 && !xyz2)) return RF_EINVAL;
-    RF_LAUNCH("three_nn", three_nn_kernel, dim3(rf::ceil_div(n, TN_TPB), b), dim3(TN_TPB), 0,
-              (hipStream_t)stream, n, m, xyz1, xyz2, dist, idx);
+    RF_LAUNCH("three_nn", three_nn_kernel<false>, dim3(rf::ceil_div(n, TN_TPB), b), dim3(TN_TPB), 0,
+              (hipStream_t)stream, n, m, xyz1, xyz2, dist, idx, rfi::Counts<false>{});
     return RF_OK;
 }
 
@@ -377,9 +404,59 @@ int rf_threenn_boxes(int b, int n, int m, const float *xyz1, const float *xyz2, 
     sv[0] = rfp::sorted_view(b, n, sorted1 ? sorted1 : workspace);
     sv[1] = rfp::sorted_view(b, m, sorted2 ? sorted2 : (const char *)workspace + rfp::sorted_bytes(b, n));
     if (int e = rfp::sort_missing(b, n, m, xyz1, xyz2, sv[0], sv[1], sorted1 != nullptr, sorted2 != nullptr, s)) return e;
-    RF_LAUNCH("three_nn_boxes", three_nn_boxes_kernel, dim3(rf::ceil_div(sv[0].npad / 64, TB_WAVES) * b), dim3(64 * TB_WAVES), 0, s,
+    RF_LAUNCH("three_nn_boxes", three_nn_boxes_kernel<false>, dim3(rf::ceil_div(sv[0].npad / 64, TB_WAVES) * b), dim3(64 * TB_WAVES), 0, s,
               n, sv[0].npad, sv[1].npad, sv[0].xyz, sv[0].orig, sv[0].box64, sv[1].xyz, sv[1].orig, sv[1].box16, sv[1].box64,
-              dist, idx);
+              dist, idx, rfi::Counts<false>{});
+    return RF_OK;
+}
+
+// ---- ragged batches (include/rfops.h).  auto: the boxed form where the Python wrapper takes it for the plain op without sort
+// handles (TN_BOXES_* of rfnet_amd/_raw.py), by the PADDED sizes.
+static int tn_lengths_form(int b, int n, int m, int form) {  // -> RF_GROUP_SCAN / RF_GROUP_BOXES, or -1
+    const bool domain = b <= 65535 && rfp::pruned_supported(b, n, m);
+    if (form == RF_GROUP_SCAN) return RF_GROUP_SCAN;
+    if (form == RF_GROUP_BOXES) return domain ? RF_GROUP_BOXES : -1;
+    if (form != RF_GROUP_AUTO) return -1;
+    const double pairs = (double)b * n * m;
+    const bool small = (n > m ? n : m) <= 16384;
+    const bool pays = n >= 1024 && m >= 512 && (pairs >= (small ? 1e8 : 4e9) || (m >= 1536 && n >= 4096 && small));
+    return domain && pays ? RF_GROUP_BOXES : RF_GROUP_SCAN;
+}
+static bool tn_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+size_t rf_threenn_lengths_workspace_bytes(int b, int n, int m, int form) {
+    if (b <= 0 || b > 65535 || n <= 0 || m <= 0) return 0;
+    return tn_lengths_form(b, n, m, form) == RF_GROUP_BOXES ? rfp::sorted_bytes(b, n) + rfp::sorted_bytes(b, m) : 0;
+}
+
+int rf_threenn_lengths(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2, float *dist,
+                       int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream, int form) {
+    if (b < 0 || b > 65535 || n < 0 || m < 0) return RF_EINVAL;  // the batch is grid.y
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
+    if (!xyz1 || !xyz2 || !dist || !idx) return RF_EINVAL;
+    if (!tn_aligned4(xyz1) || !tn_aligned4(xyz2) || !tn_aligned4(len1) || !tn_aligned4(len2) || !tn_aligned4(dist) ||
+        !tn_aligned4(idx) || !rf::aligned16(workspace))
+        return RF_EINVAL;
+    const int route = tn_lengths_form(b, n, m, form);
+    if (route < 0) return RF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const rfi::Counts<true> lens{len1, len2};
+    if (route == RF_GROUP_SCAN) {
+        RF_LAUNCH("three_nn_lengths", three_nn_kernel<true>, dim3(rf::ceil_div(n, TN_TPB), b), dim3(TN_TPB), 0, s, n, m, xyz1, xyz2,
+                  dist, idx, lens);
+        return RF_OK;
+    }
+    if (!workspace) return RF_EINVAL;
+    if (workspace_bytes < rfp::sorted_bytes(b, n) + rfp::sorted_bytes(b, m)) return RF_EWORKSPACE;
+    rfp::Sorted sv[2] = {rfp::sorted_view(b, n, workspace), rfp::sorted_view(b, m, (const char *)workspace + rfp::sorted_bytes(b, n))};
+    const int nn[2] = {n, m};
+    const float *src[2] = {xyz1, xyz2};
+    const int *ls[2] = {len1, len2};
+    if (int e = rfp::sort_sets(b, 2, nn, src, sv, s, nullptr, (len1 || len2) ? ls : nullptr)) return e;
+    RF_LAUNCH("three_nn_boxes_lengths", three_nn_boxes_kernel<true>, dim3(rf::ceil_div(sv[0].npad / 64, TB_WAVES) * b),
+              dim3(64 * TB_WAVES), 0, s, n, sv[0].npad, sv[1].npad, sv[0].xyz, sv[0].orig, sv[0].box64, sv[1].xyz, sv[1].orig,
+              sv[1].box16, sv[1].box64, dist, idx, lens);
     return RF_OK;
 }
 

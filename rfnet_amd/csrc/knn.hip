@@ -35,6 +35,7 @@
 #include "scatter_rows.hpp"
 #include "nn_pruned.hpp"
 #include "box_bound.hpp"
+#include "group_internal.hpp"
 
 namespace {
 
@@ -77,6 +78,10 @@ __device__ __forceinline__ void kn_write(const u64 (&L)[KB], int k, float *__res
         }
     }
 }
+// slots [from, k) of a row as zeros (ragged batches: behind a sample's neighbours, and the whole row of a padded query)
+__device__ __forceinline__ void kn_zero(int from, int k, float *__restrict__ val, int *__restrict__ idx) {
+    for (int t = from; t < k; t++) val[t] = 0.f, idx[t] = 0;
+}
 
 // Candidates that pass the pre-test are not inserted at once: each lane appends them to a buffer of its own in LDS, and the wave
 // inserts only when some lane's buffer is full (or at the end of a run of candidates).  Inserting at once makes the whole wave run
@@ -98,19 +103,29 @@ constexpr int KN_BUF = 16;  // entries per lane
     }
 
 // ---- scan: one lane per query, every candidate (box_bound.hpp ts_stream) ----------------------------------------------------
-template <int KB>
+// RAGGED (rf_knn_lengths; the counts arrive as rfi::Counts, group_internal.hpp): the candidates are the sample's first nv points,
+// the queries its first mv.  The list is opened for kv = min(k, nv) neighbours -- a sample with fewer candidates than k could not
+// fill k slots, and the unfilled ones would go out as the keys they start with -- so slots [0, kv) are the op's with k = kv,
+// and slots [kv, k) and the rows of padded queries are written as zeros; a wave of padded queries writes them and leaves.
+template <int KB, bool RAGGED = false>
 __global__ __launch_bounds__(KN_TPB) void knn_scan_kernel(int n, int m, int k, const float *__restrict__ xyz1,
                                                           const float *__restrict__ xyz2, float *__restrict__ val,
-                                                          int *__restrict__ idx) {
+                                                          int *__restrict__ idx, rfi::Counts<RAGGED> lens) {
     const int bi = blockIdx.y;
     const int j = blockIdx.x * KN_TPB + threadIdx.x;
     const float *__restrict__ C = xyz1 + (size_t)bi * n * 3;
     const float *__restrict__ Q = xyz2 + (size_t)bi * m * 3;
+    const int nv = rfi::count1(lens, bi, n), mv = rfi::count2(lens, bi, m);
+    const int kv = RAGGED ? min(k, nv) : k;
+    if (RAGGED && (int)(blockIdx.x * KN_TPB + (threadIdx.x & ~63u)) >= mv) {  // (uniform) a wave of padded queries
+        if (j < m) kn_zero(0, k, val + ((size_t)bi * m + j) * k, idx + ((size_t)bi * m + j) * k);
+        return;
+    }
     const int jj = min(j, m - 1);
     const float x2 = Q[jj * 3], y2 = Q[jj * 3 + 1], z2 = Q[jj * 3 + 2];
     u64 L[KB];
 #pragma unroll
-    for (int t = 0; t < KB; t++) L[t] = t < KB - k ? 0ull : ~0ull;
+    for (int t = 0; t < KB; t++) L[t] = t < KB - kv ? 0ull : ~0ull;
     float thr = __uint_as_float(0x7FC00000u);
     __shared__ float bd[KN_BUF][KN_TPB];
     __shared__ unsigned bx[KN_BUF][KN_TPB];
@@ -132,9 +147,10 @@ __global__ __launch_bounds__(KN_TPB) void knn_scan_kernel(int n, int m, int k, c
             if (__ballot(cnt == KN_BUF) != 0ull) KN_FLUSH(bd, bx, tid);
         }
     };
-    ts_stream(C, n, consider);
+    ts_stream(C, nv, consider);
     KN_FLUSH(bd, bx, tid);
-    if (j < m) kn_write<KB>(L, k, val + ((size_t)bi * m + j) * k, idx + ((size_t)bi * m + j) * k);
+    if (j < mv) kn_write<KB>(L, kv, val + ((size_t)bi * m + j) * k, idx + ((size_t)bi * m + j) * k);
+    if (RAGGED && j < m) kn_zero(j < mv ? kv : 0, k, val + ((size_t)bi * m + j) * k, idx + ((size_t)bi * m + j) * k);
 }
 
 // ---- boxed: the walk of box_bound.hpp with knn's list ----------------------------------------------------------------------
@@ -166,16 +182,22 @@ struct KnList {
     }
 };
 
-template <int KB>
+// RAGGED: both sets were sorted WITH their counts (records, boxes and the non-finite flag are those of the valid points).  The
+// list is opened for kv = min(k, nv) neighbours as in the scan: while it is not full every superblock is visited, so the nv >= kv
+// real records fill it and the padding records' keys (above everything) never enter.  Rows of padded queries belong to no
+// record: the lane at sorted position p writes the zeros of row p where mv <= p < m (npq >= m), before the walk.
+template <int KB, bool RAGGED = false>
 __global__ __launch_bounds__(64 * TB_WAVES) void knn_boxes_kernel(
     int b, int m, int k, int npq, int npc, const float *__restrict__ qxyz, const int *__restrict__ qorig,
     const float *__restrict__ qb64, const float *__restrict__ cxyz, const int *__restrict__ corig,
     const float *__restrict__ cb16, const float *__restrict__ cb64, const int *__restrict__ cflags,
-    float *__restrict__ val, int *__restrict__ idx) {
+    float *__restrict__ val, int *__restrict__ idx, int n, rfi::Counts<RAGGED> lens) {
     const TbPlace w = tb_place(npq);
     if (w.group * 64 >= npq) return;  // (uniform)
     const int bi = w.bi;
     const int p = w.group * 64 + (threadIdx.x & 63);
+    const int kv = RAGGED ? min(k, rfi::count1(lens, bi, n)) : k;
+    if (RAGGED && p >= rfi::count2(lens, bi, m) && p < m) kn_zero(0, k, val + ((size_t)bi * m + p) * k, idx + ((size_t)bi * m + p) * k);
     const float *__restrict__ Q = qxyz + ((size_t)bi * npq + p) * 3;
     TbQuery q;
     q.x = Q[0], q.y = Q[1], q.z = Q[2];
@@ -187,12 +209,13 @@ __global__ __launch_bounds__(64 * TB_WAVES) void knn_boxes_kernel(
     const int nsb = npc >> 6;
     const TbCands c = {cxyz + (size_t)bi * npc * 3, corig + (size_t)bi * npc, cb16 + (size_t)bi * nsb * 24,
                        cb64 + (size_t)bi * nsb * 8, nsb};
-    KnList<KB> L(q.search, k);
+    KnList<KB> L(q.search, kv);
     TbStats st;
     tb_walk(L, q, c, st);
     if (q.search) {
         const size_t o = ((size_t)bi * m + oq) * k;
-        kn_write<KB>(L.L, k, val + o, idx + o);
+        kn_write<KB>(L.L, kv, val + o, idx + o);
+        if (RAGGED) kn_zero(kv, k, val + o, idx + o);
 #ifdef TB_STATS
         idx[o] = st.scans;
 #endif
@@ -203,17 +226,30 @@ __global__ __launch_bounds__(64 * TB_WAVES) void knn_boxes_kernel(
 constexpr int KG_TPB = 256;
 
 // grad_xyz2[j] = sum_t 2 g (x1[i] - x2[j]); slots whose index is outside [0, n) add nothing
+// RAGGED: slots behind the sample's neighbours (t >= nv), slots that name a padded candidate and the slots of padded queries add
+// nothing, whatever idx and gval hold there; the rows of padded queries are +0.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(KG_TPB) void knn_grad_query_kernel(int n, int m, int k, const float *__restrict__ xyz1,
                                                                 const float *__restrict__ xyz2, const int *__restrict__ idx,
-                                                                const float *__restrict__ gval, float *__restrict__ grad2) {
+                                                                const float *__restrict__ gval, float *__restrict__ grad2,
+                                                                rfi::Counts<RAGGED> lens) {
     const int bi = blockIdx.y;
     const int j = blockIdx.x * KG_TPB + threadIdx.x;
     if (j >= m) return;
     const float *__restrict__ X1 = xyz1 + (size_t)bi * n * 3;
     const size_t q = (size_t)bi * m + j;
+    const int kstride = k;
+    if (RAGGED) {
+        n = rfi::count1(lens, bi, n);
+        k = min(k, n);
+        if (j >= rfi::count2(lens, bi, m)) {
+            grad2[q * 3] = grad2[q * 3 + 1] = grad2[q * 3 + 2] = 0.f;
+            return;
+        }
+    }
     const float x2 = xyz2[q * 3], y2 = xyz2[q * 3 + 1], z2 = xyz2[q * 3 + 2];
-    const int *__restrict__ I = idx + q * k;
-    const float *__restrict__ G = gval + q * k;
+    const int *__restrict__ I = idx + q * kstride;
+    const float *__restrict__ G = gval + q * kstride;
     double ax = 0.0, ay = 0.0, az = 0.0;
     for (int t = 0; t < k; t++) {
         const int i = I[t];
@@ -281,7 +317,7 @@ int rf_knn(int b, int n, int m, int k, const float *xyz1, const float *xyz2, flo
     if (!xyz1 || !xyz2 || !val || !idx) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(rf::ceil_div(m, KN_TPB), b);
-#define KN_GO(KB) RF_LAUNCH("knn", knn_scan_kernel<KB>, grid, dim3(KN_TPB), 0, s, n, m, k, xyz1, xyz2, val, idx)
+#define KN_GO(KB) RF_LAUNCH("knn", knn_scan_kernel<KB>, grid, dim3(KN_TPB), 0, s, n, m, k, xyz1, xyz2, val, idx, rfi::Counts<false>{})
     KN_DISPATCH(k, KN_GO);
 #undef KN_GO
     return RF_OK;
@@ -306,7 +342,7 @@ int rf_knn_boxes(int b, int n, int m, int k, const float *xyz1, const float *xyz
     const dim3 grid(rf::ceil_div(sv[1].npad / 64, TB_WAVES) * b);
 #define KB_GO(KB)                                                                                                              \
     RF_LAUNCH("knn_boxes", knn_boxes_kernel<KB>, grid, dim3(64 * TB_WAVES), 0, s, b, m, k, sv[1].npad, sv[0].npad, sv[1].xyz, \
-              sv[1].orig, sv[1].box64, sv[0].xyz, sv[0].orig, sv[0].box16, sv[0].box64, sv[0].pos0, val, idx)
+              sv[1].orig, sv[1].box64, sv[0].xyz, sv[0].orig, sv[0].box16, sv[0].box64, sv[0].pos0, val, idx, n, rfi::Counts<false>{})
     KN_DISPATCH(k, KB_GO);
 #undef KB_GO
     return RF_OK;
@@ -324,9 +360,80 @@ int rf_knn_grad(int b, int n, int m, int k, const float *xyz1, const float *xyz2
         return RF_EINVAL;
     if (workspace_bytes < rf_knn_grad_workspace_bytes(b, n, m, k)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    RF_LAUNCH("knn_grad_query", knn_grad_query_kernel, dim3(rf::ceil_div(m, KG_TPB), b), dim3(KG_TPB), 0, s, n, m, k, xyz1, xyz2,
-              idx, grad_val, grad_xyz2);
+    RF_LAUNCH("knn_grad_query", knn_grad_query_kernel<false>, dim3(rf::ceil_div(m, KG_TPB), b), dim3(KG_TPB), 0, s, n, m, k, xyz1,
+              xyz2, idx, grad_val, grad_xyz2, rfi::Counts<false>{});
     if (int e = rfs::rows_csr_sort(b, n, (long)m * k, idx, workspace, "knn_grad_sort", s)) return e;
+    RF_LAUNCH("knn_grad_rows", knn_grad_rows_kernel, dim3(rf::ceil_div(n, KG_TPB), b), dim3(KG_TPB), 0, s, n, m, k, xyz1, xyz2,
+              grad_val, (const int *)workspace, rfs::rows_csr_perm(b, n, workspace), grad_xyz1);
+    return RF_OK;
+}
+
+// ---- ragged batches (include/rfops.h).  auto: the boxed form where the Python wrapper takes it for the plain op
+// (KNN_BOXES_* of rfnet_amd/_raw.py), by the PADDED sizes.
+static bool kn_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+static int kn_lengths_form(int n, int m, int k, int form) {  // -> RF_GROUP_SCAN / RF_GROUP_BOXES, or -1
+    if (form == RF_GROUP_SCAN || form == RF_GROUP_BOXES) return form;
+    if (form != RF_GROUP_AUTO) return -1;
+    return m >= 8192 && n >= 16384 && k <= 32 ? RF_GROUP_BOXES : RF_GROUP_SCAN;
+}
+
+size_t rf_knn_lengths_workspace_bytes(int b, int n, int m, int k, int form) {
+    if (!kn_supported(b, n, m, k)) return 0;
+    return kn_lengths_form(n, m, k, form) == RF_GROUP_BOXES ? rfp::sorted_bytes(b, n) + rfp::sorted_bytes(b, m) : 0;
+}
+
+int rf_knn_lengths(int b, int n, int m, int k, const float *xyz1, const float *xyz2, const int *len1, const int *len2, float *val,
+                   int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream, int form) {
+    if (b == 0 && n >= 0 && m >= 0 && k >= 0) return RF_OK;
+    if (!kn_supported(b, n, m, k)) return RF_EINVAL;
+    if (!xyz1 || !xyz2 || !val || !idx) return RF_EINVAL;
+    if (!kn_aligned4(xyz1) || !kn_aligned4(xyz2) || !kn_aligned4(len1) || !kn_aligned4(len2) || !kn_aligned4(val) ||
+        !kn_aligned4(idx) || !rf::aligned16(workspace))
+        return RF_EINVAL;
+    const int route = kn_lengths_form(n, m, k, form);
+    if (route < 0) return RF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const rfi::Counts<true> lens{len1, len2};
+    if (route == RF_GROUP_SCAN) {
+        const dim3 grid(rf::ceil_div(m, KN_TPB), b);
+#define KN_GO(KB) \
+    RF_LAUNCH("knn_lengths", (knn_scan_kernel<KB, true>), grid, dim3(KN_TPB), 0, s, n, m, k, xyz1, xyz2, val, idx, lens)
+        KN_DISPATCH(k, KN_GO);
+#undef KN_GO
+        return RF_OK;
+    }
+    if (!workspace) return RF_EINVAL;
+    if (workspace_bytes < rfp::sorted_bytes(b, n) + rfp::sorted_bytes(b, m)) return RF_EWORKSPACE;
+    rfp::Sorted sv[2] = {rfp::sorted_view(b, n, workspace), rfp::sorted_view(b, m, (const char *)workspace + rfp::sorted_bytes(b, n))};
+    const int nn[2] = {n, m};
+    const float *src[2] = {xyz1, xyz2};
+    const int *ls[2] = {len1, len2};
+    if (int e = rfp::sort_sets(b, 2, nn, src, sv, s, nullptr, (len1 || len2) ? ls : nullptr)) return e;
+    const dim3 grid(rf::ceil_div(sv[1].npad / 64, TB_WAVES) * b);
+#define KB_GO(KB)                                                                                                               \
+    RF_LAUNCH("knn_boxes_lengths", (knn_boxes_kernel<KB, true>), grid, dim3(64 * TB_WAVES), 0, s, b, m, k, sv[1].npad, sv[0].npad, \
+              sv[1].xyz, sv[1].orig, sv[1].box64, sv[0].xyz, sv[0].orig, sv[0].box16, sv[0].box64, sv[0].pos0, val, idx, n, lens)
+    KN_DISPATCH(k, KB_GO);
+#undef KB_GO
+    return RF_OK;
+}
+
+size_t rf_knn_grad_lengths_workspace_bytes(int b, int n, int m, int k) { return rf_knn_grad_workspace_bytes(b, n, m, k); }
+
+int rf_knn_grad_lengths(int b, int n, int m, int k, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                        const int *idx, const float *grad_val, float *grad_xyz1, float *grad_xyz2, void *workspace,
+                        size_t workspace_bytes, rf_stream_t stream) {
+    if (b == 0 && n >= 0 && m >= 0 && k >= 0) return RF_OK;
+    if (!kn_supported(b, n, m, k)) return RF_EINVAL;
+    if (!xyz1 || !xyz2 || !idx || !grad_val || !grad_xyz1 || !grad_xyz2 || !workspace || !rf::aligned16(workspace))
+        return RF_EINVAL;
+    if (!kn_aligned4(len1) || !kn_aligned4(len2)) return RF_EINVAL;
+    if (workspace_bytes < rf_knn_grad_lengths_workspace_bytes(b, n, m, k)) return RF_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    RF_LAUNCH("knn_grad_query_lengths", knn_grad_query_kernel<true>, dim3(rf::ceil_div(m, KG_TPB), b), dim3(KG_TPB), 0, s, n, m, k,
+              xyz1, xyz2, idx, grad_val, grad_xyz2, rfi::Counts<true>{len1, len2});
+    if (int e = rfs::rows_csr_sort_masked(b, n, m, k, idx, len1, len2, workspace, "knn_grad_sort_lengths", s)) return e;
+    // (a masked slot is in no row, so the rows kernel needs no counts: a padded candidate's row sums nothing and is written +0)
     RF_LAUNCH("knn_grad_rows", knn_grad_rows_kernel, dim3(rf::ceil_div(n, KG_TPB), b), dim3(KG_TPB), 0, s, n, m, k, xyz1, xyz2,
               grad_val, (const int *)workspace, rfs::rows_csr_perm(b, n, workspace), grad_xyz1);
     return RF_OK;

@@ -18,27 +18,16 @@
 
 namespace {
 size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-}  // namespace
+bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
-extern "C" {
-
-size_t rf_sample_and_group_workspace_bytes(int b, int n) {
-    if (b <= 0 || n <= 0) return 0;
-    const size_t sorted = rf_queryballpoint_boxes_workspace_bytes(b, n);
-    if (!sorted) return 0;
-    return align256(sizeof(float) * rf_farthestpointsampling_temp_floats(b, n)) + sorted;
-}
-
-int rf_sample_and_group(int b, int n, int npoint, float radius, const float *radius_dev, int nsample, const float *xyz,
-                        int *fps_idx, float *new_xyz, int *idx, int *pts_cnt, float *grouped_xyz, void *workspace,
-                        size_t workspace_bytes, rf_stream_t stream, rf_stream_t aux_stream) {
-    if (b < 0 || n < 0 || npoint < 0 || nsample <= 0) return RF_EINVAL;
-    if ((long)b * npoint == 0) return RF_OK;
-    if (n < 64 || nsample > 64 || b > 65535 || !rfp::pruned_supported(b, n, n)) return RF_EINVAL;
-    if (!xyz || !fps_idx || !new_xyz || !idx || !pts_cnt || !grouped_xyz || !workspace || !rf::aligned16(workspace))
-        return RF_EINVAL;
-    if (workspace_bytes < rf_sample_and_group_workspace_bytes(b, n)) return RF_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream, aux = (hipStream_t)aux_stream;
+// The chain on checked arguments.  ragged (rf_sample_and_group_lengths): the sort, FPS and the ball query take the counts -- len
+// (b) points per cloud for all three, len_out (b) samples per cloud as FPS's row length and the ball query's query count --
+// through the ragged launchers; the streams are used exactly as in the plain chain.
+int chain(int b, int n, int npoint, float radius, const float *radius_dev, int nsample, const float *xyz, bool ragged,
+          const int *len, const int *len_out, int *fps_idx, float *new_xyz, int *idx, int *pts_cnt, float *grouped_xyz,
+          void *workspace, hipStream_t s, hipStream_t aux) {
+    const int *lens[1] = {len};
+    const int *const *sort_lens = (ragged && len) ? lens : nullptr;
     char *w = (char *)workspace;
     const size_t temp_floats = rf_farthestpointsampling_temp_floats(b, n);
     float *temp = temp_floats ? (float *)w : nullptr;
@@ -49,9 +38,12 @@ int rf_sample_and_group(int b, int n, int npoint, float radius, const float *rad
     if (rfi::fps_sorted_pays(n, npoint)) {
         // FPS itself runs over the sorted cloud (fps_sorted_kernel: a third shorter iterations): one sort serves both ops, on
         // the caller's stream -- nothing is left to run beside FPS
-        if (int e = rfp::sort_sets(b, 1, nn, src, &so, s, nullptr)) return e;
-        if (int e = rfi::fps_sorted(b, n, npoint, xyz, so, fps_idx, new_xyz, s)) return e;
-        return rfi::ball_boxes(b, n, npoint, radius, radius_dev, nsample, xyz, new_xyz, so, idx, pts_cnt, grouped_xyz, 1, s);
+        if (int e = rfp::sort_sets(b, 1, nn, src, &so, s, nullptr, sort_lens)) return e;
+        if (int e = ragged ? rfi::fps_sorted_lengths(b, n, npoint, xyz, len, len_out, so, fps_idx, new_xyz, s)
+                           : rfi::fps_sorted(b, n, npoint, xyz, so, fps_idx, new_xyz, s))
+            return e;
+        return rfi::ball_boxes(b, n, npoint, radius, radius_dev, nsample, xyz, new_xyz, so, idx, pts_cnt, grouped_xyz, 1, s, ragged,
+                               len, len_out);
     }
     // The sort beside FPS on the auxiliary stream: aux waits for the caller's stream (the inputs are ready there), the caller's
     // stream waits for the sort before the ball query.  The events live for this call only and are destroyed on EVERY exit (an
@@ -81,17 +73,64 @@ int rf_sample_and_group(int b, int n, int npoint, float radius, const float *rad
         RF_HIP(hipEventRecord(fk.fork, s));
         RF_HIP(hipStreamWaitEvent(aux, fk.fork, 0));
         fk.queued = true;
-        if (int e = rfp::sort_sets(b, 1, nn, src, &so, aux, nullptr)) return e;
+        if (int e = rfp::sort_sets(b, 1, nn, src, &so, aux, nullptr, sort_lens)) return e;
         RF_HIP(hipEventRecord(fk.join, aux));  // (recorded NOW, behind the sort: FPS below does not wait for it)
     } else {
-        if (int e = rfp::sort_sets(b, 1, nn, src, &so, s, nullptr)) return e;
+        if (int e = rfp::sort_sets(b, 1, nn, src, &so, s, nullptr, sort_lens)) return e;
     }
-    if (int e = rfi::fps(b, n, npoint, xyz, temp, fps_idx, new_xyz, s)) return e;
+    if (int e = ragged ? rfi::fps_lengths(b, n, npoint, xyz, len, len_out, temp, fps_idx, new_xyz, s)
+                       : rfi::fps(b, n, npoint, xyz, temp, fps_idx, new_xyz, s))
+        return e;
     if (fk.queued) {
         fk.queued = false;
         RF_HIP(hipStreamWaitEvent(s, fk.join, 0));
     }
-    return rfi::ball_boxes(b, n, npoint, radius, radius_dev, nsample, xyz, new_xyz, so, idx, pts_cnt, grouped_xyz, 1, s);
+    return rfi::ball_boxes(b, n, npoint, radius, radius_dev, nsample, xyz, new_xyz, so, idx, pts_cnt, grouped_xyz, 1, s, ragged, len,
+                           len_out);
+}
+}  // namespace
+
+extern "C" {
+
+size_t rf_sample_and_group_workspace_bytes(int b, int n) {
+    if (b <= 0 || n <= 0) return 0;
+    const size_t sorted = rf_queryballpoint_boxes_workspace_bytes(b, n);
+    if (!sorted) return 0;
+    return align256(sizeof(float) * rf_farthestpointsampling_temp_floats(b, n)) + sorted;
+}
+
+int rf_sample_and_group(int b, int n, int npoint, float radius, const float *radius_dev, int nsample, const float *xyz,
+                        int *fps_idx, float *new_xyz, int *idx, int *pts_cnt, float *grouped_xyz, void *workspace,
+                        size_t workspace_bytes, rf_stream_t stream, rf_stream_t aux_stream) {
+    if (b < 0 || n < 0 || npoint < 0 || nsample <= 0) return RF_EINVAL;
+    if ((long)b * npoint == 0) return RF_OK;
+    if (n < 64 || nsample > 64 || b > 65535 || !rfp::pruned_supported(b, n, n)) return RF_EINVAL;
+    if (!xyz || !fps_idx || !new_xyz || !idx || !pts_cnt || !grouped_xyz || !workspace || !rf::aligned16(workspace))
+        return RF_EINVAL;
+    if (workspace_bytes < rf_sample_and_group_workspace_bytes(b, n)) return RF_EWORKSPACE;
+    return chain(b, n, npoint, radius, radius_dev, nsample, xyz, false, nullptr, nullptr, fps_idx, new_xyz, idx, pts_cnt,
+                 grouped_xyz, workspace, (hipStream_t)stream, (hipStream_t)aux_stream);
+}
+
+// The chain over a ragged batch (include/rfops.h): rf_farthestpointsampling_lengths and rf_queryballpoint_lengths (boxed form,
+// len2 = len_out) chained as above, with grouped_xyz's rows of padded samples +0.
+size_t rf_sample_and_group_lengths_workspace_bytes(int b, int n) { return rf_sample_and_group_workspace_bytes(b, n); }
+
+int rf_sample_and_group_lengths(int b, int n, int npoint, float radius, const float *radius_dev, int nsample, const float *xyz,
+                                const int *len, const int *len_out, int *fps_idx, float *new_xyz, int *idx, int *pts_cnt,
+                                float *grouped_xyz, void *workspace, size_t workspace_bytes, rf_stream_t stream,
+                                rf_stream_t aux_stream) {
+    if (b < 0 || n < 0 || npoint < 0 || nsample <= 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (npoint == 0) return RF_EINVAL;  // counts are at least 1
+    if (n < 64 || nsample > 64 || b > 65535 || !rfp::pruned_supported(b, n, n)) return RF_EINVAL;
+    if (!xyz || !fps_idx || !new_xyz || !idx || !pts_cnt || !grouped_xyz || !workspace) return RF_EINVAL;
+    if (!aligned4(xyz) || !aligned4(len) || !aligned4(len_out) || !aligned4(fps_idx) || !aligned4(new_xyz) || !aligned4(idx) ||
+        !aligned4(pts_cnt) || !aligned4(grouped_xyz) || !aligned4(radius_dev) || !rf::aligned16(workspace))
+        return RF_EINVAL;
+    if (workspace_bytes < rf_sample_and_group_lengths_workspace_bytes(b, n)) return RF_EWORKSPACE;
+    return chain(b, n, npoint, radius, radius_dev, nsample, xyz, true, len, len_out, fps_idx, new_xyz, idx, pts_cnt, grouped_xyz,
+                 workspace, (hipStream_t)stream, (hipStream_t)aux_stream);
 }
 
 }  // extern "C"

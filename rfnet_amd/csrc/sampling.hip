@@ -91,6 +91,11 @@ __device__ __forceinline__ float wave_allmax(float v) {
     return vmax3(vmax3(r0, r1, r2), r3, r3);
 }
 
+// ---- ragged batches (rf_farthestpointsampling_lengths).  Every FPS kernel has a RAGGED instantiation that takes, as a last
+// argument, the per-sample counts (rfi::Counts, group_internal.hpp): len1 = valid points of the cloud, len2 = samples the cloud
+// wants, read once per workgroup (uniform: scalar loads) and clamped.  The cloud is then its first nv points -- the slots behind
+// nv hold what the slots behind n hold, (0, 0, 0) with a running minimum of -1 that never wins -- the chain stops after mo
+// samples, and the tail of the row is written as zeros.  The plain instantiations get the empty argument and nv = n, mo = m.
 // NT threads (multiple of 512), PPT points per thread, all register resident.
 // Thread t owns k = (t & 511) + 512 * (s * (NT/512) + (t >> 9)), s = 0..PPT-1, so all its points
 // share (k mod 512) and ascend with s; inside a wave a lower lane has a lower (k mod 512).
@@ -107,9 +112,11 @@ __device__ __forceinline__ float wave_allmax(float v) {
 //             min tie rank); the winner's coordinates come back by a scalar load.
 // EMIT: the samples' coordinates go out with their indices (new_xyz = gather_point(inp, out), tf_sampling_g.cu:172-181,
 // fused: the winner's coordinates are in scalar registers at that point of every iteration).
-template <int NT, int PPT, bool EMIT>
+// RAGGED: a wave leaves the scan at the first group of four slots that is padding in all its lanes (wave-uniform).
+template <int NT, int PPT, bool EMIT, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void fps_reg_kernel(int n, int m, const float *__restrict__ inp,
-                                                     int *__restrict__ out, float *__restrict__ new_xyz) {
+                                                     int *__restrict__ out, float *__restrict__ new_xyz,
+                                                     rfi::Counts<RAGGED> cnt) {
     constexpr int NW = NT / 64;
     constexpr int HALVES = NT / 512;
     static_assert(NW <= 16, "slot reduction is one 16-lane DPP row");
@@ -121,6 +128,16 @@ __global__ __launch_bounds__(NT) void fps_reg_kernel(int n, int m, const float *
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const float *__restrict__ P = inp + (size_t)bi * n * 3;
     int *__restrict__ O = out + (size_t)bi * m;
+    const int nv = rfi::count1(cnt, bi, n), mo = rfi::count2(cnt, bi, m);
+    // RAGGED: the slots of this wave that can hold a point (the wave's lowest index in slot s is at least
+    // 512 * (s * HALVES + (t >> 9))), rounded up to the scan's groups of SG slots
+    constexpr int SG = PPT >= 4 ? 4 : PPT;
+    int live = PPT;
+    if (RAGGED) {
+        const int first = 512 * (wave >> 3);
+        const int slots = nv > first ? (nv - first + 512 * HALVES - 1) / (512 * HALVES) : 0;
+        live = min(PPT, (slots + SG - 1) / SG * SG);
+    }
 
     float px[PPT], py[PPT], pz[PPT], td[PPT];
 #pragma unroll
@@ -128,7 +145,7 @@ __global__ __launch_bounds__(NT) void fps_reg_kernel(int n, int m, const float *
         int k = (t & 511) + 512 * (s * HALVES + (t >> 9));
         // (these loads are PPT branches with a wait each -- ~15 us at the head of a 1.12 ms launch at C3.  As clamped loads with selects
         // they are one batch, and the KERNEL is slower, 1.208 vs 1.124 ms: the register allocation of the iteration loop changes)
-        if (k < n) {
+        if (k < nv) {
             px[s] = P[k * 3 + 0];
             py[s] = P[k * 3 + 1];
             pz[s] = P[k * 3 + 2];
@@ -151,10 +168,11 @@ __global__ __launch_bounds__(NT) void fps_reg_kernel(int n, int m, const float *
         NX[1] = oy;
         NX[2] = oz;
     }
-    for (int j = 1; j < m; j++) {
+    for (int j = 1; j < mo; j++) {
         float mx = -1.0f;
 #pragma unroll
         for (int s = 0; s < PPT; s++) {
+            if (RAGGED && s % SG == 0 && s >= live) break;  // (uniform) padding from here on: td = -1 stays
             td[s] = vmin(rf::d2_fma(px[s] - ox, py[s] - oy, pz[s] - oz), td[s]);
             if (PPT == 1) {
                 mx = td[0];
@@ -201,6 +219,12 @@ __global__ __launch_bounds__(NT) void fps_reg_kernel(int n, int m, const float *
             }
         }
     }
+    if (RAGGED) {  // the samples this cloud did not want
+        for (int j = mo + t; j < m; j += NT) {
+            O[j] = 0;
+            if (EMIT) NX[j * 3 + 0] = NX[j * 3 + 1] = NX[j * 3 + 2] = 0.f;
+        }
+    }
 }
 
 // ---- FPS over the spatially sorted cloud: the same samples, most of the cloud left alone in most iterations (round 5) ----
@@ -221,10 +245,14 @@ __device__ __forceinline__ unsigned wave_allmin_u(unsigned v) {
     return min(min(r0, r1), min(r2, r3));
 }
 
-template <int NT, int PPT, bool EMIT>
+// RAGGED: the sort was given the same counts, so the real records are the cloud's first nv points and the compaction below finds
+// exactly nv of them; waves whose chunk lies behind them hold padding only (boxes +-inf, td = -1) and are never touched.  Once the
+// samples outnumber the real records every running minimum is 0 and every wave's cached candidate is its lowest tie rank, so the
+// chain repeats point 0 as the reference does.
+template <int NT, int PPT, bool EMIT, bool RAGGED = false>
 __global__ __launch_bounds__(NT) void fps_sorted_kernel(int n, int m, int npad, const float *__restrict__ inp,
                                                         const int *__restrict__ sorig, int *__restrict__ out,
-                                                        float *__restrict__ new_xyz) {
+                                                        float *__restrict__ new_xyz, rfi::Counts<RAGGED> cnt) {
     constexpr int NW = NT / 64;
     static_assert(NW <= 16, "slot reduction is one 16-lane DPP row");
     static_assert(PPT >= 2 && (PPT & (PPT - 1)) == 0, "the slots of a lane are ordered by a bitonic network");
@@ -245,6 +273,7 @@ __global__ __launch_bounds__(NT) void fps_sorted_kernel(int n, int m, int npad, 
     const float *__restrict__ P = inp + (size_t)bi * n * 3;
     const int *__restrict__ SO = sorig + (size_t)bi * npad;
     int *__restrict__ O = out + (size_t)bi * m;
+    const int nv = rfi::count1(cnt, bi, n), mo = rfi::count2(cnt, bi, m);
     // compaction of the real records (orig >= 0), once
     {
         int run = 0;
@@ -277,7 +306,7 @@ __global__ __launch_bounds__(NT) void fps_sorted_kernel(int n, int m, int npad, 
         constexpr int kChunkOfWave[16] = {0, 1, 3, 4, 2, 6, 5, 7, 9, 10, 8, 11, 14, 12, 15, 13};
         const int chunk = (NW == 16 && PPT >= 8) ? kChunkOfWave[wave & 15] : wave;
         const int c = ((chunk << 6) | lane) * PPT + s;
-        if (c < n) {
+        if (c < nv) {
             // (the coordinates from the cloud itself, through the original index: the winners' coordinates are re-read from there
             // every iteration, and this pass is what brings the cloud into this XCD's L2 -- read from the sorted copy, a launch that
             // follows other work paid a miss to HBM per iteration: 0.96 against 0.84 ms behind a ball query)
@@ -344,7 +373,7 @@ __global__ __launch_bounds__(NT) void fps_sorted_kernel(int n, int m, int npad, 
     __syncthreads();
     if (t == 0) cpos[0] = 0;
     float ox = P[0], oy = P[1], oz = P[2];  // old = 0
-    for (int j = 1; j < m; j++) {
+    for (int j = 1; j < mo; j++) {
         const float gx = fmaxf(fmaxf(lo[0] - ox, ox - hi[0]), 0.f);
         const float gy = fmaxf(fmaxf(lo[1] - oy, oy - hi[1]), 0.f);
         const float gz = fmaxf(fmaxf(lo[2] - oz, oz - hi[2]), 0.f);
@@ -400,6 +429,11 @@ __global__ __launch_bounds__(NT) void fps_sorted_kernel(int n, int m, int npad, 
     }
     __syncthreads();
     for (int j = t; j < m; j += NT) {
+        if (RAGGED && j >= mo) {  // the samples this cloud did not want
+            O[j] = 0;
+            if (EMIT) NX[j * 3 + 0] = NX[j * 3 + 1] = NX[j * 3 + 2] = 0.f;
+            continue;
+        }
         const int gk = cpos[j];
         O[j] = gk;
         if (EMIT) {
@@ -412,8 +446,12 @@ __global__ __launch_bounds__(NT) void fps_sorted_kernel(int n, int m, int npad, 
 
 // Fallback for clouds beyond the register-resident limit: running min-distances in the
 // caller's temp buffer (b*n floats), points re-read from global/L2.  Same selection rule.
+// RAGGED: new_xyz (or NULL) is written here, the winners' coordinates being in the slots -- the plain form leaves them to
+// gather_kernel, which would read point 0 for the zeros of a row's tail.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(1024) void fps_mem_kernel(int n, int m, const float *__restrict__ inp,
-                                                       float *__restrict__ temp, int *__restrict__ out) {
+                                                       float *__restrict__ temp, int *__restrict__ out,
+                                                       float *__restrict__ new_xyz, rfi::Counts<RAGGED> cnt) {
     constexpr int NT = 1024, NW = NT / 64;
     __shared__ Slot slots[2][NW];
     const int bi = blockIdx.x;
@@ -421,13 +459,16 @@ __global__ __launch_bounds__(1024) void fps_mem_kernel(int n, int m, const float
     const float *P = inp + (size_t)bi * n * 3;
     float *T = temp + (size_t)bi * n;
     int *O = out + (size_t)bi * m;
-    for (int k = t; k < n; k += NT) T[k] = 1e38f;
+    const int nv = rfi::count1(cnt, bi, n), mo = rfi::count2(cnt, bi, m);
+    float *NX = (RAGGED && new_xyz) ? new_xyz + (size_t)bi * m * 3 : nullptr;
+    for (int k = t; k < nv; k += NT) T[k] = 1e38f;
     if (t == 0) O[0] = 0;
     float ox = P[0], oy = P[1], oz = P[2];
-    for (int j = 1; j < m; j++) {
+    if (RAGGED && NX && t == 0) NX[0] = ox, NX[1] = oy, NX[2] = oz;
+    for (int j = 1; j < mo; j++) {
         float best = -1.0f;
         int bk = 0;
-        for (int k = (t & 511) + 512 * (t >> 9); k < n; k += NT) {
+        for (int k = (t & 511) + 512 * (t >> 9); k < nv; k += NT) {
             float d = rf::d2_fma(P[k * 3] - ox, P[k * 3 + 1] - oy, P[k * 3 + 2] - oz);
             float d2 = fminf(d, T[k]);
             T[k] = d2;
@@ -461,6 +502,13 @@ __global__ __launch_bounds__(1024) void fps_mem_kernel(int n, int m, const float
         oy = slots[buf][gw].y;
         oz = slots[buf][gw].z;
         if (t == 0) O[j] = slots[buf][gw].k;
+        if (RAGGED && NX && t == 0) NX[j * 3 + 0] = ox, NX[j * 3 + 1] = oy, NX[j * 3 + 2] = oz;
+    }
+    if (RAGGED) {  // the samples this cloud did not want
+        for (int j = mo + t; j < m; j += NT) {
+            O[j] = 0;
+            if (NX) NX[j * 3 + 0] = NX[j * 3 + 1] = NX[j * 3 + 2] = 0.f;
+        }
     }
 }
 
@@ -656,9 +704,11 @@ int fps(int b, int n, int m, const float *inp, float *temp, int *out, float *new
     if (!inp || !out) return RF_EINVAL;
 #define FPS_CASE(NT, PPT)                                                                                             \
     if (new_xyz) {                                                                                                    \
-        RF_LAUNCH("fps_reg", (fps_reg_kernel<NT, PPT, true>), dim3(b), dim3(NT), 0, s, n, m, inp, out, new_xyz);     \
+        RF_LAUNCH("fps_reg", (fps_reg_kernel<NT, PPT, true>), dim3(b), dim3(NT), 0, s, n, m, inp, out, new_xyz,      \
+                  rfi::Counts<false>{});                                                                                \
     } else {                                                                                                          \
-        RF_LAUNCH("fps_reg", (fps_reg_kernel<NT, PPT, false>), dim3(b), dim3(NT), 0, s, n, m, inp, out, new_xyz);    \
+        RF_LAUNCH("fps_reg", (fps_reg_kernel<NT, PPT, false>), dim3(b), dim3(NT), 0, s, n, m, inp, out, new_xyz,     \
+                  rfi::Counts<false>{});                                                                                \
     }                                                                                                                 \
     return RF_OK
     if (n <= 512) { FPS_CASE(512, 1); }
@@ -669,7 +719,8 @@ int fps(int b, int n, int m, const float *inp, float *temp, int *out, float *new
     if (n <= 16384) { FPS_CASE(512, 32); }
 #undef FPS_CASE
     if (!temp) return RF_EINVAL;
-    RF_LAUNCH("fps_mem", fps_mem_kernel, dim3(b), dim3(1024), 0, s, n, m, inp, temp, out);
+    RF_LAUNCH("fps_mem", fps_mem_kernel<false>, dim3(b), dim3(1024), 0, s, n, m, inp, temp, out, (float *)nullptr,
+              rfi::Counts<false>{});
     if (new_xyz) {  // (the fallback kernel keeps its form: the coordinates by the gather kernel)
         const long total = (long)b * m;
         RF_LAUNCH("gather_point", gather_kernel, dim3(rf::ceil_div(total, 256)), dim3(256), 0, s, n, m, total, inp,
@@ -696,10 +747,10 @@ int fps_sorted(int b, int n, int m, const float *inp, const rfp::Sorted &sv, int
     if (ppt == PPT) {                                                                                                          \
         if (new_xyz) {                                                                                                         \
             RF_LAUNCH("fps_sorted", (fps_sorted_kernel<1024, PPT, true>), dim3(b), dim3(1024), 0, s, n, m, sv.npad, inp, sv.orig, \
-                      out, new_xyz);                                                                                           \
+                      out, new_xyz, rfi::Counts<false>{});                                                                       \
         } else {                                                                                                               \
             RF_LAUNCH("fps_sorted", (fps_sorted_kernel<1024, PPT, false>), dim3(b), dim3(1024), 0, s, n, m, sv.npad, inp, sv.orig, \
-                      out, new_xyz);                                                                                           \
+                      out, new_xyz, rfi::Counts<false>{});                                                                       \
         }                                                                                                                      \
         return RF_OK;                                                                                                          \
     }
@@ -707,7 +758,60 @@ int fps_sorted(int b, int n, int m, const float *inp, const rfp::Sorted &sv, int
 #undef FPSS_CASE
     return RF_EINVAL;
 }
+// The two launchers over a ragged batch: the RAGGED instantiations of the same kernels, chosen by the padded n as above.
+int fps_lengths(int b, int n, int m, const float *inp, const int *len, const int *len_out, float *temp, int *out,
+                float *new_xyz, hipStream_t s) {
+    if (b < 0 || n <= 0 || m <= 0 || !inp || !out) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    const rfi::Counts<true> cnt{len, len_out};
+#define FPS_CASE(NT, PPT)                                                                                                      \
+    if (new_xyz) {                                                                                                             \
+        RF_LAUNCH("fps_reg_lengths", (fps_reg_kernel<NT, PPT, true, true>), dim3(b), dim3(NT), 0, s, n, m, inp, out, new_xyz, \
+                  cnt);                                                                                                        \
+    } else {                                                                                                                   \
+        RF_LAUNCH("fps_reg_lengths", (fps_reg_kernel<NT, PPT, false, true>), dim3(b), dim3(NT), 0, s, n, m, inp, out, new_xyz, \
+                  cnt);                                                                                                        \
+    }                                                                                                                          \
+    return RF_OK
+    if (n <= 512) { FPS_CASE(512, 1); }
+    if (n <= 1024) { FPS_CASE(1024, 1); }
+    if (n <= 2048) { FPS_CASE(1024, 2); }
+    if (n <= 4096) { FPS_CASE(1024, 4); }
+    if (n <= 8192) { FPS_CASE(1024, 8); }
+    if (n <= 16384) { FPS_CASE(512, 32); }
+#undef FPS_CASE
+    if (!temp) return RF_EINVAL;
+    RF_LAUNCH("fps_mem_lengths", fps_mem_kernel<true>, dim3(b), dim3(1024), 0, s, n, m, inp, temp, out, new_xyz, cnt);
+    return RF_OK;
+}
+int fps_sorted_lengths(int b, int n, int m, const float *inp, const int *len, const int *len_out, const rfp::Sorted &sv,
+                       int *out, float *new_xyz, hipStream_t s) {
+    if (b <= 0) return RF_OK;
+    if (n <= FPS_SORTED_MIN_POINTS || n > FPS_MAX_REG_POINTS || m <= 0 || !inp || !out) return RF_EINVAL;
+    int ppt = 2;
+    while (1024 * ppt < n) ppt *= 2;
+    if (m > 1024 * ppt) return RF_EINVAL;  // (the samples collect in LDS, in the table of the kernel's prologue)
+    const rfi::Counts<true> cnt{len, len_out};
+#define FPSS_CASE(PPT)                                                                                                       \
+    if (ppt == PPT) {                                                                                                        \
+        if (new_xyz) {                                                                                                       \
+            RF_LAUNCH("fps_sorted_lengths", (fps_sorted_kernel<1024, PPT, true, true>), dim3(b), dim3(1024), 0, s, n, m,    \
+                      sv.npad, inp, sv.orig, out, new_xyz, cnt);                                                             \
+        } else {                                                                                                             \
+            RF_LAUNCH("fps_sorted_lengths", (fps_sorted_kernel<1024, PPT, false, true>), dim3(b), dim3(1024), 0, s, n, m,   \
+                      sv.npad, inp, sv.orig, out, new_xyz, cnt);                                                             \
+        }                                                                                                                    \
+        return RF_OK;                                                                                                        \
+    }
+    FPSS_CASE(2) FPSS_CASE(4) FPSS_CASE(8) FPSS_CASE(16)
+#undef FPSS_CASE
+    return RF_EINVAL;
+}
 }  // namespace rfi
+
+namespace {
+bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+}  // namespace
 
 extern "C" {
 
@@ -758,6 +862,34 @@ int rf_farthestpointsampling_sorted(int b, int n, int m, int form, const float *
     if (int e = rfp::sort_clouds(b, n, inp, workspace, workspace_bytes, s, &sv)) return e;
     (void)form;
     return rfi::fps_sorted(b, n, m, inp, sv, out, new_xyz, s);
+}
+
+// ---- ragged batches (include/rfops.h): routed by the padded (n, m) as rf_farthestpointsampling_ws, the sort given the counts
+size_t rf_farthestpointsampling_lengths_workspace_bytes(int b, int n, int m) {
+    if (b <= 0 || n <= 0 || m <= 0) return 0;
+    return rf_farthestpointsampling_workspace_bytes(b, n, m);
+}
+
+int rf_farthestpointsampling_lengths(int b, int n, int m, const float *inp, const int *len, const int *len_out, void *workspace,
+                                     size_t workspace_bytes, int *out, float *new_xyz, rf_stream_t stream) {
+    if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
+    if (!inp || !out) return RF_EINVAL;
+    if (!aligned4(inp) || !aligned4(len) || !aligned4(len_out) || !aligned4(out) || !aligned4(new_xyz) ||
+        !rf::aligned16(workspace))
+        return RF_EINVAL;
+    const size_t need = rf_farthestpointsampling_lengths_workspace_bytes(b, n, m);
+    if (need && !workspace) return RF_EINVAL;
+    if (workspace_bytes < need) return RF_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    if (rfi::fps_sorted_pays(n, m)) {
+        const rfp::Sorted sv = rfp::sorted_view(b, n, workspace);
+        const int *lens[1] = {len};
+        if (int e = rfp::sort_sets(b, 1, &n, &inp, &sv, s, nullptr, len ? lens : nullptr)) return e;
+        return rfi::fps_sorted_lengths(b, n, m, inp, len, len_out, sv, out, new_xyz, s);
+    }
+    return rfi::fps_lengths(b, n, m, inp, len, len_out, (float *)workspace, out, new_xyz, s);
 }
 
 int rf_gatherpoint(int b, int n, int m, const float *inp, const int *idx, float *out,

@@ -16,6 +16,7 @@
 // HBM traffic = the data: src once, dst once, 12 bytes of index per slot.
 #include "common.hpp"
 #include "scatter_rows.hpp"
+#include "group_internal.hpp"
 
 namespace {
 
@@ -36,9 +37,39 @@ __device__ __forceinline__ unsigned cb_wave_incl_scan(unsigned v) {
 // REG (CB_RPT > 0): S <= CB_TPB * CB_RPT -- a thread's slots are loaded ONCE, all loads in flight together, and both passes (counts, places)
 // run from registers; otherwise each pass walks idx again (L2-resident), eight loads in flight.
 constexpr int CB_STAGE = 16384;  // slot numbers staged in LDS (REG)
-template <int CB_RPT>
+// MASKED (rows_csr_sort_masked: the gradient of a ragged knn_point): a slot's key is taken as -1 -- in no row, like any key outside
+// [0, n) -- where the slot belongs to a padded query (slot / k >= len2's count), lies behind the sample's neighbours
+// (slot % k >= len1's count) or names a padded row (key >= len1's count), whatever idx holds there: the padding falls out while
+// the keys are built, no pass of its own.  The plain instantiation gets an EMPTY last argument and takes the keys as they are:
+// its code is what it was (rfi::Counts, group_internal.hpp).
+template <bool MASKED>
+struct SlotMask {
+    const int *len1, *len2;
+    int k, m;
+};
+template <>
+struct SlotMask<false> {};
+// the sample's clamped counts, read ONCE per workgroup (behind the LDS atomics of the passes a load inside cb_key would be
+// issued again for every slot: measured, the masked sort then costs twice the plain one)
+template <bool MASKED>
+struct SlotBounds {
+    int nv, mv, k;
+};
+template <>
+struct SlotBounds<false> {};
+__device__ __forceinline__ SlotBounds<false> cb_bounds(const SlotMask<false> &, int, int) { return {}; }
+__device__ __forceinline__ SlotBounds<true> cb_bounds(const SlotMask<true> &mk, int bi, int n) {
+    return {rfi::ragged_count(mk.len1, bi, n), rfi::ragged_count(mk.len2, bi, mk.m), mk.k};
+}
+__device__ __forceinline__ int cb_key(const SlotBounds<false> &, int, int key) { return key; }
+__device__ __forceinline__ int cb_key(const SlotBounds<true> &sb, int slot, int key) {
+    const int j = slot / sb.k, t = slot - j * sb.k;
+    return (j >= sb.mv || t >= sb.nv || key >= sb.nv) ? -1 : key;
+}
+template <int CB_RPT, bool MASKED = false>
 __global__ __launch_bounds__(CB_TPB) void rows_csr_build_kernel(int n, int S, int H, int nbl, const int *__restrict__ idx,
-                                                                int *__restrict__ row_start, int *__restrict__ perm) {
+                                                                int *__restrict__ row_start, int *__restrict__ perm,
+                                                                SlotMask<MASKED> mask) {
     extern __shared__ unsigned cb_cnt[];  // [nbl] counters, then [CB_STAGE] staged slot numbers
     __shared__ unsigned wsum[CB_TPB / 64];
     __shared__ unsigned lowsum[CB_TPB / 64];
@@ -49,10 +80,11 @@ __global__ __launch_bounds__(CB_TPB) void rows_csr_build_kernel(int n, int S, in
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr bool REG = CB_RPT > 0;
     const int *__restrict__ I = idx + (size_t)bi * S;
+    const SlotBounds<MASKED> bounds = cb_bounds(mask, bi, n);
     int kr[REG ? CB_RPT : 1];
     if (REG) {
 #pragma unroll
-        for (int u = 0; u < CB_RPT; u++) kr[u] = tid + u * CB_TPB < S ? I[tid + u * CB_TPB] : -1;
+        for (int u = 0; u < CB_RPT; u++) kr[u] = tid + u * CB_TPB < S ? cb_key(bounds, tid + u * CB_TPB, I[tid + u * CB_TPB]) : -1;
     }
     for (int i = tid; i < nbl; i += CB_TPB) cb_cnt[i] = 0u;
     __syncthreads();
@@ -67,7 +99,7 @@ __global__ __launch_bounds__(CB_TPB) void rows_csr_build_kernel(int n, int S, in
         for (int s0 = tid; s0 < S; s0 += 8 * CB_TPB) {
             int k[8];
 #pragma unroll
-            for (int u = 0; u < 8; u++) k[u] = s0 + u * CB_TPB < S ? I[s0 + u * CB_TPB] : -1;
+            for (int u = 0; u < 8; u++) k[u] = s0 + u * CB_TPB < S ? cb_key(bounds, s0 + u * CB_TPB, I[s0 + u * CB_TPB]) : -1;
 #pragma unroll
             for (int u = 0; u < 8; u++) {
                 if (k[u] >= lo && k[u] < hi) atomicAdd(&cb_cnt[k[u] - lo], 1u);
@@ -130,7 +162,7 @@ __global__ __launch_bounds__(CB_TPB) void rows_csr_build_kernel(int n, int S, in
         for (int s0 = tid; s0 < S; s0 += 8 * CB_TPB) {
             int k[8];
 #pragma unroll
-            for (int u = 0; u < 8; u++) k[u] = s0 + u * CB_TPB < S ? I[s0 + u * CB_TPB] : -1;
+            for (int u = 0; u < 8; u++) k[u] = s0 + u * CB_TPB < S ? cb_key(bounds, s0 + u * CB_TPB, I[s0 + u * CB_TPB]) : -1;
 #pragma unroll
             for (int u = 0; u < 8; u++) place(k[u], s0 + u * CB_TPB);
         }
@@ -258,7 +290,9 @@ size_t rows_csr_workspace_bytes(int b, int n, long S) {
     return align256(sizeof(int) * (size_t)b * ((size_t)n + 1)) + align256(sizeof(int) * (size_t)b * (size_t)S);
 }
 
-int rows_csr_sort(int b, int n, long S, const int *idx, void *workspace, const char *build_name, hipStream_t s) {
+template <bool MASKED>
+static int rows_csr_sort_impl(int b, int n, long S, const int *idx, void *workspace, const char *build_name, hipStream_t s,
+                              SlotMask<MASKED> mask) {
     int *row_start = (int *)workspace;
     int *perm = (int *)((char *)workspace + align256(sizeof(int) * (size_t)b * ((size_t)n + 1)));
     // workgroups per sample: enough to put ~128 CUs to work, every range at least 2048 bins, at most 32768
@@ -266,10 +300,10 @@ int rows_csr_sort(int b, int n, long S, const int *idx, void *workspace, const c
     while ((long)b * H < 128 && n / (2 * H) >= 2048 && H < 8) H *= 2;
     const int nbl = rf::ceil_div(n, H);
 #define RFS_BUILD(RPT, EXTRA)                                                                                                          \
-    RF_HIP(hipFuncSetAttribute((const void *)rows_csr_build_kernel<RPT>, hipFuncAttributeMaxDynamicSharedMemorySize,                   \
+    RF_HIP(hipFuncSetAttribute((const void *)rows_csr_build_kernel<RPT, MASKED>, hipFuncAttributeMaxDynamicSharedMemorySize,           \
                                (CB_MAXBINS + (EXTRA)) * 4));                                                                           \
-    RF_LAUNCH(build_name, rows_csr_build_kernel<RPT>, dim3((unsigned)(b * H)), dim3(CB_TPB), sizeof(unsigned) * ((size_t)nbl + (EXTRA)), \
-              s, n, (int)S, H, nbl, idx, row_start, perm)
+    RF_LAUNCH(build_name, (rows_csr_build_kernel<RPT, MASKED>), dim3((unsigned)(b * H)), dim3(CB_TPB),                                 \
+              sizeof(unsigned) * ((size_t)nbl + (EXTRA)), s, n, (int)S, H, nbl, idx, row_start, perm, mask)
     if (S <= (long)CB_TPB * 32) {
         RFS_BUILD(32, CB_STAGE);
     } else {  // (48 slots per thread -- three_interpolate's 3 x 16384 -- spill: 128 registers is all a 1024-thread workgroup has)
@@ -277,6 +311,15 @@ int rows_csr_sort(int b, int n, long S, const int *idx, void *workspace, const c
     }
 #undef RFS_BUILD
     return RF_OK;
+}
+
+int rows_csr_sort(int b, int n, long S, const int *idx, void *workspace, const char *build_name, hipStream_t s) {
+    return rows_csr_sort_impl<false>(b, n, S, idx, workspace, build_name, s, {});
+}
+
+int rows_csr_sort_masked(int b, int n, int m, int k, const int *idx, const int *len1, const int *len2, void *workspace,
+                         const char *build_name, hipStream_t s) {
+    return rows_csr_sort_impl<true>(b, n, (long)m * k, idx, workspace, build_name, s, {len1, len2, k, m});
 }
 
 const int *rows_csr_perm(int b, int n, const void *workspace) {

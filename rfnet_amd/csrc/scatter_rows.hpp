@@ -16,5 +16,10 @@ int rows_csr_scatter(int b, int n, int c, long S, int K, const float *src, const
 // at rows_csr_perm -- perm[row_start[r] .. row_start[r + 1]) are the slots s of a sample with idx[s] = r (any order).
 int rows_csr_sort(int b, int n, long S, const int *idx, void *workspace, const char *build_name, hipStream_t s);
 const int *rows_csr_perm(int b, int n, const void *workspace);
+// The same sort of the S = m k slots of a ragged knn_point (idx (b, m, k); len1 (b) valid rows, len2 (b) valid queries, device
+// arrays or NULL, clamped as every count): slots of queries behind len2, slots t >= len1 of a query and slots that name a row
+// behind len1 are in no row, whatever idx holds there.
+int rows_csr_sort_masked(int b, int n, int m, int k, const int *idx, const int *len1, const int *len2, void *workspace,
+                         const char *build_name, hipStream_t s);
 
 }  // namespace rfs

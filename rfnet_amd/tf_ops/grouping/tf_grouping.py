@@ -21,6 +21,16 @@ def query_ball_point(radius, nsample, xyz1, xyz2):
     return _raw.query_ball_point(radius, nsample, xyz1, xyz2)
 
 
+def query_ball_point_lengths(radius, nsample, xyz1, xyz2, lengths1=None, lengths2=None, form="auto"):
+    '''
+    query_ball_point over a ragged batch (the reference's signature above is kept as it is: this is the extension).
+    lengths1 / lengths2: (batch_size) int -- points per dataset, queries per sample (lists, numpy arrays or tensors; on the
+    device: no host synchronisation; None = all).  Rows of queries behind lengths2[i] are idx 0, pts_cnt 0 (as are empty
+    balls); the padding of xyz1 is in no ball.  form: "auto", "scan", "boxes" (same results).
+    '''
+    return _raw.query_ball_point(radius, nsample, xyz1, xyz2, form=form, lengths1=lengths1, lengths2=lengths2)
+
+
 class _GroupPoint(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, idx):
@@ -40,6 +50,8 @@ def group_point(points, idx):
         idx: (batch_size, npoint, nsample) int32 array, indices to points
     Output:
         out: (batch_size, npoint, nsample, channel) float32 array, values sampled from points
+    Ragged batches: the zero-filled rows that query_ball_point_lengths writes for padded queries are in range -- they
+    gather point 0 (and the gradient adds there); pts_cnt and the counts say which rows mean something.
     '''
     if isinstance(points, torch.Tensor) and isinstance(idx, torch.Tensor) and points.requires_grad:
         return _GroupPoint.apply(points, idx)
@@ -65,9 +77,10 @@ def _knn_on_gpu(k, xyz1, xyz2):
 
 class _KnnPoint(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, k, xyz1, xyz2):
-        val, idx = _raw.knn_point(k, xyz1, xyz2)
+    def forward(ctx, k, xyz1, xyz2, form="auto", lengths1=None, lengths2=None):
+        val, idx = _raw.knn_point(k, xyz1, xyz2, form=form, lengths1=lengths1, lengths2=lengths2)
         ctx.save_for_backward(xyz1, xyz2, idx)
+        ctx.lengths = (lengths1, lengths2)  # (integer counts: kept for the backward as they came)
         ctx.mark_non_differentiable(idx)
         return val, idx
 
@@ -76,12 +89,13 @@ class _KnnPoint(torch.autograd.Function):
     def backward(ctx, grad_val, grad_idx):
         xyz1, xyz2, idx = ctx.saved_tensors
         if grad_val is None:
-            return None, None, None
-        g1, g2 = _raw.knn_point_grad(xyz1, xyz2, idx, grad_val.contiguous())
-        return None, g1 if ctx.needs_input_grad[1] else None, g2 if ctx.needs_input_grad[2] else None
+            return None, None, None, None, None, None
+        l1, l2 = ctx.lengths
+        g1, g2 = _raw.knn_point_grad(xyz1, xyz2, idx, grad_val.contiguous(), lengths1=l1, lengths2=l2)
+        return None, g1 if ctx.needs_input_grad[1] else None, g2 if ctx.needs_input_grad[2] else None, None, None, None
 
 
-def knn_point(k, xyz1, xyz2):
+def knn_point(k, xyz1, xyz2, lengths1=None, lengths2=None, form="auto"):
     '''
     Input:
         k: int32, number of k in k-nn search
@@ -95,11 +109,18 @@ def knn_point(k, xyz1, xyz2):
     (b, m, n) tensor; ties to the lower index, tf.nn.top_k's rule), with the gradient to both inputs (rf_knn_grad, first order
     only: no double backward there); everything else is the tensor expression below.  val is the unfused fp32 distance
     ((dx*dx)+(dy*dy))+(dz*dz), which can differ from the expression's CUDA reduction in the last bits.
+    Ragged batches: lengths1 / lengths2 (batch_size) -- candidates / queries per sample -- on the HIP path only (the tensor
+    expression raises for them): rows of padded queries are zeros, a sample with fewer candidates than k gets its lengths1[i]
+    neighbours and zeros behind, and the gradient ignores every padded slot.
     '''
+    ragged = lengths1 is not None or lengths2 is not None
     if _knn_on_gpu(k, xyz1, xyz2):
         if xyz1.requires_grad or xyz2.requires_grad:
-            return _KnnPoint.apply(int(k), xyz1, xyz2)
-        return _raw.knn_point(int(k), xyz1, xyz2)
+            return _KnnPoint.apply(int(k), xyz1, xyz2, form, lengths1, lengths2)
+        return _raw.knn_point(int(k), xyz1, xyz2, form=form, lengths1=lengths1, lengths2=lengths2)
+    if ragged:
+        raise ValueError("knn_point: lengths need the HIP path (CUDA float32 (b,n,3) / (b,m,3) tensors on one device, "
+                         "1 <= k <= min(n, 64)); the tensor expression does not take them")
     xyz1 = torch.as_tensor(xyz1)
     xyz2 = torch.as_tensor(xyz2)
     dist = ((xyz1.unsqueeze(1) - xyz2.unsqueeze(2)) ** 2).sum(-1)

@@ -6,7 +6,7 @@ import torch
 from ... import _raw
 
 
-def three_nn(xyz1, xyz2):
+def three_nn(xyz1, xyz2, lengths1=None, lengths2=None, form="auto"):
     '''
     Input:
         xyz1: (b,n,3) float32 array, unknown points
@@ -14,8 +14,12 @@ def three_nn(xyz1, xyz2):
     Output:
         dist: (b,n,3) float32 array, SQUARED distances to the 3 nearest known points
         idx: (b,n,3) int32 array, indices to known points
+    Ragged batches: lengths1 / lengths2 (b) -- unknown / known points per sample (lists, numpy arrays or tensors; on the device:
+    no host synchronisation).  Rows behind lengths1[i] are zeros; the padding of xyz2 is nobody's neighbour.
     '''
-    return _raw.three_nn(xyz1, xyz2)
+    if lengths1 is None and lengths2 is None:
+        return _raw.three_nn(xyz1, xyz2, form=form)
+    return _raw.three_nn(xyz1, xyz2, form=form, lengths1=lengths1, lengths2=lengths2)
 
 
 class _ThreeInterpolate(torch.autograd.Function):
@@ -38,6 +42,8 @@ def three_interpolate(points, idx, weight):
         weight: (b,n,3) float32 array, weights on known points
     Output:
         out: (b,n,c) float32 array, interpolated point values
+    Ragged batches: the zero-filled rows that three_nn(..., lengths1=) leaves for padded unknown points are in range -- they read
+    known point 0 with whatever weights the caller formed there; the counts say which rows mean something.
     '''
     if all(isinstance(t, torch.Tensor) for t in (points, idx, weight)) and points.requires_grad:
         return _ThreeInterpolate.apply(points, idx, weight)

@@ -25,6 +25,8 @@ input:
     batch_size * npoints        int32
 returns:
     batch_size * npoints * 3    float32
+Ragged batches: the zero-filled indices that farthest_point_sample_lengths leaves behind a cloud's samples are
+in range -- those rows gather point 0 (and its gradient adds there); the counts say which rows mean something.
     '''
     if isinstance(inp, torch.Tensor) and isinstance(idx, torch.Tensor) and inp.requires_grad:
         return _GatherPoint.apply(inp, idx)
@@ -46,6 +48,20 @@ returns:
 (no gradient, like ops.NoGradient('FarthestPointSample'))
     '''
     return _raw.farthest_point_sample(npoint, inp)
+
+
+def farthest_point_sample_lengths(npoint, inp, lengths=None, npoints=None):
+    '''
+farthest_point_sample over a ragged batch (the reference's signature above is kept as it is: this is the extension).
+input:
+    int32
+    batch_size * ndataset * 3   float32
+    lengths: batch_size int, valid points per cloud; npoints: batch_size int, samples wanted per cloud (at most npoint) --
+    lists, numpy arrays or tensors (on the device: no host synchronisation); None = all
+returns:
+    batch_size * npoint         int32: row i holds the samples of inp[i, :lengths[i]], and zeros behind npoints[i]
+    '''
+    return _raw.farthest_point_sample(npoint, inp, lengths=lengths, npoints=npoints)
 
 
 def prob_sample(inp, inpr):
