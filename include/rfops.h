@@ -24,8 +24,10 @@
  *   - `workspace` buffers and sorted-set handles (rf_nn_sort) must be 16-byte aligned -- the kernels read
  *     them with 16-byte vector loads at 256-byte-multiple offsets; any hipMalloc pointer is.  A misaligned
  *     one is RF_EINVAL (culled Chamfer paths, approx_match, earth_mover), not a fault inside a kernel.
- *     Tensor arguments need their element's natural alignment (4 bytes), except rf_point_affine's
- *     (16 bytes: rows of c % 4 == 0 floats).
+ *     Tensor arguments need their element's natural alignment (4 bytes), except the (.., c) feature tensors of the
+ *     model graph helpers, which are read and written in rows of c % 4 == 0 floats and need 16 bytes:
+ *     rf_point_affine's y, w, r and out, rf_maxpool_points' and rf_maxpool_points_idx's x, rf_act_grad_colsum's grad,
+ *     out and g (their p, out / idx and sums need 4).  A less aligned one is RF_EINVAL before anything is launched.
  *
  * Status codes: 0 = success; > 0 = the hipError_t of the failing HIP call;
  *               < 0 = RF_EINVAL-style argument errors below.

@@ -43,6 +43,7 @@ int zero_async(void *p, size_t bytes, hipStream_t s);
 // caller hands over must be 16-byte aligned (include/rfops.h; anything hipMalloc returns is).  Checked at the boundary -- a
 // misaligned sub-allocation would otherwise be a memory fault inside a kernel.
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // Workgroup ids go round the 8 XCDs (id % 8), each with an L2 of its own.  Logical position of workgroup `id` of `total` such that
 // every XCD owns a CONTIGUOUS eighth of the logical order: workgroups that read the same sample then share one L2 instead of

@@ -269,6 +269,7 @@ int rf_maxpool_points(int b, int n, int c, const float *x, float *out, void *wor
     if ((size_t)b * c == 0) return RF_OK;
     if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
     if (!x || !out || !workspace) return RF_EINVAL;
+    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out)) return RF_EINVAL;  // x, workspace: float4 rows
     if (workspace_bytes < rf_maxpool_points_workspace_bytes(b, n, c)) return RF_EWORKSPACE;
     const int nstrips = rf::ceil_div(n, MP_STRIP);
     hipStream_t s = (hipStream_t)stream;
@@ -289,6 +290,7 @@ int rf_maxpool_points_idx(int b, int n, int c, const float *x, float *out, int *
     if ((size_t)b * c == 0) return RF_OK;
     if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
     if (!x || !out || !idx || !workspace) return RF_EINVAL;
+    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out) || !rf::aligned4(idx)) return RF_EINVAL;
     if (workspace_bytes < rf_maxpool_points_idx_workspace_bytes(b, n, c)) return RF_EWORKSPACE;
     const int nstrips = rf::ceil_div(n, MP_STRIP);
     float *part = (float *)workspace;
@@ -308,7 +310,10 @@ int rf_act_grad_colsum(int b, int n, int c, const float *grad, const float *out,
     if (b < 0 || n < 0 || c < 0 || act < 0 || act > 3) return RF_EINVAL;
     if ((size_t)b * c == 0) return RF_OK;
     if (c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
-    if (!sums) return RF_EINVAL;
+    if (!sums || !rf::aligned4(sums)) return RF_EINVAL;
+    // grad, out and g are read and written as float4 rows, the workspace too.  Deliberately unconditional, as the header states
+    // it: `out` is checked with act == 0 as well, where no kernel reads it (NULL passes)
+    if (!rf::aligned16(grad) || !rf::aligned16(out) || !rf::aligned16(g) || !rf::aligned16(workspace)) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
         RF_ZERO(sums, sizeof(float) * (size_t)b * c, s);
@@ -338,6 +343,10 @@ int rf_point_affine(int b, int n, int c, const float *y, const float *p, int kp,
     if ((size_t)b * n * c == 0) return RF_OK;
     if (!rf_point_affine_supported(c, kp) || b > 65535) return RF_EINVAL;
     if (!r || !out || (kp > 0 && (!p || !w))) return RF_EINVAL;
+    // y, w, r and out are read and written as float4 rows; p by the word (checked with kp == 0 too, where it is not read:
+    // the rule does not depend on the attributes)
+    if (!rf::aligned16(y) || !rf::aligned16(r) || !rf::aligned16(out) || !rf::aligned4(p) || (kp > 0 && !rf::aligned16(w)))
+        return RF_EINVAL;
     const dim3 grid(rf::ceil_div(n, PA_STRIP), b);
     const long rs = r_per_sample ? c : 0;
     hipStream_t s = (hipStream_t)stream;
