@@ -26,7 +26,7 @@
  *     one is RF_EINVAL (culled Chamfer paths, approx_match, earth_mover), not a fault inside a kernel.
  *     Tensor arguments need their element's natural alignment (4 bytes), except the (.., c) feature tensors of the
  *     model graph helpers, which are read and written in rows of c % 4 == 0 floats and need 16 bytes:
- *     rf_point_affine's y, w, r and out, rf_maxpool_points' and rf_maxpool_points_idx's x, rf_act_grad_colsum's grad,
+ *     rf_point_affine's y, w, r and out, rf_maxpool_points' and rf_maxpool_points_idx's x (their _lengths forms too), rf_act_grad_colsum's grad,
  *     out and g (their p, out / idx and sums need 4).  A less aligned one is RF_EINVAL before anything is launched.
  *
  * Status codes: 0 = success; > 0 = the hipError_t of the failing HIP call;
@@ -568,6 +568,27 @@ int rf_merge_layer_grad(int b, int n, int m, const float *rawpts, const float *n
                         const float *decfactor_dev, const int *idx2, const float *grad_refined,
                         float *grad_newpts, float *grad_dec, float *grad_raw, rf_stream_t stream);
 
+/* merge_layer over a ragged batch: sample i merges newpts[i, :len_new[i]] into rawpts[i, :len_raw[i]].
+ * The conventions of rf_nn_distance_lengths: len_raw / len_new are DEVICE int32[b] arrays, NULL = all rows, read by the
+ * kernels (no host synchronisation: the calls can be captured into a graph), a value outside [1, n] / [1, m] is clamped
+ * inside the kernels, and rows beyond a count may hold anything (NaN, inf, copies of valid points): they reach no result.
+ * rf_merge_layer_lengths: direction 2 of rf_nn_distance_lengths (sweep chosen as RF_NN_AUTO on the padded sizes; no
+ * sorted handle -- the culled sweep sorts internally) and the pull.  On the valid new rows idx2 and refined are bit for
+ * bit rf_merge_layer's on that sample's slices alone, and idx2 < len_raw[i]; a padded new row gets idx2 = 0 and
+ * refined = +0.0f.  rf_merge_layer_grad_lengths: grad_newpts as rf_merge_layer_grad on the valid rows and exactly 0 on
+ * the padded ones, whatever grad_refined or idx2 hold there; grad_dec[i] sums over the valid new rows only, in
+ * rf_merge_layer_grad's order on the slice; grad_raw (or NULL) is exactly 0 beyond len_raw[i].  Count arrays 4-byte
+ * aligned, workspace 16-byte aligned (RF_EINVAL); a workspace smaller than rf_merge_layer_lengths_workspace_bytes(b, n, m)
+ * is RF_EWORKSPACE; both are found before any HIP call. */
+size_t rf_merge_layer_lengths_workspace_bytes(int b, int n, int m);
+int rf_merge_layer_lengths(int b, int n, int m, const float *rawpts, const float *newpts, const int *len_raw,
+                           const int *len_new, const float *decfactor_dev, float *refined, int *idx2,
+                           void *workspace, size_t workspace_bytes, rf_stream_t stream);
+int rf_merge_layer_grad_lengths(int b, int n, int m, const float *rawpts, const float *newpts, const int *len_raw,
+                                const int *len_new, const float *decfactor_dev, const int *idx2,
+                                const float *grad_refined, float *grad_newpts, float *grad_dec, float *grad_raw,
+                                rf_stream_t stream);
+
 /* ------------------------------------------------ model graph helper (row f2) ------------ */
 /* The elementwise tail of RFNet's per-point dense layers in one pass.  The reference's conv2d
  * (vv_recon.py:47-65: conv + bias_add + activation) is mostly applied to
@@ -592,6 +613,21 @@ int rf_maxpool_points(int b, int n, int c, const float *x, float *out, void *wor
 size_t rf_maxpool_points_idx_workspace_bytes(int b, int n, int c);
 int rf_maxpool_points_idx(int b, int n, int c, const float *x, float *out, int *idx, void *workspace,
                           size_t workspace_bytes, rf_stream_t stream);
+
+/* The two poolings over a ragged batch: for sample i the maximum runs over rows [0, len[i]) of x only.
+ * len: DEVICE int32[b], NULL = all rows, read by the kernels (no host synchronisation), clamped into [1, n] inside them;
+ * rows beyond a count may hold anything (NaN, +inf) and are never read.  out -- and idx, which is always < len[i] -- are
+ * bit for bit what rf_maxpool_points / rf_maxpool_points_idx return for x[i, :len[i]] alone (lowest index among ties,
+ * NaNs skipped as fmaxf skips them).  Work shrinks with the counts: a strip wholly behind a count is not read, and the
+ * fold visits only the strips that were written, so the workspace (the dense entries' sizes) may arrive uninitialised.
+ * Argument rules of the dense entries (c % 4 == 0, c <= 1024, x and workspace 16-byte aligned) plus len 4-byte aligned:
+ * RF_EINVAL; a short workspace: RF_EWORKSPACE; all found before any HIP call. */
+size_t rf_maxpool_points_lengths_workspace_bytes(int b, int n, int c);
+int rf_maxpool_points_lengths(int b, int n, int c, const float *x, const int *len, float *out, void *workspace,
+                              size_t workspace_bytes, rf_stream_t stream);
+size_t rf_maxpool_points_idx_lengths_workspace_bytes(int b, int n, int c);
+int rf_maxpool_points_idx_lengths(int b, int n, int c, const float *x, const int *len, float *out, int *idx,
+                                  void *workspace, size_t workspace_bytes, rf_stream_t stream);
 
 /* Backward of a layer tail (training step of the graph; conv2d's bias_add + activation,
  * vv_recon.py:47-65, differentiated):  g[i,j,:] = grad[i,j,:] * act'(out[i,j,:])  and

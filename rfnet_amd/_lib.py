@@ -58,6 +58,9 @@ SIGNATURES = {
     "rf_merge_layer_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_merge_layer": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_merge_layer_grad": (_i, [_i, _i, _i] + [_vp] * 9),
+    "rf_merge_layer_lengths_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_merge_layer_lengths": (_i, [_i, _i, _i] + [_vp] * 8 + [_sz, _vp]),
+    "rf_merge_layer_grad_lengths": (_i, [_i, _i, _i] + [_vp] * 11),
     "rf_approxmatch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_approxmatch": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rf_approxmatch_levels": (_i, [_i, _i, _i, _vp, _vp, _vp, C.POINTER(_f), _i, _vp, _sz, _vp]),
@@ -128,6 +131,10 @@ SIGNATURES = {
     "rf_maxpool_points": (_i, [_i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "rf_maxpool_points_idx_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_maxpool_points_idx": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rf_maxpool_points_lengths_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_maxpool_points_lengths": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rf_maxpool_points_idx_lengths_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_maxpool_points_idx_lengths": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rf_act_grad_colsum_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_act_grad_colsum": (_i, [_i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "rf_point_affine_supported": (_i, [_i, _i]),

@@ -378,15 +378,28 @@ def chamfer_loss_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, grad_loss, lengths1=
 
 
 @H.on_input_device
-def merge_layer(rawpts, newpts, decfactor, sorted_raw=None):
-    """rf_merge_layer (vv_recon.py:132-139) -> (refined (b,m,3), idx2 (b,m))."""
+def merge_layer(rawpts, newpts, decfactor, sorted_raw=None, lengths=None, lengths_new=None):
+    """rf_merge_layer (vv_recon.py:132-139) -> (refined (b,m,3), idx2 (b,m)).  `lengths` / `lengths_new`: per-sample
+    counts of rawpts / newpts in a ragged batch (rf_merge_layer_lengths): idx2 points into the sample's own raw rows,
+    padded new rows come back as idx2 = 0, refined = 0; they do not combine with a sorted handle."""
+    ragged = lengths is not None or lengths_new is not None
+    if ragged and sorted_raw is not None:
+        raise H.invalid("merge_layer: per-sample lengths do not combine with a sorted handle")
     st = H.Staged()
     a, b_ = _nn_inputs(st, rawpts, newpts)
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
+    if ragged:
+        lr, ln = _check_lengths(lengths, b, n, "lengths"), _check_lengths(lengths_new, b, m, "lengths_new")
     dev = st.device_()
     a, b_ = st.up(a, b_)
     dec = torch.as_tensor(decfactor, dtype=F32).detach().reshape(-1)[:1].to(dev).contiguous()
     out, i2 = H.empty((b, m, 3), F32, dev), H.empty((b, m), I32, dev)
+    if ragged:
+        lr, ln = _lengths_up(lr, dev, n), _lengths_up(ln, dev, m)
+        ws, wsz = H.workspace(lib.rf_merge_layer_lengths_workspace_bytes(b, n, m), dev, "nn")
+        check(lib.rf_merge_layer_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(lr), H.ptr(ln), H.ptr(dec), H.ptr(out),
+                                         H.ptr(i2), H.ptr(ws), wsz, H.stream(dev)), "rf_merge_layer_lengths")
+        return st.give(out), st.give(i2)
     ps = _sorted_ptr(sorted_raw, b, n, dev)
     ws, wsz = H.workspace(lib.rf_merge_layer_workspace_bytes(b, n, m, int(ps is not None)), dev, "nn")
     check(lib.rf_merge_layer(b, n, m, H.ptr(a), H.ptr(b_), ps, H.ptr(dec), H.ptr(out), H.ptr(i2), H.ptr(ws), wsz,
@@ -395,19 +408,30 @@ def merge_layer(rawpts, newpts, decfactor, sorted_raw=None):
 
 
 @H.on_input_device
-def merge_layer_grad(rawpts, newpts, decfactor, idx2, grad_refined, want_raw=False):
-    """rf_merge_layer_grad -> (grad_newpts (b,m,3), grad_dec (b,), grad_raw (b,n,3) or None)."""
+def merge_layer_grad(rawpts, newpts, decfactor, idx2, grad_refined, want_raw=False, lengths=None, lengths_new=None):
+    """rf_merge_layer_grad -> (grad_newpts (b,m,3), grad_dec (b,), grad_raw (b,n,3) or None).  With `lengths` /
+    `lengths_new` (rf_merge_layer_grad_lengths) padded rows of either side get a zero gradient and grad_dec sums over
+    each sample's own new points."""
     st = H.Staged()
     a, b_ = _nn_inputs(st, rawpts, newpts)
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
     ix, go = st.take(idx2, I32), st.take(grad_refined, F32)
     if tuple(ix.shape) != (b, m) or tuple(go.shape) != (b, m, 3):
         raise H.invalid("merge_layer_grad expects idx2 (batch,#new) and grad (batch,#new,3)")
+    ragged = lengths is not None or lengths_new is not None
+    if ragged:
+        lr, ln = _check_lengths(lengths, b, n, "lengths"), _check_lengths(lengths_new, b, m, "lengths_new")
     dev = st.device_()
     a, b_, ix, go = st.up(a, b_, ix, go)
     dec = torch.as_tensor(decfactor, dtype=F32).detach().reshape(-1)[:1].to(dev).contiguous()
     gn, gd = H.empty((b, m, 3), F32, dev), H.empty((b,), F32, dev)
     gr = H.empty((b, n, 3), F32, dev) if want_raw else None
+    if ragged:
+        lr, ln = _lengths_up(lr, dev, n), _lengths_up(ln, dev, m)
+        check(lib.rf_merge_layer_grad_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(lr), H.ptr(ln), H.ptr(dec), H.ptr(ix),
+                                              H.ptr(go), H.ptr(gn), H.ptr(gd), H.ptr(gr), H.stream(dev)),
+              "rf_merge_layer_grad_lengths")
+        return st.give(gn), st.give(gd), (None if gr is None else st.give(gr))
     check(lib.rf_merge_layer_grad(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(dec), H.ptr(ix), H.ptr(go), H.ptr(gn),
                                   H.ptr(gd), H.ptr(gr), H.stream(dev)), "rf_merge_layer_grad")
     return st.give(gn), st.give(gd), (None if gr is None else st.give(gr))
@@ -1198,13 +1222,22 @@ def point_affine(y, p, w, r, act="relu", out=None):
     return out
 
 
-def maxpool_points_idx(x):
+def maxpool_points_idx(x, lengths=None):
     """rf_maxpool_points_idx: max over the points axis of a (b, n, c) GPU tensor -> values (b, 1, c) and
-    the point index of each maximum (b, c) int32 (lowest index among ties)."""
+    the point index of each maximum (b, c) int32 (lowest index among ties).  `lengths`: per-sample row counts of a
+    ragged batch (rf_maxpool_points_idx_lengths): sample i pools x[i, :lengths[i]], idx < lengths[i]."""
     b, n, c = x.shape
+    ln = _check_lengths(lengths, b, n, "lengths")
     dev = x.device
     x_ = x.contiguous()
     out, idx = H.empty((b, 1, c), F32, dev), H.empty((b, c), I32, dev)
+    if ln is not None:
+        with torch.cuda.device(dev):
+            ln = _lengths_up(ln, dev, n)
+            ws, wsz = H.workspace(lib.rf_maxpool_points_idx_lengths_workspace_bytes(b, n, c), dev, "maxpool")
+            check(lib.rf_maxpool_points_idx_lengths(b, n, c, H.ptr(x_), H.ptr(ln), H.ptr(out), H.ptr(idx), H.ptr(ws), wsz,
+                                                    H.stream(dev)), "rf_maxpool_points_idx_lengths")
+        return out, idx
     with torch.cuda.device(dev):
         ws, wsz = H.workspace(lib.rf_maxpool_points_idx_workspace_bytes(b, n, c), dev, "maxpool")
         check(lib.rf_maxpool_points_idx(b, n, c, H.ptr(x_), H.ptr(out), H.ptr(idx), H.ptr(ws), wsz, H.stream(dev)),
@@ -1237,12 +1270,21 @@ def act_grad_colsum(grad, out, act, inplace=False):
     return g, sums
 
 
-def maxpool_points(x):
-    """rf_maxpool_points: max over the points axis of a (b, n, c) GPU tensor -> (b, 1, c) (keepdim)."""
+def maxpool_points(x, lengths=None):
+    """rf_maxpool_points: max over the points axis of a (b, n, c) GPU tensor -> (b, 1, c) (keepdim).  `lengths`:
+    per-sample row counts of a ragged batch (rf_maxpool_points_lengths): sample i pools x[i, :lengths[i]]."""
     b, n, c = x.shape
+    ln = _check_lengths(lengths, b, n, "lengths")
     dev = x.device
     x_ = x.contiguous()
     out = H.empty((b, 1, c), F32, dev)
+    if ln is not None:
+        with torch.cuda.device(dev):
+            ln = _lengths_up(ln, dev, n)
+            ws, wsz = H.workspace(lib.rf_maxpool_points_lengths_workspace_bytes(b, n, c), dev, "maxpool")
+            check(lib.rf_maxpool_points_lengths(b, n, c, H.ptr(x_), H.ptr(ln), H.ptr(out), H.ptr(ws), wsz, H.stream(dev)),
+                  "rf_maxpool_points_lengths")
+        return out
     with torch.cuda.device(dev):
         ws, wsz = H.workspace(lib.rf_maxpool_points_workspace_bytes(b, n, c), dev, "maxpool")
         check(lib.rf_maxpool_points(b, n, c, H.ptr(x_), H.ptr(out), H.ptr(ws), wsz, H.stream(dev)), "rf_maxpool_points")

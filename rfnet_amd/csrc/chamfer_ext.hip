@@ -164,6 +164,100 @@ __global__ __launch_bounds__(MG_TPB) void merge_pull_grad_kernel(int n, int m, c
     }
 }
 
+// The tail and its backward over a ragged batch (rf_merge_layer_lengths / rf_merge_layer_grad_lengths): sample bi has
+// len_raw[bi] raw points and len_new[bi] new points (device counts, clamped into [1, n] / [1, m] here; NULL = all).  Valid new
+// rows get merge_pull_kernel's arithmetic, expression for expression; a padded new row gets idx2 = 0 and refined = +0.0
+// whatever the sweep left in its slot ((0, -1) on the dense route, nothing on the culled one), so that gathers downstream
+// need no special case.
+__device__ __forceinline__ int mg_len(const int *__restrict__ len, int bi, int full) {
+    if (!len) return full;
+    const int v = len[bi];
+    return v < 1 ? 1 : (v > full ? full : v);
+}
+
+__global__ void merge_pull_len_kernel(int n, int m, long total, const float *__restrict__ raw,
+                                      const float *__restrict__ newpts, int *__restrict__ idx2,
+                                      const float *__restrict__ decfactor, float *__restrict__ out,
+                                      const int *__restrict__ len_new) {
+    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const long bi = e / m;
+    if ((int)(e - bi * m) >= mg_len(len_new, (int)bi, m)) {
+        idx2[e] = 0;
+        out[e * 3 + 0] = 0.f;
+        out[e * 3 + 1] = 0.f;
+        out[e * 3 + 2] = 0.f;
+        return;
+    }
+    const float dec = decfactor[0];
+    const float c = 1e-8f + dec * dec;
+    const float *g = raw + (bi * n + idx2[e]) * 3;
+    const float qx = newpts[e * 3 + 0], qy = newpts[e * 3 + 1], qz = newpts[e * 3 + 2];
+    const float dx = g[0] - qx, dy = g[1] - qy, dz = g[2] - qz;
+    const float s = (dx * dx + dy * dy) + dz * dz;
+    const float ratio = expf(-s / c);
+    out[e * 3 + 0] = qx + ratio * dx;
+    out[e * 3 + 1] = qy + ratio * dy;
+    out[e * 3 + 2] = qz + ratio * dz;
+}
+
+// One sample per workgroup, as merge_pull_grad_kernel: the same strided loop and the same reduction over the sample's
+// len_new valid rows (the order the dense kernel takes on that slice alone); padded rows get grad_newpts = 0 without their
+// grad_out or idx2 being read.  A stored index is held inside [0, len_raw) before it addresses raw / grad_raw (the forward
+// never leaves one outside), so grad_raw stays 0 behind the count whatever the caller kept in idx2.
+__global__ __launch_bounds__(MG_TPB) void merge_pull_grad_len_kernel(int n, int m, const float *__restrict__ raw,
+                                                                     const float *__restrict__ newpts,
+                                                                     const int *__restrict__ idx2,
+                                                                     const float *__restrict__ decfactor,
+                                                                     const float *__restrict__ grad_out,
+                                                                     float *__restrict__ grad_newpts,
+                                                                     float *__restrict__ grad_dec,
+                                                                     float *__restrict__ grad_raw,
+                                                                     const int *__restrict__ len_raw,
+                                                                     const int *__restrict__ len_new) {
+    __shared__ float part[MG_TPB / 64];
+    const int bi = blockIdx.x;
+    const int nl = mg_len(len_raw, bi, n), ml = mg_len(len_new, bi, m);
+    const float dec = decfactor[0];
+    const float c = 1e-8f + dec * dec;
+    float acc = 0.f;
+    for (int j = threadIdx.x; j < ml; j += MG_TPB) {
+        const size_t e = (size_t)bi * m + j;
+        int k = idx2[e];
+        k = k < 0 ? 0 : (k >= nl ? nl - 1 : k);
+        const float *g = raw + ((size_t)bi * n + k) * 3;
+        const float qx = newpts[e * 3 + 0], qy = newpts[e * 3 + 1], qz = newpts[e * 3 + 2];
+        const float dx = g[0] - qx, dy = g[1] - qy, dz = g[2] - qz;
+        const float s = (dx * dx + dy * dy) + dz * dz;
+        const float ratio = expf(-s / c);
+        const float gx = grad_out[e * 3 + 0], gy = grad_out[e * 3 + 1], gz = grad_out[e * 3 + 2];
+        const float g_ratio = (gx * dx + gy * dy) + gz * dz;
+        const float k2 = 2.f * ratio * g_ratio / c;
+        const float fx = ratio * gx - k2 * dx, fy = ratio * gy - k2 * dy, fz = ratio * gz - k2 * dz;
+        grad_newpts[e * 3 + 0] = gx - fx;
+        grad_newpts[e * 3 + 1] = gy - fy;
+        grad_newpts[e * 3 + 2] = gz - fz;
+        if (grad_raw) {
+            float *gr = grad_raw + ((size_t)bi * n + k) * 3;
+            atomicAdd(gr + 0, fx);
+            atomicAdd(gr + 1, fy);
+            atomicAdd(gr + 2, fz);
+        }
+        acc += g_ratio * ratio * s / (c * c);
+    }
+    for (int j = ml * 3 + threadIdx.x; j < m * 3; j += MG_TPB) grad_newpts[(size_t)bi * m * 3 + j] = 0.f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = part[0];
+#pragma unroll
+        for (int w = 1; w < MG_TPB / 64; w++) t += part[w];
+        grad_dec[bi] = t * (2.f * dec);
+    }
+}
+
 int dirs_of(int want1, int want2) { return (want1 ? 1 : 0) | (want2 ? 2 : 0); }
 
 // Forward with optional sorted handles.  Culled when both handles are supplied or when the size rule
@@ -398,6 +492,53 @@ int rf_merge_layer_grad(int b, int n, int m, const float *rawpts, const float *n
     if (!rawpts || !newpts || !decfactor_dev || !idx2 || !grad_refined || !grad_newpts) return RF_EINVAL;
     RF_LAUNCH("merge_pull_grad", merge_pull_grad_kernel, dim3(b), dim3(MG_TPB), 0, s, n, m, rawpts, newpts, idx2,
               decfactor_dev, grad_refined, grad_newpts, grad_dec, grad_raw);
+    return RF_OK;
+}
+
+// ------------------------------------------------------------------ merge_layer, ragged ----
+size_t rf_merge_layer_lengths_workspace_bytes(int b, int n, int m) {
+    if (b <= 0 || n <= 0 || m <= 0) return 0;
+    return align256((size_t)b * m * sizeof(float)) + rfd::ragged_workspace_bytes(b, n, m, RF_NN_AUTO, 2);
+}
+
+int rf_merge_layer_lengths(int b, int n, int m, const float *rawpts, const float *newpts, const int *len_raw,
+                           const int *len_new, const float *decfactor_dev, float *refined, int *idx2, void *workspace,
+                           size_t workspace_bytes, rf_stream_t stream) {
+    if (bad_sizes(b, n, m)) return RF_EINVAL;
+    if (b == 0 || m == 0) return RF_OK;
+    if (n == 0 || !rawpts || !newpts || !decfactor_dev || !refined || !idx2 || !workspace) return RF_EINVAL;
+    if (!rf::aligned16(workspace) || !aligned4(len_raw) || !aligned4(len_new)) return RF_EINVAL;
+    const size_t dbytes = align256((size_t)b * m * sizeof(float));
+    if (workspace_bytes < rf_merge_layer_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    float *dist2 = (float *)workspace;  // the distances themselves are not an output of merge_layer
+    // pad_culled = false: the pull kernel below writes every padded slot of idx2 itself, on either route
+    if (int e = rfd::ragged_nn_distance(b, n, m, rawpts, newpts, len_raw, len_new, nullptr, nullptr, dist2, idx2,
+                                        (char *)workspace + dbytes, workspace_bytes - dbytes, s, RF_NN_AUTO, 2, false))
+        return e;
+    const long total = (long)b * m;
+    RF_LAUNCH("merge_pull_len", merge_pull_len_kernel, dim3(rf::ceil_div(total, 256)), dim3(256), 0, s, n, m, total,
+              rawpts, newpts, idx2, decfactor_dev, refined, len_new);
+    return RF_OK;
+}
+
+int rf_merge_layer_grad_lengths(int b, int n, int m, const float *rawpts, const float *newpts, const int *len_raw,
+                                const int *len_new, const float *decfactor_dev, const int *idx2,
+                                const float *grad_refined, float *grad_newpts, float *grad_dec, float *grad_raw,
+                                rf_stream_t stream) {
+    if (bad_sizes(b, n, m)) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (!grad_dec || !aligned4(len_raw) || !aligned4(len_new)) return RF_EINVAL;
+    const bool empty = m == 0 || n == 0;
+    if (!empty && (!rawpts || !newpts || !decfactor_dev || !idx2 || !grad_refined || !grad_newpts)) return RF_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (grad_raw && n) RF_ZERO(grad_raw, sizeof(float) * 3 * (size_t)b * n, s);
+    if (empty) {
+        RF_ZERO(grad_dec, sizeof(float) * (size_t)b, s);
+        return RF_OK;
+    }
+    RF_LAUNCH("merge_pull_grad_len", merge_pull_grad_len_kernel, dim3(b), dim3(MG_TPB), 0, s, n, m, rawpts, newpts, idx2,
+              decfactor_dev, grad_refined, grad_newpts, grad_dec, grad_raw, len_raw, len_new);
     return RF_OK;
 }
 

@@ -176,6 +176,92 @@ __global__ __launch_bounds__(MP_TPB) void maxpool_idx_stage2_kernel(int c, int n
     }
 }
 
+// ---- the same two poolings over a ragged batch (rf_maxpool_points_lengths / rf_maxpool_points_idx_lengths): sample bi pools
+// its rows [0, len[bi]) only (len: device counts, clamped into [1, n] here; NULL = all rows).  Grid and partial layout are the
+// dense kernels'; a workgroup whose strip starts at or behind the count leaves at once (the count is uniform over the
+// workgroup: all of it leaves, before the barrier, having read nothing), the strip that holds the count stops its point loop
+// there, and the fold walks the ceil(len / MP_STRIP) strips that were written -- the other partials are never read, so the
+// workspace needs no initial value.  Per sample this is the dense kernels' arithmetic on x[bi, :len[bi]]: same strips, same
+// point-lane order, same tie rule.
+__device__ __forceinline__ int mp_len(const int *__restrict__ len, int bi, int n) {
+    if (!len) return n;
+    const int v = len[bi];
+    return v < 1 ? 1 : (v > n ? n : v);
+}
+
+template <bool IDX>
+__global__ __launch_bounds__(MP_TPB) void maxpool_len_stage1_kernel(int n, int c, int nstrips, const float *__restrict__ x,
+                                                                    const int *__restrict__ len, float *__restrict__ part,
+                                                                    int *__restrict__ parti) {
+    __shared__ float4 red[MP_TPB];
+    __shared__ int4 redi[IDX ? MP_TPB : 1];
+    const int bi = blockIdx.y, strip = blockIdx.x;
+    const int cnt = mp_len(len, bi, n);
+    const int jfirst = strip * MP_STRIP;
+    if (jfirst >= cnt) return;
+    const int quads = c >> 2, ppi = MP_TPB / quads;
+    const int cq = threadIdx.x % quads, pl = threadIdx.x / quads;
+    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+    int4 mi = make_int4(jfirst, jfirst, jfirst, jfirst);
+    if (pl < ppi) {
+        const int n1 = min(cnt, jfirst + MP_STRIP);
+        for (int j = jfirst + pl; j < n1; j += ppi) {
+            const float4 v = *(const float4 *)(x + ((size_t)bi * n + j) * c + cq * 4);
+            if constexpr (IDX) {
+                amax1(v.x, j, m.x, mi.x);
+                amax1(v.y, j, m.y, mi.y);
+                amax1(v.z, j, m.z, mi.z);
+                amax1(v.w, j, m.w, mi.w);
+            } else {
+                m = max4(m, v);
+            }
+        }
+    }
+    red[threadIdx.x] = m;
+    if constexpr (IDX) redi[threadIdx.x] = mi;
+    __syncthreads();
+    if (pl == 0) {
+        for (int k = 1; k < ppi; k++) {
+            const float4 v = red[k * quads + cq];
+            if constexpr (IDX) {
+                const int4 vi = redi[k * quads + cq];
+                amax1(v.x, vi.x, m.x, mi.x);
+                amax1(v.y, vi.y, m.y, mi.y);
+                amax1(v.z, vi.z, m.z, mi.z);
+                amax1(v.w, vi.w, m.w, mi.w);
+            } else {
+                m = max4(m, v);
+            }
+        }
+        const size_t o = ((size_t)bi * nstrips + strip) * c + cq * 4;
+        *(float4 *)(part + o) = m;
+        if constexpr (IDX) *(int4 *)(parti + o) = mi;
+    }
+}
+
+template <bool IDX>
+__global__ __launch_bounds__(MP_TPB) void maxpool_len_stage2_kernel(int n, int c, int nstrips, const int *__restrict__ len,
+                                                                    const float *__restrict__ part,
+                                                                    const int *__restrict__ parti, float *__restrict__ out,
+                                                                    int *__restrict__ idx) {
+    const int bi = blockIdx.x;
+    const int written = (mp_len(len, bi, n) + MP_STRIP - 1) / MP_STRIP;  // strips stage 1 wrote for this sample
+    for (int ch = threadIdx.x; ch < c; ch += MP_TPB) {
+        float m = -INFINITY;
+        int mj = 0;
+        for (int s = 0; s < written; s++) {
+            const size_t o = ((size_t)bi * nstrips + s) * c + ch;
+            if constexpr (IDX) {
+                amax1(part[o], parti[o], m, mj);
+            } else {
+                m = fmaxf(m, part[o]);
+            }
+        }
+        out[(size_t)bi * c + ch] = m;
+        if constexpr (IDX) idx[(size_t)bi * c + ch] = mj;
+    }
+}
+
 // ---- backward of a layer tail: g = grad * act'(out), and the per-sample column sums of g (the bias /
 // per-sample-row gradient) in the same pass.  As separate tensor ops that is threshold_backward (read
 // grad, read out, write g) followed by a sum reduction that reads g again; here the sums ride along.
@@ -300,6 +386,49 @@ int rf_maxpool_points_idx(int b, int n, int c, const float *x, float *out, int *
               x, part, parti);
     RF_LAUNCH("maxpool_points_idx_fold", maxpool_idx_stage2_kernel, dim3(b), dim3(MP_TPB), 0, s, c, nstrips,
               (const float *)part, (const int *)parti, out, idx);
+    return RF_OK;
+}
+
+size_t rf_maxpool_points_lengths_workspace_bytes(int b, int n, int c) { return rf_maxpool_points_workspace_bytes(b, n, c); }
+
+int rf_maxpool_points_lengths(int b, int n, int c, const float *x, const int *len, float *out, void *workspace,
+                              size_t workspace_bytes, rf_stream_t stream) {
+    if (b < 0 || n < 0 || c < 0) return RF_EINVAL;
+    if ((size_t)b * c == 0) return RF_OK;
+    if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
+    if (!x || !out || !workspace) return RF_EINVAL;
+    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out) || !rf::aligned4(len)) return RF_EINVAL;
+    if (workspace_bytes < rf_maxpool_points_lengths_workspace_bytes(b, n, c)) return RF_EWORKSPACE;
+    const int nstrips = rf::ceil_div(n, MP_STRIP);
+    hipStream_t s = (hipStream_t)stream;
+    RF_LAUNCH("maxpool_points_len", maxpool_len_stage1_kernel<false>, dim3(nstrips, b), dim3(MP_TPB), 0, s, n, c, nstrips,
+              x, len, (float *)workspace, (int *)nullptr);
+    RF_LAUNCH("maxpool_points_len_fold", maxpool_len_stage2_kernel<false>, dim3(b), dim3(MP_TPB), 0, s, n, c, nstrips, len,
+              (const float *)workspace, (const int *)nullptr, out, (int *)nullptr);
+    return RF_OK;
+}
+
+size_t rf_maxpool_points_idx_lengths_workspace_bytes(int b, int n, int c) {
+    return rf_maxpool_points_idx_workspace_bytes(b, n, c);
+}
+
+int rf_maxpool_points_idx_lengths(int b, int n, int c, const float *x, const int *len, float *out, int *idx,
+                                  void *workspace, size_t workspace_bytes, rf_stream_t stream) {
+    if (b < 0 || n < 0 || c < 0) return RF_EINVAL;
+    if ((size_t)b * c == 0) return RF_OK;
+    if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
+    if (!x || !out || !idx || !workspace) return RF_EINVAL;
+    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out) || !rf::aligned4(idx) || !rf::aligned4(len))
+        return RF_EINVAL;
+    if (workspace_bytes < rf_maxpool_points_idx_lengths_workspace_bytes(b, n, c)) return RF_EWORKSPACE;
+    const int nstrips = rf::ceil_div(n, MP_STRIP);
+    float *part = (float *)workspace;
+    int *parti = (int *)(part + (size_t)b * nstrips * c);
+    hipStream_t s = (hipStream_t)stream;
+    RF_LAUNCH("maxpool_points_idx_len", maxpool_len_stage1_kernel<true>, dim3(nstrips, b), dim3(MP_TPB), 0, s, n, c,
+              nstrips, x, len, part, parti);
+    RF_LAUNCH("maxpool_points_idx_len_fold", maxpool_len_stage2_kernel<true>, dim3(b), dim3(MP_TPB), 0, s, n, c, nstrips,
+              len, (const float *)part, (const int *)parti, out, idx);
     return RF_OK;
 }
 

@@ -26,13 +26,20 @@ def sort_if_large(xyz, min_points=1024):
     return None
 
 
-def sampling(npoint, xyz, use_type='f', generator=None):
+def sampling(npoint, xyz, use_type='f', generator=None, lengths=None):
     """Returns (idx, new_xyz).  'f': farthest point sampling + gather; 'r': one random subset of
-    `npoint` indices shared by the whole batch (the reference shuffles arange(ptnum) once)."""
+    `npoint` indices shared by the whole batch (the reference shuffles arange(ptnum) once).
+    `lengths` ('f' only): per-sample point counts of a ragged batch -- sample i is sampled from
+    xyz[i, :lengths[i]] (rf_farthestpointsampling_lengths); one shared random subset has no ragged form."""
     if use_type == 'f':
+        if lengths is not None:
+            idx = _raw.farthest_point_sample(npoint, xyz.detach(), lengths=lengths)
+            return idx, gather_point(xyz, idx)
         idx = farthest_point_sample(npoint, xyz)
         return idx, gather_point(xyz, idx)
     if use_type == 'r':
+        if lengths is not None:
+            raise ValueError("sampling: use_type 'r' draws one subset for the whole batch and takes no lengths")
         perm = torch.randperm(xyz.shape[1], device=xyz.device, generator=generator)[:npoint]
         idx = perm.to(torch.int32).unsqueeze(0).expand(xyz.shape[0], -1).contiguous()
         return idx, gather_point(xyz, idx)
@@ -43,9 +50,10 @@ class _MergeLayer(torch.autograd.Function):
     """rf_merge_layer / rf_merge_layer_grad: direction-2 Chamfer + gather + Gaussian pull as one op."""
 
     @staticmethod
-    def forward(ctx, rawpts, newpts, decfactor, sorted_raw):
-        refined, idx2 = _raw.merge_layer(rawpts, newpts, decfactor, sorted_raw)
+    def forward(ctx, rawpts, newpts, decfactor, sorted_raw, lengths=None):
+        refined, idx2 = _raw.merge_layer(rawpts, newpts, decfactor, sorted_raw, lengths=lengths)
         ctx.save_for_backward(rawpts, newpts, decfactor, idx2)
+        ctx.lengths = lengths
         ctx.mark_non_differentiable(idx2)
         return refined, idx2
 
@@ -53,18 +61,21 @@ class _MergeLayer(torch.autograd.Function):
     def backward(ctx, grad_refined, _):
         rawpts, newpts, decfactor, idx2 = ctx.saved_tensors
         gn, gd, gr = _raw.merge_layer_grad(rawpts, newpts, decfactor, idx2, grad_refined.contiguous(),
-                                           want_raw=ctx.needs_input_grad[0])
-        return gr, gn, gd.sum().reshape(decfactor.shape).to(decfactor.dtype), None
+                                           want_raw=ctx.needs_input_grad[0], lengths=ctx.lengths)
+        return gr, gn, gd.sum().reshape(decfactor.shape).to(decfactor.dtype), None, None
 
 
-def merge_layer(rawpts, newpts, decfactor, knum=16, sorted_raw=None, return_idx=False):
+def merge_layer(rawpts, newpts, decfactor, knum=16, sorted_raw=None, return_idx=False, lengths=None):
     """Pull every new point towards its nearest raw point with a Gaussian weight:
     refine = newpts + exp(-|g-newpts|^2 / (1e-8 + decfactor^2)) * (g - newpts), g = nn of newpts
     in rawpts (idx2 of nn_distance, grouped with nsample = 1).  `knum` is unused in the reference.
     One fused op (direction 2 of the Chamfer only, gather and pull in its epilogue); `sorted_raw`:
-    optional SortedCloud of rawpts (the model merges into the same `pointcloud` three times)."""
+    optional SortedCloud of rawpts (the model merges into the same `pointcloud` three times).
+    `lengths`: per-sample point counts of rawpts in a ragged batch (rf_merge_layer_lengths): the nearest raw
+    point is looked for in rawpts[i, :lengths[i]] only and padded raw rows get a zero gradient; not combined
+    with `sorted_raw`."""
     dec = torch.as_tensor(decfactor, dtype=newpts.dtype, device=newpts.device)
-    refined, idx2 = _MergeLayer.apply(rawpts, newpts.contiguous(), dec, sorted_raw)
+    refined, idx2 = _MergeLayer.apply(rawpts, newpts.contiguous(), dec, sorted_raw, lengths)
     return (refined, idx2) if return_idx else refined
 
 

@@ -112,11 +112,13 @@ def _tail_grad(grad, y, act):
 
 class _MaxPool(torch.autograd.Function):
     """max over the points axis with rf_maxpool_points_idx; the backward routes each channel's gradient
-    to its arg-max point (zero fill + one scatter)."""
+    to its arg-max point (zero fill + one scatter).  `lengths`: per-sample row counts of a ragged batch
+    (rf_maxpool_points_idx_lengths); every arg-max lies below its sample's count, so the same scatter leaves
+    the padded rows at zero."""
 
     @staticmethod
-    def forward(ctx, t):
-        out, idx = _raw.maxpool_points_idx(t)
+    def forward(ctx, t, lengths=None):
+        out, idx = _raw.maxpool_points_idx(t, lengths)
         ctx.save_for_backward(idx)
         ctx.n = t.shape[1]
         return out
@@ -127,7 +129,7 @@ class _MaxPool(torch.autograd.Function):
         b, _, c = grad.shape
         gin = grad.new_zeros(b, ctx.n, c)
         gin.scatter_(1, idx.long().unsqueeze(1), grad.contiguous())
-        return gin
+        return gin, None
 
 
 class _PooledChain(torch.autograd.Function):
@@ -139,16 +141,18 @@ class _PooledChain(torch.autograd.Function):
     (the diagonal of the recomputed (B, C, C) block is the pooled output).  Same derivative as the dense
     backward -- which multiplies (B, N, C) matrices that are zero outside those rows: at C5 size 75 % of
     the step's backward GEMM flops plus the activation-gradient and zero-fill passes over them -- and the
-    (B, N, C) activations of the chain are not kept for the backward at all."""
+    (B, N, C) activations of the chain are not kept for the backward at all.
+    `lengths`: per-sample row counts of a ragged batch; the arg-max rows then lie below each sample's count
+    and the backward, which lives on those rows, is unchanged."""
 
     @staticmethod
-    def forward(ctx, fn, nparams, *args):
+    def forward(ctx, fn, nparams, lengths, *args):
         # args = the chain's parameters (the module's own Parameter objects: `fn` reads them from the
         # module; they are inputs here so that autograd accumulates their gradients), then its tensors
         tensors = args[nparams:]
         with torch.no_grad():
             t = fn(*tensors)
-            out, idx = _raw.maxpool_points_idx(t)
+            out, idx = _raw.maxpool_points_idx(t, lengths)
         ctx.fn, ctx.params, ctx.n = fn, args[:nparams], t.shape[1]
         # the backward RE-RUNS fn, which reads the module's CURRENT weights: their versions are recorded
         # so that an in-place update between forward and backward (two forwards, an optimizer step, then
@@ -165,7 +169,7 @@ class _PooledChain(torch.autograd.Function):
                                "and its backward (the backward recomputes the chain from the current weights)")
         ix = idx.long()  # (B, C): the arg-max row of every channel
         np_ = len(ctx.params)
-        need_p, need_t = ctx.needs_input_grad[2:2 + np_], ctx.needs_input_grad[2 + np_:]
+        need_p, need_t = ctx.needs_input_grad[3:3 + np_], ctx.needs_input_grad[3 + np_:]
         with torch.enable_grad():
             leaves, rows = [], []
             for t, nd in zip(tensors, need_t):
@@ -179,7 +183,7 @@ class _PooledChain(torch.autograd.Function):
             got = iter(torch.autograd.grad(pooled, wanted, grad.reshape(pooled.shape), allow_unused=True))
         gp = tuple(next(got) if nd else None for nd in need_p)
         gt = tuple(next(got) if nd else None for nd in need_t)
-        return (None, None) + gp + gt
+        return (None, None, None) + gp + gt
 
 
 class _MatW(torch.autograd.Function):
@@ -271,14 +275,21 @@ class _PointAffine(torch.autograd.Function):
         return gy, gp, gw, gr.reshape(ctx.rshape), None
 
 
-def maxpool_points(t):
+def maxpool_points(t, lengths=None):
     """max over the points axis, keepdim (tf.reduce_max(axis=1), e.g. vv_recon.py:90,107,129).  Without
     autograd: rf_maxpool_points (values only); with autograd: rf_maxpool_points_idx and an index-scatter
     backward (one pass, as torch's `max`, instead of amax's compare / count / divide / multiply; every
     pooled tensor of the graph comes out of a ReLU, so how ties share the gradient is immaterial: tied
     entries are zeros, whose ReLU passes no gradient).  torch's own max reduction takes 0.14 ms per call
-    at 32 x 16384 x 256 against 0.03 ms here."""
+    at 32 x 16384 x 256 against 0.03 ms here.  `lengths`: per-sample row counts of a ragged batch -- sample i
+    pools t[i, :lengths[i]]; only the library's kernels do that (a tensor they cannot take is an error)."""
     own = t.is_cuda and t.dtype == torch.float32 and t.shape[-1] % 4 == 0 and t.shape[-1] <= 1024 and t.shape[1] > 0
+    if lengths is not None:
+        if not own:
+            raise ValueError("maxpool_points: lengths need a float32 GPU tensor with a multiple of 4 (<= 1024) channels")
+        if torch.is_grad_enabled() and t.requires_grad:
+            return _MaxPool.apply(t, lengths)
+        return _raw.maxpool_points(t, lengths)
     if torch.is_grad_enabled() and t.requires_grad:
         return _MaxPool.apply(t) if own else t.max(1, keepdim=True).values
     if own:
@@ -400,8 +411,9 @@ class RFNet(nn.Module):
     # chains that feed only a max-pool: dense forward, row-sparse backward (_PooledChain)
     sparse_pool_backward = True
 
-    def pooled(self, fn, layers, *tensors):
-        """maxpool_points(fn(*tensors)); `layers` = [(scope, name, call)] the chain applies.
+    def pooled(self, fn, layers, *tensors, lengths=None):
+        """maxpool_points(fn(*tensors)); `layers` = [(scope, name, call)] the chain applies; `lengths`: per-sample
+        row counts of the per-point tensors in a ragged batch (the pooling skips the rows behind them).
         The row-sparse backward (_PooledChain) sends each channel's pooled gradient to ONE arg-max row, as
         torch's `max` does; every chain routed here ENDS IN A ReLU (ties are zeros, whose derivative is
         zero on every tied row, so the choice of row cannot matter) -- a chain ending otherwise must use
@@ -415,8 +427,8 @@ class RFNet(nn.Module):
         cout = ps[-1].shape[0]
         if (self.sparse_pool_backward and torch.is_grad_enabled() and tensors[0].is_cuda and npts > 2 * cout
                 and cout % 4 == 0 and cout <= 1024 and any(t.requires_grad for t in list(tensors) + ps)):
-            return _PooledChain.apply(fn, len(ps), *ps, *tensors)
-        return maxpool_points(fn(*tensors))
+            return _PooledChain.apply(fn, len(ps), lengths, *ps, *tensors)
+        return maxpool_points(fn(*tensors), lengths)
 
     def mlp(self, scope, prefix, n, x, call=0, first=0):
         for i in range(first, n):
@@ -424,21 +436,22 @@ class RFNet(nn.Module):
         return x
 
     # -- cells ---------------------------------------------------------------------------------
-    def global_mlp(self, scope, xyz):  # vv_recon.py:84-91
+    def global_mlp(self, scope, xyz, lengths=None):  # vv_recon.py:84-91
         return self.pooled(lambda x: self.mlp(scope, "ini_layer", 3, x),
-                           [(scope, f"ini_layer{i}", 0) for i in range(3)], xyz)
+                           [(scope, f"ini_layer{i}", 0) for i in range(3)], xyz, lengths=lengths)
 
-    def encode_cell(self, x, state, call):  # :93-112
+    def encode_cell(self, x, state, call, lengths=None):  # :93-112
         def chain(x_, st):
             s = self.dcat("cell", "state0", [x_, st], call=call)
             s = self.mlp("cell", "state", 2, s, call, first=1)
             return self.d("cell", "state_end", s, call=call)
-        new_state = self.pooled(chain, [("cell", n, call) for n in ("state0", "state1", "state_end")], x, state)
+        new_state = self.pooled(chain, [("cell", n, call) for n in ("state0", "state1", "state_end")], x, state,
+                                lengths=lengths)
         return self.mlp("cell", "codemlp", 2, new_state, call), new_state
 
-    def recover_cell(self, scope, code, con):  # :124-131
+    def recover_cell(self, scope, code, con, lengths=None):  # :124-131
         t = self.pooled(lambda cd, cn: self.mlp(scope, "recover2", 2, self.dcat(scope, "recover20", [cd, cn]), first=1),
-                        [(scope, "recover20", 0), (scope, "recover21", 0)], code, con)
+                        [(scope, "recover20", 0), (scope, "recover21", 0)], code, con, lengths=lengths)
         return self.d(scope, "recover2out1", t, act=None)
 
     def init_move_layer(self, startpts, codeword):  # :140-159
@@ -510,11 +523,22 @@ class RFNet(nn.Module):
         return pts, (state.unsqueeze(2) + move_state).reshape(-1, n * up_ratio, state.shape[-1])
 
     # -- the graph -------------------------------------------------------------------------------
-    def forward(self, pointcloud, collect=None):
+    def forward(self, pointcloud, collect=None, lengths=None):
         """`collect` (optional dict) receives what the reference keeps in graph collections for the
         loss block ('points1', 'points2', 'refine_layer_final16384', 'decode_cell64',
         'decode_cell1024': vv_recon.py:210,222,298,338) and the indices taken by the
-        index-producing operators ('fps32', 'merge1', 'merge2', 'merge3')."""
+        index-producing operators ('fps32', 'merge1', 'merge2', 'merge3').
+
+        `lengths`: per-sample point counts of a ragged batch -- sample i is pointcloud[i, :lengths[i]], the rows behind
+        may hold anything (NaN included); list, tuple, numpy array, CPU or CUDA tensor.  The counts reach the three
+        places where the raw cloud enters the graph: the poolings over the points axis, the three merge layers and the
+        FPS of the 32 start points; every output is what the sample's own slice gives up to the batch size of the GEMMs.
+        The graph draws 32 FPS samples, so 32 <= lengths[i] <= N: host-given counts outside that raise; counts on the
+        device are not read on the host (no synchronisation, the call can be captured into a graph) -- the kernels hold
+        them inside [1, N], and keeping them at 32 or above is the caller's responsibility.  The per-point GEMMs still
+        run over the padded rows (of a private copy whose padding is zeroed): that work is not removed here."""
+        if lengths is not None:
+            return self._forward_lengths(pointcloud, collect, lengths)
         x = pointcloud
         c = collect
         # `pointcloud` is the raw side of all three merge layers: put it in curve order once
@@ -550,6 +574,53 @@ class RFNet(nn.Module):
         points3, _ = self.decode_cell(code3, points2, dstate, 1, collect=c, need_state=False)
         final, m3 = glue.merge_layer(pointcloud, points3.contiguous(), self.decline_factor, knum=1,
                                      sorted_raw=raw_sorted, return_idx=True)
+        final, _ = self.refine_layer("refine_layer_final", final, code3, None, c, need_feat=False)
+        if c is not None:
+            c.update({"points1": pre1, "points2": pre2, "fps32": fidx, "merge1": m1, "merge2": m2, "merge3": m3})
+        return points1, points2, points3, final
+
+    def _forward_lengths(self, pointcloud, collect, lengths):
+        """forward() over a ragged batch.  The graph of forward(), with three differences: the raw cloud is a private
+        copy whose padded rows are zeros (one masked pass, driven by the device counts: what the per-point layers and
+        their weight gradients then see on a padded row is finite, and its upstream gradient is zero); the poolings
+        over raw + generated points see cat([generated, raw]) with counts n_generated + lengths, formed on the device
+        (a max does not depend on the order, and each sample keeps ONE contiguous valid range); no sorted handle of the
+        raw cloud is built (the ragged merge layer sorts inside when it takes the culled sweep)."""
+        b, n = pointcloud.shape[0], pointcloud.shape[1]
+        ln = _raw._check_lengths(lengths, b, n, "lengths")
+        if not ln.is_cuda and b > 0 and int(ln.min()) < 32:
+            raise ValueError("RFNet.forward: lengths must lie in [32, N] (the graph draws 32 FPS samples per cloud)")
+        # (held inside [1, N] on the device, as the kernels hold them: the sums n_generated + lengths below rely on it)
+        ln = _raw._lengths_up(ln, pointcloud.device, n).clamp(1, n)
+        valid = torch.arange(n, device=pointcloud.device, dtype=torch.int32).view(1, n, 1) < ln.view(b, 1, 1)
+        x = torch.where(valid, pointcloud, pointcloud.new_zeros(()))
+        c = collect
+        state0 = self.global_mlp("init_mlp", x, ln)
+        code1, state = self.encode_cell(x, state0, 0, ln)
+        code1 = self.recover_cell("recover1", code1, x, ln)
+        fidx, start = glue.sampling(32, x, use_type="f", lengths=ln)
+        points1, dstate = self.init_move_layer(start, code1)
+        partfeat = self.global_mlp("part_mlp", torch.cat([points1, x], 1), ln + points1.shape[1])
+        ft = self.mlp("", "partfeat", 2, torch.cat([partfeat, code1], -1))
+        points0, dstate0 = self.init_decode_layer(ft)
+        points1, dstate = torch.cat([points0, points1], 1), torch.cat([dstate0, dstate], 1)
+        pre1 = points1
+        points1, m1 = glue.merge_layer(x, points1.contiguous(), self.decline_factor0, knum=1, return_idx=True, lengths=ln)
+        points1, dstate = self.refine_layer("refine_layer1", points1, code1, dstate, c)
+
+        pin, lp = torch.cat([points1, x], 1), ln + points1.shape[1]
+        code2, state = self.encode_cell(pin, state, 1, lp)
+        code2 = code1 + self.recover_cell("recover2", code2, pin, lp)
+        points2, dstate = self.decode_cell(code2, points1, dstate, 0, collect=c)
+        pre2 = points2
+        points2, m2 = glue.merge_layer(x, points2.contiguous(), self.decline_factor1, knum=1, return_idx=True, lengths=ln)
+        points2, dstate = self.refine_layer("refine_layer2", points2, code2, dstate, c)
+
+        pin, lp = torch.cat([points2, x], 1), ln + points2.shape[1]
+        code3, state = self.encode_cell(pin, state, 2, lp)
+        code3 = code2 + self.recover_cell("recover3", code3, pin, lp)
+        points3, _ = self.decode_cell(code3, points2, dstate, 1, collect=c, need_state=False)
+        final, m3 = glue.merge_layer(x, points3.contiguous(), self.decline_factor, knum=1, return_idx=True, lengths=ln)
         final, _ = self.refine_layer("refine_layer_final", final, code3, None, c, need_feat=False)
         if c is not None:
             c.update({"points1": pre1, "points2": pre2, "fps32": fidx, "merge1": m1, "merge2": m2, "merge3": m3})
