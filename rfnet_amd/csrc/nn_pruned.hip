@@ -101,6 +101,22 @@ namespace {
                       // OWN list of candidate blocks with gathered scans (round 4); 0 = four waves share a
                       // 64-query group and stream every needed block through SGPRs to all 64 lanes (rounds 1-3)
 #endif
+#ifndef RFP_KK1
+#define RFP_KK1 1  // one-wave groups whose list is one entry per lane (candidate sets of up to 4096 points) run an instance of the
+                   // traversal with ONE key register and none of the longer lists' branches; 0 = every list in the five-register form
+#endif
+#ifndef RFP_REKEY_BOX
+#define RFP_REKEY_BOX 1  // (RFP_KK1) 1 = the lane's candidate box stays in six registers between the prologue and the re-keys; 0 = a
+                         // re-key loads it again (two 16-byte loads on the wave's serial chain).  (A third home, the wave's slice of
+                         // the dynamic LDS key list, measured between the two and was removed: profiles/sweep_rekey_ab.txt.)
+#endif
+#ifndef RFP_REKEY_STATS
+#define RFP_REKEY_STATS 0  // 1: a stats call's counters [16 + k] / [24 + k] count the first / second traversals of one-wave groups
+                           // that re-keyed k times (k <= 6), in place of the sort's phase stamps; a measuring build only.  To read
+                           // them: python tools/build_variant.py stats -DRFP_REKEY_STATS=1, then with RFOPS_LIB naming that library
+                           //   st = []; rfnet_amd._raw.nn_distance(a, c, mode="culled", stats=st); st[16:23], st[24:31]
+                           // (the lines that printed profiles/sweep_rekey_ab.txt section 1 are at the end of that file)
+#endif
 constexpr int NSH = RFP_NSH;
 constexpr int BS = 16;             // candidates per block
 constexpr int SBB = 4;             // blocks per superblock
@@ -1047,6 +1063,31 @@ __device__ __forceinline__ float wave_max_nonneg(float f) {
 }
 #undef RFP_DPP
 
+// Bounding box of the lanes with `on` set: the three wave_min_f32 and the three wave_max_f32 of a re-key as ONE
+// instruction stream.  Each of the six chains is the body of wave_min_f32 / wave_max_f32 -- the same four row
+// rotations in the same order, the same combination of the four row results -- but the chains are interleaved: a
+// rotation reads a register written five instructions earlier, so one s_nop at the head covers all 24 of them
+// (one by one they are 24 x (s_nop 1 + DPP), all on the traversal's serial chain).
+#define RFP_ROW6(N)                                                          \
+    "v_min_f32_dpp %0, %0, %0 row_ror:" #N " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_min_f32_dpp %1, %1, %1 row_ror:" #N " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_min_f32_dpp %2, %2, %2 row_ror:" #N " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_max_f32_dpp %3, %3, %3 row_ror:" #N " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_max_f32_dpp %4, %4, %4 row_ror:" #N " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_max_f32_dpp %5, %5, %5 row_ror:" #N " row_mask:0xf bank_mask:0xf\n\t"
+__device__ __forceinline__ void wave_box_f32(bool on, float qx, float qy, float qz, float (&lo)[3], float (&hi)[3]) {
+    float l0 = on ? qx : INFINITY, l1 = on ? qy : INFINITY, l2 = on ? qz : INFINITY;
+    float h0 = on ? qx : -INFINITY, h1 = on ? qy : -INFINITY, h2 = on ? qz : -INFINITY;
+    asm volatile("s_nop 1\n\t" RFP_ROW6(8) RFP_ROW6(4) RFP_ROW6(2) RFP_ROW6(1)
+                 : "+v"(l0), "+v"(l1), "+v"(l2), "+v"(h0), "+v"(h1), "+v"(h2));
+    auto rows = [](float v, int r) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), r)); };
+    auto mn = [&](float v) { return fminf(fminf(rows(v, 0), rows(v, 16)), fminf(rows(v, 32), rows(v, 48))); };
+    auto mx = [&](float v) { return fmaxf(fmaxf(rows(v, 0), rows(v, 16)), fmaxf(rows(v, 32), rows(v, 48))); };
+    lo[0] = mn(l0), lo[1] = mn(l1), lo[2] = mn(l2);
+    hi[0] = mx(h0), hi[1] = mx(h1), hi[2] = mx(h2);
+}
+#undef RFP_ROW6
+
 // lower bound of d2 between point q and the box [lo,hi], same instruction sequence as d2
 __device__ __forceinline__ float box_bound(float qx, float qy, float qz, float lx, float ly, float lz, float hx,
                                            float hy, float hz) {
@@ -1143,23 +1184,48 @@ __device__ __forceinline__ void sweep_group(
     // key whose low 10 bits are the superblock id: the wave minimum of the keys is the next
     // superblock.  Entry e of this wave's list is superblock sub + nsub*e; lane e % 64 owns it
     // (writes it, consumes it, keeps the minimum of its entries in `lmin`).
-    auto traverse = [&](auto track_c, const float *blo, const float *bhi, unsigned &besti2, int &wpos2) {
+    // KK (kk_c): key registers per lane.  5 is the general form.  1 (one-wave groups with nmine <= 64, chosen by a uniform
+    // branch at the call: at C2 two thirds of the launch's waves) carries one key and one select per step instead of five
+    // with a minimum over five, and none of the longer lists' branches; and the lane keeps the box of its ONE candidate
+    // superblock from the prologue (RFP_REKEY_BOX), so that a re-key issues no load: its two 16-byte gathers fetched the
+    // bytes the lane already had, one more L2 round trip on the wave's serial chain each time the active lanes halve.
+    auto traverse = [&](auto track_c, auto kk_c, const float *blo, const float *bhi, unsigned &besti2, int &wpos2) {
         constexpr bool TRACK = decltype(track_c)::value;
         // up to 320 entries (every cloud that fits the register-resident sort: 16384 points = 256
         // superblocks, 257 when two workgroups sorted it): the lane's entries e = lane + 64 i live in
         // KK registers and the LDS list is not used at all
-        constexpr int KK = 5;
-        const bool inreg = nmine <= 64 * KK;  // uniform
-        unsigned kk[KK] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-        auto kk_min = [&]() { return min(min(min(kk[0], kk[1]), min(kk[2], kk[3])), kk[4]); };
+        constexpr int KK = decltype(kk_c)::value;
+        constexpr bool ONE = KK == 1;
+        static_assert(KK == 1 || KK == 5, "the key registers of a lane: one, or the general five");
+        const bool inreg = ONE || nmine <= 64 * KK;  // uniform
+        unsigned kk[KK];
+#pragma unroll
+        for (int i = 0; i < KK; i++) kk[i] = 0xFFFFFFFFu;
+        auto kk_min = [&]() {
+            if constexpr (ONE) return kk[0];
+            else return min(min(min(kk[0], kk[1]), min(kk[2], kk[3])), kk[4]);
+        };
+        auto box_key = [&](int s, const float *lo3, const float *hi3, const float4 cl, const float4 ch) {
+            const float lb = boxbox_bound(lo3, hi3, cl, ch);
+            return (__float_as_uint(lb) & ~IDMASK) | (unsigned)s;
+        };
         auto entry_key = [&](int e, const float *lo3, const float *hi3) {
             const int s = sub + nsub * e;
             const float4 *cb = (const float4 *)(CB64 + (size_t)s * B64F);
-            const float lb = boxbox_bound(lo3, hi3, cb[0], cb[1]);
-            return (__float_as_uint(lb) & ~IDMASK) | (unsigned)s;
+            return box_key(s, lo3, hi3, cb[0], cb[1]);
         };
         unsigned lmin = 0xFFFFFFFFu;
-        if (nmine <= 64) {  // uniform: one entry per lane
+        [[maybe_unused]] float cbx[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (ONE, RFP_REKEY_BOX) the lane's candidate box
+        [[maybe_unused]] unsigned n_rekey = 0;
+        if constexpr (ONE && RFP_REKEY_BOX != 0) {
+            // (a clamped entry and a select: the lanes behind the list hold a box they never use)
+            const int s = sub + nsub * min(lane, nmine - 1);
+            const float4 *cb = (const float4 *)(CB64 + (size_t)s * B64F);
+            const float4 cl = cb[0], ch = cb[1];
+            kk[0] = lane < nmine ? box_key(s, blo, bhi, cl, ch) : 0xFFFFFFFFu;
+            lmin = kk[0];
+            cbx[0] = cl.x, cbx[1] = cl.y, cbx[2] = cl.z, cbx[3] = ch.x, cbx[4] = ch.y, cbx[5] = ch.z;
+        } else if (ONE || nmine <= 64) {  // uniform: one entry per lane
             kk[0] = lane < nmine ? entry_key(lane, blo, bhi) : 0xFFFFFFFFu;
             lmin = kk[0];
         } else if (inreg) {
@@ -1207,12 +1273,23 @@ __device__ __forceinline__ void sweep_group(
             if (nact * 2 <= nact_ref) {  // (thresholds between 1/4 and 7/8 measure the same)
                 nact_ref = nact;
                 const bool on = (act >> lane) & 1ull;
-                const float alo[3] = {wave_min_f32(on ? qx : INFINITY), wave_min_f32(on ? qy : INFINITY),
-                                      wave_min_f32(on ? qz : INFINITY)};
-                const float ahi[3] = {wave_max_f32(on ? qx : -INFINITY), wave_max_f32(on ? qy : -INFINITY),
-                                      wave_max_f32(on ? qz : -INFINITY)};
+                float alo[3], ahi[3];
+                if constexpr (ONE) {
+                    wave_box_f32(on, qx, qy, qz, alo, ahi);
+                } else {
+                    alo[0] = wave_min_f32(on ? qx : INFINITY), alo[1] = wave_min_f32(on ? qy : INFINITY);
+                    alo[2] = wave_min_f32(on ? qz : INFINITY);
+                    ahi[0] = wave_max_f32(on ? qx : -INFINITY), ahi[1] = wave_max_f32(on ? qy : -INFINITY);
+                    ahi[2] = wave_max_f32(on ? qz : -INFINITY);
+                }
+                if constexpr (RFP_REKEY_STATS) n_rekey++;
                 lmin = 0xFFFFFFFFu;
-                if (inreg) {
+                if constexpr (ONE && RFP_REKEY_BOX != 0) {
+                    const float4 cl = make_float4(cbx[0], cbx[1], cbx[2], 0.f), ch = make_float4(cbx[3], cbx[4], cbx[5], 0.f);
+                    // (consumed entries and the lanes behind the list stay; entry `lane` is superblock sub + nsub * lane)
+                    kk[0] = kk[0] != 0xFFFFFFFFu ? box_key(sub + nsub * lane, alo, ahi, cl, ch) : kk[0];
+                    lmin = kk[0];
+                } else if (inreg) {
 #pragma unroll
                     for (int i = 0; i < KK; i++)
                         if (i * 64 < nmine && kk[i] != 0xFFFFFFFFu) kk[i] = entry_key(lane + 64 * i, alo, ahi);  // (consumed ones stay)
@@ -1240,7 +1317,7 @@ __device__ __forceinline__ void sweep_group(
 #pragma unroll
                 for (int i = 0; i < B16F; i++) bx[i] = bp[i];
             }
-            if (nmine <= 64) {  // one entry per lane (C2: 32 superblocks, or a quarter of 256)
+            if (ONE || nmine <= 64) {  // one entry per lane (C2: 32 superblocks, or a quarter of 256)
                 kk[0] = lane == e ? 0xFFFFFFFFu : kk[0];
                 lmin = kk[0];
             } else if (inreg) {  // (a two-register path for 65..128 entries measured slower for every shape: one more branch level)
@@ -1361,11 +1438,17 @@ __device__ __forceinline__ void sweep_group(
             if (shared4) atomicMin(&shbest[lane], __float_as_int(cull));
             stamp(2);
         }
+        if constexpr (RFP_REKEY_STATS && !shared4) {
+            if (stats && lane == 0) atomicAdd(&stats[(TRACK ? 24 : 16) + min(n_rekey, 7u)], 1ull);
+        }
     };
+    // (uniform) the one-key instance: a one-wave group whose list is one entry per lane; the shared groups keep the general form
+    const bool one_key = RFP_KK1 && !shared4 && nmine <= 64;
 
     unsigned besti = 0xFFFFFFFFu;
     int wpos = -1;  // (GRAD) sorted position of the winner in the candidate set
-    traverse(std::false_type{}, glo, ghi, besti, wpos);
+    if (one_key) traverse(std::false_type{}, std::integral_constant<int, 1>{}, glo, ghi, besti, wpos);
+    else traverse(std::false_type{}, std::integral_constant<int, 5>{}, glo, ghi, besti, wpos);
     __builtin_amdgcn_s_setprio(0);
     stamp(1);
 
@@ -1436,7 +1519,8 @@ __device__ __forceinline__ void sweep_group(
         cull = flagged ? best : -INFINITY;  // the wave's own minima are final: match against them
         unsigned besti2 = 0xFFFFFFFFu;
         int wpos2 = -1;
-        traverse(std::true_type{}, flo, fhi, besti2, wpos2);
+        if (one_key) traverse(std::true_type{}, std::integral_constant<int, 1>{}, flo, fhi, besti2, wpos2);
+        else traverse(std::true_type{}, std::integral_constant<int, 5>{}, flo, fhi, besti2, wpos2);
         if (flagged) {
             besti = besti2;
             wpos = wpos2;
@@ -2439,7 +2523,7 @@ int pruned_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2
     const int nn[2] = {n, m};
     const float *src[2] = {xyz1, xyz2};
     const int *lens[2] = {len1, len2};
-    if (int e = sort_sets(b, 2, nn, src, so, s, stats, (len1 || len2) ? lens : nullptr)) return e;
+    if (int e = sort_sets(b, 2, nn, src, so, s, RFP_REKEY_STATS ? nullptr : stats, (len1 || len2) ? lens : nullptr)) return e;
     if (int e = sweep_sorted(b, n, m, so[0], so[1], dist1, idx1, dist2, idx2, dirs, s, stats)) return e;
     if (stats_out) {
         RF_HIP(hipMemcpyAsync(stats_out, stats, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
