@@ -508,43 +508,66 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
     // (yhist's words are staging space again from phase 6 on; the histogram proper is the first NBINS words)
     const int ncol = SS * SS;
     auto col_start = [&](int q) { return (q * ncol + H - 1) / H; };  // first column of slice q (H slices of equal column count)
-    const int cs1 = H > 1 ? col_start(1) : 0x7FFFFFFF, cs2 = H > 2 ? col_start(2) : 0x7FFFFFFF,
-              cs3 = H > 3 ? col_start(3) : 0x7FFFFFFF;  // (uniform; the divisions stay out of the per-point loop)
+    const int cs1 = H > 1 ? col_start(1) : 0x7FFFFFFF;  // (uniform; the divisions stay out of the per-point loop)
+#if RFP_SORT_SPLIT > 2
+    const int cs2 = H > 2 ? col_start(2) : 0x7FFFFFFF, cs3 = H > 3 ? col_start(3) : 0x7FFFFFFF;
+#endif
     const unsigned kbase = (unsigned)col_start(half) << 9;
     const int nb_local = (col_start(half + 1) - col_start(half)) << 9;
 
     stamp();
     unsigned below[3] = {0u, 0u, 0u};  // wave-uniform counters
-    // 3. keys and their histogram: three table lookups and an atomic per point -- the LDS pipe, 12 k of the sort's 45 k cycles.
-    // (Looking the strip / z rank up only in the lanes whose point may be / is this workgroup's own -- the slab alone decides
-    // that outside the one slab the cut runs through -- was built and is SLOWER, 16.2 k cycles: the lookups then sit in
-    // per-lane branches, one wait each, instead of 48 independent reads the scheduler interleaves.)
+    const unsigned dkeep = dense ? ~15u : ~0u, dlane = dense ? (unsigned)(lane & 15) : 0u;  // (a crowded wave's ranks, below)
+    // 3. keys and their histogram: three table lookups and an atomic per point.  The phase is bound by the VALU, not by the LDS
+    // pipe: its time follows the loop's VALU count from build to build, about 14 cycles per instruction with four waves per
+    // SIMD (682 instructions per thread: 12.1 k cycles; 457: 8.6 k; 951: 15.9 k -- profiles/sort_valu_tables_ab.txt,
+    // DESIGN_NOTES 5.1l).  So the loop carries no instruction it can do without:
+    // * one comparison decides `own` when a cloud has at most two workgroups (RFP_SORT_SPLIT <= 2), not three with their carries;
+    // * the lower slice's points are counted behind the loop (valid less own), not by three ballots per point in uniform branches;
+    // * the column is a 24-bit multiply-add, the crowded wave's rank spread one v_and_or with operands set up once.
+    // Two forms that move work from the LDS pipe to the VALU were built and LOSE for that reason (same profile; the code is
+    // tools/experiments/sort_valu_tables.patch.txt): slab and strip as counts of thresholds crossed (keys +3.4 k cycles, quantiles
+    // +1.4 k) and z rank + atomic for a workgroup's own points only in a second straight-line pass (+2.2 k).  Round 5's branchy
+    // form of the latter (16.2 k cycles) lost for the same reason and not, as was written here, for its waits.
 #pragma unroll
     for (int k = 0; k < RPT; k++) {
         const bool valid = tid + k * STPB < n;
-        const int slab = slabmap[axis_bin(px[k], fl[0], fs[0])];
-        const int col = slab * SS + (int)stripmap[slab * HB + axis_bin(py[k], fl[1], fs[1])];
+        const int xb = axis_bin(px[k], fl[0], fs[0]), yb = axis_bin(py[k], fl[1], fs[1]);
+        const int slab = slabmap[xb];
+        const int col = (int)__umul24(slab, SS) + (int)stripmap[slab * HB + yb];  // (v_mad_u32_u24, not a 64-bit multiply-add)
+#if RFP_SORT_SPLIT > 2
+        int slice = col >= cs1;
+        if (H > 2) slice += (col >= cs2) + (col >= cs3);  // (uniform)
+        const bool own = valid && slice == half;
+        // points of the slices below this workgroup's (its segment starts behind theirs)
+#pragma unroll
+        for (int q = 0; q < 3; q++) below[q] += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(valid && slice == q));
+#else
+        const bool own = valid && (col >= cs1) == (half != 0);  // (at most two workgroups per cloud, the product's split)
+#endif
         unsigned zq = zmap[axis_bin(pz[k], fl[2], fs[2])];
         // a crowded wave (near-copies on a few spots) spreads its points over 16 adjacent z ranks by lane: the key
         // histogram and the positions are exact and their same-address LDS atomics serialise -- 46 of 64 lanes on one
         // bin otherwise; copies of one spot are the same place, so the ORDER among them is free and culling loses nothing
-        if (dense) zq = (zq & ~15u) | (unsigned)(lane & 15);
+        zq = (zq & dkeep) | dlane;
         const unsigned key = ((unsigned)col << 9) | ((col & 1) ? 511u - zq : zq);
-        int slice = col >= cs1;  // (two workgroups per cloud, the product's split: one comparison)
-        if (H > 2) slice += (col >= cs2) + (col >= cs3);  // (uniform)
-        const bool own = valid && slice == half;
         pk[k] = own ? key - kbase : 0xFFFFFFFFu;
         if (own) atomicAdd(&hist[pk[k]], 1u);
-        // points of the slices below this workgroup's (its segment starts behind theirs)
-        if (H > 1) {
+    }
+#if RFP_SORT_SPLIT <= 2
+    // points of the slice below this workgroup's (its segment starts behind theirs): with two slices, the second one's
+    // foreign points -- the wave's valid points less its own
+    if (half == 1) {  // (uniform)
 #pragma unroll
-            for (int q = 0; q < 3; q++)
-                if (q < half) below[q] += (unsigned)__builtin_popcountll(__ballot(valid && slice == q));
+        for (int k = 0; k < RPT; k++) {
+            const int nv = n - (__builtin_amdgcn_readfirstlane(wave) * 64 + k * STPB);  // valid points of the wave's k-th row (scalar)
+            below[0] += (unsigned)(nv < 0 ? 0 : (nv > 64 ? 64 : nv)) - (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(pk[k] != 0xFFFFFFFFu));
         }
     }
+#endif
     if (H > 1 && lane == 0) {
 #pragma unroll
-        for (int q = 0; q < 3; q++) lowcnt[wave][q] = below[q];
+        for (int q = 0; q < 3; q++) lowcnt[wave][q] = q < half ? below[q] : 0u;
     }
     __syncthreads();
 
