@@ -180,6 +180,63 @@ int rf_chamfer_loss_grad_lengths(int b, int n, int m, const float *xyz1, const f
                                  const int *idx2, const float *grad_loss, float *grad_xyz1, float *grad_xyz2,
                                  rf_stream_t stream);
 
+/* ---- evaluation metrics on the sweep's outputs (Chamfer, continued) ---------------------- */
+/* What a completion result is judged by, per sample, in one call: CD-L1, CD-L2, Hausdorff, F-score at a threshold
+ * and the density-aware Chamfer distance (DCD), with the per-point counts DCD needs.  Conventions are
+ * rf_nn_distance_lengths': len1 / len2 device int32 counts or NULL, read and clamped into [1, n] / [1, m] by the
+ * kernels (no host synchronisation: a call can be captured in a HIP graph); L1, L2 below are the clamped counts.
+ * Direction 1 is "points of xyz1 looking into xyz2" (dist1 / idx1 (b,n)), direction 2 the reverse ((b,m)).
+ *
+ *   count2[i][k] (b,m) = #{j < L1 : idx1[i][j] == k}      count1[i][j] (b,n) = #{k < L2 : idx2[i][k] == j}
+ *   (exact integers; slots behind a count are 0; a valid point's own neighbour always has a count >= 1)
+ *
+ * metrics (b, RF_CM_NCOL), every sum over the valid slots only; direction d = 1, 2 in the even / odd column of a pair:
+ *   0, 1   mean of sqrtf(dist_d)               the two halves of CD-L1 (rf_chamfer_loss_lengths' numbers)
+ *   2, 3   mean of dist_d                      the halves of CD-L2
+ *   4, 5   max of dist_d                       squared directed Hausdorff distances
+ *   6, 7   (float)#{dist_d < thr2} / (float)L_d    strict fp32 compare with thr2 as given: pass the SQUARED threshold
+ *   8      2 c6 c7 / (c6 + c7), +0 when c6 + c7 == 0    (F-score; c6 is the precision when xyz1 is the prediction)
+ *   9, 10  mean_j (1 - expf(-alpha dist_d[j]) / (float)cnt),  cnt = the count of j's own neighbour
+ *          (count2[idx1[j]] for d = 1, count1[idx2[k]] for d = 2): DCD with exponent 1 on the count and no
+ *          set-size ratio factor
+ * Columns 4-7 are exact (max and integer counts are order-free, one correctly rounded division); the float sums
+ * take a fixed order, so two calls return identical bits; within rel 1e-5 (0-3), 1e-6 (8), rel 1e-5 + abs 1e-6
+ * (9, 10) of the definitions in float64.  No float atomics.
+ *
+ * rf_nn_metrics: the epilogue alone on nn_distance outputs the caller holds (any route, sorted handles included);
+ * padded slots of dist / idx are not read.  An index outside the other cloud is not counted and weighs as count 1.
+ * Its workspace (256 bytes for positive sizes) is currently unused by the kernels; the pointer and size rules below
+ * are checked all the same.
+ * rf_chamfer_metrics: rf_nn_distance_lengths (RF_NN_AUTO, both directions: dist / idx bit for bit its outputs,
+ * padded slots (0, -1)) and then the epilogue.  Inputs with non-finite coordinates never make a kernel read or
+ * write out of bounds; the metric values for them are unspecified.
+ * rf_chamfer_metrics_grad: columns 0-3, 9 and 10 are differentiable, columns 4-8 of grad_metrics are not read;
+ * the counts are constants (a detached weight).  With g = grad_metrics[i]:
+ *   gd_d[j] = g[d-1] 0.5 / (L_d sqrtf(dist_d[j])) + g[1+d] / L_d + g[8+d] alpha expf(-alpha dist_d[j]) / (cnt L_d)
+ * where a term whose upstream value is exactly 0 is not formed (a zero distance then cannot turn 0 * inf into NaN
+ * when only DCD is trained), followed by rf_nn_distance_grad_lengths: grad_xyz1 (b,n,3) / grad_xyz2 (b,m,3) fully
+ * overwritten, rows behind a count exactly +0; within rel 1e-4 + abs 1e-5 as the other fused gradients.
+ *
+ * Argument rules, all checked before any HIP call: b == 0 is RF_OK; RF_EINVAL for n < 1 or m < 1, b > 65535, a NULL
+ * tensor, a count array or tensor not 4-byte aligned, a workspace that is NULL or not 16-byte aligned, thr2 NaN or
+ * negative (+inf is allowed), alpha negative or not finite; RF_EWORKSPACE for a workspace smaller than the matching
+ * _workspace_bytes (0 for non-positive sizes, positive otherwise). */
+#define RF_CM_NCOL 11
+size_t rf_nn_metrics_workspace_bytes(int b, int n, int m);
+int rf_nn_metrics(int b, int n, int m, const float *dist1, const int *idx1, const float *dist2, const int *idx2,
+                  const int *len1, const int *len2, float thr2, float alpha, float *metrics, int *count1,
+                  int *count2, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+size_t rf_chamfer_metrics_workspace_bytes(int b, int n, int m);
+int rf_chamfer_metrics(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
+                       float thr2, float alpha, float *metrics, float *dist1, int *idx1, float *dist2, int *idx2,
+                       int *count1, int *count2, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+size_t rf_chamfer_metrics_grad_workspace_bytes(int b, int n, int m);
+int rf_chamfer_metrics_grad(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                            const int *len2, const float *dist1, const int *idx1, const float *dist2,
+                            const int *idx2, const int *count1, const int *count2, float alpha,
+                            const float *grad_metrics, float *grad_xyz1, float *grad_xyz2, void *workspace,
+                            size_t workspace_bytes, rf_stream_t stream);
+
 /* ----------------------------------------------------------- EMD (pc_distance) ---------- */
 /* Replaces approxmatchLauncher(b,n,m,xyz1,xyz2,match,temp) (pc_distance/tf_approxmatch.cpp:141,
  * tf_approxmatch.cu:180-182).  xyz1 (b,n,3) "dataset", xyz2 (b,m,3) "query" (b <= 65535 for

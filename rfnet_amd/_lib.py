@@ -55,6 +55,12 @@ SIGNATURES = {
     "rf_chamfer_loss_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "rf_chamfer_loss_lengths": (_i, [_i, _i, _i] + [_vp] * 10 + [_sz, _vp]),
     "rf_chamfer_loss_grad_lengths": (_i, [_i, _i, _i] + [_vp] * 12),
+    "rf_nn_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_nn_metrics": (_i, [_i, _i, _i] + [_vp] * 6 + [_f, _f] + [_vp] * 4 + [_sz, _vp]),
+    "rf_chamfer_metrics_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_chamfer_metrics": (_i, [_i, _i, _i] + [_vp] * 4 + [_f, _f] + [_vp] * 8 + [_sz, _vp]),
+    "rf_chamfer_metrics_grad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_chamfer_metrics_grad": (_i, [_i, _i, _i] + [_vp] * 10 + [_f] + [_vp] * 4 + [_sz, _vp]),
     "rf_merge_layer_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_merge_layer": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_merge_layer_grad": (_i, [_i, _i, _i] + [_vp] * 9),

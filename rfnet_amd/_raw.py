@@ -377,6 +377,100 @@ def chamfer_loss_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, grad_loss, lengths1=
     return st.give(g1), st.give(g2)
 
 
+CM_NCOL = 11  # RF_CM_NCOL (include/rfops.h): columns of the metrics tensor
+
+
+def _metric_args(tau, alpha, op):
+    """(thr2, alpha) as the C ABI takes them: `tau` is a distance, the kernels compare squared distances with
+    float32(tau) * float32(tau).  tau <= 0 or NaN, alpha negative or not finite: invalid, before any launch."""
+    tau, alpha = float(tau), float(alpha)
+    if not tau > 0.0:
+        raise H.invalid(f"{op}: tau must be a positive distance")
+    if not (alpha >= 0.0 and np.isfinite(alpha)):
+        raise H.invalid(f"{op}: alpha must be finite and non-negative")
+    with np.errstate(over="ignore"):
+        return float(np.float32(tau) * np.float32(tau)), alpha
+
+
+@H.on_input_device
+def nn_metrics(dist1, idx1, dist2, idx2, tau, alpha, lengths1=None, lengths2=None):
+    """rf_nn_metrics: the metrics epilogue on nn_distance outputs the caller holds (any route) ->
+    (metrics (b, 11), count1 (b, n), count2 (b, m)); columns and counts as include/rfops.h defines them."""
+    thr2, alpha = _metric_args(tau, alpha, "nn_metrics")
+    st = H.Staged()
+    d1, d2 = st.take(dist1, F32), st.take(dist2, F32)
+    i1, i2 = st.take(idx1, I32), st.take(idx2, I32)
+    if d1.dim() != 2 or d2.dim() != 2 or d1.shape[0] != d2.shape[0]:
+        raise H.invalid("nn_metrics requires dist1 (batch,#points1) and dist2 (batch,#points2)")
+    if i1.shape != d1.shape or i2.shape != d2.shape:
+        raise H.invalid("nn_metrics requires idx1 / idx2 be of the shapes of dist1 / dist2")
+    b, n, m = d1.shape[0], d1.shape[1], d2.shape[1]
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    d1, i1, d2, i2 = st.up(d1, i1, d2, i2)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    met = H.empty((b, CM_NCOL), F32, dev)
+    c1, c2 = H.empty((b, n), I32, dev), H.empty((b, m), I32, dev)
+    ws, wsz = H.workspace(lib.rf_nn_metrics_workspace_bytes(b, n, m), dev, "nn_metrics")
+    check(lib.rf_nn_metrics(b, n, m, H.ptr(d1), H.ptr(i1), H.ptr(d2), H.ptr(i2), H.ptr(l1), H.ptr(l2), thr2, alpha,
+                            H.ptr(met), H.ptr(c1), H.ptr(c2), H.ptr(ws), wsz, H.stream(dev)), "rf_nn_metrics")
+    return tuple(st.give(t) for t in (met, c1, c2))
+
+
+@H.on_input_device
+def chamfer_metrics(xyz1, xyz2, tau, alpha, lengths1=None, lengths2=None):
+    """rf_chamfer_metrics: the Chamfer sweep (both directions, padded slots (0, -1)) and the metrics epilogue in
+    one call -> (metrics (b, 11), dist1, idx1, dist2, idx2, count1, count2)."""
+    thr2, alpha = _metric_args(tau, alpha, "chamfer_metrics")
+    st = H.Staged()
+    a, b_ = _nn_inputs(st, xyz1, xyz2)
+    b, n, m = a.shape[0], a.shape[1], b_.shape[1]
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, b_ = st.up(a, b_)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    met = H.empty((b, CM_NCOL), F32, dev)
+    d1, i1, c1 = H.empty((b, n), F32, dev), H.empty((b, n), I32, dev), H.empty((b, n), I32, dev)
+    d2, i2, c2 = H.empty((b, m), F32, dev), H.empty((b, m), I32, dev), H.empty((b, m), I32, dev)
+    ws, wsz = H.workspace(lib.rf_chamfer_metrics_workspace_bytes(b, n, m), dev, "nn")
+    check(lib.rf_chamfer_metrics(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), thr2, alpha, H.ptr(met),
+                                 H.ptr(d1), H.ptr(i1), H.ptr(d2), H.ptr(i2), H.ptr(c1), H.ptr(c2), H.ptr(ws), wsz,
+                                 H.stream(dev)), "rf_chamfer_metrics")
+    return tuple(st.give(t) for t in (met, d1, i1, d2, i2, c1, c2))
+
+
+@H.on_input_device
+def chamfer_metrics_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, count1, count2, alpha, grad_metrics, lengths1=None,
+                         lengths2=None):
+    """rf_chamfer_metrics_grad -> (grad_xyz1, grad_xyz2): the backward of columns 0-3, 9 and 10 of the metrics
+    (columns 4-8 of grad_metrics are not read; the counts are constants)."""
+    _, alpha = _metric_args(1.0, alpha, "chamfer_metrics_grad")
+    st = H.Staged()
+    a, b_ = _nn_inputs(st, xyz1, xyz2, "NnDistanceGrad")
+    b, n, m = a.shape[0], a.shape[1], b_.shape[1]
+    gm = st.take(grad_metrics, F32)
+    if tuple(gm.shape) != (b, CM_NCOL):
+        raise H.invalid(f"chamfer_metrics_grad requires grad_metrics be of shape (batch,{CM_NCOL})")
+    per = []
+    for t, dt, shape in ((dist1, F32, (b, n)), (idx1, I32, (b, n)), (dist2, F32, (b, m)), (idx2, I32, (b, m)),
+                         (count1, I32, (b, n)), (count2, I32, (b, m))):
+        t = st.take(t, dt)
+        if tuple(t.shape) != shape:
+            raise H.invalid("NnDistanceGrad requires idx/dist/count be of shape(batch,#points)")
+        per.append(t)
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, b_, gm = st.up(a, b_, gm)
+    d1, i1, d2, i2, c1, c2 = st.up(*per)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    g1, g2 = H.empty((b, n, 3), F32, dev), H.empty((b, m, 3), F32, dev)
+    ws, wsz = H.workspace(lib.rf_chamfer_metrics_grad_workspace_bytes(b, n, m), dev, "nn_metrics_grad")
+    check(lib.rf_chamfer_metrics_grad(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(d1), H.ptr(i1),
+                                      H.ptr(d2), H.ptr(i2), H.ptr(c1), H.ptr(c2), alpha, H.ptr(gm), H.ptr(g1),
+                                      H.ptr(g2), H.ptr(ws), wsz, H.stream(dev)), "rf_chamfer_metrics_grad")
+    return st.give(g1), st.give(g2)
+
+
 @H.on_input_device
 def merge_layer(rawpts, newpts, decfactor, sorted_raw=None, lengths=None, lengths_new=None):
     """rf_merge_layer (vv_recon.py:132-139) -> (refined (b,m,3), idx2 (b,m)).  `lengths` / `lengths_new`: per-sample

@@ -93,6 +93,28 @@ def write_results_csv(path, rows):
             w.writerow(list(r))
 
 
+METRICS_HEADER = ["id", "cd", "fd", "fscore", "hausdorff", "dcd"]
+
+
+def write_metrics_csv(path, rows):
+    """rows: iterable of (model_id, cd, fd, fscore, hausdorff, dcd) -> metrics.csv, the table of the extra metrics
+    (evalrun.evaluate(extra_metrics=True)); results.csv keeps the reference's three columns."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(METRICS_HEADER)
+        for r in rows:
+            w.writerow(list(r))
+
+
+def read_metrics_csv(path):
+    with open(path, newline="") as f:
+        rd = csv.reader(f)
+        header = next(rd)
+        assert header == METRICS_HEADER, header
+        return [(r[0],) + tuple(float(v) for v in r[1:]) for r in rd]
+
+
 def read_results_csv(path):
     with open(path, newline="") as f:
         rd = csv.reader(f)

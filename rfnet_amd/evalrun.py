@@ -77,15 +77,20 @@ class GraphedForward:
 
 
 def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_pcd=False, graph=True, rng=None,
-             warm_models=10):
+             warm_models=10, extra_metrics=False, tau=0.01, alpha=1000.0):
     """recon_test.py's test(): returns the summary dict it prints (average time / CD / "EMD" and the
-    per-category means) and writes <results_dir>/results.csv."""
+    per-category means) and writes <results_dir>/results.csv.
+
+    `extra_metrics`: the per-model Chamfer comes from glue.chamfer_metrics(completion, gt) (the completion is the
+    prediction) and its F-score at `tau`, Hausdorff distance and density-aware Chamfer distance (`alpha`) go to
+    <results_dir>/metrics.csv (id, cd, fd, fscore, hausdorff, dcd) and, averaged, into the summary as
+    average_fscore / average_hausdorff / average_dcd.  Off (the default): outputs exactly as before."""
     dev = next(net.parameters()).device
     with open(list_path) as f:
         model_list = f.read().splitlines()
     os.makedirs(results_dir, exist_ok=True)
     fwd = None
-    rows, total_time = [], 0.0
+    rows, extra_rows, total_time = [], [], 0.0
     rng = rng if rng is not None else np.random.RandomState(0)
     for i, model_id in enumerate(model_list):
         partial = evalio.read_pcd(os.path.join(data_dir, "partial", "%s.pcd" % model_id))
@@ -104,15 +109,26 @@ def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_
         if i >= warm_models:
             total_time += mytime
         with torch.no_grad():
-            cd = float(glue.chamfer_big(completion, gt)[0])
+            if extra_metrics:
+                met = glue.chamfer_metrics(completion, gt, tau=tau, alpha=alpha)
+                cd = float(met["cd_l1"].mean())
+            else:
+                cd = float(glue.chamfer_big(completion, gt)[0])
             fd = float(glue.fidelity_loss(x, completion))
         rows.append((model_id, cd, fd))
+        if extra_metrics:
+            extra_rows.append((model_id, cd, fd, float(met["fscore"][0]), float(met["hausdorff"][0]), float(met["dcd"][0])))
         if save_pcd:
             synset_id, name = model_id.split("/")
             os.makedirs(os.path.join(results_dir, "pcds", synset_id), exist_ok=True)
             evalio.save_pcd(os.path.join(results_dir, "pcds", synset_id, "%s.pcd" % name), completion[0].cpu().numpy())
     evalio.write_results_csv(os.path.join(results_dir, "results.csv"), rows)
     timed = max(len(model_list) - warm_models, 1)
+    extra = {}
+    if extra_metrics:
+        evalio.write_metrics_csv(os.path.join(results_dir, "metrics.csv"), extra_rows)
+        for col, key in ((3, "average_fscore"), (4, "average_hausdorff"), (5, "average_dcd")):
+            extra[key] = float(np.mean([r[col] for r in extra_rows])) if extra_rows else 0.0
     return {
         "models": len(model_list),
         "average_time_s": total_time / timed,
@@ -121,6 +137,7 @@ def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_
         "per_category": evalio.per_category_means(rows),
         "graph": fwd is not None and fwd.graph is not None,
         "mode": fwd.mode if fwd is not None else "eager (graph not requested)",
+        **extra,
     }
 
 
@@ -139,16 +156,25 @@ def main(argv=None):
     ap.add_argument("--num_gt_points", type=int, default=16384)  # kept for the reference's CLI; gt size comes from the files
     ap.add_argument("--save_pcd", action="store_true")
     ap.add_argument("--no_graph", action="store_true", help="eager forward instead of the captured HIP graph")
+    ap.add_argument("--extra_metrics", action="store_true",
+                    help="F-score, Hausdorff and density-aware Chamfer distance per model into metrics.csv")
+    ap.add_argument("--tau", type=float, default=0.01, help="F-score distance threshold")
+    ap.add_argument("--alpha", type=float, default=1000.0, help="DCD's exponent scale")
     a = ap.parse_args(argv)
     from . import enable_graph_safe_runtime
     enable_graph_safe_runtime()  # before the HIP runtime starts
     net = RFNet().cuda().eval()
     if a.checkpoint:
         net.load_state_dict(torch.load(a.checkpoint, map_location="cuda"))
-    res = evaluate(net, a.list_path, a.data_dir, a.results_dir, save_pcd=a.save_pcd, graph=not a.no_graph)
+    res = evaluate(net, a.list_path, a.data_dir, a.results_dir, save_pcd=a.save_pcd, graph=not a.no_graph,
+                   extra_metrics=a.extra_metrics, tau=a.tau, alpha=a.alpha)
     print("Average time: %f" % res["average_time_s"])
     print("Average Chamfer distance: %f" % res["average_cd"])
     print("Average Earth mover distance: %f" % res["average_emd"])
+    if a.extra_metrics:
+        print("Average F-score@%g: %f" % (a.tau, res["average_fscore"]))
+        print("Average Hausdorff distance: %f" % res["average_hausdorff"])
+        print("Average density-aware Chamfer distance: %f" % res["average_dcd"])
     print("Chamfer distance per category")
     for k, v in res["per_category"].items():
         print(k, "%f" % v[0])

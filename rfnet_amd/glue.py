@@ -170,6 +170,60 @@ def fidelity_loss(pcd1, pcd2, sorted1=None, sorted2=None, lengths1=None, lengths
     return loss[:, 0].mean()
 
 
+class _ChamferMetrics(torch.autograd.Function):
+    """rf_chamfer_metrics / rf_chamfer_metrics_grad: the (b, 11) metrics tensor and idx1.  Columns 0-3, 9 and 10
+    carry gradients; the maxima, the threshold fractions and the F-score (4-8) do not, and the counts inside DCD
+    are constants."""
+
+    @staticmethod
+    def forward(ctx, xyz1, xyz2, tau, alpha, lengths1, lengths2):
+        met, d1, i1, d2, i2, c1, c2 = _raw.chamfer_metrics(xyz1, xyz2, tau, alpha, lengths1=lengths1, lengths2=lengths2)
+        ctx.save_for_backward(xyz1, xyz2, d1, i1, d2, i2, c1, c2)
+        ctx.alpha, ctx.lens = alpha, (lengths1, lengths2)
+        ctx.mark_non_differentiable(i1)
+        return met, i1
+
+    @staticmethod
+    def backward(ctx, grad_metrics, _):
+        xyz1, xyz2, d1, i1, d2, i2, c1, c2 = ctx.saved_tensors
+        g1, g2 = _raw.chamfer_metrics_grad(xyz1, xyz2, d1, i1, d2, i2, c1, c2, ctx.alpha, grad_metrics.contiguous(),
+                                           lengths1=ctx.lens[0], lengths2=ctx.lens[1])
+        return g1, g2, None, None, None, None
+
+
+def chamfer_metrics(pcd1, pcd2, tau=0.01, alpha=1000.0, lengths1=None, lengths2=None):
+    """What a completion is judged by, per sample, from one fused call (sweep + metrics epilogue).  `pcd1` plays the
+    PREDICTION and `pcd2` the ground truth: precision is the fraction of pcd1's points within `tau` (a distance) of
+    pcd2, recall the fraction of pcd2's points within `tau` of pcd1.  Returns a dict of (b,) tensors
+      cd_l1      (mean sqrt(dist1) + mean sqrt(dist2)) / 2   (chamfer_big's number, per sample)
+      cd_l2      mean dist1 + mean dist2
+      hausdorff  sqrt(max(max dist1, max dist2))
+      precision, recall, fscore   (fscore = their harmonic mean, 0 when both are 0)
+      dcd        density-aware Chamfer distance: the mean over both directions of 1 - exp(-alpha dist) / count, count =
+                 the number of queries that chose the point's neighbour (exponent 1, no set-size ratio factor)
+    plus "raw", the (b, 11) tensor of include/rfops.h, and "idx1".  cd_l1, cd_l2 and dcd are differentiable (one
+    fused backward); hausdorff, precision, recall and fscore carry no gradient.  lengths1 / lengths2: per-sample
+    point counts of a ragged batch (every mean over a sample's own points)."""
+    raw, idx1 = _ChamferMetrics.apply(pcd1.contiguous(), pcd2.contiguous(), float(tau), float(alpha), lengths1, lengths2)
+    fixed = raw.detach()
+    return {
+        "cd_l1": (raw[:, 0] + raw[:, 1]) / 2,
+        "cd_l2": raw[:, 2] + raw[:, 3],
+        "hausdorff": torch.sqrt(torch.maximum(fixed[:, 4], fixed[:, 5])),
+        "precision": fixed[:, 6],
+        "recall": fixed[:, 7],
+        "fscore": fixed[:, 8],
+        "dcd": (raw[:, 9] + raw[:, 10]) / 2,
+        "raw": raw,
+        "idx1": idx1,
+    }
+
+
+def dcd_loss(pcd1, pcd2, alpha=1000.0, lengths1=None, lengths2=None):
+    """The batch mean of chamfer_metrics(...)["dcd"]: the density-aware Chamfer distance as a training loss."""
+    return chamfer_metrics(pcd1, pcd2, alpha=alpha, lengths1=lengths1, lengths2=lengths2)["dcd"].mean()
+
+
 def earth_mover(pcd1, pcd2, lengths1=None, lengths2=None):
     """mean over the batch of cost_i / #points (vv_recon.py:392-399).  lengths1 / lengths2: per-sample point counts of a
     ragged batch (rf_earth_mover_lengths): the mean of cost_i / lengths1[i], the ragged form of the division by
