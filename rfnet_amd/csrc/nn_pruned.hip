@@ -197,15 +197,40 @@ __device__ __forceinline__ unsigned hilbert15(unsigned x, unsigned y, unsigned z
     return key & (NBINS - 1);
 }
 
-// bin of a coordinate: (v - lo) * scale clamped to [0, HB-1].  One v_med3_f32 does the clamp; a NaN
-// (NaN input, or inf * 0 when the axis has no extent) leaves it as NaN or a bound and converts to
-// 0 or a bound -- any bin is acceptable, the keys only steer the order.
-// (`off` = -lo * scale: one fma, one float clamp, one conversion -- the clamp leaves [0, HB - 1] or, for a NaN, whatever
-// v_med3_f32 makes of it, which v_cvt_i32_f32 turns into 0 or a bound; as (v - lo) * scale with an integer clamp behind the
-// conversion it was six instructions, 15 times per point of the sort)
+// bin of a coordinate: (v - lo) * scale clamped to [0, HB-1], as an fma (`off` = -lo * scale) and ONE conversion:
+// v_cvt_pk_u8_f32 makes a byte of a float, rounding to nearest and saturating at 0 and 255, and a NaN (NaN input, or
+// inf * 0 when the axis has no extent) becomes 0 (observed: profiles/sort_issue_costs.txt) -- any bin is acceptable, the keys
+// only steer the order, and a byte is inside a table of HB = 256 entries whatever it is.  (With a v_med3_f32 clamp, v_cvt_i32_f32 and
+// & 255 behind the fma it was four instructions, 8 times per point of the sort; the three bins of a point packed into one
+// register by the instruction's byte select take as many instructions as three registers do -- an extract per table address
+// instead of nothing -- so they stay apart.)
+// `off` of axis_bin for a frame's lower bound: -lo * scale, less the half that turns the conversion's round-to-nearest into the
+// truncation the bins are defined by (they differ on exact bin boundaries only, where the tie goes to the even bin)
+__device__ __forceinline__ float axis_off(float lo, float scale) {
+    return fmaf(-lo, scale, -0.5f);
+}
 __device__ __forceinline__ int axis_bin(float v, float off, float scale) {
-    const int b = (int)__builtin_amdgcn_fmed3f(fmaf(v, scale, off), 0.f, (float)(HB - 1));
-    return b & (HB - 1);  // (free insurance: a table index stays inside its table whatever the conversion returned)
+    static_assert(HB == 256, "a bin is a byte");
+    return (int)__builtin_amdgcn_cvt_pk_u8_f32(fmaf(v, scale, off), 0, 0u);
+}
+// v_min_f32 / v_max_f32 as they are: fminf / fmaxf put a canonicalising v_max_f32 x, x, x in front of every operand (to quiet
+// a signalling NaN: five instructions for a coordinate's minimum and maximum).  Operands canonicalised ONCE (`canon`, in front of
+// a coordinate's first use) need none: a quiet NaN operand returns the other operand, as with fminf / fmaxf.
+__device__ __forceinline__ float canon(float v) {
+    // (as asm, and volatile: the compiler moves __builtin_canonicalizef up into the branch of the load it follows, where it waits
+    // for that load before the next one is issued)
+    asm volatile("v_max_f32 %0, %0, %0" : "+v"(v));
+    return v;
+}
+__device__ __forceinline__ float bare_min(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float bare_max(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
 }
 
 __device__ __forceinline__ unsigned spread5(unsigned v) {  // bit b -> bit 3b
@@ -279,20 +304,40 @@ constexpr int HALF = 9216;  // records staged in LDS at a time (16 B each, over 
 // are the set's padding (+inf records, original index -1, empty boxes), which the sweep already skips --
 // padding lanes take no part in a traversal and an empty box is never within a query's bound.  So the frame,
 // the order and the boxes are the sample's own, and the work shrinks with the count.
-template <bool RAGGED>
+// FLAG: the cloud's "has a non-finite coordinate" flag is worked out and written (sorted handles: the ball query reads it);
+// without it the pass over the points and the ballot are left out (the Chamfer's private sorts: nobody reads their flag).
+template <bool RAGGED, bool FLAG>
 __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const int *__restrict__ len0,
                                                             const int *__restrict__ len1) {
-    __shared__ __attribute__((aligned(16))) unsigned hist[HALF * 4];  // NBINS bins, later HALF staged records
-    __shared__ unsigned ahist[3][HB];
-    __shared__ unsigned char slabmap[HB];        // x bin -> slab (equal mass)
-    __shared__ unsigned short zmap[HB];          // z bin -> rank in 0..511 (equal mass)
-    __shared__ unsigned char stripmap[16 * HB];  // (slab, y bin) -> strip of that slab (equal mass inside the slab), snaked
-    __shared__ float red[STPB / 64][6];
-    __shared__ unsigned wsum[STPB / 64];
-    __shared__ unsigned lowcnt[STPB / 64][3];
-    __shared__ float frame[6];  // lo[3], scale[3]
-    __shared__ unsigned ncrowded;  // waves whose points crowd into few bins
-    __shared__ unsigned badw[STPB / 64];  // per wave: a NaN or infinite coordinate among its points (query_ball_boxes reads the cloud's flag)
+    // ONE LDS object, the small tables in front: the kernel's LDS addresses are then compile-time offsets, and an LDS
+    // instruction's 16-bit offset field carries the base of every table below 64 KiB -- a lookup's address is the bin itself.
+    // (As separate __shared__ arrays the 147 KiB `hist` came first and every table base was an add of its own in front of the read:
+    // two VALU instructions per point of the keys loop.)
+    struct Lds {
+        unsigned ahist[3][HB];
+        unsigned char slabmap[HB];        // x bin -> slab (equal mass)
+        unsigned short zmap[HB];          // z bin -> rank in 0..511 (equal mass)
+        unsigned char stripmap[16 * HB];  // (slab, y bin) -> strip of that slab (equal mass inside the slab), snaked
+        float red[STPB / 64][6];
+        unsigned wsum[STPB / 64];
+        unsigned lowcnt[STPB / 64][3];
+        float frame[6];  // lo[3], scale[3]
+        unsigned ncrowded;  // waves whose points crowd into few bins
+        unsigned badw[STPB / 64];  // per wave: a NaN or infinite coordinate among its points (query_ball_boxes reads the cloud's flag)
+        __attribute__((aligned(16))) unsigned hist[HALF * 4];  // NBINS bins, later HALF staged records
+    };
+    __shared__ Lds lds;
+    auto &hist = lds.hist;
+    auto &ahist = lds.ahist;
+    auto &slabmap = lds.slabmap;
+    auto &zmap = lds.zmap;
+    auto &stripmap = lds.stripmap;
+    auto &red = lds.red;
+    auto &wsum = lds.wsum;
+    auto &lowcnt = lds.lowcnt;
+    auto &frame = lds.frame;
+    auto &ncrowded = lds.ncrowded;
+    auto &badw = lds.badw;
 
     // cloud-major logical order, each XCD a contiguous eighth (as the sweep: the XCD that sorts a
     // batch element is the one that sweeps it, its L2 still holding the records)
@@ -353,10 +398,19 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
     for (int i = tid; i < 16 * HB; i += STPB) yhist[i] = 0;
 
     stamp();
-    // 1. bounding box of the finite coordinates.  Fast path: plain min / max (fminf / fmaxf drop NaN by themselves); only a wave
+    // 1. bounding box of the finite coordinates.  Fast path: plain min / max (they drop a quiet NaN by themselves); only a wave
     // whose result is not finite -- an infinite coordinate, or no point at all -- repeats its pass with the per-coordinate filter
     // (wave-uniform branch; the filter is 3 of the 5 instructions per coordinate: 1.3 k of the sort's 50 k cycles)
     {
+        // (the coordinates are canonicalised here, once, where they are first used -- next to the loads it would make every load
+        // wait for the one before: the boxes take bare minima and maxima of them, and a signalling NaN becomes the quiet NaN that
+        // any arithmetic on it returns)
+#pragma unroll
+        for (int k = 0; k < RPT; k++) {
+            px[k] = canon(px[k]);
+            py[k] = canon(py[k]);
+            pz[k] = canon(pz[k]);
+        }
         float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
 #define RFP_BBOX_PASS(FILTER)                                                     \
     _Pragma("unroll") for (int k = 0; k < RPT; k++) {                             \
@@ -364,8 +418,8 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
             const float v[3] = {px[k], py[k], pz[k]};                             \
             _Pragma("unroll") for (int c = 0; c < 3; c++) {                       \
                 if (!(FILTER) || isfinite(v[c])) {                                \
-                    lo[c] = fminf(lo[c], v[c]);                                   \
-                    hi[c] = fmaxf(hi[c], v[c]);                                   \
+                    lo[c] = bare_min(lo[c], v[c]);                                \
+                    hi[c] = bare_max(hi[c], v[c]);                                \
                 }                                                                 \
             }                                                                     \
         }                                                                         \
@@ -394,18 +448,20 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
         // any NaN or infinite coordinate in the cloud?  (v * 0 is NaN exactly then; absent points hold 0.)  The boxes below
         // exclude such points, which is all the Chamfer sweep needs; the ball query must know, because a NaN distance IS inside
         // every ball (grouping.hip).  3 VALU per point here instead of a launch of its own there.
-        float nf = 0.f;
+        if (FLAG) {
+            float nf = 0.f;
 #pragma unroll
-        for (int k = 0; k < RPT; k++) nf = fmaf(pz[k], 0.f, fmaf(py[k], 0.f, fmaf(px[k], 0.f, nf)));
-        const unsigned long long bad_lanes = __ballot(nf != nf);  // (by the whole wave: not inside the lane-0 branch)
-        if (lane == 0) badw[wave] = bad_lanes != 0ull ? 1u : 0u;  // (read behind the barriers below)
+            for (int k = 0; k < RPT; k++) nf = fmaf(pz[k], 0.f, fmaf(py[k], 0.f, fmaf(px[k], 0.f, nf)));
+            const unsigned long long bad_lanes = __ballot(nf != nf);  // (by the whole wave: not inside the lane-0 branch)
+            if (lane == 0) badw[wave] = bad_lanes != 0ull ? 1u : 0u;  // (read behind the barriers below)
+        }
     }
     __syncthreads();
     if (tid < 3) {
         float l = INFINITY, h = -INFINITY;
         for (int w = 0; w < STPB / 64; w++) {
-            l = fminf(l, red[w][tid]);
-            h = fmaxf(h, red[w][3 + tid]);
+            l = bare_min(l, red[w][tid]);  // (the waves' results are never NaN)
+            h = bare_max(h, red[w][3 + tid]);
         }
         const float ext = h - l;
         const bool ok = isfinite(ext) && ext > 0.f;
@@ -414,7 +470,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
     }
     __syncthreads();
     const float fs[3] = {frame[3], frame[4], frame[5]};
-    const float fl[3] = {-frame[0] * fs[0], -frame[1] * fs[1], -frame[2] * fs[2]};  // axis_bin's offsets
+    const float fl[3] = {axis_off(frame[0], fs[0]), axis_off(frame[1], fs[1]), axis_off(frame[2], fs[2])};  // axis_bin's offsets
 
     stamp();
     // 2. per-axis histograms of a quarter of the points: the cells only need approximate
@@ -655,9 +711,11 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
     // time (258 us instead of 120 at C2) -- the sweep reads this flag per cloud (all workgroups of a cloud agree: same data)
     if (tid == 0 && half == 0) {
         a.pos0[set][a.b + bi] = ncrowded * RFP_CROWD_DIV > STPB / 64 ? 1 : 0;
-        unsigned nbad = 0;
-        for (int w = 0; w < STPB / 64; w++) nbad |= badw[w];
-        a.pos0[set][2 * a.b + bi] = nbad != 0u ? 1 : 0;
+        if (FLAG) {
+            unsigned nbad = 0;
+            for (int w = 0; w < STPB / 64; w++) nbad |= badw[w];
+            a.pos0[set][2 * a.b + bi] = nbad != 0u ? 1 : 0;
+        }
     }
     for (int h0 = 0; h0 < seglen; h0 += HALF) {
         const int cnt = min(HALF, seglen - h0);  // multiple of 64
@@ -684,16 +742,16 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
             for (int u = 0; u < BS / 2; u++) {
                 const int r = blk * BS + hf * (BS / 2) + ((u + blk + 4 * hf) & (BS / 2 - 1));
                 const float4 v = stg[r];
-                if (h0 + r < cown) {  // padding excluded; NaN coordinates drop out of fminf/fmaxf
-                    l[0] = fminf(l[0], v.x); hh[0] = fmaxf(hh[0], v.x);
-                    l[1] = fminf(l[1], v.y); hh[1] = fmaxf(hh[1], v.y);
-                    l[2] = fminf(l[2], v.z); hh[2] = fmaxf(hh[2], v.z);
+                if (h0 + r < cown) {  // padding excluded; NaN coordinates (quiet: canonicalised in phase 1) drop out of min / max
+                    l[0] = bare_min(l[0], v.x); hh[0] = bare_max(hh[0], v.x);
+                    l[1] = bare_min(l[1], v.y); hh[1] = bare_max(hh[1], v.y);
+                    l[2] = bare_min(l[2], v.z); hh[2] = bare_max(hh[2], v.z);
                 }
             }
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-                l[c] = fminf(l[c], __shfl_xor(l[c], 1, 64));
-                hh[c] = fmaxf(hh[c], __shfl_xor(hh[c], 1, 64));
+                l[c] = bare_min(l[c], __shfl_xor(l[c], 1, 64));  // (results of min / max: never NaN)
+                hh[c] = bare_max(hh[c], __shfl_xor(hh[c], 1, 64));
             }
             const int gblk = (base + h0) / BS + blk;
             if (hf == 0) {
@@ -708,8 +766,8 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
             for (int x = 2; x <= 4; x <<= 1) {
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
-                    l[c] = fminf(l[c], __shfl_xor(l[c], x, 64));
-                    hh[c] = fmaxf(hh[c], __shfl_xor(hh[c], x, 64));
+                    l[c] = bare_min(l[c], __shfl_xor(l[c], x, 64));
+                    hh[c] = bare_max(hh[c], __shfl_xor(hh[c], x, 64));
                 }
             }
             if ((gblk & 3) == 0 && hf == 0) {
@@ -845,7 +903,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_kernel(SortArgs a, const int *_
     }
     __syncthreads();
     const float fs[3] = {frame[3], frame[4], frame[5]};
-    const float fl[3] = {-frame[0] * fs[0], -frame[1] * fs[1], -frame[2] * fs[2]};  // axis_bin's offsets
+    const float fl[3] = {axis_off(frame[0], fs[0]), axis_off(frame[1], fs[1]), axis_off(frame[2], fs[2])};  // axis_bin's offsets
 
     // 2. per-axis histograms of a quarter of the points (every 4th, staggered over the threads:
     // the cells only need approximate quantiles, and same-address LDS atomics serialise)
@@ -2365,7 +2423,7 @@ size_t pruned_workspace_bytes(int b, int n, int m) {
 
 // Sort `nsets` (1 or 2) sets of b clouds in ONE launch (one workgroup per cloud).
 int sort_sets(int b, int nsets, const int *n, const float *const *src, const Sorted *out, hipStream_t s,
-              unsigned long long *dbg, const int *const *lens) {
+              unsigned long long *dbg, const int *const *lens, bool flag) {
     if (b <= 0 || nsets < 1 || nsets > 2) return RF_EINVAL;
     SortArgs sa;
     sa.b = b;
@@ -2400,14 +2458,22 @@ int sort_sets(int b, int nsets, const int *n, const float *const *src, const Sor
     if (lens) {  // per-sample counts (ragged batches)
         const int *l0 = lens[0], *l1 = nsets > 1 ? lens[1] : nullptr;
         if (reg) {
-            RF_LAUNCH("nnp_sort", nnp_sort_reg_kernel<true>, dim3(wpb * b), dim3(STPB), 0, s, sa, l0, l1);
+            if (flag) {
+                RF_LAUNCH("nnp_sort", (nnp_sort_reg_kernel<true, true>), dim3(wpb * b), dim3(STPB), 0, s, sa, l0, l1);
+            } else {
+                RF_LAUNCH("nnp_sort", (nnp_sort_reg_kernel<true, false>), dim3(wpb * b), dim3(STPB), 0, s, sa, l0, l1);
+            }
         } else {
             RF_LAUNCH("nnp_sort", (nnp_sort_kernel<false, true>), dim3(nsets * b), dim3(STPB), 0, s, sa, l0, l1);
         }
         return RF_OK;
     }
     if (reg) {
-        RF_LAUNCH("nnp_sort", nnp_sort_reg_kernel<false>, dim3(wpb * b), dim3(STPB), 0, s, sa, nullptr, nullptr);
+        if (flag) {
+            RF_LAUNCH("nnp_sort", (nnp_sort_reg_kernel<false, true>), dim3(wpb * b), dim3(STPB), 0, s, sa, nullptr, nullptr);
+        } else {
+            RF_LAUNCH("nnp_sort", (nnp_sort_reg_kernel<false, false>), dim3(wpb * b), dim3(STPB), 0, s, sa, nullptr, nullptr);
+        }
     } else {
         RF_LAUNCH("nnp_sort", (nnp_sort_kernel<false, false>), dim3(nsets * b), dim3(STPB), 0, s, sa, nullptr, nullptr);
     }
@@ -2523,7 +2589,7 @@ int pruned_step(int b, int n, int m, const float *xyz1, const float *xyz2, const
         ga.mask[k] = ev.mask;
         ga.grad[k] = grads[k];
     }
-    if (int e = sort_sets(b, 2, nn, src, so, s, nullptr)) return e;
+    if (int e = sort_sets(b, 2, nn, src, so, s, nullptr, nullptr, false)) return e;  // (private: nobody reads its non-finite flag)
     if (int e = sweep_sorted_impl(b, n, m, so[0], so[1], dist1, idx1, dist2, idx2, 3, s, nullptr, &ge)) return e;
     const int gtmax = ga.gt[0] > ga.gt[1] ? ga.gt[0] : ga.gt[1];
     RF_LAUNCH("nnp_grad_sorted", nnp_grad_sorted_kernel, dim3(b * (ga.tiles[0] + ga.tiles[1])), dim3(GS_TPB),
@@ -2546,7 +2612,7 @@ int pruned_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2
     const int nn[2] = {n, m};
     const float *src[2] = {xyz1, xyz2};
     const int *lens[2] = {len1, len2};
-    if (int e = sort_sets(b, 2, nn, src, so, s, RFP_REKEY_STATS ? nullptr : stats, (len1 || len2) ? lens : nullptr)) return e;
+    if (int e = sort_sets(b, 2, nn, src, so, s, RFP_REKEY_STATS ? nullptr : stats, (len1 || len2) ? lens : nullptr, false)) return e;  // (private too)
     if (int e = sweep_sorted(b, n, m, so[0], so[1], dist1, idx1, dist2, idx2, dirs, s, stats)) return e;
     if (stats_out) {
         RF_HIP(hipMemcpyAsync(stats_out, stats, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

@@ -37,12 +37,17 @@ struct Sorted {
 size_t sort_workspace_bytes(int b, int n);
 int sort_clouds(int b, int n, const float *src, void *workspace, size_t workspace_bytes, hipStream_t s, Sorted *out);
 
+// A sorted set's xyz records are the points with their coordinates CANONICALISED (v_max_f32 x, x, x, once, before the boxes are
+// taken): a signalling NaN is stored as the quiet NaN that any arithmetic on it returns; every other value, -0.0 and (in the
+// library's default denormal mode) denormals included, is stored bit for bit.
+// sort_sets' `flag`: work out each cloud's non-finite flag (behind pos0).  Only the ball query over a sorted set reads it; a
+// caller whose sorted sets never reach one (the Chamfer's private sorts) passes false and saves that pass.
 // The pieces, for callers that keep a sorted set across several sweeps (a "handle" is a caller-owned
 // buffer of sorted_bytes(b, n) bytes whose layout is a pure function of (b, n)).
 size_t sorted_bytes(int b, int n);
 Sorted sorted_view(int b, int n, const void *buf);
 int sort_sets(int b, int nsets, const int *n, const float *const *src, const Sorted *out, hipStream_t s,
-              unsigned long long *dbg, const int *const *lens = nullptr);
+              unsigned long long *dbg, const int *const *lens = nullptr, bool flag = true);
 // Sort the sets of a pair (xyz1 -> s1, xyz2 -> s2) that did not come from the caller as handles (have1 / have2), in one
 // sort_sets launch; nothing when both did.
 int sort_missing(int b, int n, int m, const float *xyz1, const float *xyz2, const Sorted &s1, const Sorted &s2, bool have1,
