@@ -237,6 +237,51 @@ int rf_chamfer_metrics_grad(int b, int n, int m, const float *xyz1, const float 
                             const float *grad_metrics, float *grad_xyz1, float *grad_xyz2, void *workspace,
                             size_t workspace_bytes, rf_stream_t stream);
 
+/* ---- the Chamfer matrix of two collections of clouds (Chamfer, continued) ----------------- */
+/* What a set metric needs (minimal matching distance, MMD / coverage / 1-NN accuracy, nearest-shape retrieval): for
+ * EVERY cloud i of xyz1 (s, n, 3) and EVERY cloud j of xyz2 (r, m, 3) the first six columns of rf_chamfer_metrics, in
+ * out (s, r, RF_CX_NCOL).  Each collection is sorted once (s + r sorts, not s * r), nothing is stored per point, and no
+ * index is tracked.  Conventions are rf_nn_distance_lengths': len1 (s) / len2 (r) device int32 counts or NULL, read and
+ * clamped into [1, n] / [1, m] by the kernels; rows behind a count never reach a result.  No host synchronisation: a
+ * call can be captured in a HIP graph.  With L1, L2 the clamped counts of cloud i of xyz1 and cloud j of xyz2:
+ *
+ *   d1[k] = min_{l < L2} d(xyz2[j][l], xyz1[i][k]), k < L1      d2[l] = min_{k < L1} d(xyz1[i][k], xyz2[j][l]), l < L2
+ *   d = fmaf(dz, dz, fmaf(dx, dx, dy * dy)) on "other - own": every d1 / d2 is bit for bit rf_nn_distance's value
+ *
+ *   0, 1   mean of sqrtf(d1), mean of sqrtf(d2)      within rel 1e-5 of the float64 mean of the fp32 values
+ *   2, 3   mean of d1, mean of d2                    the same
+ *   4, 5   max of d1, max of d2                      exact
+ *
+ * Guarantees:
+ *   - No float atomics and no float sum at all: every sum is an exact INTEGER sum of the terms on a fixed-point grid
+ *     that is a function of the pair alone, followed by one division: with D the squared diagonal of the joint box
+ *     of the two clouds and P the power of two with P / 4 <= D < P / 2, the grid step is P 2^-111 for d and, with P'
+ *     the power of two with sqrt(P) <= P' < 2 sqrt(P), P' 2^-111 for sqrtf(d).  Two calls return identical bits,
+ *     whatever order the sort left the points in.  A term is truncated only below the step: the bar above holds
+ *     whenever a mean is at least 2^-94 of P (of P'), and below that the absolute error stays under one step.  A
+ *     direction with one valid point returns its sqrtf(d) and d exactly (d >= 2^-88 P).
+ *   - Batch invariance: the six numbers of a pair depend only on that pair's two clouds and counts -- not on s, r,
+ *     the position of the clouds in their collections or on what the other clouds hold.
+ *   - Self-distance: with xyz1 == xyz2, len1 == len2, s == r and n == m the collection is sorted once and only one
+ *     direction is swept (direction 2 of (i, j) is direction 1 of (j, i)); the results are the bits of the general call.
+ *   - Memory safety: non-finite coordinates in valid rows never cause a read or write out of bounds -- every loop
+ *     bound is a count, never a data value.  The numbers returned for such clouds are unspecified.
+ *
+ * Workspace, with sb(n) = (padded record count of a sorted cloud of n points) / 64 <= n / 64 + 2, each part rounded
+ * up to 256 bytes:  rf_nn_sort_bytes(s, n) + rf_nn_sort_bytes(r, m) + 32 (s + r) + 48 s r sb(n) + 48 s r sb(m)
+ * -- the two sorted collections, a box per cloud, and one 48-byte record per (i, j, 64 points) and direction; nothing
+ * of size s r n or s r m.
+ *
+ * Argument rules, all checked before any HIP call: RF_EINVAL for a negative size; then s == 0 or r == 0 is RF_OK;
+ * RF_EINVAL for n < 1 or m < 1, n or m above 65536, s or r above 65535, a NULL tensor, a tensor or count array not
+ * 4-byte aligned, a workspace that is NULL or not 16-byte aligned; RF_EWORKSPACE for a workspace smaller than
+ * rf_chamfer_cross_workspace_bytes (0 for non-positive or unsupported sizes, positive otherwise).  All index
+ * arithmetic is in size_t. */
+#define RF_CX_NCOL 6
+size_t rf_chamfer_cross_workspace_bytes(int s, int r, int n, int m);
+int rf_chamfer_cross(int s, int r, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
+                     const int *len2, float *out, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+
 /* ----------------------------------------------------------- EMD (pc_distance) ---------- */
 /* Replaces approxmatchLauncher(b,n,m,xyz1,xyz2,match,temp) (pc_distance/tf_approxmatch.cpp:141,
  * tf_approxmatch.cu:180-182).  xyz1 (b,n,3) "dataset", xyz2 (b,m,3) "query" (b <= 65535 for

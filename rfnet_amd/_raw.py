@@ -439,6 +439,55 @@ def chamfer_metrics(xyz1, xyz2, tau, alpha, lengths1=None, lengths2=None):
     return tuple(st.give(t) for t in (met, d1, i1, d2, i2, c1, c2))
 
 
+CX_NCOL = 6  # RF_CX_NCOL (include/rfops.h): columns of the Chamfer matrix
+CX_MAX_CLOUDS, CX_MAX_POINTS = 65535, 65536
+
+
+@H.on_input_device
+def chamfer_cross(xyz1, xyz2=None, lengths1=None, lengths2=None):
+    """rf_chamfer_cross: the Chamfer matrix of two collections of clouds, xyz1 (s, n, 3) against xyz2 (r, m, 3) ->
+    (s, r, 6) float32: per pair (i, j) the means of sqrt(dist), the means of dist and the maxima of dist in both
+    directions (columns 0-5 of chamfer_metrics).  Each collection is sorted once; nothing is stored per point.
+    xyz2=None is the collection against itself (sorted once, `lengths2` must then be None too: lengths1 holds for
+    both sides).  lengths1 (s,) / lengths2 (r,): per-cloud point counts.  The result carries no gradient."""
+    st = H.Staged()
+    a = st.take(xyz1, F32)
+    if a.dim() != 3 or a.shape[2] != 3:
+        raise H.invalid("chamfer_cross requires xyz1 be of shape (#clouds1,#points,3)")
+    self_ = xyz2 is None
+    if self_:
+        if lengths2 is not None:
+            raise H.invalid("chamfer_cross of a collection against itself takes lengths1 only")
+        b_ = a
+    else:
+        b_ = st.take(xyz2, F32)
+        if b_.dim() != 3 or b_.shape[2] != 3:
+            raise H.invalid("chamfer_cross requires xyz2 be of shape (#clouds2,#points,3)")
+    s, n, r, m = a.shape[0], a.shape[1], b_.shape[0], b_.shape[1]
+    if s > 0 and r > 0 and (n < 1 or m < 1):
+        raise H.invalid("chamfer_cross requires at least one point per cloud")
+    if n > CX_MAX_POINTS or m > CX_MAX_POINTS:
+        raise H.invalid(f"chamfer_cross takes clouds of up to {CX_MAX_POINTS} points")
+    if s > CX_MAX_CLOUDS or r > CX_MAX_CLOUDS:
+        raise H.invalid(f"chamfer_cross takes up to {CX_MAX_CLOUDS} clouds per collection: split the collection")
+    l1 = _check_lengths(lengths1, s, n, "lengths1")
+    l2 = l1 if self_ else _check_lengths(lengths2, r, m, "lengths2")
+    dev = st.device_()
+    if self_:
+        (a,) = st.up(a)
+        b_ = a
+        l1 = l2 = _lengths_up(l1, dev, n)
+    else:
+        a, b_ = st.up(a, b_)
+        l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    out = H.empty((s, r, CX_NCOL), F32, dev)
+    if s > 0 and r > 0:
+        ws, wsz = H.workspace(lib.rf_chamfer_cross_workspace_bytes(s, r, n, m), dev, "chamfer_cross")
+        check(lib.rf_chamfer_cross(s, r, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(out), H.ptr(ws), wsz,
+                                   H.stream(dev)), "rf_chamfer_cross")
+    return st.give(out)
+
+
 @H.on_input_device
 def chamfer_metrics_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, count1, count2, alpha, grad_metrics, lengths1=None,
                          lengths2=None):

@@ -115,6 +115,28 @@ def read_metrics_csv(path):
         return [(r[0],) + tuple(float(v) for v in r[1:]) for r in rd]
 
 
+MMD_HEADER = ["id", "mmd", "ref_index"]
+
+
+def write_mmd_csv(path, rows):
+    """rows: iterable of (model_id, mmd, ref_index) -> mmd.csv, the minimal matching distance of every completion
+    to a shelf of reference shapes and the shelf position of its match (evalrun.evaluate(mmd_refs=...))."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(MMD_HEADER)
+        for r in rows:
+            w.writerow([r[0], repr(float(r[1])), int(r[2])])
+
+
+def read_mmd_csv(path):
+    with open(path, newline="") as f:
+        rd = csv.reader(f)
+        header = next(rd)
+        assert header == MMD_HEADER, header
+        return [(r[0], float(r[1]), int(r[2])) for r in rd]
+
+
 def read_results_csv(path):
     with open(path, newline="") as f:
         rd = csv.reader(f)

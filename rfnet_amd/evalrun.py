@@ -77,20 +77,26 @@ class GraphedForward:
 
 
 def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_pcd=False, graph=True, rng=None,
-             warm_models=10, extra_metrics=False, tau=0.01, alpha=1000.0):
+             warm_models=10, extra_metrics=False, tau=0.01, alpha=1000.0, mmd_refs=None):
     """recon_test.py's test(): returns the summary dict it prints (average time / CD / "EMD" and the
     per-category means) and writes <results_dir>/results.csv.
 
     `extra_metrics`: the per-model Chamfer comes from glue.chamfer_metrics(completion, gt) (the completion is the
     prediction) and its F-score at `tau`, Hausdorff distance and density-aware Chamfer distance (`alpha`) go to
     <results_dir>/metrics.csv (id, cd, fd, fscore, hausdorff, dcd) and, averaged, into the summary as
-    average_fscore / average_hausdorff / average_dcd.  Off (the default): outputs exactly as before."""
+    average_fscore / average_hausdorff / average_dcd.  Off (the default): outputs exactly as before.
+
+    `mmd_refs`: an (r, m, 3) array or tensor of reference clouds (a shelf of shapes, for scans without a ground
+    truth).  The completions stay on the device, glue.minimal_matching (CD-L2 of the Chamfer matrix, one sort per
+    cloud) runs after the loop, <results_dir>/mmd.csv gets id, mmd, ref_index and the summary `average_mmd`.  None
+    (the default): outputs exactly as before."""
     dev = next(net.parameters()).device
     with open(list_path) as f:
         model_list = f.read().splitlines()
     os.makedirs(results_dir, exist_ok=True)
     fwd = None
     rows, extra_rows, total_time = [], [], 0.0
+    kept = []  # the completions, on the device (mmd_refs only)
     rng = rng if rng is not None else np.random.RandomState(0)
     for i, model_id in enumerate(model_list):
         partial = evalio.read_pcd(os.path.join(data_dir, "partial", "%s.pcd" % model_id))
@@ -116,6 +122,8 @@ def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_
                 cd = float(glue.chamfer_big(completion, gt)[0])
             fd = float(glue.fidelity_loss(x, completion))
         rows.append((model_id, cd, fd))
+        if mmd_refs is not None:
+            kept.append(completion[0].clone())  # (a replayed graph hands out the same buffer every time)
         if extra_metrics:
             extra_rows.append((model_id, cd, fd, float(met["fscore"][0]), float(met["hausdorff"][0]), float(met["dcd"][0])))
         if save_pcd:
@@ -129,6 +137,15 @@ def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_
         evalio.write_metrics_csv(os.path.join(results_dir, "metrics.csv"), extra_rows)
         for col, key in ((3, "average_fscore"), (4, "average_hausdorff"), (5, "average_dcd")):
             extra[key] = float(np.mean([r[col] for r in extra_rows])) if extra_rows else 0.0
+    if mmd_refs is not None:
+        refs = torch.as_tensor(mmd_refs, dtype=torch.float32).to(dev)
+        mmd_rows = []
+        if kept:
+            with torch.no_grad():
+                val, at = glue.minimal_matching(torch.stack(kept), refs)
+            mmd_rows = list(zip(model_list, val.cpu().tolist(), at.cpu().tolist()))
+        evalio.write_mmd_csv(os.path.join(results_dir, "mmd.csv"), mmd_rows)
+        extra["average_mmd"] = float(np.mean([r[1] for r in mmd_rows])) if mmd_rows else 0.0
     return {
         "models": len(model_list),
         "average_time_s": total_time / timed,
@@ -160,14 +177,22 @@ def main(argv=None):
                     help="F-score, Hausdorff and density-aware Chamfer distance per model into metrics.csv")
     ap.add_argument("--tau", type=float, default=0.01, help="F-score distance threshold")
     ap.add_argument("--alpha", type=float, default=1000.0, help="DCD's exponent scale")
+    ap.add_argument("--mmd_list", default=None,
+                    help="a list of model ids whose complete/<id>.pcd files are the reference shelf: minimal matching "
+                         "distance of every completion to it into mmd.csv (the clouds must have one size)")
     a = ap.parse_args(argv)
     from . import enable_graph_safe_runtime
     enable_graph_safe_runtime()  # before the HIP runtime starts
     net = RFNet().cuda().eval()
     if a.checkpoint:
         net.load_state_dict(torch.load(a.checkpoint, map_location="cuda"))
+    refs = None
+    if a.mmd_list:
+        with open(a.mmd_list) as f:
+            refs = np.stack([evalio.read_pcd(os.path.join(a.data_dir, "complete", "%s.pcd" % ref_id)).astype(np.float32)
+                             for ref_id in f.read().splitlines() if ref_id])
     res = evaluate(net, a.list_path, a.data_dir, a.results_dir, save_pcd=a.save_pcd, graph=not a.no_graph,
-                   extra_metrics=a.extra_metrics, tau=a.tau, alpha=a.alpha)
+                   extra_metrics=a.extra_metrics, tau=a.tau, alpha=a.alpha, mmd_refs=refs)
     print("Average time: %f" % res["average_time_s"])
     print("Average Chamfer distance: %f" % res["average_cd"])
     print("Average Earth mover distance: %f" % res["average_emd"])
@@ -175,6 +200,8 @@ def main(argv=None):
         print("Average F-score@%g: %f" % (a.tau, res["average_fscore"]))
         print("Average Hausdorff distance: %f" % res["average_hausdorff"])
         print("Average density-aware Chamfer distance: %f" % res["average_dcd"])
+    if refs is not None:
+        print("Average minimal matching distance: %f" % res["average_mmd"])
     print("Chamfer distance per category")
     for k, v in res["per_category"].items():
         print(k, "%f" % v[0])

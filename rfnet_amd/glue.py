@@ -224,6 +224,88 @@ def dcd_loss(pcd1, pcd2, alpha=1000.0, lengths1=None, lengths2=None):
     return chamfer_metrics(pcd1, pcd2, alpha=alpha, lengths1=lengths1, lengths2=lengths2)["dcd"].mean()
 
 
+def _matrix_keys(raw):
+    return {
+        "cd_l1": (raw[..., 0] + raw[..., 1]) / 2,
+        "cd_l2": raw[..., 2] + raw[..., 3],
+        "hausdorff": torch.sqrt(torch.maximum(raw[..., 4], raw[..., 5])),
+        "raw": raw,
+    }
+
+
+def chamfer_matrix(set1, set2=None, lengths1=None, lengths2=None):
+    """The Chamfer matrix of two collections of clouds, set1 (s, n, 3) against set2 (r, m, 3), from one call
+    (rf_chamfer_cross: each collection sorted once, nothing stored per point).  set2=None: set1 against itself.
+    Returns a dict of (s, r) tensors with chamfer_metrics' conventions -- cd_l1, cd_l2, hausdorff -- plus "raw", the
+    (s, r, 6) tensor of include/rfops.h.  An entry depends on its two clouds alone, not on the collections around
+    them.  No gradient.  lengths1 (s,) / lengths2 (r,): per-cloud point counts."""
+    return _matrix_keys(_raw.chamfer_cross(set1, set2, lengths1=lengths1, lengths2=lengths2))
+
+
+def _argmin_low(d, dim):
+    """(min, argmin) along `dim` with the LOWEST index on ties (torch.min leaves the choice open)."""
+    v = d.min(dim=dim, keepdim=True).values
+    pos = torch.arange(d.shape[dim], device=d.device).view([-1 if k == dim % d.dim() else 1 for k in range(d.dim())])
+    idx = torch.where(d == v, pos, d.shape[dim]).min(dim=dim).values
+    return v.squeeze(dim), idx.clamp_(max=max(d.shape[dim] - 1, 0))  # (a row of NaN matches nothing)
+
+
+def minimal_matching(pred, refs, metric="cd_l2", lengths1=None, lengths2=None, chunk=None):
+    """Minimal matching distance: for every cloud of pred (s, n, 3) the smallest chamfer_matrix entry `metric`
+    ("cd_l1", "cd_l2" or "hausdorff") over the reference clouds refs (r, m, 3), and where it is -> (value (s,),
+    index (s,) int64), ties to the lowest index.  `chunk`: references per rf_chamfer_cross call, which bounds the
+    matrix and the workspace; the results are the same bits for every chunk (an entry depends on its pair alone)."""
+    if metric not in ("cd_l1", "cd_l2", "hausdorff"):
+        raise ValueError(f"minimal_matching: unknown metric {metric!r}")
+    r = refs.shape[0]
+    if r < 1:
+        raise ValueError("minimal_matching needs at least one reference cloud")
+    step = r if chunk is None else int(chunk)
+    if step < 1:
+        raise ValueError("minimal_matching: chunk must be positive")
+    l2 = None if lengths2 is None else _raw._check_lengths(lengths2, r, refs.shape[1], "lengths2")
+    best = best_at = None
+    for j0 in range(0, r, step):
+        d = chamfer_matrix(pred, refs[j0:j0 + step], lengths1=lengths1,
+                           lengths2=None if l2 is None else l2[j0:j0 + step])[metric]
+        v, at = _argmin_low(d, 1)
+        at = at + j0
+        if best is None:
+            best, best_at = v, at
+        else:
+            take = v < best  # strict: a tie stays with the earlier chunk
+            best, best_at = torch.where(take, v, best), torch.where(take, at, best_at)
+    return best, best_at
+
+
+def set_metrics(d_gr, d_gg=None, d_rr=None):
+    """Set-level scores from distance matrices (any entry of chamfer_matrix): d_gr (g, r) generated against
+    reference clouds, and optionally d_gg (g, g) and d_rr (r, r).  Plain tensor ops (CPU tensors allowed), 0-d
+    results, no host synchronisation.
+      mmd      mean over references j of min_i d_gr[i, j]
+      cov      #{distinct argmin_j d_gr[i, :] over i} / r
+      one_nna  (with d_gg and d_rr) the leave-one-out 1-NN accuracy over the g + r clouds: the fraction whose nearest
+               other cloud, in [[d_gg, d_gr], [d_gr^T, d_rr]] with an infinite diagonal, carries their own label
+    Every argmin is the lowest index on ties."""
+    if d_gr.dim() != 2 or d_gr.shape[0] < 1 or d_gr.shape[1] < 1:
+        raise ValueError("set_metrics requires a non-empty (generated, references) matrix")
+    g, r = d_gr.shape
+    out = {"mmd": d_gr.min(dim=0).values.mean()}
+    hit = torch.zeros(r, dtype=d_gr.dtype, device=d_gr.device)
+    hit[_argmin_low(d_gr, 1)[1]] = 1
+    out["cov"] = hit.sum() / r
+    if d_gg is not None and d_rr is not None:
+        if d_gg.shape != (g, g) or d_rr.shape != (r, r):
+            raise ValueError("set_metrics requires d_gg (g, g) and d_rr (r, r)")
+        full = torch.cat([torch.cat([d_gg, d_gr], 1), torch.cat([d_gr.t(), d_rr], 1)], 0).clone()
+        full.fill_diagonal_(float("inf"))
+        own = torch.arange(g + r, device=full.device) < g
+        out["one_nna"] = ((_argmin_low(full, 1)[1] < g) == own).to(d_gr.dtype).mean()
+    elif d_gg is not None or d_rr is not None:
+        raise ValueError("set_metrics: one_nna needs both d_gg and d_rr")
+    return out
+
+
 def earth_mover(pcd1, pcd2, lengths1=None, lengths2=None):
     """mean over the batch of cost_i / #points (vv_recon.py:392-399).  lengths1 / lengths2: per-sample point counts of a
     ragged batch (rf_earth_mover_lengths): the mean of cost_i / lengths1[i], the ragged form of the division by
