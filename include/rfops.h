@@ -282,6 +282,54 @@ size_t rf_chamfer_cross_workspace_bytes(int s, int r, int n, int m);
 int rf_chamfer_cross(int s, int r, int n, int m, const float *xyz1, const float *xyz2, const int *len1,
                      const int *len2, float *out, void *workspace, size_t workspace_bytes, rf_stream_t stream);
 
+/* ---- the sliced Wasserstein distance of two clouds, with gradients ------------------------- */
+/* A transport-type loss that is cheap at 16384 points and takes unequal and ragged counts exactly: both clouds are
+ * projected on nproj directions, in 1-D optimal transport is sorting, and the per-direction costs are averaged.
+ * xyz1 (b, n, 3), xyz2 (b, m, 3); dirs (nproj, 3) fp32 on the device, used as given (not normalised, no gradient).
+ * len1 / len2: device int32 (b) or NULL with rf_nn_distance_lengths' conventions -- read and clamped into [1, n] /
+ * [1, m] by the kernels, rows behind a count never reach a result.  No host synchronisation: a call can be captured in
+ * a HIP graph.  Per sample and direction l = (tx, ty, tz), with L1, L2 the clamped counts:
+ *
+ *   1. p = fmaf(z, tz, fmaf(x, tx, y * ty)) + 0.0f for every valid point (the + 0.0f makes -0 sort as +0);
+ *   2. each cloud's projections are ordered ascending by (value, original index) -- ties go to the lower index, which
+ *      fixes the permutation and therefore the gradient: u[0..L1), v[0..L2) the sorted values, r1, r2 the ranks;
+ *   3. c_l = sum_{i, j} w_ij (u_i - v_j)^2, w_ij the length of [i / L1, (i + 1) / L1) with [j / L2, (j + 1) / L2) cut out:
+ *      (min((i + 1) L2, (j + 1) L1) - max(i L2, j L1)) / (L1 L2), the numerator an exact integer.  For L1 == L2 this
+ *      is mean((u - v)^2).  Rank i meets the ranks floor(i L2 / L1) ... ceil((i + 1) L2 / L1) - 1.
+ *
+ *   loss[b]     = (1 / nproj) sum_l c_l
+ *   grad1[b][k] =  (2 / nproj) sum_l dir_l sum_j w_{r1(k), j} (u_{r1(k)} - v_j)      k < L1, exactly +0 behind the count
+ *   grad2[b][k] = -(2 / nproj) sum_l dir_l sum_i w_{i, r2(k)} (u_i - v_{r2(k)})      k < L2, exactly +0 behind the count
+ *
+ * grad1 (b, n, 3) and grad2 (b, m, 3) are either both given or both NULL (loss only).  Only the projection is fp32:
+ * differences, weights, squares and every sum are double, in a fixed order (ranks within a direction, then the
+ * directions 0 ... nproj - 1), with one rounding to fp32 at the end.  No atomics.
+ *
+ * Guarantees:
+ *   - Two calls return identical bits.
+ *   - Batch invariance: sample i's loss and gradients are bit for bit those of the call on [i : i + 1], for every b
+ *     and position, whatever the other samples hold.
+ *   - Memory safety: non-finite coordinates in valid rows never move a memory access -- every loop bound is a count
+ *     and every index a rank or an original index below its count.  The numbers of such a sample are unspecified; the
+ *     other samples are unaffected.
+ *
+ * Directions are processed RF_SW_DIR_CHUNK at a time and nothing in the workspace grows with nproj beyond a chunk.
+ * With c = min(nproj, RF_SW_DIR_CHUNK) and each part rounded up to 256 bytes:
+ *   4 c b (n + m)  sorted values       + 4 c b (n + m)  original indices   + 8 c b  costs   + 8 b  one double per sample
+ *   and with gradients   + 8 c b (n + m)  per-point coefficients   + 24 b (n + m)  double accumulators.
+ *
+ * Argument rules, all checked before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for
+ * n, m or nproj < 1, n or m above RF_SW_MAX_POINTS, b above 65535, a NULL xyz1 / xyz2 / dirs / loss, exactly one of
+ * grad1 / grad2 given, a tensor or count array not 4-byte aligned, a workspace that is NULL or not 16-byte aligned;
+ * RF_EWORKSPACE for a workspace smaller than rf_sliced_wasserstein_workspace_bytes (0 for non-positive or unsupported
+ * sizes, positive otherwise).  All index arithmetic is in size_t. */
+#define RF_SW_MAX_POINTS 16384
+#define RF_SW_DIR_CHUNK 16
+size_t rf_sliced_wasserstein_workspace_bytes(int b, int n, int m, int nproj, int want_grad);
+int rf_sliced_wasserstein(int b, int n, int m, int nproj, const float *xyz1, const float *xyz2, const int *len1,
+                          const int *len2, const float *dirs, float *loss, float *grad1, float *grad2, void *workspace,
+                          size_t workspace_bytes, rf_stream_t stream);
+
 /* ----------------------------------------------------------- EMD (pc_distance) ---------- */
 /* Replaces approxmatchLauncher(b,n,m,xyz1,xyz2,match,temp) (pc_distance/tf_approxmatch.cpp:141,
  * tf_approxmatch.cu:180-182).  xyz1 (b,n,3) "dataset", xyz2 (b,m,3) "query" (b <= 65535 for

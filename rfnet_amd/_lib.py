@@ -63,6 +63,8 @@ SIGNATURES = {
     "rf_chamfer_metrics_grad": (_i, [_i, _i, _i] + [_vp] * 10 + [_f] + [_vp] * 4 + [_sz, _vp]),
     "rf_chamfer_cross_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_chamfer_cross": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_sz, _vp]),
+    "rf_sliced_wasserstein_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "rf_sliced_wasserstein": (_i, [_i, _i, _i, _i] + [_vp] * 9 + [_sz, _vp]),
     "rf_merge_layer_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_merge_layer": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_merge_layer_grad": (_i, [_i, _i, _i] + [_vp] * 9),

@@ -488,6 +488,51 @@ def chamfer_cross(xyz1, xyz2=None, lengths1=None, lengths2=None):
     return st.give(out)
 
 
+SW_MAX_POINTS, SW_DIR_CHUNK = 16384, 16  # RF_SW_MAX_POINTS, RF_SW_DIR_CHUNK (include/rfops.h)
+
+
+@H.on_input_device
+def sliced_wasserstein(xyz1, xyz2, directions, lengths1=None, lengths2=None, want_grad=False):
+    """rf_sliced_wasserstein: the sliced Wasserstein distance SW_2^2 of xyz1 (b, n, 3) and xyz2 (b, m, 3) over the
+    rows of `directions` (nproj, 3), used as given -> loss (b,), or with `want_grad` (loss, grad_xyz1, grad_xyz2)
+    from the same call.  n != m and per-sample counts lengths1 / lengths2 are exact (the quantile functions are
+    merged); ties in a projection go to the lower index; rows behind a count get a gradient of exactly 0."""
+    st = H.Staged()
+    a, b_ = st.take(xyz1, F32), st.take(xyz2, F32)
+    if a.dim() != 3 or a.shape[2] != 3:
+        raise H.invalid("sliced_wasserstein requires xyz1 be of shape (batch,#points,3)")
+    if b_.dim() != 3 or b_.shape[2] != 3:
+        raise H.invalid("sliced_wasserstein requires xyz2 be of shape (batch,#points,3)")
+    if b_.shape[0] != a.shape[0]:
+        raise H.invalid("sliced_wasserstein expects xyz1 and xyz2 have same batch size")
+    d = st.take(directions, F32)
+    if d.dim() != 2 or d.shape[1] != 3 or d.shape[0] < 1:
+        raise H.invalid("sliced_wasserstein requires directions be of shape (#projections,3), at least one")
+    b, n, m, nproj = a.shape[0], a.shape[1], b_.shape[1], d.shape[0]
+    if b > 0 and (n < 1 or m < 1):
+        raise H.invalid("sliced_wasserstein requires at least one point per cloud")
+    if n > SW_MAX_POINTS or m > SW_MAX_POINTS:
+        raise H.invalid(f"sliced_wasserstein takes clouds of up to {SW_MAX_POINTS} points")
+    if b > 65535:
+        raise H.invalid("sliced_wasserstein takes up to 65535 samples per call: split the batch")
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, b_, d = st.up(a, b_, d)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    loss = H.empty((b,), F32, dev)
+    g1 = H.empty((b, n, 3), F32, dev) if want_grad else None
+    g2 = H.empty((b, m, 3), F32, dev) if want_grad else None
+    if b > 0:
+        ws, wsz = H.workspace(lib.rf_sliced_wasserstein_workspace_bytes(b, n, m, nproj, 1 if want_grad else 0), dev,
+                              "sliced")
+        check(lib.rf_sliced_wasserstein(b, n, m, nproj, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(d),
+                                        H.ptr(loss), H.ptr(g1), H.ptr(g2), H.ptr(ws), wsz, H.stream(dev)),
+              "rf_sliced_wasserstein")
+    if want_grad:
+        return st.give(loss), st.give(g1), st.give(g2)
+    return st.give(loss)
+
+
 @H.on_input_device
 def chamfer_metrics_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, count1, count2, alpha, grad_metrics, lengths1=None,
                          lengths2=None):

@@ -306,6 +306,40 @@ def set_metrics(d_gr, d_gg=None, d_rr=None):
     return out
 
 
+class _SlicedWasserstein(torch.autograd.Function):
+    """rf_sliced_wasserstein: the loss (b,) and, when an input needs it, both gradients from the same call."""
+
+    @staticmethod
+    def forward(ctx, xyz1, xyz2, directions, lengths1, lengths2):
+        if xyz1.requires_grad or xyz2.requires_grad:
+            loss, g1, g2 = _raw.sliced_wasserstein(xyz1, xyz2, directions, lengths1, lengths2, want_grad=True)
+            ctx.save_for_backward(g1, g2)
+            return loss
+        return _raw.sliced_wasserstein(xyz1, xyz2, directions, lengths1, lengths2)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        g1, g2 = ctx.saved_tensors
+        w = grad_loss[:, None, None]
+        return (w * g1 if ctx.needs_input_grad[0] else None, w * g2 if ctx.needs_input_grad[1] else None, None, None,
+                None)
+
+
+def sliced_wasserstein(pcd1, pcd2, nproj=128, directions=None, generator=None, lengths1=None, lengths2=None):
+    """The sliced Wasserstein distance SW_2^2 per sample, (b,): the mean over the directions of the 1-D optimal
+    transport cost between the projections of pcd1 (b, n, 3) and pcd2 (b, m, 3) -- a transport-type loss at
+    O(nproj n log n) that takes n != m and ragged batches exactly (lengths1 / lengths2: per-sample point counts; padded
+    rows get a zero gradient).  `directions` (nproj, 3) are used as given; None draws `nproj` unit vectors on the
+    inputs' device from `generator` (no host round trip).  Differentiable in pcd1 and pcd2: one fused call returns the
+    loss and both gradients, with ties in a projection going to the lower index (rf_sliced_wasserstein)."""
+    if directions is None:
+        if int(nproj) < 1:
+            raise ValueError("sliced_wasserstein: nproj must be positive")
+        directions = torch.randn(int(nproj), 3, device=pcd1.device, dtype=torch.float32, generator=generator)
+        directions = directions / directions.norm(dim=1, keepdim=True).clamp_min(1e-30)
+    return _SlicedWasserstein.apply(pcd1.contiguous(), pcd2.contiguous(), directions.detach(), lengths1, lengths2)
+
+
 def earth_mover(pcd1, pcd2, lengths1=None, lengths2=None):
     """mean over the batch of cost_i / #points (vv_recon.py:392-399).  lengths1 / lengths2: per-sample point counts of a
     ragged batch (rf_earth_mover_lengths): the mean of cost_i / lengths1[i], the ragged form of the division by
