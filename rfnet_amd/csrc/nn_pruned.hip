@@ -276,6 +276,16 @@ __device__ __forceinline__ float wave_max_f32(float v) {
 }
 #undef RFP_ROW
 
+// One step of the staging boxes' octet reduction: three minima and three maxima with a DPP operand, interleaved
+#define RFP_OCT6(CTL)                                                   \
+    "v_min_f32_dpp %0, %0, %0 " CTL " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_min_f32_dpp %1, %1, %1 " CTL " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_min_f32_dpp %2, %2, %2 " CTL " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_max_f32_dpp %3, %3, %3 " CTL " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_max_f32_dpp %4, %4, %4 " CTL " row_mask:0xf bank_mask:0xf\n\t" \
+    "v_max_f32_dpp %5, %5, %5 " CTL " row_mask:0xf bank_mask:0xf\n\t"
+#define RFP_BOX6 "+v"(l[0]), "+v"(l[1]), "+v"(l[2]), "+v"(hh[0]), "+v"(hh[1]), "+v"(hh[2])
+
 // LDS histogram increments on DEGENERATE clouds.  ds_add_u32 serialises over lanes that hit the same address: on a
 // cloud collapsed onto a few spots (the untrained RFNet's output: 16384 points on ~120 spots, 3-5 distinct bins among
 // the 64 consecutive points of a wave instruction, interleaved) the histogram phases take 2-5x their normal time
@@ -319,8 +329,9 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
         unsigned short zmap[HB];          // z bin -> rank in 0..511 (equal mass)
         unsigned char stripmap[16 * HB];  // (slab, y bin) -> strip of that slab (equal mass inside the slab), snaked
         float red[STPB / 64][6];
-        unsigned wsum[STPB / 64];
-        unsigned lowcnt[STPB / 64][3];
+        // row 0: the scan's wave totals; rows 1..3: per wave, its points of slices 0..2 below this workgroup's -- one table, so
+        // that the scan's ONE read per lane fetches both (lane 16 (q + 1) + w holds wave w's count of slice q)
+        unsigned wtab[4][STPB / 64];
         float frame[6];  // lo[3], scale[3]
         unsigned ncrowded;  // waves whose points crowd into few bins
         unsigned badw[STPB / 64];  // per wave: a NaN or infinite coordinate among its points (query_ball_boxes reads the cloud's flag)
@@ -333,8 +344,8 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
     auto &zmap = lds.zmap;
     auto &stripmap = lds.stripmap;
     auto &red = lds.red;
-    auto &wsum = lds.wsum;
-    auto &lowcnt = lds.lowcnt;
+    auto &wsum = lds.wtab[0];
+    unsigned(&lowcnt)[3][STPB / 64] = *(unsigned(*)[3][STPB / 64]) & lds.wtab[1];
     auto &frame = lds.frame;
     auto &ncrowded = lds.ncrowded;
     auto &badw = lds.badw;
@@ -563,7 +574,13 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
     __syncthreads();
     // (yhist's words are staging space again from phase 6 on; the histogram proper is the first NBINS words)
     const int ncol = SS * SS;
+#if RFP_SORT_SPLIT <= 2
+    // first column of slice q (H slices of equal column count): H is 1 or 2, the quotient a shift (a division by a runtime H is
+    // sixty scalar instructions in front of the keys, three times)
+    auto col_start = [&](int q) { return H > 1 ? (q * ncol + 1) >> 1 : q * ncol; };
+#else
     auto col_start = [&](int q) { return (q * ncol + H - 1) / H; };  // first column of slice q (H slices of equal column count)
+#endif
     const int cs1 = H > 1 ? col_start(1) : 0x7FFFFFFF;  // (uniform; the divisions stay out of the per-point loop)
 #if RFP_SORT_SPLIT > 2
     const int cs2 = H > 2 ? col_start(2) : 0x7FFFFFFF, cs3 = H > 3 ? col_start(3) : 0x7FFFFFFF;
@@ -623,7 +640,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
 #endif
     if (H > 1 && lane == 0) {
 #pragma unroll
-        for (int q = 0; q < 3; q++) lowcnt[wave][q] = q < half ? below[q] : 0u;
+        for (int q = 0; q < 3; q++) lowcnt[q][wave] = q < half ? below[q] : 0u;
     }
     __syncthreads();
 
@@ -631,6 +648,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
     // 4. exclusive scan of the 32768 bins: each wave owns 2048 consecutive bins, 8 steps of 256
     // (4 per lane, one ds_read_b128: consecutive lanes on consecutive banks)
     int cown = 0;  // points of this workgroup's half
+    int base = 0;  // first record of this workgroup's segment: every slice's segment is padded to a multiple of 64 records on its own
     {
         constexpr int STEPS = NBINS / (STPB / 64) / 256;  // 8
         const int steps = min(STEPS, (nb_local + 4095) / 4096);  // each wave owns steps * 256 consecutive bins
@@ -647,10 +665,21 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
         __syncthreads();
         // the 16 wave totals: ONE LDS read per lane and a wave scan (a loop over wsum[] is a chain of
         // dependent LDS latencies in every wave)
-        const unsigned wtot = lane < STPB / 64 ? wsum[lane] : 0u;
+        // (the same read brings the lower slices' counts in the lanes behind the 16 totals, 16 lanes per slice: the scan runs over
+        // them as well -- the sums of lanes 0..15 are not touched by the lanes behind them -- and a slice's count is the difference
+        // of two row ends.  Summed by a loop at the head of the staging it was 16 LDS reads in every thread of a second slice.)
+        const unsigned wtot = lane < (half + 1) * (STPB / 64) ? (&lds.wtab[0][0])[lane] : 0u;
         const unsigned wincl = wave_incl_scan(wtot);
         unsigned carry = (unsigned)__builtin_amdgcn_readlane((int)(wincl - wtot), __builtin_amdgcn_readfirstlane(wave));
         cown = __builtin_amdgcn_readlane((int)wincl, STPB / 64 - 1);
+        static_assert(STPB / 64 == 16 && RFP_SORT_SPLIT <= 4, "a row of the wave scan per slice");
+#pragma unroll
+        for (int q = 0; q < (RFP_SORT_SPLIT > 2 ? 3 : 1); q++) {
+            if (q < half) {  // (uniform)
+                const int c = __builtin_amdgcn_readlane((int)wincl, 16 * q + 31) - __builtin_amdgcn_readlane((int)wincl, 16 * q + 15);
+                base += (c + SB - 1) / SB * SB;
+            }
+        }
 #pragma unroll
         for (int it = 0; it < STEPS; it++) {
             if (it < steps) {  // uniform
@@ -684,12 +713,6 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
     // this workgroup's segment of the sorted set: records [base, base + seglen), of which the first
     // `cown` are points and the rest padding.  Half 0: [0, roundup(cown, 64)); half 1 (or the only
     // workgroup): from behind half 0's segment to the end of the set.
-    int base = 0;  // every slice's segment is padded to a multiple of 64 records on its own
-    for (int q = 0; q < half; q++) {
-        unsigned c = 0;
-        for (int w = 0; w < STPB / 64; w++) c += lowcnt[w][q];
-        base += ((int)c + SB - 1) / SB * SB;
-    }
     const int seglen = ((cown + SB - 1) / SB) * SB;  // the points and the padding of their last superblock
     // whole superblocks of padding behind the last segment (a split set is allocated one more than
     // it may need): written straight to memory, no staging round for them
@@ -733,6 +756,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
         // octets are complete and inside one wave).  Record (u + block + 4 half) % 8 of the half at step u: the two halves of a
         // block and blocks 8 apart would otherwise meet in the same banks.  (One thread per block left half the workgroup idle
         // behind a chain of 16 dependent-issue LDS reads: 3.8 k of the sort's 48 k cycles.)
+        const int sb0 = (base + h0) / SB;  // the round's first superblock
         // (a split half may hold up to HALF = 9216 records: 1152 half-blocks for 1024 threads -- a second trip for the first lanes)
 #pragma unroll 1
         for (int t2 = tid; t2 < cnt / BS * 2; t2 += STPB) {
@@ -748,30 +772,23 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
                     l[2] = bare_min(l[2], v.z); hh[2] = bare_max(hh[2], v.z);
                 }
             }
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                l[c] = bare_min(l[c], __shfl_xor(l[c], 1, 64));  // (results of min / max: never NaN)
-                hh[c] = bare_max(hh[c], __shfl_xor(hh[c], 1, 64));
-            }
-            const int gblk = (base + h0) / BS + blk;
+            // the octet's steps: lane ^ 1 and lane ^ 2 are quad permutations, and behind them every lane of a quad holds the quad's
+            // result, so the mirror of the row's half (lane 7 - i) stands in for lane ^ 4: minima and maxima with a DPP operand, six
+            // chains interleaved -- a step reads a register written five instructions earlier, one s_nop at the head covers them
+            // (five wait states: a v_cmpx in front of a DPP operand needs them; results of min / max: never NaN).  As __shfl_xor
+            // the three steps were 18 ds_bpermute_b32 in three dependent batches through the LDS pipe.
+            asm volatile("s_nop 4\n\t" RFP_OCT6("quad_perm:[1,0,3,2]") : RFP_BOX6);
             if (hf == 0) {
-                float *o = b16 + (size_t)(gblk >> 2) * B16F + (gblk & 3) * 6;
+                float *o = b16 + (size_t)sb0 * B16F + (size_t)blk * 6;  // (B16F = 4 blocks of 6)
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
                     o[c] = l[c];
                     o[3 + c] = hh[c];
                 }
             }
-#pragma unroll
-            for (int x = 2; x <= 4; x <<= 1) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    l[c] = bare_min(l[c], __shfl_xor(l[c], x, 64));
-                    hh[c] = bare_max(hh[c], __shfl_xor(hh[c], x, 64));
-                }
-            }
-            if ((gblk & 3) == 0 && hf == 0) {
-                float *o64 = b64 + (size_t)(gblk >> 2) * B64F;
+            asm volatile("s_nop 4\n\t" RFP_OCT6("quad_perm:[2,3,0,1]") RFP_OCT6("row_half_mirror") : RFP_BOX6);
+            if ((t2 & 7) == 0) {
+                float *o64 = b64 + (size_t)(sb0 + (blk >> 2)) * B64F;
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
                     o64[c] = l[c];
@@ -799,6 +816,9 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
         stamp();
     }
 }
+
+#undef RFP_OCT6
+#undef RFP_BOX6
 
 // REG: the cloud (n <= RPT * STPB points) is loaded once into registers -- every later phase is
 // LDS and ALU work only; otherwise each phase re-reads the points (L2-resident) from `src`.
