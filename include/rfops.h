@@ -330,6 +330,75 @@ int rf_sliced_wasserstein(int b, int n, int m, int nproj, const float *xyz1, con
                           const int *len2, const float *dirs, float *loss, float *grad1, float *grad2, void *workspace,
                           size_t workspace_bytes, rf_stream_t stream);
 
+/* ---- the exact earth mover's distance: optimal assignment with a certificate and gradients -- */
+/* The one-to-one assignment of minimal total distance between two clouds of EQUAL counts, by a deterministic Jacobi
+ * auction with eps-scaling on an integer cost grid: a pure function of its inputs with a machine-checkable optimality
+ * certificate (a dual lower bound in exact integers).  xyz1 (b, n, 3) are the persons, xyz2 (b, n, 3) the objects, both
+ * fp32; 1 <= n <= RF_EA_MAX_POINTS.  len: device int32 (b) or NULL, shared by both clouds, with rf_nn_distance_lengths'
+ * conventions -- read and clamped into [1, n] by the kernel; L below is the clamped count, rows behind it never reach a
+ * result.  max_rounds: 0 means 64 L + 1024.  No host synchronisation, one launch: a call can be captured in a HIP graph.
+ * One workgroup works on a sample: spreading a sample over several workgroups, n above RF_EA_MAX_POINTS and unequal
+ * counts (n != m) are out of scope.  Per sample:
+ *
+ *   1. Grid.  lo / hi per axis over the 2 L valid points in fp32, E = the largest of the three hi - lo.  E NaN or
+ *      infinite (any non-finite valid coordinate, or an extent that overflows): status RF_EA_NONFINITE, match12 =
+ *      match21 = the identity, the numbers unspecified, rounds = bids = k = 0; the other samples are unaffected and no
+ *      memory access depends on a data value.  Otherwise frexpf(E) = (., ex) with ex = 0 for E = 0,
+ *      k = 19 - max(ex, -100) and S = 2^k.
+ *   2. Costs.  d_ij = sqrtf(((x1 - x2)^2 + (y1 - y2)^2) + (z1 - z2)^2), unfused fp32 with a correctly rounded square
+ *      root; c_ij = (int)rintf(fminf(d_ij S, 2^20)).  The product is exact and c_ij < 2^20 (the fminf acts only where the
+ *      squares overflow fp32, E >= 2^63: memory-safe and terminating there, the numbers unspecified).  Costs are
+ *      recomputed on the fly: nothing of size n^2 is stored anywhere.
+ *   3. Phases.  eps = 2^17, 2^14, 2^11, 2^8, 2^5, 2^2, 1: always seven.  Prices p_j are int32, start at 0 and carry over;
+ *      every phase starts with all persons unassigned and all objects free.
+ *   4. One round works on the prices and the unassigned set U as they are at its start.  Every i in U forms
+ *      v_j = c_ij + p_j; j* minimises (v_j, (j - i) mod L) lexicographically (the rotating tie rule keeps collapsed or
+ *      duplicated clouds from costing L rounds per phase); w = min_{j != j*} v_j (v_j* when L = 1); the bid is
+ *      beta_i = p_j* + (w - v_j*) + eps.  Every object that received bids goes to the highest beta, ties to the lowest i;
+ *      its price becomes that beta and its previous owner becomes unassigned.  A phase ends when U is empty; `rounds`
+ *      counts rounds over all phases, `bids` the bids (saturating at 2^31 - 1).
+ *   5. Cap.  If rounds reaches max_rounds while someone is unassigned: status RF_EA_CAPPED, and the unassigned persons
+ *      in ascending i take the free objects in ascending j -- the result is still a permutation.
+ *   6. Prices and values stay below 2^26 (emd_assign.hip's header gives the argument), so int32 suffices.
+ *
+ * Outputs.  match12 (b, n), match21 (b, n) int32: inverse permutations of [0, L).  dist (b, n): the unquantised
+ * d_{i, match12[i]}.  Slots behind L are zeros (index 0, +0.0f).  val (b, 3): cost = sum_i dist_i summed in double in
+ * index order and rounded once; gap = (P - D) / S; bound = (P - D + L) / S.  cert (b, 2) long long:
+ * P = sum_i c_{i, match12[i]} and D = sum_i min_j (c_ij + p_j) - sum_j p_j with the final prices and one more sweep.
+ * info (b, 4) int32: status, rounds, bids, k.  The workspace receives the final prices, int32 (b, n), valid slots only:
+ * with them anyone can recompute D.
+ *
+ * Guarantees:
+ *   - D <= OPT_int <= P always, for any prices (weak duality), OPT_int the optimum on the integer grid.
+ *   - With status RF_EA_OK, P - D <= L: every phase ends in eps-complementary slackness and the last eps is 1.
+ *   - In true distances cost - EMD <= bound up to the fp32 rounding of cost: the L / S pays for the quantisation (at
+ *     most 1 / (2 S) per pair on either side).
+ *   - Two calls return identical bits; sample i's outputs are those of the call on [i : i + 1].  No float atomics (the
+ *     only atomics are a 64-bit integer maximum and a list counter in LDS, and no result depends on their order).
+ *   - The kernel ends on any input: every loop is bounded by a count or by max_rounds.
+ *
+ * rf_emd_assign_grad: the gradients of cost under the fixed assignment, scaled by gcost (b).  grad1[i] = gcost *
+ * ((x_i - y_a(i)) / d_i), a = match12, d recomputed as above: exactly 0 where d_i == 0 and exactly +0 behind L;
+ * grad2[j] is the negative of its partner's term, read through match21.  The assignment is a permutation, so there are no
+ * atomics; an index outside [0, L) is clamped into it.  grad1, grad2 (b, n, 3) fully overwritten.
+ *
+ * Argument rules, all checked before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for
+ * n < 1, n above RF_EA_MAX_POINTS, b above 65535, a NULL tensor, a tensor or count array not 4-byte aligned (cert: 8
+ * bytes), a workspace that is NULL or not 16-byte aligned, a negative max_rounds; RF_EWORKSPACE for a workspace smaller
+ * than rf_emd_assign_workspace_bytes (4 b n rounded up to 256 bytes; 0 for non-positive or unsupported sizes).  All
+ * index arithmetic is in size_t.  rf_emd_assign_supported(n): 1 for 1 <= n <= RF_EA_MAX_POINTS, else 0. */
+#define RF_EA_MAX_POINTS 4096
+#define RF_EA_OK 0
+#define RF_EA_CAPPED 1
+#define RF_EA_NONFINITE 2
+int rf_emd_assign_supported(int n);
+size_t rf_emd_assign_workspace_bytes(int b, int n);
+int rf_emd_assign(int b, int n, const float *xyz1, const float *xyz2, const int *len, int max_rounds, int *match12,
+                  int *match21, float *dist, float *val, long long *cert, int *info, void *workspace,
+                  size_t workspace_bytes, rf_stream_t stream);
+int rf_emd_assign_grad(int b, int n, const float *xyz1, const float *xyz2, const int *match12, const int *match21,
+                       const int *len, const float *gcost, float *grad1, float *grad2, rf_stream_t stream);
+
 /* ----------------------------------------------------------- EMD (pc_distance) ---------- */
 /* Replaces approxmatchLauncher(b,n,m,xyz1,xyz2,match,temp) (pc_distance/tf_approxmatch.cpp:141,
  * tf_approxmatch.cu:180-182).  xyz1 (b,n,3) "dataset", xyz2 (b,m,3) "query" (b <= 65535 for

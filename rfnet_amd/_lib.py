@@ -65,6 +65,10 @@ SIGNATURES = {
     "rf_chamfer_cross": (_i, [_i, _i, _i, _i] + [_vp] * 6 + [_sz, _vp]),
     "rf_sliced_wasserstein_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "rf_sliced_wasserstein": (_i, [_i, _i, _i, _i] + [_vp] * 9 + [_sz, _vp]),
+    "rf_emd_assign_supported": (_i, [_i]),
+    "rf_emd_assign_workspace_bytes": (_sz, [_i, _i]),
+    "rf_emd_assign": (_i, [_i, _i, _vp, _vp, _vp, _i] + [_vp] * 7 + [_sz, _vp]),
+    "rf_emd_assign_grad": (_i, [_i, _i] + [_vp] * 9),
     "rf_merge_layer_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_merge_layer": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_merge_layer_grad": (_i, [_i, _i, _i] + [_vp] * 9),

@@ -533,6 +533,78 @@ def sliced_wasserstein(xyz1, xyz2, directions, lengths1=None, lengths2=None, wan
     return st.give(loss)
 
 
+EA_MAX_POINTS = 4096  # RF_EA_MAX_POINTS (include/rfops.h)
+EA_OK, EA_CAPPED, EA_NONFINITE = 0, 1, 2  # RF_EA_* status values
+EA_TPB, EA_WAVE = 1024, 64  # emd_assign.hip's tiles: threads of the one workgroup per sample; lanes a bidder's scan strides by
+
+
+def _ea_inputs(st, xyz1, xyz2, lengths, what):
+    a, b_ = st.take(xyz1, F32), st.take(xyz2, F32)
+    if a.dim() != 3 or a.shape[2] != 3:
+        raise H.invalid(f"{what} requires xyz1 be of shape (batch,#points,3)")
+    if b_.dim() != 3 or b_.shape[2] != 3:
+        raise H.invalid(f"{what} requires xyz2 be of shape (batch,#points,3)")
+    if b_.shape[0] != a.shape[0]:
+        raise H.invalid(f"{what} expects xyz1 and xyz2 have same batch size")
+    if b_.shape[1] != a.shape[1]:
+        raise H.invalid(f"{what} expects xyz1 and xyz2 have same number of points")
+    b, n = a.shape[0], a.shape[1]
+    if b > 0 and n < 1:
+        raise H.invalid(f"{what} requires at least one point per cloud")
+    if n > EA_MAX_POINTS:
+        raise H.invalid(f"{what} takes clouds of up to {EA_MAX_POINTS} points")
+    if b > 65535:
+        raise H.invalid(f"{what} takes up to 65535 samples per call: split the batch")
+    return a, b_, _check_lengths(lengths, b, n, "lengths")
+
+
+@H.on_input_device
+def emd_assign(xyz1, xyz2, lengths=None, max_rounds=0):
+    """rf_emd_assign: the optimal one-to-one assignment of xyz1 (b, n, 3) (persons) to xyz2 (b, n, 3) (objects) by the
+    deterministic integer auction of include/rfops.h -> (match12 (b, n) int32, match21 (b, n) int32, dist (b, n),
+    val (b, 3) = cost / gap / bound, cert (b, 2) int64 = P / D, info (b, 4) int32 = status / rounds / bids / k).
+    `lengths` (b,): per-sample point counts shared by both clouds (slots behind a count are zeros); max_rounds = 0:
+    64 L + 1024 rounds.  n <= 4096."""
+    st = H.Staged()
+    a, b_, ln = _ea_inputs(st, xyz1, xyz2, lengths, "emd_assign")
+    max_rounds = int(max_rounds)
+    if max_rounds < 0:
+        raise H.invalid("emd_assign expects max_rounds >= 0 (0: 64 * #points + 1024)")
+    b, n = a.shape[0], a.shape[1]
+    dev = st.device_()
+    a, b_ = st.up(a, b_)
+    ln = _lengths_up(ln, dev, n)
+    m12, m21, dist = H.empty((b, n), I32, dev), H.empty((b, n), I32, dev), H.empty((b, n), F32, dev)
+    val, cert, info = H.empty((b, 3), F32, dev), H.empty((b, 2), torch.int64, dev), H.empty((b, 4), I32, dev)
+    if b > 0:
+        ws, wsz = H.workspace(lib.rf_emd_assign_workspace_bytes(b, n), dev, "emd_assign")
+        check(lib.rf_emd_assign(b, n, H.ptr(a), H.ptr(b_), H.ptr(ln), max_rounds, H.ptr(m12), H.ptr(m21), H.ptr(dist),
+                                H.ptr(val), H.ptr(cert), H.ptr(info), H.ptr(ws), wsz, H.stream(dev)), "rf_emd_assign")
+    return tuple(st.give(t) for t in (m12, m21, dist, val, cert, info))
+
+
+@H.on_input_device
+def emd_assign_grad(xyz1, xyz2, match12, match21, grad_cost, lengths=None):
+    """rf_emd_assign_grad -> (grad_xyz1, grad_xyz2), both (b, n, 3): the gradients of emd_assign's cost under the
+    fixed assignment, scaled by grad_cost (b,); exactly 0 where a pair's distance is 0 and behind a count."""
+    st = H.Staged()
+    a, b_, ln = _ea_inputs(st, xyz1, xyz2, lengths, "emd_assign_grad")
+    b, n = a.shape[0], a.shape[1]
+    m12, m21, gc = st.take(match12, I32), st.take(match21, I32), st.take(grad_cost, F32)
+    if tuple(m12.shape) != (b, n) or tuple(m21.shape) != (b, n):
+        raise H.invalid("emd_assign_grad requires match12 and match21 be of shape (batch,#points)")
+    if tuple(gc.shape) != (b,):
+        raise H.invalid("emd_assign_grad requires grad_cost be of shape (batch,)")
+    dev = st.device_()
+    a, b_, m12, m21, gc = st.up(a, b_, m12, m21, gc)
+    ln = _lengths_up(ln, dev, n)
+    g1, g2 = H.empty((b, n, 3), F32, dev), H.empty((b, n, 3), F32, dev)
+    if b > 0:
+        check(lib.rf_emd_assign_grad(b, n, H.ptr(a), H.ptr(b_), H.ptr(m12), H.ptr(m21), H.ptr(ln), H.ptr(gc), H.ptr(g1),
+                                     H.ptr(g2), H.stream(dev)), "rf_emd_assign_grad")
+    return st.give(g1), st.give(g2)
+
+
 @H.on_input_device
 def chamfer_metrics_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, count1, count2, alpha, grad_metrics, lengths1=None,
                          lengths2=None):

@@ -340,6 +340,52 @@ def sliced_wasserstein(pcd1, pcd2, nproj=128, directions=None, generator=None, l
     return _SlicedWasserstein.apply(pcd1.contiguous(), pcd2.contiguous(), directions.detach(), lengths1, lengths2)
 
 
+class _EmdAssign(torch.autograd.Function):
+    """rf_emd_assign / rf_emd_assign_grad: the exact assignment; only the cost (b,) carries a gradient, under the
+    fixed assignment."""
+
+    @staticmethod
+    def forward(ctx, xyz1, xyz2, lengths, max_rounds):
+        m12, m21, dist, val, cert, info = _raw.emd_assign(xyz1, xyz2, lengths, max_rounds)
+        ctx.save_for_backward(xyz1, xyz2, m12, m21)
+        ctx.lengths = lengths
+        ctx.mark_non_differentiable(m12, m21, dist, val, cert, info)
+        return val[:, 0].clone(), m12, m21, dist, val, cert, info
+
+    @staticmethod
+    def backward(ctx, grad_cost, *_):
+        xyz1, xyz2, m12, m21 = ctx.saved_tensors
+        g1, g2 = _raw.emd_assign_grad(xyz1, xyz2, m12, m21, grad_cost.contiguous(), ctx.lengths)
+        return g1, g2, None, None
+
+
+def emd_assignment(pcd1, pcd2, lengths=None, max_rounds=0):
+    """The earth mover's distance itself: the one-to-one assignment of pcd1 (b, n, 3) to pcd2 (b, n, 3) of minimal total
+    distance, n <= 4096, by a deterministic integer auction (rf_emd_assign).  Returns a dict of per-sample tensors:
+      match12, match21  (b, n) int32, inverse permutations     dist  (b, n) the distance of every pair
+      cost   (b,) the sum of dist -- differentiable in pcd1 and pcd2 under the fixed assignment
+      gap    (b,) the certified distance of the integer cost from the integer optimum, in units of distance
+      bound  (b,) cost - EMD <= bound (gap plus the price of the quantisation)
+      status (b,) 0 ok, 1 stopped at max_rounds (still a permutation; gap and bound still hold), 2 non-finite input
+      rounds (b,) auction rounds
+    plus "cert" (b, 2) int64 (P, D: the exact integers behind gap) and "info" (b, 4).  lengths (b,): per-sample point
+    counts shared by both clouds; slots behind a count are zeros and get a zero gradient."""
+    cost, m12, m21, dist, val, cert, info = _EmdAssign.apply(pcd1.contiguous(), pcd2.contiguous(), lengths, max_rounds)
+    return {"match12": m12, "match21": m21, "dist": dist, "cost": cost, "gap": val[:, 1], "bound": val[:, 2],
+            "status": info[:, 0], "rounds": info[:, 1], "cert": cert, "info": info}
+
+
+def emd_exact(pcd1, pcd2, lengths=None):
+    """The batch mean of cost_i / #points of the exact assignment (emd_assignment): earth_mover's normalisation, so the
+    two numbers compare directly.  With lengths: cost_i / lengths[i]."""
+    cost = emd_assignment(pcd1, pcd2, lengths=lengths)["cost"]
+    b, n = pcd1.shape[0], pcd1.shape[1]
+    ln = _raw._check_lengths(lengths, b, n, "lengths")
+    if ln is None:
+        return (cost / float(n)).mean()
+    return (cost / ln.to(device=cost.device, dtype=cost.dtype).clamp(1, n)).mean()
+
+
 def earth_mover(pcd1, pcd2, lengths1=None, lengths2=None):
     """mean over the batch of cost_i / #points (vv_recon.py:392-399).  lengths1 / lengths2: per-sample point counts of a
     ragged batch (rf_earth_mover_lengths): the mean of cost_i / lengths1[i], the ragged form of the division by
