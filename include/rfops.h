@@ -330,6 +330,66 @@ int rf_sliced_wasserstein(int b, int n, int m, int nproj, const float *xyz1, con
                           const int *len2, const float *dirs, float *loss, float *grad1, float *grad2, void *workspace,
                           size_t workspace_bytes, rf_stream_t stream);
 
+/* ---- the Sinkhorn divergence of two clouds: debiased entropic optimal transport, with gradients -- */
+/* A transport-type loss that is differentiable, takes unequal and ragged counts at every size the other entries take, and
+ * has a stated relation to optimal transport: S_eps(a, a) = 0, S_eps >= 0, and S_eps goes to the transport cost as eps -> 0
+ * and to an energy distance as eps -> infinity.  xyz1 (b, n, 3), xyz2 (b, m, 3) fp32; len1 / len2: device int32 (b) or NULL
+ * with rf_nn_distance_lengths' conventions -- read and clamped into [1, n] / [1, m] by the kernels, rows behind a count
+ * never reach a result.  p: 1 or 2.  eps: a HOST array of T positive finite floats, 1 <= T <= RF_SK_MAX_ITERS, the
+ * regularisation of every step (an annealing schedule ends at blur^p); it is read at call time, so a captured graph replays
+ * the schedule it was captured with.  No host synchronisation, T + 2 launches on `stream`: a call can be captured.
+ *
+ * With L1, L2 the clamped counts, uniform weights a_i = 1 / L1, b_j = 1 / L2, and
+ *   C(x, y) = sqrt(((dx dx) + (dy dy)) + (dz dz)) for p = 1 (unfused; the root from v_sqrt_f32, 1 ulp),  0.5f d^2 for p = 2
+ *   softmin_e(C, h, w)_i = -e log sum_j w_j exp((h_j - C_ij) / e)
+ * the iteration is Jacobi and averaged, from zero potentials: for t = 0 ... T - 1, e = eps[t], all four from the OLD values
+ *   f  <- (f  + softmin_e(C_xy, g,  b)) / 2        g  <- (g  + softmin_e(C_yx, f,  a)) / 2
+ *   fx <- (fx + softmin_e(C_xx, fx, a)) / 2        gy <- (gy + softmin_e(C_yy, gy, b)) / 2
+ * and the final step at e = eps[T - 1] is not averaged:
+ *   f1 = softmin_e(C_xy, g, b)   g1 = softmin_e(C_yx, f, a)   fx1 = softmin_e(C_xx, fx, a)   gy1 = softmin_e(C_yy, gy, b)
+ *
+ *   loss[b]  = sum_i a_i (f1_i - fx1_i) + sum_j b_j (g1_j - gy1_j): the differences added in double, a thread taking every
+ *              1024th row in ascending order, the threads of a wave by a butterfly, the waves in order; one rounding to fp32
+ *   pot[b]   (n + m): f1 then g1, slots behind a count +0
+ *   delta[b] = max(max_i |f1_i - f_i|, max_j |g1_j - g_j|): how far the cross potentials still moved in the last step, in
+ *              units of cost -- the convergence read-out (NaN when loss is NaN)
+ *   grad1 (b, n, 3), grad2 (b, m, 3), both given or both NULL: the gradient of loss through the final step only, the
+ *              potentials before it and the column arguments held fixed:
+ *                grad1_i = a_i (sum_j pi_ij d1C(x_i, y_j) - sum_k pix_ik d1C(x_i, x_k)),
+ *                pi_ij = b_j exp((f1_i + g_j - C_ij) / e) -- the rows sum to 1 by construction: the numerators are carried
+ *              beside the final soft-min's running sum and divided by it once -- pix the same with fx1, fx, a; grad2 the
+ *              mirror image.  d1C = (x - y) / C for p = 1 and 0 where C = 0 (as rf_emd_assign_grad), x - y for p = 2.  Rows
+ *              behind a count are +0.
+ * The exponent is formed as (h_j - C_ij) (log2(e) / eps) -- the difference first, which is where the terms that matter
+ * cancel -- and the sums are base 2 (v_exp_f32, v_log_f32) under a running maximum renewed once per 8 columns.
+ *
+ * Guarantees:
+ *   - Purity: a sample's numbers are a function of its own valid points, p and the schedule.  Two calls return identical
+ *     bits; sample i is bit for bit the call on [i : i + 1]; a ragged call is bit for bit the call on the sliced clouds.  The
+ *     column structure of every sum is a function of the valid column count L alone: tiles of 256 columns from column 0,
+ *     ceil(ceil(L / 256) / 4) consecutive tiles to a chunk, the chunks merged in ascending order -- whichever workgroup
+ *     computed them.  The loss-only form returns the bits of the form with gradients.
+ *   - Self distance: with xyz1 == xyz2 and len1 == len2 the loss is +0 and both gradients are +0 in every slot: the four
+ *     problems run through one code path.
+ *   - Finite in, finite out, as long as C log2(e) / eps is finite in fp32 for the largest cost (C / eps below 2e38).
+ *   - Memory safety: every loop bound is a count.  A non-finite coordinate in a valid row gives NaN in that sample only.
+ *
+ * Workspace, each part rounded up to 256 bytes, with r = 2 b (n + m):  2 * 4 r  potentials, double-buffered  + 2 * 32 r
+ * (max, sum) partials of every (row, chunk), double-buffered  + 48 r  the gradient numerators of the final step.
+ *
+ * Argument rules, all checked before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for n or
+ * m outside 1 ... RF_SK_MAX_POINTS, b above 65535, p not 1 or 2, T outside 1 ... RF_SK_MAX_ITERS, a NULL eps, an eps[t]
+ * that is not positive and finite, a NULL xyz1 / xyz2 / loss / pot / delta, exactly one of grad1 / grad2 given, a tensor
+ * or count array not 4-byte aligned, a workspace that is NULL or not 16-byte aligned; RF_EWORKSPACE for a workspace smaller
+ * than rf_sinkhorn_workspace_bytes (0 for non-positive or unsupported sizes, positive otherwise).  All index arithmetic is
+ * in size_t. */
+#define RF_SK_MAX_POINTS 65536
+#define RF_SK_MAX_ITERS 256
+size_t rf_sinkhorn_workspace_bytes(int b, int n, int m);
+int rf_sinkhorn(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2, int p,
+                const float *eps, int T, float *loss, float *pot, float *delta, float *grad1, float *grad2, void *workspace,
+                size_t workspace_bytes, rf_stream_t stream);
+
 /* ---- the exact earth mover's distance: optimal assignment with a certificate and gradients -- */
 /* The one-to-one assignment of minimal total distance between two clouds of EQUAL counts, by a deterministic Jacobi
  * auction with eps-scaling on an integer cost grid: a pure function of its inputs with a machine-checkable optimality

@@ -533,6 +533,64 @@ def sliced_wasserstein(xyz1, xyz2, directions, lengths1=None, lengths2=None, wan
     return st.give(loss)
 
 
+SK_MAX_POINTS, SK_MAX_ITERS = 65536, 256  # RF_SK_MAX_POINTS, RF_SK_MAX_ITERS (include/rfops.h)
+SK_COL_TILE, SK_NSPLIT = 256, 4  # sinkhorn.hip's column tile and the chunks a row's columns are spread over at most
+
+
+def _sk_schedule(eps):
+    """The eps schedule of rf_sinkhorn as a host float32 array, checked: 1 ... SK_MAX_ITERS positive finite values."""
+    if isinstance(eps, torch.Tensor):
+        if eps.is_cuda:
+            raise H.invalid("sinkhorn expects eps on the host: the schedule is read when the call is made")
+        eps = eps.detach().numpy()
+    e = np.ascontiguousarray(np.asarray(eps, np.float64).reshape(-1)).astype(np.float32)
+    if e.size < 1 or e.size > SK_MAX_ITERS:
+        raise H.invalid(f"sinkhorn expects an eps schedule of 1 to {SK_MAX_ITERS} steps")
+    if not (np.isfinite(e).all() and (e > 0).all()):
+        raise H.invalid("sinkhorn expects every eps be positive and finite (in float32)")
+    return e
+
+
+@H.on_input_device
+def sinkhorn(xyz1, xyz2, eps, p=1, lengths1=None, lengths2=None, want_grad=False):
+    """rf_sinkhorn: the Sinkhorn divergence of xyz1 (b, n, 3) and xyz2 (b, m, 3) for the cost |x - y| (p = 1) or
+    |x - y|^2 / 2 (p = 2) along the host schedule `eps` -> (loss (b,), pot (b, n + m) = the final potentials f1 | g1,
+    delta (b,) = how far they moved in the last step), with `want_grad` also (grad_xyz1, grad_xyz2) of the same call.
+    n != m and per-sample counts lengths1 / lengths2 are exact; slots and rows behind a count are +0."""
+    st = H.Staged()
+    a, b_ = st.take(xyz1, F32), st.take(xyz2, F32)
+    if a.dim() != 3 or a.shape[2] != 3:
+        raise H.invalid("sinkhorn requires xyz1 be of shape (batch,#points,3)")
+    if b_.dim() != 3 or b_.shape[2] != 3:
+        raise H.invalid("sinkhorn requires xyz2 be of shape (batch,#points,3)")
+    if b_.shape[0] != a.shape[0]:
+        raise H.invalid("sinkhorn expects xyz1 and xyz2 have same batch size")
+    if p not in (1, 2):
+        raise H.invalid("sinkhorn expects p be 1 or 2")
+    e = _sk_schedule(eps)
+    b, n, m = a.shape[0], a.shape[1], b_.shape[1]
+    if b > 0 and (n < 1 or m < 1):
+        raise H.invalid("sinkhorn requires at least one point per cloud")
+    if n > SK_MAX_POINTS or m > SK_MAX_POINTS:
+        raise H.invalid(f"sinkhorn takes clouds of up to {SK_MAX_POINTS} points")
+    if b > 65535:
+        raise H.invalid("sinkhorn takes up to 65535 samples per call: split the batch")
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, b_ = st.up(a, b_)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    loss, pot, delta = H.empty((b,), F32, dev), H.empty((b, n + m), F32, dev), H.empty((b,), F32, dev)
+    g1 = H.empty((b, n, 3), F32, dev) if want_grad else None
+    g2 = H.empty((b, m, 3), F32, dev) if want_grad else None
+    if b > 0:
+        ws, wsz = H.workspace(lib.rf_sinkhorn_workspace_bytes(b, n, m), dev, "sinkhorn")
+        check(lib.rf_sinkhorn(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), int(p), e.ctypes.data, int(e.size),
+                              H.ptr(loss), H.ptr(pot), H.ptr(delta), H.ptr(g1), H.ptr(g2), H.ptr(ws), wsz, H.stream(dev)),
+              "rf_sinkhorn")
+    out = (loss, pot, delta) + ((g1, g2) if want_grad else ())
+    return tuple(st.give(t) for t in out)
+
+
 EA_MAX_POINTS = 4096  # RF_EA_MAX_POINTS (include/rfops.h)
 EA_OK, EA_CAPPED, EA_NONFINITE = 0, 1, 2  # RF_EA_* status values
 EA_TPB, EA_WAVE = 1024, 64  # emd_assign.hip's tiles: threads of the one workgroup per sample; lanes a bidder's scan strides by

@@ -340,6 +340,61 @@ def sliced_wasserstein(pcd1, pcd2, nproj=128, directions=None, generator=None, l
     return _SlicedWasserstein.apply(pcd1.contiguous(), pcd2.contiguous(), directions.detach(), lengths1, lengths2)
 
 
+def sinkhorn_schedule(p=1, blur=0.05, scaling=0.5, diameter=2.0, extra=0):
+    """The annealed eps schedule of sinkhorn_divergence, on the host: diameter^p, then down by factors scaling^p while
+    above blur^p, then 1 + extra steps at blur^p.  The default diameter covers clouds in the unit ball; it is a number the
+    caller states, never read from the device.  (rf_sinkhorn takes up to 256 steps; the helper itself has no cap.)"""
+    p, blur, scaling, diameter, extra = int(p), float(blur), float(scaling), float(diameter), int(extra)
+    if p not in (1, 2):
+        raise ValueError("sinkhorn_schedule: p must be 1 or 2")
+    if not (blur > 0.0 and diameter > 0.0 and 0.0 < scaling < 1.0 and extra >= 0):
+        raise ValueError("sinkhorn_schedule: expects blur > 0, diameter > 0, 0 < scaling < 1, extra >= 0")
+    eps, s = [], diameter
+    while s > blur:
+        eps.append(s ** p)
+        s *= scaling
+    return eps + [blur ** p] * (1 + extra)
+
+
+class _Sinkhorn(torch.autograd.Function):
+    """rf_sinkhorn: the loss (b,) with pot and delta and, when an input needs it, both gradients from the same call."""
+
+    @staticmethod
+    def forward(ctx, xyz1, xyz2, eps, p, lengths1, lengths2):
+        if xyz1.requires_grad or xyz2.requires_grad:
+            loss, pot, delta, g1, g2 = _raw.sinkhorn(xyz1, xyz2, eps, p, lengths1, lengths2, want_grad=True)
+            ctx.save_for_backward(g1, g2)
+        else:
+            loss, pot, delta = _raw.sinkhorn(xyz1, xyz2, eps, p, lengths1, lengths2)
+        ctx.mark_non_differentiable(pot, delta)
+        return loss, pot, delta
+
+    @staticmethod
+    def backward(ctx, grad_loss, *_):
+        g1, g2 = ctx.saved_tensors
+        w = grad_loss[:, None, None]
+        return (w * g1 if ctx.needs_input_grad[0] else None, w * g2 if ctx.needs_input_grad[1] else None, None, None,
+                None, None)
+
+
+def sinkhorn_divergence(pcd1, pcd2, p=1, blur=0.05, scaling=0.5, diameter=2.0, extra=0, eps=None, lengths1=None,
+                        lengths2=None, return_info=False):
+    """The Sinkhorn divergence S_eps per sample, (b,): debiased entropy-regularised optimal transport between pcd1
+    (b, n, 3) and pcd2 (b, m, 3) with uniform weights, for the cost |x - y| (p = 1) or |x - y|^2 / 2 (p = 2).  S(a, a) = 0,
+    S >= 0; it approaches the transport cost as blur -> 0.  The regularisation is annealed along
+    sinkhorn_schedule(p, blur, scaling, diameter, extra), or along `eps` (a host sequence) when given.  n != m and ragged
+    batches (lengths1 / lengths2: per-sample point counts) are exact; padded rows get a zero gradient.  Differentiable in
+    pcd1 and pcd2 through the last step, the potentials before it held fixed: one fused call returns the loss and both
+    gradients (rf_sinkhorn).  return_info: also {"pot": (b, n + m) the final potentials f | g, "delta": (b,) how far they
+    moved in the last step, in units of cost}."""
+    if eps is None:
+        eps = sinkhorn_schedule(p, blur, scaling, diameter, extra)
+    loss, pot, delta = _Sinkhorn.apply(pcd1.contiguous(), pcd2.contiguous(), eps, p, lengths1, lengths2)
+    if return_info:
+        return loss, {"pot": pot, "delta": delta}
+    return loss
+
+
 class _EmdAssign(torch.autograd.Function):
     """rf_emd_assign / rf_emd_assign_grad: the exact assignment; only the cost (b,) carries a gradient, under the
     fixed assignment."""
