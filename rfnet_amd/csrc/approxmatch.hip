@@ -71,11 +71,6 @@ struct AmInit {
 };
 // Ragged batches (rf_approxmatch_lengths): sample bi uses the first len[bi] points of its cloud; a NULL array means all n, and a
 // device value outside [1, n] is clamped into it (rf_nn_distance_lengths' rule), so no kernel reads past the tensors.
-__device__ __forceinline__ int am_len(const int *__restrict__ len, int bi, int n) {
-    if (!len) return n;
-    const int v = len[bi];
-    return v < 1 ? 1 : (v > n ? n : v);
-}
 // the reference's multipliers (am_multipliers: multiL = am_multi(n, m), multiR = am_multi(m, n)) from a sample's own counts
 __device__ __forceinline__ float am_multi(int self, int other) { return self >= other ? 1.f : (float)(other / self); }
 constexpr int AI_TPB = 1024;
@@ -88,7 +83,7 @@ __global__ __launch_bounds__(AI_TPB) void am_init_kernel(AmInit a) {
     const int npts = c ? a.npts[1] : a.npts[0], npad = c ? a.npad[1] : a.npad[0];
     int nval = npts;  // the points of this sample that are real (LEN: its count)
     if (LEN) {
-        const int l1 = am_len(a.len[0], bi, a.npts[0]), l2 = am_len(a.len[1], bi, a.npts[1]);
+        const int l1 = rf::ragged_count(a.len[0], bi, a.npts[0]), l2 = rf::ragged_count(a.len[1], bi, a.npts[1]);
         a.fill[0] = am_multi(l1, l2), a.fill[1] = am_multi(l2, l1);
         nval = c ? l2 : l1;
     }
@@ -167,7 +162,7 @@ __global__ __launch_bounds__(1024) void am_rowk_kernel(
     const int seg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr bool HAS_P1 = P1 != 0;
     const int nseg = blockDim.x >> 6;
-    const int nrow = LEN ? am_len(len1, bi, n) : n;
+    const int nrow = LEN ? rf::ragged_count(len1, bi, n) : n;
     if (LEN && bx * 64 * RPT >= nrow) return;  // (uniform) every row of the workgroup lies beyond the sample's count
     const float *__restrict__ A = xyz1 + (size_t)bi * n * 3;
     float x1[RPT], y1[RPT], z1[RPT], rl[RPT], rem0[RPT], acc3[RPT], acc1[RPT];
@@ -194,7 +189,7 @@ __global__ __launch_bounds__(1024) void am_rowk_kernel(
         c0 = min(seg * slen, cnt);
         c1 = min(c0 + slen, cnt);
     }
-    if (LEN) c1 = min(c1, max(c0, (am_len(len2, bi, nseg * seglen) + SUB - 1) / SUB * SUB));  // (uniform; nseg * seglen = mpad)
+    if (LEN) c1 = min(c1, max(c0, (rf::ragged_count(len2, bi, nseg * seglen) + SUB - 1) / SUB * SUB));  // (uniform; nseg * seglen = mpad)
     // one column (its coordinates and scalars wave-uniform) against the lane's RPT rows
     // (PK: the lane's two rows as the halves of packed fp32 operations, as in am_rowl_kernel -- bit-identical sums -- together
     // with the column operands through two scalar register sets in turn: the dense fused P3 + P1 sweep 61.8 -> 47.5 us at C4, P3
@@ -485,7 +480,7 @@ __global__ __launch_bounds__(1024) void am_rowl_kernel(
     const int seg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nseg = blockDim.x >> 6;
     if (LIST && bx * 64 * RPT >= ((const __attribute__((address_space(4))) int *)counts)[bi * 4 + 1]) return;  // (uniform)
-    const int nrow = LEN ? am_len(len2, bi, m) : m;
+    const int nrow = LEN ? rf::ragged_count(len2, bi, m) : m;
     if (LEN && bx * 64 * RPT >= nrow) return;  // (uniform)
     const float *__restrict__ B = xyz2 + (size_t)bi * m * 3;
     float x2[RPT], y2[RPT], z2[RPT], rem0[RPT], acc[RPT];
@@ -503,7 +498,7 @@ __global__ __launch_bounds__(1024) void am_rowl_kernel(
     const float *__restrict__ C = xyz1p + (size_t)bi * xyz1p_stride;
     const float *__restrict__ S = ratioL + (size_t)bi * stride;
     const int c0 = seg * seglen;
-    const int c1 = LEN ? min(c0 + seglen, max(c0, (am_len(len1, bi, nseg * seglen) + SUB - 1) / SUB * SUB)) : c0 + seglen;
+    const int c1 = LEN ? min(c0 + seglen, max(c0, (rf::ragged_count(len1, bi, nseg * seglen) + SUB - 1) / SUB * SUB)) : c0 + seglen;
     // PKL: the lane's two rows as the two halves of packed fp32 operations (v_pk_add / v_pk_mul / v_pk_fma: the same IEEE
     // operations in the same order -- bit-identical sums): 6 instead of 16 vector instructions per column beside the exponentials
     constexpr bool PKL = RPT == 2 && !SKIP;
@@ -1116,8 +1111,8 @@ __global__ __launch_bounds__(AMM_TPB) void am_match_kernel(int n, int m, const f
     xyz2 += (size_t)bi * m * 3;
     ratios += (size_t)bi * b_stride + (size_t)lv0 * lv_stride;
     match += (size_t)bi * n * m;
-    const int nv = LEN ? am_len(len1, bi, n) : n;                                     // (LEN) valid columns k ...
-    const int lval = LEN ? max(0, min(lcnt, am_len(len2, bi, m) - l0)) : lcnt;  // ... and rows l of this workgroup
+    const int nv = LEN ? rf::ragged_count(len1, bi, n) : n;                                     // (LEN) valid columns k ...
+    const int lval = LEN ? max(0, min(lcnt, rf::ragged_count(len2, bi, m) - l0)) : lcnt;  // ... and rows l of this workgroup
     if (LEN && (bx * AMM_TPB >= nv || lval == 0)) {  // (uniform)
         if (k < n) am_match_zeros(match, n, k, l0, 0, lcnt);
         return;
@@ -1237,8 +1232,8 @@ __global__ __launch_bounds__(AMM_TPB) void am_match_any_kernel(int n, int m, con
     xyz2 += (size_t)bi * m * 3;
     ratios += (size_t)bi * b_stride;
     match += (size_t)bi * n * m;
-    const int nv = LEN ? am_len(len1, bi, n) : n;  // (LEN: see am_match_kernel)
-    const int lval = LEN ? max(0, min(lcnt, am_len(len2, bi, m) - l0)) : lcnt;
+    const int nv = LEN ? rf::ragged_count(len1, bi, n) : n;  // (LEN: see am_match_kernel)
+    const int lval = LEN ? max(0, min(lcnt, rf::ragged_count(len2, bi, m) - l0)) : lcnt;
     if (LEN && (bx * AMM_TPB >= nv || lval == 0)) {  // (uniform)
         if (k < n) am_match_zeros(match, n, k, l0, 0, lcnt);
         return;
@@ -1326,7 +1321,7 @@ __global__ __launch_bounds__(AM_SMALL) void am_small_kernel(int n, int m, int nl
     const int bi = blockIdx.x, t = threadIdx.x;
     const int ns = n, ms = m;  // the tensors' widths (strides)
     if (LEN) {
-        n = am_len(len1, bi, ns), m = am_len(len2, bi, ms);
+        n = rf::ragged_count(len1, bi, ns), m = rf::ragged_count(len2, bi, ms);
         multiL = am_multi(n, m), multiR = am_multi(m, n);
     }
     float x1 = 0.f, y1 = 0.f, z1 = 0.f, x2 = 0.f, y2 = 0.f, z2 = 0.f;
@@ -1423,8 +1418,8 @@ __global__ __launch_bounds__(TPB) void mc_partial_kernel(int n, int m, const flo
     const int l0 = (gridDim.y - 1 - blockIdx.y) * MC_L;
     const int k = blockIdx.x * TPB + threadIdx.x;
     const int lcnt0 = min(MC_L, m - l0);
-    const int nv = LEN ? am_len(len1, bi, n) : n;
-    const int lcnt = LEN ? max(0, min(lcnt0, am_len(len2, bi, m) - l0)) : lcnt0;
+    const int nv = LEN ? rf::ragged_count(len1, bi, n) : n;
+    const int lcnt = LEN ? max(0, min(lcnt0, rf::ragged_count(len2, bi, m) - l0)) : lcnt0;
     if (LEN && (blockIdx.x * TPB >= nv || lcnt == 0)) {  // (uniform)
         if (threadIdx.x == 0) partial[((size_t)bi * gridDim.y + l0 / MC_L) * gridDim.x + blockIdx.x] = 0.f;
         return;
@@ -1520,7 +1515,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int t = threadIdx.x;
     const int k0 = blockIdx.x * TPB;
     const int k = k0 + t;
-    const int nv = LEN ? am_len(len1, bi, n) : n, mcnt = LEN ? am_len(len2, bi, m) : m;
+    const int nv = LEN ? rf::ragged_count(len1, bi, n) : n, mcnt = LEN ? rf::ragged_count(len2, bi, m) : m;
     if (LEN && (k0 >= nv || blockIdx.y * lspan >= mcnt)) return;  // (uniform)
     const bool live = k < nv;
     const int kk = live ? k : nv - 1;
@@ -1874,7 +1869,7 @@ __global__ void emd_pack_cols_kernel(int m, int mpad, int nlv, const float *__re
     float r[EF_REC];
 #pragma unroll
     for (int i = 0; i < EF_REC; i++) r[i] = 0.f;
-    if (l < (LEN ? am_len(len2, bi, m) : m)) {
+    if (l < (LEN ? rf::ragged_count(len2, bi, m) : m)) {
         const float *p = xyz2 + ((size_t)bi * m + l) * 3;
         r[0] = p[0]; r[1] = p[1]; r[2] = p[2];
         for (int v = 0; v < nlv; v++) r[4 + v] = ratios[(size_t)bi * b_stride + (size_t)v * lv_stride + roff + l];
@@ -1916,7 +1911,7 @@ __global__ __launch_bounds__(TPB) void emd_fused_kernel(int n, int m, int mpad, 
     const int by = (lgc_ - bi * per_) / gridDim.x, bx = (lgc_ - bi * per_) - by * gridDim.x;
     const int t = threadIdx.x;
     const int k = bx * TPB + t;
-    const int nv = LEN ? am_len(len1, bi, n) : n, mv = LEN ? am_len(len2, bi, m) : m;
+    const int nv = LEN ? rf::ragged_count(len1, bi, n) : n, mv = LEN ? rf::ragged_count(len2, bi, m) : m;
     if (LEN && (bx * TPB >= nv || by * lspan >= mv)) {  // (uniform)
         if (t == 0) partial[((size_t)bi * gridDim.y + by) * gridDim.x + bx] = 0.f;
         return;

@@ -1,37 +1,13 @@
 // box_bound.hpp -- the k-nearest search shared by three_nn (interpolate.hip) and knn_point (knn.hip): the scalar candidate
-// stream of their scans, and the boxed walk over sorted clouds with the wave reductions and the point/box bound it tests.  Each
-// op brings its own candidate list (TnList, KnList), so the walk and the stream exist once.  Not part of the C ABI.
+// stream of their scans, and the boxed walk over sorted clouds with the point/box bound it tests (its wave minimum / maximum
+// are rf::wave_min_f32 / rf::wave_max_f32, wave.hpp).  Each op brings its own candidate list (TnList, KnList), so the walk and
+// the stream exist once.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
 
 namespace {
-
-#define TB_ROW(OP, N) asm volatile("s_nop 1\n\t" OP " %0, %0, %0 row_ror:" #N " row_mask:0xf bank_mask:0xf" : "+v"(v))
-__device__ __forceinline__ float tb_wave_max(float v) {  // uniform result; inputs not NaN
-    TB_ROW("v_max_f32_dpp", 8);
-    TB_ROW("v_max_f32_dpp", 4);
-    TB_ROW("v_max_f32_dpp", 2);
-    TB_ROW("v_max_f32_dpp", 1);
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-}
-__device__ __forceinline__ float tb_wave_min(float v) {
-    TB_ROW("v_min_f32_dpp", 8);
-    TB_ROW("v_min_f32_dpp", 4);
-    TB_ROW("v_min_f32_dpp", 2);
-    TB_ROW("v_min_f32_dpp", 1);
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return fminf(fminf(r0, r1), fminf(r2, r3));
-}
-#undef TB_ROW
 
 // squared distance from a point (or, with plo != phi, a box) to a box, per axis the gap max(lo - phi, plo - hi, 0): the
 // unfused expression of the op itself, so that bound <= d in fp32 (below).  An empty box (lo = +inf, hi = -inf) is at +inf.
@@ -237,14 +213,14 @@ __device__ __forceinline__ void tb_walk(List &L, const TbQuery &q, const TbCands
         }
         if (lb < best) best = lb, arg = g;
     }
-    const float wmin = tb_wave_min(best);
+    const float wmin = rf::wave_min_f32(best);
     const unsigned long long at = __ballot(best == wmin);
     const int seed = at != 0ull ? __builtin_amdgcn_readlane(arg, __builtin_ctzll(at)) : 0;
     visit(seed, false);
     // 2. every other superblock whose box is not beyond the wave's largest pruning distance (which shrinks as the visits go),
     //    64 superblocks at a time, nearest box first: the pruning distances shrink fastest that way, and the first box beyond
     //    the wave's largest ends the round.  (Where a lane's pruning distance is +inf, no finite bound is skipped.)
-    float wk = tb_wave_max(L.prune());
+    float wk = rf::wave_max_f32(L.prune());
     for (int r0 = 0; r0 < c.nsb; r0 += 64) {
         const int g = r0 + lane;
         float lb = INFINITY;
@@ -254,12 +230,12 @@ __device__ __forceinline__ void tb_walk(List &L, const TbQuery &q, const TbCands
         }
         bool pend = g < c.nsb && g != seed && lb <= wk && (List::kNonFinite || lb != INFINITY);
         while (__ballot(pend) != 0ull) {  // (uniform)
-            const float wmin2 = tb_wave_min(pend ? lb : INFINITY);
+            const float wmin2 = rf::wave_min_f32(pend ? lb : INFINITY);
             if (!(wmin2 <= wk)) break;
             const int jn = __builtin_ctzll(__ballot(pend && lb == wmin2));
             pend = pend && lane != jn;
             visit(r0 + jn, true);
-            wk = tb_wave_max(L.prune());
+            wk = rf::wave_max_f32(L.prune());
         }
     }
 }

@@ -23,8 +23,6 @@
 
 namespace {
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 constexpr int CX_WAVES = 4;   // waves per workgroup, each on its own (no barrier, no LDS)
 constexpr int CX_STRIP = 8;   // partner clouds a wave goes through with its queries in registers
 constexpr int CX_REC = 12;    // 32-bit words per (i, j, superblock) record: 5 limbs of sum d, 5 of sum sqrtf(d), max bits, 0
@@ -45,35 +43,11 @@ struct CxSide {
     int clouds, nfull, nsb;
 };
 
-__device__ __forceinline__ int cx_len(const int *__restrict__ len, int ci, int full) {
-    if (!len) return full;
-    const int v = len[ci];
-    return v < 1 ? 1 : (v > full ? full : v);
-}
-
-// ---- wave reductions (uniform results): rotate-adds inside the rows of 16 lanes, then the four rows -----------------------
+// ---- wave minimum / maximum of floats (uniform results), none of them NaN.  -inf marks a lane that takes no part in a max, +inf
+// one that takes no part in a min.  Local on purpose: with rf::wave_min_f32 / rf::wave_max_f32 (wave.hpp) the sweep is slower,
+// 414 against 290 us at 32 x 32 clouds of 2048 points (profiles/wave_primitives_ab.txt).
+// The integer reductions are rf::wave_add_u32 / rf::wave_max_u32.
 #define CX_ROR(n) (0x120 + (n))
-__device__ __forceinline__ unsigned cx_rows(unsigned v) {
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 0) + (unsigned)__builtin_amdgcn_readlane((int)v, 16) +
-           (unsigned)__builtin_amdgcn_readlane((int)v, 32) + (unsigned)__builtin_amdgcn_readlane((int)v, 48);
-}
-__device__ __forceinline__ unsigned cx_wave_add(unsigned v) {  // the sum must fit 32 bits
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CX_ROR(8), 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CX_ROR(4), 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CX_ROR(2), 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CX_ROR(1), 0xf, 0xf, false);
-    return cx_rows(v);
-}
-__device__ __forceinline__ unsigned cx_wave_umax(unsigned v) {
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CX_ROR(8), 0xf, 0xf, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CX_ROR(4), 0xf, 0xf, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CX_ROR(2), 0xf, 0xf, false));
-    v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CX_ROR(1), 0xf, 0xf, false));
-    const unsigned r0 = (unsigned)__builtin_amdgcn_readlane((int)v, 0), r1 = (unsigned)__builtin_amdgcn_readlane((int)v, 16);
-    const unsigned r2 = (unsigned)__builtin_amdgcn_readlane((int)v, 32), r3 = (unsigned)__builtin_amdgcn_readlane((int)v, 48);
-    return max(max(r0, r1), max(r2, r3));
-}
-// floats, none of them NaN.  -inf marks a lane that takes no part in a max, +inf one that takes no part in a min.
 __device__ __forceinline__ float cx_wave_fmax(float v) {
 #define CX_STEP(n) v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CX_ROR(n), 0xf, 0xf, false)))
     CX_STEP(8);
@@ -100,6 +74,7 @@ __device__ __forceinline__ float cx_wave_fmin(float v) {
     const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
     return fminf(fminf(r0, r1), fminf(r2, r3));
 }
+#undef CX_ROR
 
 // ---- the fixed-point grid of a pair ----------------------------------------------------------------------------------------
 // The biased exponent of the squared diagonal D of the joint box of cloud i of xyz1 (a) and cloud j of xyz2 (b): every
@@ -286,10 +261,10 @@ __global__ __launch_bounds__(CX_WAVES * 64) void chamfer_cross_sweep_kernel(CxSi
         unsigned word = 0u;
 #pragma unroll
         for (int k = 0; k < CX_LIMBS; k++) {
-            const unsigned a = cx_wave_add(ld[k]), b = cx_wave_add(ls[k]);
+            const unsigned a = rf::wave_add_u32(ld[k]), b = rf::wave_add_u32(ls[k]);
             word = lane == k ? a : (lane == CX_LIMBS + k ? b : word);
         }
-        const unsigned mx = cx_wave_umax(__float_as_uint(dv));  // bits of non-negative floats order as the floats do
+        const unsigned mx = rf::wave_max_u32(__float_as_uint(dv));  // bits of non-negative floats order as the floats do
         word = lane == 2 * CX_LIMBS ? mx : word;
         const size_t pair = DIR == 0 ? (size_t)qi * C.clouds + cj : (size_t)cj * Q.clouds + qi;
         if (lane < CX_REC) rec[(pair * Q.nsb + sb) * CX_REC + lane] = word;
@@ -305,12 +280,6 @@ struct CxReduce {
     int self;
     float *out;
 };
-
-__device__ __forceinline__ unsigned long long cx_wave_add64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // the integer sum_k t[k] * 2^(26 k) on the grid of eref, divided by the count.  Integers and one fixed sequence of double
 // operations: the same bits whoever added the limbs up.  A single term (count 1, nothing truncated) comes back exactly.
@@ -341,13 +310,13 @@ __global__ __launch_bounds__(CX_WAVES * 64) void chamfer_cross_reduce_kernel(CxR
     }
 #pragma unroll
     for (int k = 0; k < CX_LIMBS; k++) {
-        td[k] = cx_wave_add64(td[k]);
-        ts[k] = cx_wave_add64(ts[k]);
+        td[k] = rf::wave_sum(td[k]);
+        ts[k] = rf::wave_sum(ts[k]);
     }
-    mx = cx_wave_umax(mx);
+    mx = rf::wave_max_u32(mx);
     if (lane == 0) {
         const int e1 = cx_pair_exp(a.cbox1 + (size_t)i * 8, a.cbox2 + (size_t)j * 8);
-        const int L = dir ? cx_len(a.len2, j, a.m) : cx_len(a.len1, i, a.n);
+        const int L = dir ? rf::ragged_count(a.len2, j, a.m) : rf::ragged_count(a.len1, i, a.n);
         float *__restrict__ o = a.out + ((size_t)i * a.r + j) * RF_CX_NCOL;
         o[0 + dir] = cx_mean(ts, cx_sqrt_exp(e1), L);
         o[2 + dir] = cx_mean(td, e1, L);
@@ -356,7 +325,7 @@ __global__ __launch_bounds__(CX_WAVES * 64) void chamfer_cross_reduce_kernel(CxR
 }
 
 size_t cx_rec_bytes(int s, int r, int npad) {
-    return align256((size_t)s * (size_t)r * (size_t)(npad / 64) * CX_REC * sizeof(unsigned));
+    return rf::align256((size_t)s * (size_t)r * (size_t)(npad / 64) * CX_REC * sizeof(unsigned));
 }
 
 }  // namespace
@@ -365,7 +334,7 @@ extern "C" {
 
 size_t rf_chamfer_cross_workspace_bytes(int s, int r, int n, int m) {
     if (s <= 0 || r <= 0 || n <= 0 || m <= 0 || n > rfp::kMaxPoints || m > rfp::kMaxPoints) return 0;
-    return rfp::sorted_bytes(s, n) + rfp::sorted_bytes(r, m) + align256(((size_t)s + (size_t)r) * 8 * sizeof(float)) +
+    return rfp::sorted_bytes(s, n) + rfp::sorted_bytes(r, m) + rf::align256(((size_t)s + (size_t)r) * 8 * sizeof(float)) +
            cx_rec_bytes(s, r, rfp::sorted_view(s, n, nullptr).npad) + cx_rec_bytes(s, r, rfp::sorted_view(r, m, nullptr).npad);
 }
 
@@ -389,7 +358,7 @@ int rf_chamfer_cross(int s, int r, int n, int m, const float *xyz1, const float 
     const rfp::Sorted s2 = self ? s1 : rfp::sorted_view(r, m, w);
     w += rfp::sorted_bytes(r, m);
     float *cbox = (float *)w;
-    w += align256(((size_t)s + (size_t)r) * 8 * sizeof(float));
+    w += rf::align256(((size_t)s + (size_t)r) * 8 * sizeof(float));
     unsigned *rec1 = (unsigned *)w;
     w += cx_rec_bytes(s, r, s1.npad);
     unsigned *rec2 = self ? rec1 : (unsigned *)w;

@@ -26,7 +26,6 @@
 
 namespace {
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // loss[bi][dir] = mean_j sqrt(dist_dir[bi][j]): one workgroup per (sample, direction), fixed
@@ -169,11 +168,6 @@ __global__ __launch_bounds__(MG_TPB) void merge_pull_grad_kernel(int n, int m, c
 // rows get merge_pull_kernel's arithmetic, expression for expression; a padded new row gets idx2 = 0 and refined = +0.0
 // whatever the sweep left in its slot ((0, -1) on the dense route, nothing on the culled one), so that gathers downstream
 // need no special case.
-__device__ __forceinline__ int mg_len(const int *__restrict__ len, int bi, int full) {
-    if (!len) return full;
-    const int v = len[bi];
-    return v < 1 ? 1 : (v > full ? full : v);
-}
 
 __global__ void merge_pull_len_kernel(int n, int m, long total, const float *__restrict__ raw,
                                       const float *__restrict__ newpts, int *__restrict__ idx2,
@@ -182,7 +176,7 @@ __global__ void merge_pull_len_kernel(int n, int m, long total, const float *__r
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= total) return;
     const long bi = e / m;
-    if ((int)(e - bi * m) >= mg_len(len_new, (int)bi, m)) {
+    if ((int)(e - bi * m) >= rf::ragged_count(len_new, (int)bi, m)) {
         idx2[e] = 0;
         out[e * 3 + 0] = 0.f;
         out[e * 3 + 1] = 0.f;
@@ -217,7 +211,7 @@ __global__ __launch_bounds__(MG_TPB) void merge_pull_grad_len_kernel(int n, int 
                                                                      const int *__restrict__ len_new) {
     __shared__ float part[MG_TPB / 64];
     const int bi = blockIdx.x;
-    const int nl = mg_len(len_raw, bi, n), ml = mg_len(len_new, bi, m);
+    const int nl = rf::ragged_count(len_raw, bi, n), ml = rf::ragged_count(len_new, bi, m);
     const float dec = decfactor[0];
     const float c = 1e-8f + dec * dec;
     float acc = 0.f;
@@ -273,12 +267,12 @@ FwdPlan plan_forward(int b, int n, int m, int dirs, bool have1, bool have2) {
     size_t off = 0;
     if (p.culled) {
         p.off_s1 = off;
-        if (!have1) off += align256(rfp::sorted_bytes(b, n));
+        if (!have1) off += rf::align256(rfp::sorted_bytes(b, n));
         p.off_s2 = off;
-        if (!have2) off += align256(rfp::sorted_bytes(b, m));
+        if (!have2) off += rf::align256(rfp::sorted_bytes(b, m));
     } else {
         p.off_dense = off;
-        off += align256(rfd::dense_workspace_bytes(b, n, m, dirs));
+        off += rf::align256(rfd::dense_workspace_bytes(b, n, m, dirs));
     }
     p.bytes = off;
     return p;
@@ -455,7 +449,7 @@ int rf_chamfer_loss_grad_lengths(int b, int n, int m, const float *xyz1, const f
 // ------------------------------------------------------------------ merge_layer ------------
 size_t rf_merge_layer_workspace_bytes(int b, int n, int m, int have_sorted_raw) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
-    return align256((size_t)b * m * sizeof(float)) + plan_forward(b, n, m, 2, have_sorted_raw != 0, false).bytes;
+    return rf::align256((size_t)b * m * sizeof(float)) + plan_forward(b, n, m, 2, have_sorted_raw != 0, false).bytes;
 }
 
 int rf_merge_layer(int b, int n, int m, const float *rawpts, const float *newpts, const void *sorted_raw,
@@ -464,7 +458,7 @@ int rf_merge_layer(int b, int n, int m, const float *rawpts, const float *newpts
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0 || m == 0) return RF_OK;
     if (n == 0 || !rawpts || !newpts || !decfactor_dev || !refined || !idx2 || !workspace) return RF_EINVAL;
-    const size_t dbytes = align256((size_t)b * m * sizeof(float));
+    const size_t dbytes = rf::align256((size_t)b * m * sizeof(float));
     if (workspace_bytes < dbytes) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float *dist2 = (float *)workspace;  // the distances themselves are not an output of merge_layer
@@ -498,7 +492,7 @@ int rf_merge_layer_grad(int b, int n, int m, const float *rawpts, const float *n
 // ------------------------------------------------------------------ merge_layer, ragged ----
 size_t rf_merge_layer_lengths_workspace_bytes(int b, int n, int m) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
-    return align256((size_t)b * m * sizeof(float)) + rfd::ragged_workspace_bytes(b, n, m, RF_NN_AUTO, 2);
+    return rf::align256((size_t)b * m * sizeof(float)) + rfd::ragged_workspace_bytes(b, n, m, RF_NN_AUTO, 2);
 }
 
 int rf_merge_layer_lengths(int b, int n, int m, const float *rawpts, const float *newpts, const int *len_raw,
@@ -508,7 +502,7 @@ int rf_merge_layer_lengths(int b, int n, int m, const float *rawpts, const float
     if (b == 0 || m == 0) return RF_OK;
     if (n == 0 || !rawpts || !newpts || !decfactor_dev || !refined || !idx2 || !workspace) return RF_EINVAL;
     if (!rf::aligned16(workspace) || !aligned4(len_raw) || !aligned4(len_new)) return RF_EINVAL;
-    const size_t dbytes = align256((size_t)b * m * sizeof(float));
+    const size_t dbytes = rf::align256((size_t)b * m * sizeof(float));
     if (workspace_bytes < rf_merge_layer_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float *dist2 = (float *)workspace;  // the distances themselves are not an output of merge_layer

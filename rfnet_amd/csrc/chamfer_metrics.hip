@@ -20,8 +20,6 @@
 
 namespace {
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 constexpr int CM_TPB = 1024;
 constexpr int CM_NW = CM_TPB / 64;
 constexpr int CM_U = 8;  // points per thread and trip
@@ -29,12 +27,6 @@ constexpr int CM_U = 8;  // points per thread and trip
 // A direction with more bins counts with global atomics into its count array.  tests/test_gpu_chamfer_metrics.py
 // cites this number for the shapes on either side of it.
 constexpr int CM_LDS_BINS = 32768;
-
-__device__ __forceinline__ int cm_len(const int *__restrict__ len, int bi, int full) {
-    if (!len) return full;
-    const int v = len[bi];
-    return v < 1 ? 1 : (v > full ? full : v);
-}
 
 struct CmArgs {
     int n, m;
@@ -46,13 +38,6 @@ struct CmArgs {
     int *count1, *count2;
     int pad;  // the culled sweep leaves the padded slots of dist / idx to this kernel: (0, -1)
 };
-
-template <typename T, typename Op>
-__device__ __forceinline__ T cm_wave(T v, Op op) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // LDS_HIST: the histogram lives in `hist` (LDS, zeroed here); otherwise `hist` is the sample's row of the count
 // array in global memory, zeroed by the host side before the launch, written with atomics that execute at L2 and
@@ -71,7 +56,7 @@ __device__ __forceinline__ void cm_direction(const CmArgs &a, int bi, int dir, i
     int *__restrict__ ifull = (dir ? a.idx2 : a.idx1) + (size_t)bi * full;
     const float *__restrict__ d = dfull;
     const int *__restrict__ ix = ifull;
-    const int L = cm_len(dir ? a.len2 : a.len1, bi, full);
+    const int L = rf::ragged_count(dir ? a.len2 : a.len1, bi, full);
     int *__restrict__ cnt_out = (dir ? a.count1 : a.count2) + (size_t)bi * nb;
 
     if (a.pad) {
@@ -92,7 +77,7 @@ __device__ __forceinline__ void cm_direction(const CmArgs &a, int bi, int dir, i
     // direction 2's as well -- its loads ride in the same trips -- and gets exactly the number its neighbour workgroup
     // does: no second launch, nothing to order between workgroups.
     const float thr2 = a.thr2, nalpha = -a.alpha;
-    const int Lo = cm_len(dir ? a.len1 : a.len2, bi, nb);
+    const int Lo = rf::ragged_count(dir ? a.len1 : a.len2, bi, nb);
     const int Lr = dir == 0 ? Lo : 0;
     const float *__restrict__ dother = a.dist2 + (size_t)bi * a.m;  // read by direction 1's workgroup only
     int below_o = 0;
@@ -155,12 +140,12 @@ __device__ __forceinline__ void cm_direction(const CmArgs &a, int bi, int dir, i
     }
 
     auto add = [](auto x, auto y) { return x + y; };
-    const float sr = cm_wave((r[0] + r[1]) + (r[2] + r[3]), add);
-    const float sq = cm_wave((q[0] + q[1]) + (q[2] + q[3]), add);
-    const float se = cm_wave((e[0] + e[1]) + (e[2] + e[3]), add);
-    mx = cm_wave(mx, [](float x, float y) { return fmaxf(x, y); });
-    below = cm_wave(below, add);
-    below_o = cm_wave(below_o, add);
+    const float sr = rf::wave_reduce((r[0] + r[1]) + (r[2] + r[3]), add);
+    const float sq = rf::wave_reduce((q[0] + q[1]) + (q[2] + q[3]), add);
+    const float se = rf::wave_reduce((e[0] + e[1]) + (e[2] + e[3]), add);
+    mx = rf::wave_reduce(mx, [](float x, float y) { return fmaxf(x, y); });
+    below = rf::wave_reduce(below, add);
+    below_o = rf::wave_reduce(below_o, add);
     if ((tid & 63) == 0) {
         const int w = tid >> 6;
         part[0][w] = sr;
@@ -228,7 +213,7 @@ __global__ void chamfer_metrics_gradw_kernel(int b, int n, int m, const int *__r
     if (g >= (long)b * full) return;
     const int bi = (int)(g / full);
     float *__restrict__ out = dir ? gd2 : gd1;
-    const int L = cm_len(dir ? len2 : len1, bi, full);
+    const int L = rf::ragged_count(dir ? len2 : len1, bi, full);
     if ((int)(g - (long)bi * full) >= L) {
         out[g] = 0.f;
         return;
@@ -333,7 +318,7 @@ int rf_chamfer_metrics(int b, int n, int m, const float *xyz1, const float *xyz2
 
 size_t rf_chamfer_metrics_grad_workspace_bytes(int b, int n, int m) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
-    return align256(sizeof(float) * (size_t)b * n) + align256(sizeof(float) * (size_t)b * m);
+    return rf::align256(sizeof(float) * (size_t)b * n) + rf::align256(sizeof(float) * (size_t)b * m);
 }
 
 int rf_chamfer_metrics_grad(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
@@ -350,7 +335,7 @@ int rf_chamfer_metrics_grad(int b, int n, int m, const float *xyz1, const float 
     if (workspace_bytes < rf_chamfer_metrics_grad_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float *gd1 = (float *)workspace;
-    float *gd2 = (float *)((char *)workspace + align256(sizeof(float) * (size_t)b * n));
+    float *gd2 = (float *)((char *)workspace + rf::align256(sizeof(float) * (size_t)b * n));
     const long total = (long)b * n + (long)b * m;
     RF_LAUNCH("chamfer_metrics_gradw", chamfer_metrics_gradw_kernel, dim3(rf::ceil_div(total, 256)), dim3(256), 0, s, b,
               n, m, len1, len2, dist1, idx1, dist2, idx2, count1, count2, alpha, grad_metrics, gd1, gd2);

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "../../include/rfops.h"
+#include "wave.hpp"  // ragged_count, align256 and the wave reductions / scans, each once
 
 namespace rf {
 

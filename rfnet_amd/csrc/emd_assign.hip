@@ -39,14 +39,6 @@ constexpr int EA_GTPB = 256;           // the gradient kernel
 constexpr u64 EA_NOKEY = ~0ull;
 constexpr float EA_CMAX = 1048576.0f;  // 2^20: reached only when the squares overflow fp32 (E >= 2^63)
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
-__device__ __forceinline__ int ea_len(const int *__restrict__ len, int s, int full) {
-    if (!len) return full;
-    const int v = len[s];
-    return v < 1 ? 1 : (v > full ? full : v);
-}
-
 __device__ __forceinline__ float ea_dist(float ax, float ay, float az, float bx, float by, float bz) {
     const float dx = ax - bx, dy = ay - by, dz = az - bz;
     return sqrtf(((dx * dx) + (dy * dy)) + (dz * dz));
@@ -66,11 +58,6 @@ __device__ __forceinline__ void ea_reduce(u64 &k1, u64 &k2) {
         const u64 b1 = __shfl_xor(k1, o, 64), b2 = __shfl_xor(k2, o, 64);
         ea_merge(k1, k2, b1, b2);
     }
-}
-__device__ __forceinline__ long long ea_wave_sum(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 struct EaArgs {
@@ -94,7 +81,7 @@ __global__ __launch_bounds__(EA_TPB) void emd_assign_kernel(EaArgs a) {
     const int s = blockIdx.x, n = a.n, tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int np = (n + 3) & ~3;
-    const int L = ea_len(a.len, s, n);
+    const int L = rf::ragged_count(a.len, s, n);
     u64 *__restrict__ bid = (u64 *)ea_lds;                         // per object: (beta << 32 | ~i), 0 = no bid
     float *__restrict__ ox = (float *)(bid + np), *__restrict__ oy = ox + np, *__restrict__ oz = oy + np;
     int *__restrict__ price = (int *)(oz + np), *__restrict__ owner = price + np;
@@ -263,11 +250,10 @@ __global__ __launch_bounds__(EA_TPB) void emd_assign_kernel(EaArgs a) {
         const float ax = X1[i * 3], ay = X1[i * 3 + 1], az = X1[i * 3 + 2];
         int m = 0x7FFFFFFF;
         for (int j = lane; j < L; j += 64) m = min(m, ea_cost(ea_dist(ax, ay, az, ox[j], oy[j], oz[j]), S) + price[j]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = min(m, __shfl_xor(m, o, 64));
+        m = rf::wave_reduce(m, [](int x, int y) { return min(x, y); });
         if (lane == 0) sMin += m;
     }
-    sP = ea_wave_sum(sP), sPrice = ea_wave_sum(sPrice), sMin = ea_wave_sum(sMin);
+    sP = rf::wave_sum(sP), sPrice = rf::wave_sum(sPrice), sMin = rf::wave_sum(sMin);
     if (lane == 0) red[0][wave] = sP, red[1][wave] = sPrice, red[2][wave] = sMin;
     __syncthreads();
     if (tid == 0) {
@@ -294,7 +280,7 @@ __global__ __launch_bounds__(EA_GTPB) void emd_assign_grad_kernel(int n, const f
                                                                    float *__restrict__ grad1, float *__restrict__ grad2) {
     const int s = blockIdx.y, k = blockIdx.x * EA_GTPB + threadIdx.x;
     if (k >= n) return;
-    const int L = ea_len(len, s, n);
+    const int L = rf::ragged_count(len, s, n);
     const size_t row = (size_t)s * n;
     float *__restrict__ g1 = grad1 + (row + k) * 3, *__restrict__ g2 = grad2 + (row + k) * 3;
     if (k >= L) {
@@ -327,7 +313,7 @@ int rf_emd_assign_supported(int n) { return n >= 1 && n <= RF_EA_MAX_POINTS; }
 
 size_t rf_emd_assign_workspace_bytes(int b, int n) {
     if (b <= 0 || !rf_emd_assign_supported(n) || b > 65535) return 0;
-    return align256((size_t)b * (size_t)n * sizeof(int));
+    return rf::align256((size_t)b * (size_t)n * sizeof(int));
 }
 
 int rf_emd_assign(int b, int n, const float *xyz1, const float *xyz2, const int *len, int max_rounds, int *match12,

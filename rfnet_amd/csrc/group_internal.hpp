@@ -1,25 +1,19 @@
 // group_internal.hpp -- launchers shared by the entry points of sampling.hip / grouping.hip and the one-call
-// sample-and-group of sample_group.hip.  Not part of the C ABI.
+// sample-and-group of sample_group.hip, and rfi::Counts, the argument through which a RAGGED kernel instantiation receives
+// its per-sample counts.  Not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "nn_pruned.hpp"
+#include "wave.hpp"
 
 namespace rfi {
 
-// ---- ragged batches (the _lengths entries of include/rfops.h) ----
-// A ragged batch's count of batch element bi (NULL = all n), clamped into [1, n]: the rule of include/rfops.h for every _lengths
-// entry (and of the sort, nn_pruned.hip ragged_count, which is given the same array).  bi is uniform over a wave wherever this is
-// called, so the load is scalar.
-__device__ __forceinline__ int ragged_count(const int *__restrict__ len, int bi, int n) {
-    if (!len) return n;
-    const int v = len[bi];
-    return v < 1 ? 1 : (v > n ? n : v);
-}
+// ---- ragged batches (the _lengths entries of include/rfops.h; the count of a batch element is rf::ragged_count, wave.hpp) ----
 // How a kernel with a RAGGED instantiation receives the counts: as its LAST argument, a Counts<RAGGED> by value.  The plain
 // instantiation's is EMPTY and count1 / count2 return the padded sizes themselves, so its code is what it was before the counts
 // existed, instruction for instruction (checked on the disassembly); the ragged one carries the two device arrays
-// (either may be NULL) and reads them through ragged_count.
+// (either may be NULL) and reads them through rf::ragged_count.
 template <bool RAGGED>
 struct Counts {
     const int *len1, *len2;
@@ -28,8 +22,8 @@ template <>
 struct Counts<false> {};
 __device__ __forceinline__ int count1(const Counts<false> &, int, int n) { return n; }
 __device__ __forceinline__ int count2(const Counts<false> &, int, int m) { return m; }
-__device__ __forceinline__ int count1(const Counts<true> &c, int bi, int n) { return ragged_count(c.len1, bi, n); }
-__device__ __forceinline__ int count2(const Counts<true> &c, int bi, int m) { return ragged_count(c.len2, bi, m); }
+__device__ __forceinline__ int count1(const Counts<true> &c, int bi, int n) { return rf::ragged_count(c.len1, bi, n); }
+__device__ __forceinline__ int count2(const Counts<true> &c, int bi, int m) { return rf::ragged_count(c.len2, bi, m); }
 
 // farthest_point_sample (sampling.hip).  new_xyz (b, m, 3): the samples' coordinates, written by the same launch (NULL: not
 // wanted) -- gather_point(inp, out) fused: the kernel reloads every winner's coordinates anyway.  temp: b*n floats when

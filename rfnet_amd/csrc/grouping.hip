@@ -335,22 +335,6 @@ __device__ __forceinline__ float qx_gap(float a, float b) {
     return r;
 }
 
-template <int N>
-__device__ __forceinline__ int dpp_row_shr(int v) {  // lane - N inside its row of 16, 0 where there is none
-    return __builtin_amdgcn_update_dpp(0, v, 0x110 + N, 0xf, 0xf, false);
-}
-// inclusive prefix sum over the wave's 64 lanes
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-    v += dpp_row_shr<1>(v);
-    v += dpp_row_shr<2>(v);
-    v += dpp_row_shr<4>(v);
-    v += dpp_row_shr<8>(v);
-    const int r0 = __builtin_amdgcn_readlane(v, 15), r1 = __builtin_amdgcn_readlane(v, 31),
-              r2 = __builtin_amdgcn_readlane(v, 47);
-    const int row = lane >> 4;
-    return v + (row >= 1 ? r0 : 0) + (row >= 2 ? r1 : 0) + (row >= 3 ? r2 : 0);
-}
-
 // LDS (dynamic): the cloud's superblock boxes as six arrays of gpad floats (lo.x lo.y lo.z hi.x hi.y hi.z: lanes read
 // consecutive dwords, conflict-free), staged ONCE per workgroup -- with every wave reading its 8 KB of boxes from global
 // memory the box phase alone was 20 of the launch's 36 us at C3 (the vector L1's 64 B/clk) -- then per wave its bitmap,
@@ -492,7 +476,7 @@ __global__ __launch_bounds__(1024) void query_ball_boxes_kernel(
             const uint2 v2 = *(const uint2 *)(bm + w0 + 2 * lane);
             unsigned long long val = ((unsigned long long)v2.y << 32) | v2.x;
             const int c = __builtin_popcountll(val);
-            const int incl = wave_incl_scan(c, lane);
+            const int incl = (int)rf::wave_incl_scan((unsigned)c);
             int p = placed + incl - c;
             while (val != 0ull && p < nsample) {
                 stage[p] = (w0 + 2 * lane) * 32 + __builtin_ctzll(val);

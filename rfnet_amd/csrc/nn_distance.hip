@@ -44,7 +44,7 @@ constexpr int PADQ = 512; // packed arrays are padded to a multiple of this many
 
 // Which point counts a kernel instantiation serves: `all` (every sample has the tensor's n / m points -- the
 // instantiations rf_nn_distance has always used, compiled exactly as before) or `per_sample` (ragged
-// batches, rf_nn_distance_lengths: trailing count arrays, see clamp_len).
+// batches, rf_nn_distance_lengths: trailing count arrays, see rf::ragged_count).
 enum class Counts { all, per_sample };
 
 // Buffers (separate __restrict__ kernel parameters so the candidate loads can be scalar loads):
@@ -87,15 +87,7 @@ __global__ void pack_kernel(int b, int n_own, int n_own_pad, const float *__rest
     dst[g * 3 + 2] = z;
 }
 
-// Ragged batches (rf_nn_distance_lengths): sample bi uses the first len[bi] points of its row.  A NULL
-// array means "all n"; a device value outside [1, n] is clamped into it, so no kernel ever reads past
-// the tensor whatever the caller's lengths hold.
-__device__ __forceinline__ int clamp_len(const int *__restrict__ len, int bi, int n) {
-    if (!len) return n;
-    const int v = len[bi];
-    return v < 1 ? 1 : (v > n ? n : v);
-}
-
+// Ragged batches (rf_nn_distance_lengths): sample bi uses the first rf::ragged_count(len, bi, n) points of its row.
 // pack_kernel for ragged batches: each sample padded from its OWN length (own -inf, candidates +inf,
 // as the alignment padding above), so every point beyond a sample's length is a pad of the sweep.
 __global__ void pack_len_kernel(int b, int n_own, int n_own_pad, const float *__restrict__ src_own,
@@ -113,21 +105,13 @@ __global__ void pack_len_kernel(int b, int n_own, int n_own_pad, const float *__
     long bi = g / n_pad;
     int j = (int)(g - bi * n_pad);
     float x = padval, y = 0.f, z = 0.f;
-    if (j < clamp_len(is_cand ? len_cand : len_own, (int)bi, n)) {
+    if (j < rf::ragged_count(is_cand ? len_cand : len_own, (int)bi, n)) {
         const float *p = src + (bi * n + j) * 3;
         x = p[0]; y = p[1]; z = p[2];
     }
     dst[g * 3 + 0] = x;
     dst[g * 3 + 1] = y;
     dst[g * 3 + 2] = z;
-}
-
-// running minimum as ONE v_min3_f32.  Written as asm so that LLVM cannot re-associate the chain
-// of minima over a chunk into a tree evaluated at the end of the chunk (minnum is exactly
-// associative, so it does -- and then keeps all 16 x R distances of the chunk alive: spills).
-__device__ __forceinline__ float min3_acc(float acc, float a, float b) {
-    asm("v_min3_f32 %0, %0, %1, %2" : "+v"(acc) : "v"(a), "v"(b));
-    return acc;
 }
 
 template <int R>
@@ -222,8 +206,8 @@ __global__ __launch_bounds__(TPB) void nn_sweep_kernel(Sweep a, const float *__r
     int c_end = min(a.nc, c_begin + a.span);  // exclusive, real candidates
     int no_i = a.no;
     if constexpr (LEN) {
-        no_i = clamp_len(own_len, bi, a.no);
-        c_end = min(clamp_len(cand_len, bi, a.nc), c_begin + a.span);
+        no_i = rf::ragged_count(own_len, bi, a.no);
+        c_end = min(rf::ragged_count(cand_len, bi, a.nc), c_begin + a.span);
         if (ob * 64 * R >= no_i) c_end = c_begin;  // nothing but padding in this own block
     }
 #pragma unroll
@@ -283,7 +267,7 @@ __global__ __launch_bounds__(TPB) void nn_sweep_kernel(Sweep a, const float *__r
                 for (int r = 0; r < R; r++) {
                     d0[r] = rf::d2_fma(px - ax[r], py - ay[r], pz - az[r]);
                     d1[r] = rf::d2_fma(qx - ax[r], qy - ay[r], qz - az[r]);
-                    cm[r] = min3_acc(cm[r], d0[r], d1[r]);
+                    cm[r] = rf::min3_acc(cm[r], d0[r], d1[r]);
                 }
                 if constexpr (COLS) {
                     colv[sub * SUB + u] = min_over<R>(d0);
@@ -397,7 +381,7 @@ __device__ __forceinline__ void rowmerge_body(long g, const float *__restrict__ 
     if (g >= total) return;
     if constexpr (LEN) {  // a row beyond its sample's count: the pad values
         const long bi = g / no;
-        if (g - bi * no >= clamp_len(own_len, (int)bi, no)) {
+        if (g - bi * no >= rf::ragged_count(own_len, (int)bi, no)) {
             dist[g] = 0.f;
             idx[g] = -1;
             return;
@@ -457,14 +441,14 @@ __global__ __launch_bounds__(TPB) void nn_resolve_kernel(Sweep a, const float *_
     const bool writer = q == 0 && (int)(blockIdx.x - bi * cblocks) * CPB + (int)(threadIdx.x >> 2) < a.nc;
     int no_i = a.no, oblocks_i = a.oblocks;
     if constexpr (LEN) {
-        if (c >= clamp_len(cand_len, bi, a.nc)) {  // (quad-uniform: the quad shares c)
+        if (c >= rf::ragged_count(cand_len, bi, a.nc)) {  // (quad-uniform: the quad shares c)
             if (writer) {
                 dist[(size_t)bi * a.nc + c] = 0.f;
                 idx[(size_t)bi * a.nc + c] = -1;
             }
             return;
         }
-        no_i = clamp_len(own_len, bi, a.no);
+        no_i = rf::ragged_count(own_len, bi, a.no);
         oblocks_i = (no_i + 64 * R - 1) / (64 * R);
     }
     const float *own = own_all + (size_t)bi * a.no_pad * 3;
@@ -582,8 +566,8 @@ __global__ __launch_bounds__(GTPB) void nn_grad_kernel(GradArgs a, const int *__
     const float *__restrict__ sxyz = D.src_xyz + (size_t)bi * D.ns * 3;
     int nd_i = D.nd, ns_i = D.ns;
     if constexpr (LEN) {
-        nd_i = clamp_len(which ? len2 : len1, bi, D.nd);
-        ns_i = clamp_len(which ? len1 : len2, bi, D.ns);
+        nd_i = rf::ragged_count(which ? len2 : len1, bi, D.nd);
+        ns_i = rf::ragged_count(which ? len1 : len2, bi, D.ns);
     }
     for (int i = threadIdx.x; i < jn * 3; i += GTPB) acc[i] = (acc_t)0;
     // own term first: its idx -> gather chain is independent of the scatter scan below, so the two
@@ -690,7 +674,7 @@ __global__ void pad_outputs_kernel(int b, int n, int m, const int *__restrict__ 
     int *__restrict__ id = second ? idx2 : idx1;
     if (!d || g >= (long)b * cnt) return;
     const long bi = g / cnt;
-    if (g - bi * cnt >= clamp_len(second ? len2 : len1, (int)bi, cnt)) {
+    if (g - bi * cnt >= rf::ragged_count(second ? len2 : len1, (int)bi, cnt)) {
         d[g] = 0.f;
         id[g] = -1;
     }

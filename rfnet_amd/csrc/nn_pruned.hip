@@ -156,13 +156,6 @@ struct SortArgs {
     unsigned long long *dbg;  // optional (with stats): s_memtime stamps of the sort's phases, [16..31]
 };
 
-// A ragged batch's count of batch element bi (NULL = all n), clamped into [1, n].
-__device__ __forceinline__ int ragged_count(const int *__restrict__ len, int bi, int n) {
-    if (!len) return n;
-    const int v = len[bi];
-    return v < 1 ? 1 : (v > n ? n : v);
-}
-
 // Skilling's axes-to-transpose Hilbert mapping, 5 bits per axis -> 15-bit index.
 __device__ __forceinline__ unsigned hilbert15(unsigned x, unsigned y, unsigned z) {
     unsigned X[3] = {x, y, z};
@@ -239,42 +232,6 @@ __device__ __forceinline__ unsigned spread5(unsigned v) {  // bit b -> bit 3b
     v = (v | (v << 2)) & 0x1249u;
     return v;
 }
-
-// inclusive prefix sum over the wave in 6 DPP steps (row shifts, then the two row broadcasts)
-__device__ __forceinline__ unsigned wave_incl_scan(unsigned v) {
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1,3
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2,3
-    return v;
-}
-
-#define RFP_ROW(OP, N) asm volatile("s_nop 1\n\t" OP " %0, %0, %0 row_ror:" #N " row_mask:0xf bank_mask:0xf" : "+v"(v))
-__device__ __forceinline__ float wave_min_f32(float v) {  // uniform result; inputs not NaN
-    RFP_ROW("v_min_f32_dpp", 8);
-    RFP_ROW("v_min_f32_dpp", 4);
-    RFP_ROW("v_min_f32_dpp", 2);
-    RFP_ROW("v_min_f32_dpp", 1);
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return fminf(fminf(r0, r1), fminf(r2, r3));
-}
-__device__ __forceinline__ float wave_max_f32(float v) {
-    RFP_ROW("v_max_f32_dpp", 8);
-    RFP_ROW("v_max_f32_dpp", 4);
-    RFP_ROW("v_max_f32_dpp", 2);
-    RFP_ROW("v_max_f32_dpp", 1);
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-    return fmaxf(fmaxf(r0, r1), fmaxf(r2, r3));
-}
-#undef RFP_ROW
 
 // One step of the staging boxes' octet reduction: three minima and three maxima with a DPP operand, interleaved
 #define RFP_OCT6(CTL)                                                   \
@@ -370,7 +327,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
     const int nfull = a.n[set], npad = a.npad[set];
     const float *__restrict__ src = a.src[set] + (size_t)bi * nfull * 3;
     // RAGGED: only the sample's first len points are sorted; the rest of the set is padding, as past n
-    const int n = RAGGED ? ragged_count(set ? len1 : len0, bi, nfull) : nfull;
+    const int n = RAGGED ? rf::ragged_count(set ? len1 : len0, bi, nfull) : nfull;
     float *__restrict__ oxyz = a.xyz[set] + (size_t)bi * npad * 3;
     int *__restrict__ oorig = a.orig[set] + (size_t)bi * npad;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -436,8 +393,8 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
         }                                                                         \
     }                                                                             \
     _Pragma("unroll") for (int c = 0; c < 3; c++) {                               \
-        lo[c] = wave_min_f32(lo[c]);                                              \
-        hi[c] = wave_max_f32(hi[c]);                                              \
+        lo[c] = rf::wave_min_f32(lo[c]);                                          \
+        hi[c] = rf::wave_max_f32(hi[c]);                                          \
     }
         RFP_BBOX_PASS(false)
         if (!(isfinite(lo[0]) && isfinite(lo[1]) && isfinite(lo[2]) && isfinite(hi[0]) && isfinite(hi[1]) && isfinite(hi[2]))) {  // (uniform)
@@ -525,7 +482,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
             c4[k] = ahist[wave][lane * 4 + k];
             sm += c4[k];
         }
-        const unsigned incl = wave_incl_scan(sm);
+        const unsigned incl = rf::wave_incl_scan(sm);
         const unsigned total = max((unsigned)__builtin_amdgcn_readlane((int)incl, 63), 1u);
         unsigned run = incl - sm;
         // (equal-mass cells by ONE float reciprocal per table instead of an integer division per bin: a cell boundary may move by
@@ -559,7 +516,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
             c4[k] = yhist[wave * HB + lane * 4 + k];
             sm += c4[k];
         }
-        const unsigned incl = wave_incl_scan(sm);
+        const unsigned incl = rf::wave_incl_scan(sm);
         const unsigned total = max((unsigned)__builtin_amdgcn_readlane((int)incl, 63), 1u);
         unsigned run = incl - sm;
         const float per = (float)SS / (float)total;
@@ -660,7 +617,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
             v[it] = it < steps ? h4[it * 64 + lane] : make_uint4(0, 0, 0, 0);
             tot += v[it].x + v[it].y + v[it].z + v[it].w;
         }
-        tot = wave_incl_scan(tot);
+        tot = rf::wave_incl_scan(tot);
         if (lane == 63) wsum[wave] = tot;
         __syncthreads();
         // the 16 wave totals: ONE LDS read per lane and a wave scan (a loop over wsum[] is a chain of
@@ -669,7 +626,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
         // them as well -- the sums of lanes 0..15 are not touched by the lanes behind them -- and a slice's count is the difference
         // of two row ends.  Summed by a loop at the head of the staging it was 16 LDS reads in every thread of a second slice.)
         const unsigned wtot = lane < (half + 1) * (STPB / 64) ? (&lds.wtab[0][0])[lane] : 0u;
-        const unsigned wincl = wave_incl_scan(wtot);
+        const unsigned wincl = rf::wave_incl_scan(wtot);
         unsigned carry = (unsigned)__builtin_amdgcn_readlane((int)(wincl - wtot), __builtin_amdgcn_readfirstlane(wave));
         cown = __builtin_amdgcn_readlane((int)wincl, STPB / 64 - 1);
         static_assert(STPB / 64 == 16 && RFP_SORT_SPLIT <= 4, "a row of the wave scan per slice");
@@ -684,7 +641,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_reg_kernel(SortArgs a, const in
         for (int it = 0; it < STEPS; it++) {
             if (it < steps) {  // uniform
                 const unsigned sm = v[it].x + v[it].y + v[it].z + v[it].w;
-                const unsigned incl = wave_incl_scan(sm);
+                const unsigned incl = rf::wave_incl_scan(sm);
                 uint4 out;
                 out.x = carry + incl - sm;
                 out.y = out.x + v[it].x;
@@ -842,7 +799,7 @@ __global__ __launch_bounds__(STPB) void nnp_sort_kernel(SortArgs a, const int *_
     if (threadIdx.x == 0) nbad = 0;
     const int nfull = a.n[set], npad = a.npad[set];
     const float *__restrict__ src = a.src[set] + (size_t)bi * nfull * 3;
-    const int n = RAGGED ? ragged_count(set ? len1 : len0, bi, nfull) : nfull;  // (as nnp_sort_reg_kernel)
+    const int n = RAGGED ? rf::ragged_count(set ? len1 : len0, bi, nfull) : nfull;  // (as nnp_sort_reg_kernel)
     float *__restrict__ oxyz = a.xyz[set] + (size_t)bi * npad * 3;
     int *__restrict__ oorig = a.orig[set] + (size_t)bi * npad;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1120,52 +1077,21 @@ struct EmitView {
     int4 *rec;                 // (b, npad) one 16-byte record per query: {wp, own.x, own.y, own.z (float bits)}
     unsigned long long *mask;  // (b, npad / 64)
 };
-__host__ __device__ inline size_t emit_align(size_t v) { return (v + 255) / 256 * 256; }
 __host__ __device__ inline size_t emit_set_bytes(int b, int npad) {
-    return emit_align((size_t)b * npad * sizeof(int4)) + emit_align((size_t)b * (npad / 64) * sizeof(unsigned long long));
+    return rf::align256((size_t)b * npad * sizeof(int4)) + rf::align256((size_t)b * (npad / 64) * sizeof(unsigned long long));
 }
 __host__ __device__ inline EmitView emit_layout(char *base, int b, int npad0, int npad1, int set) {
     char *p = base + (set ? emit_set_bytes(b, npad0) : 0);
     const int npad = set ? npad1 : npad0;
     EmitView v;
     v.rec = (int4 *)p;
-    p += emit_align((size_t)b * npad * sizeof(int4));
+    p += rf::align256((size_t)b * npad * sizeof(int4));
     v.mask = (unsigned long long *)p;
     return v;
 }
 
-__device__ __forceinline__ float min3_acc(float acc, float a, float b) {
-    asm("v_min3_f32 %0, %0, %1, %2" : "+v"(acc) : "v"(a), "v"(b));
-    return acc;
-}
-
-#define RFP_DPP(OP, N) asm volatile("s_nop 1\n\t" OP " %0, %0, %0 row_ror:" #N " row_mask:0xf bank_mask:0xf" : "+v"(v))
-// uniform minimum / maximum over the wave: DPP row rotations, then the four row results
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
-    RFP_DPP("v_min_u32_dpp", 8);
-    RFP_DPP("v_min_u32_dpp", 4);
-    RFP_DPP("v_min_u32_dpp", 2);
-    RFP_DPP("v_min_u32_dpp", 1);
-    const unsigned r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
-    const unsigned r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
-    return min(min(r0, r1), min(r2, r3));
-}
-// (inputs are +-inf or non-negative distances, never NaN; non-negative floats order as integers)
-__device__ __forceinline__ float wave_max_nonneg(float f) {
-    // -inf (lanes that do not take part) maps to 0, which never exceeds a participant's value
-    unsigned v = f < 0.f ? 0u : __float_as_uint(f);
-    RFP_DPP("v_max_u32_dpp", 8);
-    RFP_DPP("v_max_u32_dpp", 4);
-    RFP_DPP("v_max_u32_dpp", 2);
-    RFP_DPP("v_max_u32_dpp", 1);
-    const unsigned r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
-    const unsigned r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
-    return __uint_as_float(max(max(r0, r1), max(r2, r3)));
-}
-#undef RFP_DPP
-
-// Bounding box of the lanes with `on` set: the three wave_min_f32 and the three wave_max_f32 of a re-key as ONE
-// instruction stream.  Each of the six chains is the body of wave_min_f32 / wave_max_f32 -- the same four row
+// Bounding box of the lanes with `on` set: the three rf::wave_min_f32 and the three rf::wave_max_f32 of a re-key as ONE
+// instruction stream.  Each of the six chains is the body of rf::wave_min_f32 / rf::wave_max_f32 (wave.hpp) -- the same four row
 // rotations in the same order, the same combination of the four row results -- but the chains are interleaved: a
 // rotation reads a register written five instructions earlier, so one s_nop at the head covers all 24 of them
 // (one by one they are 24 x (s_nop 1 + DPP), all on the traversal's serial chain).
@@ -1211,7 +1137,7 @@ __device__ __forceinline__ float scan8(const float (&r)[24], float qx, float qy,
     for (int u = 0; u < 8; u += 2) {
         const float d0 = rf::d2_fma(r[u * 3 + 0] - qx, r[u * 3 + 1] - qy, r[u * 3 + 2] - qz);
         const float d1 = rf::d2_fma(r[u * 3 + 3] - qx, r[u * 3 + 4] - qy, r[u * 3 + 5] - qz);
-        cm = min3_acc(cm, d0, d1);
+        cm = rf::min3_acc(cm, d0, d1);
     }
     return cm;
 }
@@ -1357,7 +1283,7 @@ __device__ __forceinline__ void sweep_group(
             // the step's serial chain (reduction, box load, tests) goes ahead of other waves' scans:
             // -3 % at 16384^2, nothing at C2; the opposite priority is 3 % slower
             __builtin_amdgcn_s_setprio(2);
-            unsigned kmin = wave_min_u32(lmin);
+            unsigned kmin = rf::wave_min_u32(lmin);
             if (kmin == 0xFFFFFFFFu) break;
             if (shared4 && !TRACK) cull = fminf(cull, __int_as_float(shbest[lane]));
             float bound = __uint_as_float(kmin & ~IDMASK);
@@ -1378,10 +1304,10 @@ __device__ __forceinline__ void sweep_group(
                 if constexpr (ONE) {
                     wave_box_f32(on, qx, qy, qz, alo, ahi);
                 } else {
-                    alo[0] = wave_min_f32(on ? qx : INFINITY), alo[1] = wave_min_f32(on ? qy : INFINITY);
-                    alo[2] = wave_min_f32(on ? qz : INFINITY);
-                    ahi[0] = wave_max_f32(on ? qx : -INFINITY), ahi[1] = wave_max_f32(on ? qy : -INFINITY);
-                    ahi[2] = wave_max_f32(on ? qz : -INFINITY);
+                    alo[0] = rf::wave_min_f32(on ? qx : INFINITY), alo[1] = rf::wave_min_f32(on ? qy : INFINITY);
+                    alo[2] = rf::wave_min_f32(on ? qz : INFINITY);
+                    ahi[0] = rf::wave_max_f32(on ? qx : -INFINITY), ahi[1] = rf::wave_max_f32(on ? qy : -INFINITY);
+                    ahi[2] = rf::wave_max_f32(on ? qz : -INFINITY);
                 }
                 if constexpr (RFP_REKEY_STATS) n_rekey++;
                 lmin = 0xFFFFFFFFu;
@@ -1404,7 +1330,7 @@ __device__ __forceinline__ void sweep_group(
                         lmin = min(lmin, key);
                     }
                 }
-                kmin = wave_min_u32(lmin);
+                kmin = rf::wave_min_u32(lmin);
                 if (kmin == 0xFFFFFFFFu) break;
                 bound = __uint_as_float(kmin & ~IDMASK);
                 if (__builtin_amdgcn_ballot_w64(cull >= bound) == 0ull) break;
@@ -1613,10 +1539,10 @@ __device__ __forceinline__ void sweep_group(
     // queries whose minimum was attained in more than one visited block: second traversal
     const bool flagged = tie && part;
     if (__ballot(flagged) != 0ull) {
-        const float flo[3] = {wave_min_f32(flagged ? qx : INFINITY), wave_min_f32(flagged ? qy : INFINITY),
-                              wave_min_f32(flagged ? qz : INFINITY)};
-        const float fhi[3] = {wave_max_f32(flagged ? qx : -INFINITY), wave_max_f32(flagged ? qy : -INFINITY),
-                              wave_max_f32(flagged ? qz : -INFINITY)};
+        const float flo[3] = {rf::wave_min_f32(flagged ? qx : INFINITY), rf::wave_min_f32(flagged ? qy : INFINITY),
+                              rf::wave_min_f32(flagged ? qz : INFINITY)};
+        const float fhi[3] = {rf::wave_max_f32(flagged ? qx : -INFINITY), rf::wave_max_f32(flagged ? qy : -INFINITY),
+                              rf::wave_max_f32(flagged ? qz : -INFINITY)};
         cull = flagged ? best : -INFINITY;  // the wave's own minima are final: match against them
         unsigned besti2 = 0xFFFFFFFFu;
         int wpos2 = -1;
@@ -1663,7 +1589,7 @@ __device__ __forceinline__ void sweep_group(
     if constexpr (GRAD) {
         // index 0 of the NaN / no-match policy above = the candidate set's point with ORIGINAL index 0
         const int *pos0 = (const int *)((const char *)(cd ? b64_1 : b64_0) +
-                                        emit_align((size_t)a.b * (a.npad[cd] / SB) * B64F * sizeof(float)));
+                                        rf::align256((size_t)a.b * (a.npad[cd] / SB) * B64F * sizeof(float)));
         const int p0 = pos0[bi];  // uniform
         const EmitView ev = emit_layout(ge.base, a.b, a.npad[0], a.npad[1], dir);
         const int w = (qnan || besti == 0xFFFFFFFFu) ? p0 : wpos;
@@ -1833,8 +1759,8 @@ __device__ __forceinline__ void sweep_tile16(
         const float4 r0 = g.r0, r1 = g.r1, r2 = g.r2;
         const float d0 = rf::d2_fma(r0.x - qx, r0.y - qy, r0.z - qz), d1 = rf::d2_fma(r0.w - qx, r1.x - qy, r1.y - qz);
         const float d2 = rf::d2_fma(r1.z - qx, r1.w - qy, r2.x - qz), d3 = rf::d2_fma(r2.y - qx, r2.z - qy, r2.w - qz);
-        float cm = min3_acc(INFINITY, d0, d1);
-        cm = min3_acc(cm, d2, d3);
+        float cm = rf::min3_acc(INFINITY, d0, d1);
+        cm = rf::min3_acc(cm, d2, d3);
         return quad_min_f32(cm);
     };
     auto take = [&](bool on, float cm, int blk) {
@@ -1895,7 +1821,7 @@ __device__ __forceinline__ void sweep_tile16(
             for (int s0 = 0; s0 < nsb; s0 += 64) seed_cand(s0 + lane, s0 + lane < nsb ? tile_key(s0 + lane) : INFINITY);
         }
         if (n0 == 0) {  // uniform
-            kmin = wave_min_u32(kmin);
+            kmin = rf::wave_min_u32(kmin);
             if (lane == 0) sbl[0] = kmin & IDMASK;
             n0 = 1;
         }
@@ -1927,7 +1853,7 @@ __device__ __forceinline__ void sweep_tile16(
         }
         stamp(1);
         // 3. the tile's superblock list: box-to-box bound <= the largest minimum of the tile's queries
-        const float U = wave_max_nonneg(part ? best : -INFINITY);
+        const float U = rf::wave_max_nonneg(part ? best : -INFINITY);
         int nl = 0;
         auto list_cand = [&](int s, float lb) {
             const bool keep = s < nsb && lb <= U;
@@ -2103,7 +2029,7 @@ __device__ __forceinline__ void sweep_tile16(
     }
     if constexpr (GRAD) {
         const int *pos0 = (const int *)((const char *)(cd ? b64_1 : b64_0) +
-                                        emit_align((size_t)a.b * (a.npad[cd] / SB) * B64F * sizeof(float)));
+                                        rf::align256((size_t)a.b * (a.npad[cd] / SB) * B64F * sizeof(float)));
         const int p0 = pos0[bi];  // uniform
         const EmitView ev = emit_layout(ge.base, a.b, a.npad[0], a.npad[1], dir);
         const int w = (qnan || besti == 0xFFFFFFFFu) ? p0 : wpos;
@@ -2184,7 +2110,7 @@ __global__ __launch_bounds__(64 * NSH) __attribute__((amdgpu_waves_per_eu(RFP_WP
         // the candidate cloud's crowded flag (written by the sort behind pos0): uniform per workgroup
         const int cdk = 1 - dir;
         const int *flags = (const int *)((const char *)(cdk ? b64_1 : b64_0) +
-                                         emit_align((size_t)a.b * (a.npad[cdk] / SB) * B64F * sizeof(float))) + a.b;
+                                         rf::align256((size_t)a.b * (a.npad[cdk] / SB) * B64F * sizeof(float))) + a.b;
         if (flags[bi]) {
             sweep_group<true, GRAD>(a, ge, dir, bi * a.groups[dir] + wg, wib, lane, keys_dyn, shbest, md, mi, mp, xyz0, xyz1,
                                     orig0, orig1, b16_0, b16_1, b64_0, b64_1, dist0, dist1, idx0, idx1, stats);
@@ -2394,8 +2320,6 @@ __global__ __launch_bounds__(GS_TPB) void nnp_grad_sorted_kernel(GradSArgs a) {
 
 int round_up(long v, int q) { return (int)((v + q - 1) / q * q); }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 // workgroups sorting one cloud of n points, and the padded record count of a sorted set: a split
 // cloud carries one more superblock (half 0's segment is padded to a multiple of 64 on its own)
 int sort_split_of(int n) { return (RFP_SORT_SPLIT > 1 && n > RFP_SORT_SPLIT_ABOVE && n <= RPT * STPB) ? RFP_SORT_SPLIT : 1; }
@@ -2414,9 +2338,9 @@ bool pruned_supported(int b, int n, int m) {
 size_t sorted_bytes(int b, int n) {
     if (b <= 0 || n <= 0 || n > kMaxPoints) return 0;
     const size_t npad = npad_of(n);
-    return align256((size_t)b * npad * 3 * sizeof(float) + 256)  // + prefetch overrun
-           + align256((size_t)b * npad * sizeof(int)) + align256((size_t)b * (npad / SB) * B16F * sizeof(float)) +
-           align256((size_t)b * (npad / SB) * B64F * sizeof(float)) + align256((size_t)3 * b * sizeof(int));  // pos0 (b) | crowded (b) | non-finite (b)
+    return rf::align256((size_t)b * npad * 3 * sizeof(float) + 256)  // + prefetch overrun
+           + rf::align256((size_t)b * npad * sizeof(int)) + rf::align256((size_t)b * (npad / SB) * B16F * sizeof(float)) +
+           rf::align256((size_t)b * (npad / SB) * B64F * sizeof(float)) + rf::align256((size_t)3 * b * sizeof(int));  // pos0 (b) | crowded (b) | non-finite (b)
 }
 
 Sorted sorted_view(int b, int n, const void *buf) {
@@ -2425,20 +2349,20 @@ Sorted sorted_view(int b, int n, const void *buf) {
     Sorted v;
     v.npad = (int)npad;
     v.xyz = (const float *)w;
-    w += align256((size_t)b * npad * 3 * sizeof(float) + 256);
+    w += rf::align256((size_t)b * npad * 3 * sizeof(float) + 256);
     v.orig = (const int *)w;
-    w += align256((size_t)b * npad * sizeof(int));
+    w += rf::align256((size_t)b * npad * sizeof(int));
     v.box16 = (const float *)w;
-    w += align256((size_t)b * (npad / SB) * B16F * sizeof(float));
+    w += rf::align256((size_t)b * (npad / SB) * B16F * sizeof(float));
     v.box64 = (const float *)w;
-    w += align256((size_t)b * (npad / SB) * B64F * sizeof(float));
+    w += rf::align256((size_t)b * (npad / SB) * B64F * sizeof(float));
     v.pos0 = (const int *)w;
     return v;
 }
 
 size_t pruned_workspace_bytes(int b, int n, int m) {
     if (!pruned_supported(b, n, m)) return 0;
-    return sorted_bytes(b, n) + sorted_bytes(b, m) + align256(32 * sizeof(unsigned long long));
+    return sorted_bytes(b, n) + sorted_bytes(b, m) + rf::align256(32 * sizeof(unsigned long long));
 }
 
 // Sort `nsets` (1 or 2) sets of b clouds in ONE launch (one workgroup per cloud).

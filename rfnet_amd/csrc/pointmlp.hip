@@ -183,11 +183,6 @@ __global__ __launch_bounds__(MP_TPB) void maxpool_idx_stage2_kernel(int c, int n
 // there, and the fold walks the ceil(len / MP_STRIP) strips that were written -- the other partials are never read, so the
 // workspace needs no initial value.  Per sample this is the dense kernels' arithmetic on x[bi, :len[bi]]: same strips, same
 // point-lane order, same tie rule.
-__device__ __forceinline__ int mp_len(const int *__restrict__ len, int bi, int n) {
-    if (!len) return n;
-    const int v = len[bi];
-    return v < 1 ? 1 : (v > n ? n : v);
-}
 
 template <bool IDX>
 __global__ __launch_bounds__(MP_TPB) void maxpool_len_stage1_kernel(int n, int c, int nstrips, const float *__restrict__ x,
@@ -196,7 +191,7 @@ __global__ __launch_bounds__(MP_TPB) void maxpool_len_stage1_kernel(int n, int c
     __shared__ float4 red[MP_TPB];
     __shared__ int4 redi[IDX ? MP_TPB : 1];
     const int bi = blockIdx.y, strip = blockIdx.x;
-    const int cnt = mp_len(len, bi, n);
+    const int cnt = rf::ragged_count(len, bi, n);
     const int jfirst = strip * MP_STRIP;
     if (jfirst >= cnt) return;
     const int quads = c >> 2, ppi = MP_TPB / quads;
@@ -245,7 +240,7 @@ __global__ __launch_bounds__(MP_TPB) void maxpool_len_stage2_kernel(int n, int c
                                                                     const int *__restrict__ parti, float *__restrict__ out,
                                                                     int *__restrict__ idx) {
     const int bi = blockIdx.x;
-    const int written = (mp_len(len, bi, n) + MP_STRIP - 1) / MP_STRIP;  // strips stage 1 wrote for this sample
+    const int written = (rf::ragged_count(len, bi, n) + MP_STRIP - 1) / MP_STRIP;  // strips stage 1 wrote for this sample
     for (int ch = threadIdx.x; ch < c; ch += MP_TPB) {
         float m = -INFINITY;
         int mj = 0;

@@ -17,7 +17,6 @@
 #include "nn_pruned.hpp"
 
 namespace {
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // The chain on checked arguments.  ragged (rf_sample_and_group_lengths): the sort, FPS and the ball query take the counts -- len
@@ -31,7 +30,7 @@ int chain(int b, int n, int npoint, float radius, const float *radius_dev, int n
     char *w = (char *)workspace;
     const size_t temp_floats = rf_farthestpointsampling_temp_floats(b, n);
     float *temp = temp_floats ? (float *)w : nullptr;
-    w += align256(sizeof(float) * temp_floats);
+    w += rf::align256(sizeof(float) * temp_floats);
     const rfp::Sorted so = rfp::sorted_view(b, n, w);
     const int nn[1] = {n};
     const float *src[1] = {xyz};
@@ -96,7 +95,7 @@ size_t rf_sample_and_group_workspace_bytes(int b, int n) {
     if (b <= 0 || n <= 0) return 0;
     const size_t sorted = rf_queryballpoint_boxes_workspace_bytes(b, n);
     if (!sorted) return 0;
-    return align256(sizeof(float) * rf_farthestpointsampling_temp_floats(b, n)) + sorted;
+    return rf::align256(sizeof(float) * rf_farthestpointsampling_temp_floats(b, n)) + sorted;
 }
 
 int rf_sample_and_group(int b, int n, int npoint, float radius, const float *radius_dev, int nsample, const float *xyz,

@@ -48,9 +48,9 @@ struct Slot {
     int k;
 };
 
-// ---- single-instruction helpers.  hipcc wraps fminf/fmaxf in canonicalising v_max x,x and
-// expands a float DPP reduction step into mov/nop/mov_dpp/max/max; on the serial path of FPS
-// every instruction counts, so these are written as the one instruction they are.  (Inputs are
+// ---- single-instruction helpers.  hipcc wraps fminf/fmaxf in canonicalising v_max x,x; on the
+// serial path of FPS every instruction counts, so these are written as the one instruction they
+// are, as are the DPP row reductions rf::row_allmax / rf::row_allmin_u (wave.hpp).  (Inputs are
 // never NaN here: distances of finite points, or the -1 / 1e38 sentinels.)
 __device__ __forceinline__ float vmin(float a, float b) {
     float r;
@@ -62,28 +62,9 @@ __device__ __forceinline__ float vmax3(float a, float b, float c) {
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
-// v = max(v, v rotated by N lanes inside each 16-lane row).  The s_nop covers the
-// VALU-write -> DPP-read hazard (the assembler/hazard recogniser does not look inside asm).
-#define RF_DPP_STEP(OP, N)                                                                          \
-    asm volatile("s_nop 1\n\t" OP " %0, %0, %0 row_ror:" #N " row_mask:0xf bank_mask:0xf" : "+v"(v))
-__device__ __forceinline__ float row_allmax(float v) {
-    RF_DPP_STEP("v_max_f32_dpp", 8);
-    RF_DPP_STEP("v_max_f32_dpp", 4);
-    RF_DPP_STEP("v_max_f32_dpp", 2);
-    RF_DPP_STEP("v_max_f32_dpp", 1);
-    return v;
-}
-__device__ __forceinline__ unsigned row_allmin_u(unsigned v) {
-    RF_DPP_STEP("v_min_u32_dpp", 8);
-    RF_DPP_STEP("v_min_u32_dpp", 4);
-    RF_DPP_STEP("v_min_u32_dpp", 2);
-    RF_DPP_STEP("v_min_u32_dpp", 1);
-    return v;
-}
-#undef RF_DPP_STEP
 // maximum over the wave, uniform: row all-reduce, then the four row results
 __device__ __forceinline__ float wave_allmax(float v) {
-    v = row_allmax(v);
+    v = rf::row_allmax(v);
     const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
     const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
     const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32));
@@ -203,9 +184,9 @@ __global__ __launch_bounds__(NT) void fps_reg_kernel(int n, int m, const float *
         __syncthreads();
         const float sd = slot_d[buf][lane & 15];
         const int sk = slot_k[buf][lane & 15];
-        const float gm = row_allmax(sd);
+        const float gm = rf::row_allmax(sd);
         const unsigned rank = sd == gm ? tie_rank(sk) : 0xFFFFFFFFu;
-        const unsigned gr = __builtin_amdgcn_readfirstlane(row_allmin_u(rank));
+        const unsigned gr = __builtin_amdgcn_readfirstlane(rf::row_allmin_u(rank));
         const int gk = (int)(((gr & 0x3FFFFFu) << 9) | (gr >> 22));
         ox = P[gk * 3 + 0];  // uniform address: scalar loads
         oy = P[gk * 3 + 1];
@@ -238,12 +219,6 @@ __global__ __launch_bounds__(NT) void fps_reg_kernel(int n, int m, const float *
 // Round 3 built this with 8 waves x 32 points per lane and it lost (1.16 vs 1.12 ms: the one wave that must scan issues alone at
 // half the rate of two interleaved ones).  Here 16 waves x 16 points: a touched wave's scan is half as long, the regions are
 // tighter, and the wave's rank reduction is taken only when two lanes tie for the maximum.
-__device__ __forceinline__ unsigned wave_allmin_u(unsigned v) {
-    v = row_allmin_u(v);
-    const unsigned r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
-    const unsigned r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
-    return min(min(r0, r1), min(r2, r3));
-}
 
 // RAGGED: the sort was given the same counts, so the real records are the cloud's first nv points and the compaction below finds
 // exactly nv of them; waves whose chunk lies behind them hold padding only (boxes +-inf, td = -1) and are never touched.  Once the
@@ -400,7 +375,7 @@ __global__ __launch_bounds__(NT) void fps_sorted_kernel(int n, int m, int npad, 
                 unsigned lr = 0xFFFFFFFFu;
 #pragma unroll
                 for (int s = 0; s < PPT; s++) lr = min(lr, td[s] == mx ? rk[s] : 0xFFFFFFFFu);
-                const unsigned best = wave_allmin_u(mx == wm ? lr : 0xFFFFFFFFu);
+                const unsigned best = rf::wave_min_u32(mx == wm ? lr : 0xFFFFFFFFu);
                 const unsigned long long bl = __ballot(mx == wm && lr == best);
                 wl = bl ? __builtin_ctzll(bl) : wl;
             }
@@ -418,9 +393,9 @@ __global__ __launch_bounds__(NT) void fps_sorted_kernel(int n, int m, int npad, 
         __syncthreads();
         const float sd = slot_d[buf][lane & 15];
         const unsigned sr = slot_r[buf][lane & 15];
-        const float gm = row_allmax(sd);
+        const float gm = rf::row_allmax(sd);
         const unsigned rank = sd == gm ? sr : 0xFFFFFFFFu;
-        const unsigned gr = __builtin_amdgcn_readfirstlane(row_allmin_u(rank));
+        const unsigned gr = __builtin_amdgcn_readfirstlane(rf::row_allmin_u(rank));
         const int gk = gr == 0xFFFFFFFFu ? 0 : (int)(((gr & 0x3FFFFFu) << 9) | (gr >> 22));
         ox = P[gk * 3 + 0];  // uniform address: scalar loads
         oy = P[gk * 3 + 1];

@@ -23,15 +23,6 @@ namespace {
 constexpr int CB_TPB = 1024;
 constexpr int CB_MAXBINS = 20480;  // counters per workgroup (80 KiB of LDS; + 64 KiB of staged slot numbers: 144 of the CU's 160)
 
-__device__ __forceinline__ unsigned cb_wave_incl_scan(unsigned v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(v, o, 64);
-        if ((int)(threadIdx.x & 63) >= o) v += t;
-    }
-    return v;
-}
-
 // idx (b, S) -> row_start (b, n + 1), perm (b, S): perm[row_start[r] .. row_start[r + 1]) = the slots whose idx is r (any order).
 // Slots whose idx is outside [0, n) are in no row (the reference would write outside its tensor for them).
 // REG (CB_RPT > 0): S <= CB_TPB * CB_RPT -- a thread's slots are loaded ONCE, all loads in flight together, and both passes (counts, places)
@@ -59,7 +50,7 @@ template <>
 struct SlotBounds<false> {};
 __device__ __forceinline__ SlotBounds<false> cb_bounds(const SlotMask<false> &, int, int) { return {}; }
 __device__ __forceinline__ SlotBounds<true> cb_bounds(const SlotMask<true> &mk, int bi, int n) {
-    return {rfi::ragged_count(mk.len1, bi, n), rfi::ragged_count(mk.len2, bi, mk.m), mk.k};
+    return {rf::ragged_count(mk.len1, bi, n), rf::ragged_count(mk.len2, bi, mk.m), mk.k};
 }
 __device__ __forceinline__ int cb_key(const SlotBounds<false> &, int, int key) { return key; }
 __device__ __forceinline__ int cb_key(const SlotBounds<true> &sb, int slot, int key) {
@@ -118,7 +109,7 @@ __global__ __launch_bounds__(CB_TPB) void rows_csr_build_kernel(int n, int S, in
         const int i = tid * per + q;
         mine += i < nbl ? cb_cnt[i] : 0u;
     }
-    const unsigned incl = cb_wave_incl_scan(mine);
+    const unsigned incl = rf::wave_incl_scan(mine);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     unsigned base = 0;
@@ -274,8 +265,6 @@ __global__ __launch_bounds__(CG_TPB) void rows_csr_gather_kernel(int n, int c, i
     }
 }
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 
 namespace rfs {
@@ -287,14 +276,14 @@ bool rows_csr_supported(int b, int n, int c, long S, int K) {
 }
 
 size_t rows_csr_workspace_bytes(int b, int n, long S) {
-    return align256(sizeof(int) * (size_t)b * ((size_t)n + 1)) + align256(sizeof(int) * (size_t)b * (size_t)S);
+    return rf::align256(sizeof(int) * (size_t)b * ((size_t)n + 1)) + rf::align256(sizeof(int) * (size_t)b * (size_t)S);
 }
 
 template <bool MASKED>
 static int rows_csr_sort_impl(int b, int n, long S, const int *idx, void *workspace, const char *build_name, hipStream_t s,
                               SlotMask<MASKED> mask) {
     int *row_start = (int *)workspace;
-    int *perm = (int *)((char *)workspace + align256(sizeof(int) * (size_t)b * ((size_t)n + 1)));
+    int *perm = (int *)((char *)workspace + rf::align256(sizeof(int) * (size_t)b * ((size_t)n + 1)));
     // workgroups per sample: enough to put ~128 CUs to work, every range at least 2048 bins, at most 32768
     int H = rf::ceil_div(n, CB_MAXBINS);
     while ((long)b * H < 128 && n / (2 * H) >= 2048 && H < 8) H *= 2;
@@ -323,7 +312,7 @@ int rows_csr_sort_masked(int b, int n, int m, int k, const int *idx, const int *
 }
 
 const int *rows_csr_perm(int b, int n, const void *workspace) {
-    return (const int *)((const char *)workspace + align256(sizeof(int) * (size_t)b * ((size_t)n + 1)));
+    return (const int *)((const char *)workspace + rf::align256(sizeof(int) * (size_t)b * ((size_t)n + 1)));
 }
 
 int rows_csr_scatter(int b, int n, int c, long S, int K, const float *src, const int *idx, const float *weight, float *dst,

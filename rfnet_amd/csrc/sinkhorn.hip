@@ -20,8 +20,6 @@
 
 namespace {
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 constexpr int SK_TPB = 256;      // rows of a workgroup: one per lane
 constexpr int SK_CT = 256;       // columns staged in LDS at a time (4 KiB)
 constexpr int SK_CB = 8;         // columns per renewal of the running maximum; divides SK_CT
@@ -33,12 +31,6 @@ __host__ __device__ __forceinline__ int sk_tiles(int L) { return (L + SK_CT - 1)
 // tiles per chunk and chunks, from the valid column count alone
 __host__ __device__ __forceinline__ int sk_tpc(int L) { return (sk_tiles(L) + SK_NSPLIT - 1) / SK_NSPLIT; }
 __device__ __forceinline__ int sk_nch(int L) { return (sk_tiles(L) + sk_tpc(L) - 1) / sk_tpc(L); }
-
-__device__ __forceinline__ int sk_len(const int *__restrict__ len, int s, int full) {
-    if (!len) return full;
-    const int v = len[s];
-    return v < 1 ? 1 : (v > full ? full : v);
-}
 
 __device__ __forceinline__ float sk_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float sk_log2(float x) { return __builtin_amdgcn_logf(x); }
@@ -97,7 +89,7 @@ __global__ __launch_bounds__(SK_TPB) void sk_sweep_kernel(SkStep a) {
     const int k = blockIdx.z, s = blockIdx.y, tid = threadIdx.x;
     const int rt = blockIdx.x / SK_NSPLIT, ch = blockIdx.x % SK_NSPLIT;
     const int n = a.n, m = a.m;
-    const int L1 = sk_len(a.len1, s, n), L2 = sk_len(a.len2, s, m);
+    const int L1 = rf::ragged_count(a.len1, s, n), L2 = rf::ragged_count(a.len2, s, m);
     const bool rows2 = (k & 1) != 0, cols2 = k == 0 || k == 3;
     const int Lr = rows2 ? L2 : L1, Lc = cols2 ? L2 : L1;
     const int tpc = sk_tpc(Lc), tiles = sk_tiles(Lc), t0 = ch * tpc;
@@ -192,7 +184,7 @@ __global__ __launch_bounds__(SK_FIN_TPB) void sk_finish_kernel(SkFin a) {
     __shared__ double wsum[2][SK_FIN_TPB / 64];
     __shared__ float wmax[SK_FIN_TPB / 64];
     const int s = blockIdx.x, tid = threadIdx.x, n = a.n, m = a.m;
-    const int L1 = sk_len(a.len1, s, n), L2 = sk_len(a.len2, s, m);
+    const int L1 = rf::ragged_count(a.len1, s, n), L2 = rf::ragged_count(a.len2, s, m);
     const size_t R = 2 * ((size_t)n + m), base = (size_t)s * R;
     const bool grad = a.gpart != nullptr;
     double acc[2] = {0.0, 0.0};
@@ -253,9 +245,9 @@ SkLayout sk_layout(int b, int n, int m) {
     const size_t rows = (size_t)b * 2 * ((size_t)n + (size_t)m);
     SkLayout l;
     l.pot = 0;
-    l.part = l.pot + 2 * align256(rows * sizeof(float));
-    l.gpart = l.part + 2 * align256(rows * SK_NSPLIT * sizeof(float2));
-    l.total = l.gpart + align256(rows * SK_NSPLIT * 3 * sizeof(float));
+    l.part = l.pot + 2 * rf::align256(rows * sizeof(float));
+    l.gpart = l.part + 2 * rf::align256(rows * SK_NSPLIT * sizeof(float2));
+    l.total = l.gpart + rf::align256(rows * SK_NSPLIT * 3 * sizeof(float));
     return l;
 }
 
@@ -296,8 +288,8 @@ int rf_sinkhorn(int b, int n, int m, const float *xyz1, const float *xyz2, const
     // buffers | the gradient numerators of the final soft-min
     char *w = (char *)workspace;
     const size_t rows = (size_t)b * 2 * ((size_t)n + (size_t)m);
-    float *potb[2] = {(float *)(w + l.pot), (float *)(w + l.pot + align256(rows * sizeof(float)))};
-    float2 *partb[2] = {(float2 *)(w + l.part), (float2 *)(w + l.part + align256(rows * SK_NSPLIT * sizeof(float2)))};
+    float *potb[2] = {(float *)(w + l.pot), (float *)(w + l.pot + rf::align256(rows * sizeof(float)))};
+    float2 *partb[2] = {(float2 *)(w + l.part), (float2 *)(w + l.part + rf::align256(rows * SK_NSPLIT * sizeof(float2)))};
     float *gpart = grad1 ? (float *)(w + l.gpart) : nullptr;
 
     const int big = n > m ? n : m;

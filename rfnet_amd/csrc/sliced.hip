@@ -21,19 +21,11 @@
 
 namespace {
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 constexpr int SW_CHUNK = RF_SW_DIR_CHUNK;
 constexpr int SW_SORT_TPB = 1024;  // at most; a thread per 4 words below 8192 words, per 16 from there on
 constexpr int SW_TPB = 256;        // accumulate, and the merge of small clouds
 constexpr int SW_MERGE_MAX = 1024; // the merge of large ones: its walks are chains of dependent loads, so waves hide them
 constexpr unsigned long long SW_PAD = ~0ull;
-
-__device__ __forceinline__ int sw_len(const int *__restrict__ len, int s, int full) {
-    if (!len) return full;
-    const int v = len[s];
-    return v < 1 ? 1 : (v > full ? full : v);
-}
 
 // fp32 bits <-> uint32 that orders as the floats do (negative: all bits flipped, else the sign bit set)
 __device__ __forceinline__ unsigned sw_key(float p) {
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(SW_SORT_TPB) void sliced_sort_kernel(int b, int n, 
     extern __shared__ __attribute__((aligned(16))) unsigned long long sw_words[];  // [P]
     const int c = blockIdx.x, s = blockIdx.y, second = blockIdx.z;
     const int full = second ? m : n;
-    const int L = sw_len(second ? len2 : len1, s, full);
+    const int L = rf::ragged_count(second ? len2 : len1, s, full);
     const float *__restrict__ xyz = (second ? xyz2 : xyz1) + (size_t)s * full * 3;
     const size_t row = ((size_t)c * b + s) * full;
     float *__restrict__ val = (second ? val2 : val1) + row;
@@ -155,7 +147,7 @@ __global__ __launch_bounds__(SW_MERGE_MAX) void sliced_merge_kernel(int b, int n
                                                               double *__restrict__ coef2, double *__restrict__ cost) {
     __shared__ double wsum[SW_MERGE_MAX / 64];
     const int c = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
-    const int L1 = sw_len(len1, s, n), L2 = sw_len(len2, s, m);
+    const int L1 = rf::ragged_count(len1, s, n), L2 = rf::ragged_count(len2, s, m);
     const size_t row1 = ((size_t)c * b + s) * n, row2 = ((size_t)c * b + s) * m;
     const float *__restrict__ u = val1 + row1, *__restrict__ v = val2 + row2;
     const double den = (double)L1 * (double)L2;  // exact; applied once, as a division
@@ -204,7 +196,7 @@ __global__ __launch_bounds__(SW_TPB) void sliced_accumulate_kernel(SwAcc a) {
     if (a.grad1 && k < a.n + a.m) {
         const bool second = k >= a.n;
         const int kk = second ? k - a.n : k, full = second ? a.m : a.n;
-        const int L = sw_len(second ? a.len2 : a.len1, s, full);
+        const int L = rf::ragged_count(second ? a.len2 : a.len1, s, full);
         float *__restrict__ g = (second ? a.grad2 : a.grad1) + ((size_t)s * full + kk) * 3;
         if (kk < L) {
             double *__restrict__ ac = a.acc + ((size_t)s * (a.n + a.m) + k) * 3;
@@ -244,12 +236,12 @@ SwLayout sw_layout(int b, int n, int m, int nproj, int want_grad) {
     const size_t cc = nproj < SW_CHUNK ? nproj : SW_CHUNK, pts = (size_t)n + (size_t)m, rows = cc * (size_t)b;
     SwLayout l;
     l.val = 0;
-    l.idx = l.val + align256(rows * pts * sizeof(float));
-    l.cost = l.idx + align256(rows * pts * sizeof(int));
-    l.lacc = l.cost + align256(rows * sizeof(double));
-    l.coef = l.lacc + align256((size_t)b * sizeof(double));
-    l.acc = l.coef + (want_grad ? align256(rows * pts * sizeof(double)) : 0);
-    l.total = l.acc + (want_grad ? align256((size_t)b * pts * 3 * sizeof(double)) : 0);
+    l.idx = l.val + rf::align256(rows * pts * sizeof(float));
+    l.cost = l.idx + rf::align256(rows * pts * sizeof(int));
+    l.lacc = l.cost + rf::align256(rows * sizeof(double));
+    l.coef = l.lacc + rf::align256((size_t)b * sizeof(double));
+    l.acc = l.coef + (want_grad ? rf::align256(rows * pts * sizeof(double)) : 0);
+    l.total = l.acc + (want_grad ? rf::align256((size_t)b * pts * 3 * sizeof(double)) : 0);
     return l;
 }
 
