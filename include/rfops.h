@@ -390,6 +390,76 @@ int rf_sinkhorn(int b, int n, int m, const float *xyz1, const float *xyz2, const
                 const float *eps, int T, float *loss, float *pot, float *delta, float *grad1, float *grad2, void *workspace,
                 size_t workspace_bytes, rf_stream_t stream);
 
+/* ---- the Gridding layer and the Gridding loss: trilinear voxel grids, exact sums, with gradients -- */
+/* The occupancy family of completion losses (GRNet): every point spreads its mass trilinearly over the eight vertices of
+ * its cell of a regular grid, and the loss is the L1 difference of the two grids.  No correspondence, linear in the point
+ * count, and the cost of one cloud does not depend on the size of the other.  xyz1 (b, n, 3), xyz2 (b, m, 3) fp32; len1 /
+ * len2: device int32 (b) or NULL with rf_nn_distance_lengths' conventions -- read and clamped into [1, n] / [1, m] by the
+ * kernels.  No host synchronisation, at most three launches on `stream`: a call can be captured in a HIP graph.
+ *
+ * Grid: R = res vertices per axis, 2 <= R <= RF_GR_MAX_RES; lo < hi finite floats, the same box on all three axes; vertex k
+ * sits at lo + k h, h = (hi - lo) / (R - 1); the library forms inv_h = (float)((double)(R - 1) / ((double)hi - (double)lo))
+ * on the host.  Per point and axis, all in fp32:
+ *   u = (x - lo) * inv_h                        a subtraction, then a multiplication: two roundings
+ *   inside iff u >= 0 && u <= (float)(R - 1)    on all three axes; a NaN fails.  Points outside and rows behind the count
+ *                                               contribute nothing and get a gradient of exactly +0
+ *   i = min((int)floorf(u), R - 2),  t = u - (float)i      t is exact, in [0, 1], and 1 on the upper face
+ *   q1 = (int)rintf(t * 512.0f),  q0 = RF_GR_Q - q1
+ * For d in {0, 1}^3 the weight on vertex (ix + dx, iy + dy, iz + dz) is the INTEGER W_d = q_dx(x) q_dy(y) q_dz(z) <= 2^27;
+ * the eight weights of a point sum to exactly Q^3.  G(v) = sum over the points of W is an exact integer and mass is conserved
+ * exactly: sum_v G(v) = inside * Q^3.
+ *
+ * rf_gridding_loss: with (mu1, mu2) = (1, 1) for RF_GR_COUNTS and (L2, L1), the clamped counts, for RF_GR_DENSITY,
+ *   D(v) = mu1 G1(v) - mu2 G2(v), an int64: |D(v)| <= 2^16 2^16 2^27 = 2^59 and sum_v |D(v)| <= 2^60
+ *   loss[b]   = (float)((double)sum_v |D| / Q^3 / R^3)                  COUNTS: the mean over the vertices (GRNet's L1Loss)
+ *             = (float)((double)sum_v |D| / Q^3 / ((double)L1 * L2))    DENSITY: sum_v |G1 / L1 - G2 / L2|, in [0, 2]
+ *   inside[b] (2) int32: the inside counts of the two clouds
+ *   grad1 (b, n, 3), grad2 (b, m, 3), both given or both NULL.  With s(v) = sign(D(v)) in {-1, 0, 1}, w_k(0) = 1.0f - t_k and
+ *   w_k(1) = t_k in fp32, sigma_a(d) = +1 if d_a = 1 else -1:
+ *     grad1[i][a] = (float)((sum_{d = 0..7, dz fastest} (s(v_i + d) sigma_a(d)) (prod_{k != a} (double)w_k(d_k))) ((double)inv_h c1))
+ *   the sum in double from +0, c1 = 1 / (double)R^3 (COUNTS) or 1 / (double)L1 (DENSITY); grad2 the same with -s and c2 = 1 / R^3
+ *   or 1 / L2.  This is the analytic gradient of the unquantised trilinear loss under the signs of the quantised grid, 0 where
+ *   D(v) = 0.  Each product of two fp32 factors is exact in double, so a fused multiply-add could not change a bit.
+ *
+ * rf_gridding: the Gridding layer itself.  grid (b, R, R, R) fp32, x slowest: v = (ix R + iy) R + iz, the value
+ * (float)((double)G(v) / Q^3); every element is written, zeros where nothing fell.  inside (b) int32.
+ * rf_gridding_grad: its backward.  grad_xyz[i][a] = (float)((double)inv_h sum_d (sigma_a(d) (double)gg[v_i + d]) (prod_{k != a}
+ * (double)w_k(d_k))), the same order of d, the sum in double from +0; +0 for outside points and rows behind the count.
+ *
+ * Guarantees:
+ *   - Purity: two calls return identical bits; sample i is bit for bit the call on [i : i + 1]; a ragged call is bit for bit
+ *     the call on the sliced clouds; loss, grid and inside are bit-identical under any permutation of a cloud's points (the
+ *     sums are integers); the loss-only form returns the bits of the form with gradients.
+ *   - Self distance: loss(x, x) is +0 with all-zero gradients.
+ *   - Memory safety: a non-finite coordinate never moves a memory access -- it is simply outside.  Every loop bound is a count.
+ *   - No float atomics anywhere; no call uses hipMemset.
+ *
+ * Workspace, each part rounded up to 256 bytes, with nb = ceil(R / 16) bricks per axis:
+ *   rf_gridding_loss   4 * 2 b (nb^3 + 1)  list starts  + 8 b (n + m)  one record per point  + 8 b nb^3  one partial per brick,
+ *                      and with gradients  + b R^3  one sign byte per vertex
+ *   rf_gridding        4 b (nb^3 + 1)  + 8 b n
+ *
+ * Argument rules, all checked before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for n or m
+ * outside 1 ... RF_GR_MAX_POINTS, res outside 2 ... RF_GR_MAX_RES, b above 65535, a non-finite lo or hi or lo >= hi, an unknown
+ * mode, a NULL xyz / loss / grid / inside / grad_grid / grad_xyz, exactly one of grad1 / grad2 given, a tensor or count array
+ * not 4-byte aligned, a workspace that is NULL or not 16-byte aligned; RF_EWORKSPACE for a workspace smaller than the
+ * _workspace_bytes function states (0 for non-positive or unsupported sizes, positive otherwise).  All index arithmetic is in
+ * size_t. */
+#define RF_GR_Q 512
+#define RF_GR_MAX_RES 256
+#define RF_GR_MAX_POINTS 65536
+#define RF_GR_COUNTS 0
+#define RF_GR_DENSITY 1
+size_t rf_gridding_loss_workspace_bytes(int b, int n, int m, int res, int want_grad);
+int rf_gridding_loss(int b, int n, int m, int res, float lo, float hi, int mode, const float *xyz1, const float *xyz2,
+                     const int *len1, const int *len2, float *loss, int *inside, float *grad1, float *grad2, void *workspace,
+                     size_t workspace_bytes, rf_stream_t stream);
+size_t rf_gridding_workspace_bytes(int b, int n, int res);
+int rf_gridding(int b, int n, int res, float lo, float hi, const float *xyz, const int *len, float *grid, int *inside,
+                void *workspace, size_t workspace_bytes, rf_stream_t stream);
+int rf_gridding_grad(int b, int n, int res, float lo, float hi, const float *xyz, const int *len, const float *grad_grid,
+                     float *grad_xyz, rf_stream_t stream);
+
 /* ---- the exact earth mover's distance: optimal assignment with a certificate and gradients -- */
 /* The one-to-one assignment of minimal total distance between two clouds of EQUAL counts, by a deterministic Jacobi
  * auction with eps-scaling on an integer cost grid: a pure function of its inputs with a machine-checkable optimality

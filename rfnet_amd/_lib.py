@@ -67,6 +67,11 @@ SIGNATURES = {
     "rf_sliced_wasserstein": (_i, [_i, _i, _i, _i] + [_vp] * 9 + [_sz, _vp]),
     "rf_sinkhorn_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_sinkhorn": (_i, [_i, _i, _i] + [_vp] * 4 + [_i, _vp, _i] + [_vp] * 6 + [_sz, _vp]),  # (eps: a HOST float array)
+    "rf_gridding_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "rf_gridding_loss": (_i, [_i, _i, _i, _i, _f, _f, _i] + [_vp] * 9 + [_sz, _vp]),
+    "rf_gridding_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_gridding": (_i, [_i, _i, _i, _f, _f] + [_vp] * 5 + [_sz, _vp]),
+    "rf_gridding_grad": (_i, [_i, _i, _i, _f, _f] + [_vp] * 5),
     "rf_emd_assign_supported": (_i, [_i]),
     "rf_emd_assign_workspace_bytes": (_sz, [_i, _i]),
     "rf_emd_assign": (_i, [_i, _i, _vp, _vp, _vp, _i] + [_vp] * 7 + [_sz, _vp]),

@@ -591,6 +591,109 @@ def sinkhorn(xyz1, xyz2, eps, p=1, lengths1=None, lengths2=None, want_grad=False
     return tuple(st.give(t) for t in out)
 
 
+GR_Q, GR_MAX_RES, GR_MAX_POINTS = 512, 256, 65536  # RF_GR_Q, RF_GR_MAX_RES, RF_GR_MAX_POINTS (include/rfops.h)
+GR_MODES = {"counts": 0, "density": 1}  # RF_GR_COUNTS, RF_GR_DENSITY
+GR_BRICK = 16  # gridding.hip's brick edge, in vertices
+
+
+def _gr_box(op, res, lo, hi):
+    """The grid arguments of the gridding entries, checked -> (res, lo, hi) as an int and two floats that are fp32 values."""
+    res = int(res)
+    if res < 2 or res > GR_MAX_RES:
+        raise H.invalid(f"{op} expects a resolution of 2 to {GR_MAX_RES} vertices per axis")
+    with np.errstate(over="ignore"):
+        lo, hi = float(np.float32(lo)), float(np.float32(hi))
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise H.invalid(f"{op} expects finite bounds lo < hi (in float32)")
+    return res, lo, hi
+
+
+def _gr_cloud(op, st, xyz, name):
+    a = st.take(xyz, F32)
+    if a.dim() != 3 or a.shape[2] != 3:
+        raise H.invalid(f"{op} requires {name} be of shape (batch,#points,3)")
+    if a.shape[0] > 0 and a.shape[1] < 1:
+        raise H.invalid(f"{op} requires at least one point per cloud")
+    if a.shape[1] > GR_MAX_POINTS:
+        raise H.invalid(f"{op} takes clouds of up to {GR_MAX_POINTS} points")
+    if a.shape[0] > 65535:
+        raise H.invalid(f"{op} takes up to 65535 samples per call: split the batch")
+    return a
+
+
+@H.on_input_device
+def gridding_loss(xyz1, xyz2, res, lo, hi, mode="counts", lengths1=None, lengths2=None, want_grad=False):
+    """rf_gridding_loss: the L1 difference of the trilinear grids of xyz1 (b, n, 3) and xyz2 (b, m, 3) on `res` vertices per
+    axis over the box [lo, hi]^3 -> (loss (b,), inside (b, 2) int32), with `want_grad` also (grad_xyz1, grad_xyz2) of the same
+    call.  mode "counts": the mean over the vertices of |G1 - G2|; "density": sum |G1 / L1 - G2 / L2|.  The sums are integers:
+    the bits do not depend on the order of the points.  Points outside the box and rows behind a count contribute nothing and
+    get a gradient of exactly 0."""
+    st = H.Staged()
+    a, b_ = _gr_cloud("gridding_loss", st, xyz1, "xyz1"), _gr_cloud("gridding_loss", st, xyz2, "xyz2")
+    if b_.shape[0] != a.shape[0]:
+        raise H.invalid("gridding_loss expects xyz1 and xyz2 have same batch size")
+    if mode not in GR_MODES:
+        raise H.invalid("gridding_loss expects mode be 'counts' or 'density'")
+    res, lo, hi = _gr_box("gridding_loss", res, lo, hi)
+    b, n, m = a.shape[0], a.shape[1], b_.shape[1]
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, b_ = st.up(a, b_)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    loss, inside = H.empty((b,), F32, dev), H.empty((b, 2), I32, dev)
+    g1 = H.empty((b, n, 3), F32, dev) if want_grad else None
+    g2 = H.empty((b, m, 3), F32, dev) if want_grad else None
+    if b > 0:
+        ws, wsz = H.workspace(lib.rf_gridding_loss_workspace_bytes(b, n, m, res, 1 if want_grad else 0), dev, "gridding")
+        check(lib.rf_gridding_loss(b, n, m, res, lo, hi, GR_MODES[mode], H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2),
+                                   H.ptr(loss), H.ptr(inside), H.ptr(g1), H.ptr(g2), H.ptr(ws), wsz, H.stream(dev)),
+              "rf_gridding_loss")
+    out = (loss, inside) + ((g1, g2) if want_grad else ())
+    return tuple(st.give(t) for t in out)
+
+
+@H.on_input_device
+def gridding(xyz, res, lo, hi, lengths=None):
+    """rf_gridding: the Gridding layer -> (grid (b, res, res, res) fp32 with x slowest, inside (b,) int32): every point of xyz
+    (b, n, 3) inside [lo, hi]^3 spreads a mass of 1 trilinearly over the eight vertices of its cell, in exact integer sums."""
+    st = H.Staged()
+    a = _gr_cloud("gridding", st, xyz, "xyz")
+    res, lo, hi = _gr_box("gridding", res, lo, hi)
+    b, n = a.shape[0], a.shape[1]
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    (a,) = st.up(a)
+    ln = _lengths_up(ln, dev, n)
+    grid, inside = H.empty((b, res, res, res), F32, dev), H.empty((b,), I32, dev)
+    if b > 0:
+        ws, wsz = H.workspace(lib.rf_gridding_workspace_bytes(b, n, res), dev, "gridding")
+        check(lib.rf_gridding(b, n, res, lo, hi, H.ptr(a), H.ptr(ln), H.ptr(grid), H.ptr(inside), H.ptr(ws), wsz,
+                              H.stream(dev)), "rf_gridding")
+    return st.give(grid), st.give(inside)
+
+
+@H.on_input_device
+def gridding_grad(xyz, grad_grid, res, lo, hi, lengths=None):
+    """rf_gridding_grad: the backward of gridding -> grad_xyz (b, n, 3) from grad_grid (b, res, res, res); exactly 0 for points
+    outside the box and rows behind the count."""
+    st = H.Staged()
+    a = _gr_cloud("gridding_grad", st, xyz, "xyz")
+    res, lo, hi = _gr_box("gridding_grad", res, lo, hi)
+    b, n = a.shape[0], a.shape[1]
+    gg = st.take(grad_grid, F32)
+    if tuple(gg.shape) != (b, res, res, res):
+        raise H.invalid("gridding_grad requires grad_grid be of shape (batch,res,res,res)")
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    a, gg = st.up(a, gg)
+    ln = _lengths_up(ln, dev, n)
+    out = H.empty((b, n, 3), F32, dev)
+    if b > 0:
+        check(lib.rf_gridding_grad(b, n, res, lo, hi, H.ptr(a), H.ptr(ln), H.ptr(gg), H.ptr(out), H.stream(dev)),
+              "rf_gridding_grad")
+    return st.give(out)
+
+
 EA_MAX_POINTS = 4096  # RF_EA_MAX_POINTS (include/rfops.h)
 EA_OK, EA_CAPPED, EA_NONFINITE = 0, 1, 2  # RF_EA_* status values
 EA_TPB, EA_WAVE = 1024, 64  # emd_assign.hip's tiles: threads of the one workgroup per sample; lanes a bidder's scan strides by
