@@ -460,6 +460,79 @@ int rf_gridding(int b, int n, int res, float lo, float hi, const float *xyz, con
 int rf_gridding_grad(int b, int n, int res, float lo, float hi, const float *xyz, const int *len, const float *grad_grid,
                      float *grad_xyz, rf_stream_t stream);
 
+/* ---- Gridding Reverse and Cubic Feature Sampling: from a voxel grid back to points, with gradients -- */
+/* The two GRNet layers behind the Gridding layer (cloud -> grid -> 3-D CNN -> cloud -> per-point refinement).  The grid
+ * geometry is the gridding section's, verbatim: R = res vertices per axis, 2 <= R <= RF_GR_MAX_RES, the box [lo, hi]^3,
+ * inv_h = (float)((double)(R - 1) / ((double)hi - (double)lo)) formed on the host, per axis u = (x - lo) * inv_h in fp32,
+ * inside iff 0 <= u <= (float)(R - 1) on all three axes (a NaN fails), the cell i = min((int)floorf(u), R - 2), the vertex
+ * index v = (ix R + iy) R + iz, the corners d in {0, 1}^3 with dz fastest: v + d = v + (dx R + dy) R + dz.  The library is
+ * built with -ffp-contract=off: the double arithmetic below has exactly the roundings written.  Counts are device int32 (b)
+ * or NULL with rf_nn_distance_lengths' conventions, clamped into [1, n] by the kernels.  No host synchronisation, no
+ * hipMemset, no float atomics in global memory, a fixed number of launches on `stream` (forward 1, its backward 2; reverse
+ * 3, its backward 1): every call can be captured in a HIP graph.
+ *
+ * rf_cubic_feature_sampling: xyz (b, n, 3) fp32, 1 <= n <= RF_GR_MAX_POINTS; vol (b, c, R, R, R) fp32, channel-first and
+ * contiguous (what a 3-D convolution returns), 1 <= c <= RF_CFS_MAX_CHANNELS.
+ *   feat (b, n, 8, c) fp32: for an inside point feat[s][i][d][ch] = vol[s][ch][v_i + d], a copy bit for bit (NaN payloads
+ *   included); for a point outside the box and a row behind the count all 8 c floats are +0.  Every element is written.
+ *   inside (b) int32: how many points of the sample are inside.
+ * rf_cubic_feature_sampling_grad: grad_vol (b, c, R, R, R) from grad_feat (b, n, 8, c); grad_vol[s][ch][v] is the sum of
+ * grad_feat[s][i][d][ch] over the (i, d) with v_i + d = v, i inside and below the count.  Every element is written exactly
+ * once, +0 where nothing fell; the value is the fp32 rounding of a DOUBLE sum of the contributions.  THE ORDER OF THE
+ * ADDITIONS IS NOT FIXED (it is the order in which the points arrive at a workgroup).  The promise: identical bits, for
+ * every call and batch, whenever the double sum is exact (for instance integer-valued gradients with sums below 2^53);
+ * otherwise |got - exact| <= 2^-23 |exact| + k 2^-52 sum |terms| for k contributions -- one fp32 rounding plus the double
+ * sum's own roundings -- and two calls may differ within that.  The points get no gradient: the op is piecewise constant
+ * in xyz, as in GRNet.  The backward takes xyz and len again and recomputes the cells; it takes no index tensor, so no
+ * corrupt index can move a store.  Only GRNet's neighborhood_size = 1 (the eight vertices of the cell) is provided: larger
+ * neighbourhoods and trilinear (PVCNN-style) devoxelisation are out of scope.
+ *
+ * rf_gridding_reverse: grid (b, R, R, R) fp32, eps fp32 finite and > 0, compact 0 or 1.  There are M = (R - 1)^3 cells,
+ * cell = (ix (R - 1) + iy) (R - 1) + iz with its first vertex v = (ix R + iy) R + iz.  Per cell, all in double:
+ *   w_d = (double)grid[v + d]
+ *   S   = ((((((w_0 + w_1) + w_2) + w_3) + w_4) + w_5) + w_6) + w_7                left to right from w_0
+ *   T_x = ((w_4 + w_5) + w_6) + w_7,  T_y = ((w_2 + w_3) + w_6) + w_7,  T_z = ((w_1 + w_3) + w_5) + w_7
+ *   valid iff S >= (double)eps && S < +inf         a NaN anywhere makes the cell invalid; negative entries may pass
+ *   f_a = T_a / S,   p_a = (float)((double)lo + ((double)i_a + f_a) * h_d)
+ * with h_d = ((double)hi - (double)lo) / (double)(R - 1) formed on the host.
+ *   points (b, M, 3) fp32, row (b, M) int32: the row cell c was written to, -1 for an invalid cell; count (b) int32: the
+ *   number of valid cells.  compact = 0: cell c writes row c, invalid rows are (+0, +0, +0).  compact = 1: the valid cells
+ *   occupy the rows 0 ... count - 1 IN INCREASING CELL ORDER (an ordered scan, no atomics: the placement is a pure function
+ *   of the grid) and the rows from count on are zeros.  Every element of all three outputs is written.  points and count
+ *   are a padded batch with device counts: what the _lengths entries take.
+ * rf_gridding_reverse_grad: grad_grid (b, R, R, R) from grid, row and grad_points gp (b, M, 3), every element written once:
+ *   grad_grid[v] = (float) sum over the <= 8 cells c with v = v_c + d and row[c] in [0, M) of
+ *                  (h_d / S_c) (((d_x - f_x(c)) gp[row[c]][0] + (d_y - f_y(c)) gp[row[c]][1]) + (d_z - f_z(c)) gp[row[c]][2])
+ * in double from +0 with d ascending, rounded once; S_c and f_a(c) are recomputed from grid as above.  row is the forward's:
+ * an entry outside [0, M) is treated as -1 and never moves a load.
+ *
+ * Guarantees: two calls return identical bits, sample i is bit for bit the call on [i : i + 1], a ragged call is bit for
+ * bit the call on the sliced clouds and rows behind a count are never read -- for rf_cubic_feature_sampling_grad as far as
+ * its promise above goes.  A non-finite coordinate never moves a memory access; every loop bound is a count.
+ *
+ * Workspace, each part rounded up to 256 bytes, with nb = ceil(R / 16):
+ *   rf_cubic_feature_sampling_grad   4 b (nb^3 + 1)  list starts  + 8 b n  one record per point (its cell and its index)
+ *   rf_gridding_reverse              4 b ceil(M / 256)  the valid cells per tile of 256 cells
+ *
+ * Argument rules, all checked before any HIP call, as for rf_gridding: RF_EINVAL for a negative size; then b == 0 is RF_OK;
+ * RF_EINVAL for n outside 1 ... RF_GR_MAX_POINTS, c outside 1 ... RF_CFS_MAX_CHANNELS, res outside 2 ... RF_GR_MAX_RES, b
+ * above 65535, a non-finite lo or hi or lo >= hi, eps not finite or not > 0, compact not 0 or 1, a NULL tensor (len may be
+ * NULL), a tensor or count array not 4-byte aligned, a workspace that is NULL or not 16-byte aligned; RF_EWORKSPACE for a
+ * workspace smaller than the _workspace_bytes function states (0 for non-positive or unsupported sizes, positive
+ * otherwise).  All index arithmetic is in size_t. */
+#define RF_CFS_MAX_CHANNELS 1024
+int rf_cubic_feature_sampling(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len,
+                              const float *vol, float *feat, int *inside, rf_stream_t stream);
+size_t rf_cubic_feature_sampling_grad_workspace_bytes(int b, int n, int res);
+int rf_cubic_feature_sampling_grad(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len,
+                                   const float *grad_feat, float *grad_vol, void *workspace, size_t workspace_bytes,
+                                   rf_stream_t stream);
+size_t rf_gridding_reverse_workspace_bytes(int b, int res);
+int rf_gridding_reverse(int b, int res, float lo, float hi, float eps, int compact, const float *grid, float *points,
+                        int *row, int *count, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+int rf_gridding_reverse_grad(int b, int res, float lo, float hi, const float *grid, const int *row,
+                             const float *grad_points, float *grad_grid, rf_stream_t stream);
+
 /* ---- the exact earth mover's distance: optimal assignment with a certificate and gradients -- */
 /* The one-to-one assignment of minimal total distance between two clouds of EQUAL counts, by a deterministic Jacobi
  * auction with eps-scaling on an integer cost grid: a pure function of its inputs with a machine-checkable optimality

@@ -72,6 +72,12 @@ SIGNATURES = {
     "rf_gridding_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_gridding": (_i, [_i, _i, _i, _f, _f] + [_vp] * 5 + [_sz, _vp]),
     "rf_gridding_grad": (_i, [_i, _i, _i, _f, _f] + [_vp] * 5),
+    "rf_cubic_feature_sampling": (_i, [_i, _i, _i, _i, _f, _f] + [_vp] * 6),
+    "rf_cubic_feature_sampling_grad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_cubic_feature_sampling_grad": (_i, [_i, _i, _i, _i, _f, _f] + [_vp] * 5 + [_sz, _vp]),
+    "rf_gridding_reverse_workspace_bytes": (_sz, [_i, _i]),
+    "rf_gridding_reverse": (_i, [_i, _i, _f, _f, _f, _i] + [_vp] * 5 + [_sz, _vp]),
+    "rf_gridding_reverse_grad": (_i, [_i, _i, _f, _f] + [_vp] * 5),
     "rf_emd_assign_supported": (_i, [_i]),
     "rf_emd_assign_workspace_bytes": (_sz, [_i, _i]),
     "rf_emd_assign": (_i, [_i, _i, _vp, _vp, _vp, _i] + [_vp] * 7 + [_sz, _vp]),

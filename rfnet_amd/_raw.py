@@ -694,6 +694,124 @@ def gridding_grad(xyz, grad_grid, res, lo, hi, lengths=None):
     return st.give(out)
 
 
+CFS_MAX_CHANNELS = 1024  # RF_CFS_MAX_CHANNELS (include/rfops.h)
+CFS_BRICK, CFS_CHUNK = 8, 8  # grnet_layers.hip: a backward workgroup's sub-brick edge in vertices, and its channels
+GREV_TILE = 256  # grnet_layers.hip: cells per tile of Gridding Reverse's ordered compaction
+
+
+def _cfs_volume(op, st, vol, name, b):
+    v = st.take(vol, F32)
+    if v.dim() != 5 or v.shape[0] != b or not (v.shape[2] == v.shape[3] == v.shape[4]):
+        raise H.invalid(f"{op} requires {name} be of shape (batch,channels,res,res,res)")
+    if v.shape[1] < 1 or v.shape[1] > CFS_MAX_CHANNELS:
+        raise H.invalid(f"{op} takes 1 to {CFS_MAX_CHANNELS} channels")
+    return v
+
+
+@H.on_input_device
+def cubic_feature_sampling(xyz, vol, lo, hi, lengths=None):
+    """rf_cubic_feature_sampling: GRNet's Cubic Feature Sampling -> (feat (b, n, 8, c) fp32, inside (b,) int32): for every point
+    of xyz (b, n, 3) inside [lo, hi]^3 the feature vectors of vol (b, c, R, R, R) at the eight vertices of its cell (dz fastest),
+    copied bit for bit; +0 for points outside the box and rows behind the count."""
+    st = H.Staged()
+    a = _gr_cloud("cubic_feature_sampling", st, xyz, "xyz")
+    b, n = a.shape[0], a.shape[1]
+    v = _cfs_volume("cubic_feature_sampling", st, vol, "vol", b)
+    c = v.shape[1]
+    res, lo, hi = _gr_box("cubic_feature_sampling", v.shape[2], lo, hi)
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    a, v = st.up(a, v)
+    ln = _lengths_up(ln, dev, n)
+    feat, inside = H.empty((b, n, 8, c), F32, dev), H.empty((b,), I32, dev)
+    if b > 0:
+        check(lib.rf_cubic_feature_sampling(b, n, c, res, lo, hi, H.ptr(a), H.ptr(ln), H.ptr(v), H.ptr(feat), H.ptr(inside),
+                                            H.stream(dev)), "rf_cubic_feature_sampling")
+    return st.give(feat), st.give(inside)
+
+
+@H.on_input_device
+def cubic_feature_sampling_grad(xyz, grad_feat, res, lo, hi, lengths=None):
+    """rf_cubic_feature_sampling_grad: the backward of cubic_feature_sampling -> grad_vol (b, c, res, res, res) from grad_feat
+    (b, n, 8, c): fp32 roundings of double sums, every element written once, no float atomics in memory.  The cells are
+    recomputed from xyz."""
+    st = H.Staged()
+    a = _gr_cloud("cubic_feature_sampling_grad", st, xyz, "xyz")
+    res, lo, hi = _gr_box("cubic_feature_sampling_grad", res, lo, hi)
+    b, n = a.shape[0], a.shape[1]
+    gf = st.take(grad_feat, F32)
+    if gf.dim() != 4 or tuple(gf.shape[:3]) != (b, n, 8):
+        raise H.invalid("cubic_feature_sampling_grad requires grad_feat be of shape (batch,#points,8,channels)")
+    c = gf.shape[3]
+    if c < 1 or c > CFS_MAX_CHANNELS:
+        raise H.invalid(f"cubic_feature_sampling_grad takes 1 to {CFS_MAX_CHANNELS} channels")
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    a, gf = st.up(a, gf)
+    ln = _lengths_up(ln, dev, n)
+    out = H.empty((b, c, res, res, res), F32, dev)
+    if b > 0:
+        ws, wsz = H.workspace(lib.rf_cubic_feature_sampling_grad_workspace_bytes(b, n, res), dev, "grnet_layers")
+        check(lib.rf_cubic_feature_sampling_grad(b, n, c, res, lo, hi, H.ptr(a), H.ptr(ln), H.ptr(gf), H.ptr(out), H.ptr(ws),
+                                                 wsz, H.stream(dev)), "rf_cubic_feature_sampling_grad")
+    return st.give(out)
+
+
+def _grev_grid(op, st, grid):
+    g = st.take(grid, F32)
+    if g.dim() != 4 or not (g.shape[1] == g.shape[2] == g.shape[3]):
+        raise H.invalid(f"{op} requires grid be of shape (batch,res,res,res)")
+    if g.shape[0] > 65535:
+        raise H.invalid(f"{op} takes up to 65535 samples per call: split the batch")
+    return g
+
+
+@H.on_input_device
+def gridding_reverse(grid, lo, hi, eps=1e-6, compact=False):
+    """rf_gridding_reverse: GRNet's Gridding Reverse -> (points (b, M, 3) fp32, row (b, M) int32, count (b,) int32) with
+    M = (res - 1)^3: every cell of grid (b, res, res, res) whose eight corner weights sum to S >= eps (and < inf) gives one point,
+    the weighted mean of its corners.  row[c] is the row cell c was written to (-1: invalid).  compact: the valid cells fill the
+    rows 0 ... count - 1 in cell order and the rest is zeros -- a padded batch with device counts, without a host sync."""
+    st = H.Staged()
+    g = _grev_grid("gridding_reverse", st, grid)
+    res, lo, hi = _gr_box("gridding_reverse", g.shape[1], lo, hi)
+    with np.errstate(over="ignore"):
+        eps = float(np.float32(eps))
+    if not (np.isfinite(eps) and eps > 0):
+        raise H.invalid("gridding_reverse expects a finite eps > 0 (in float32)")
+    b, M = g.shape[0], (res - 1) ** 3
+    dev = st.device_()
+    (g,) = st.up(g)
+    points, row, count = H.empty((b, M, 3), F32, dev), H.empty((b, M), I32, dev), H.empty((b,), I32, dev)
+    if b > 0:
+        ws, wsz = H.workspace(lib.rf_gridding_reverse_workspace_bytes(b, res), dev, "grnet_layers")
+        check(lib.rf_gridding_reverse(b, res, lo, hi, eps, 1 if compact else 0, H.ptr(g), H.ptr(points), H.ptr(row),
+                                      H.ptr(count), H.ptr(ws), wsz, H.stream(dev)), "rf_gridding_reverse")
+    return st.give(points), st.give(row), st.give(count)
+
+
+@H.on_input_device
+def gridding_reverse_grad(grid, row, grad_points, lo, hi):
+    """rf_gridding_reverse_grad: the backward of gridding_reverse -> grad_grid (b, res, res, res) from the forward's grid and row
+    and grad_points (b, M, 3): a gather per vertex in double.  A row entry outside [0, M) counts as -1."""
+    st = H.Staged()
+    g = _grev_grid("gridding_reverse_grad", st, grid)
+    res, lo, hi = _gr_box("gridding_reverse_grad", g.shape[1], lo, hi)
+    b, M = g.shape[0], (res - 1) ** 3
+    r, gp = st.take(row, I32), st.take(grad_points, F32)
+    if tuple(r.shape) != (b, M):
+        raise H.invalid("gridding_reverse_grad requires row be of shape (batch,(res-1)^3)")
+    if tuple(gp.shape) != (b, M, 3):
+        raise H.invalid("gridding_reverse_grad requires grad_points be of shape (batch,(res-1)^3,3)")
+    dev = st.device_()
+    g, r, gp = st.up(g, r, gp)
+    out = H.empty((b, res, res, res), F32, dev)
+    if b > 0:
+        check(lib.rf_gridding_reverse_grad(b, res, lo, hi, H.ptr(g), H.ptr(r), H.ptr(gp), H.ptr(out), H.stream(dev)),
+              "rf_gridding_reverse_grad")
+    return st.give(out)
+
+
 EA_MAX_POINTS = 4096  # RF_EA_MAX_POINTS (include/rfops.h)
 EA_OK, EA_CAPPED, EA_NONFINITE = 0, 1, 2  # RF_EA_* status values
 EA_TPB, EA_WAVE = 1024, 64  # emd_assign.hip's tiles: threads of the one workgroup per sample; lanes a bidder's scan strides by

@@ -22,35 +22,16 @@
 //
 // No float atomics, no hipMemset, no sum whose order is left open.  Every loop bound is a count or a list length that the bin
 // kernel derived from counts; a non-finite coordinate fails the inside test and never moves a memory access.
-#include "common.hpp"
+#include "gridding.hpp"  // GrBox, gr_axis, gr_nb, GR_E: shared with grnet_layers.hip
 
 namespace {
 
-constexpr int GR_E = 16;                 // vertices per brick edge: GR_E^3 int64 = 32 KiB of LDS
 constexpr int GR_E3 = GR_E * GR_E * GR_E;
 constexpr int GR_MAX_NB3 = 4096;         // (RF_GR_MAX_RES / GR_E)^3 bricks per sample at most
 constexpr int GR_BIN_TPB = 1024, GR_BRICK_TPB = 256, GR_PT_TPB = 256;
 constexpr double GR_Q3 = 134217728.0;    // RF_GR_Q^3
 static_assert(RF_GR_Q == 512 && RF_GR_MAX_RES == 256 && GR_MAX_NB3 == (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E), "");
 static_assert(GR_MAX_NB3 == 4 * GR_BIN_TPB, "the scan of gr_bin_kernel gives a thread four bins");
-
-struct GrBox {
-    float lo, inv_h, top;  // top = (float)(R - 1)
-    int R;
-};
-
-__host__ __device__ __forceinline__ int gr_nb(int R) { return (R + GR_E - 1) / GR_E; }
-
-// one axis of the contract: u = (x - lo) * inv_h (two roundings), inside iff 0 <= u <= R - 1 (a NaN fails), the cell
-// i = min(floor(u), R - 2) and t = u - i in [0, 1]
-__device__ __forceinline__ bool gr_axis(float x, const GrBox &g, int &i, float &t) {
-    const float u = (x - g.lo) * g.inv_h;
-    const bool in = u >= 0.f && u <= g.top;
-    const int k = in ? (int)floorf(u) : 0;
-    i = k < g.R - 2 ? k : g.R - 2;
-    t = u - (float)i;
-    return in;
-}
 
 __device__ __forceinline__ unsigned gr_q1(float t) { return (unsigned)(int)rintf(t * 512.0f); }
 
@@ -349,21 +330,6 @@ GrLayout gr_layout(int b, int n, int m, int res, int clouds, bool want_grad) {
     l.sign = l.partial + (clouds == 2 ? rf::align256((size_t)b * nb3 * sizeof(long long)) : 0);
     l.total = l.sign + (clouds == 2 && want_grad ? rf::align256((size_t)b * res * res * res) : 0);
     return l;
-}
-
-bool gr_sizes_ok(int b, int n, int res) {
-    return b >= 1 && b <= 65535 && n >= 1 && n <= RF_GR_MAX_POINTS && res >= 2 && res <= RF_GR_MAX_RES;
-}
-
-bool gr_box_ok(float lo, float hi) { return isfinite(lo) && isfinite(hi) && lo < hi; }
-
-GrBox gr_box(int res, float lo, float hi) {
-    GrBox g;
-    g.lo = lo;
-    g.inv_h = (float)((double)(res - 1) / ((double)hi - (double)lo));
-    g.top = (float)(res - 1);
-    g.R = res;
-    return g;
 }
 
 }  // namespace

@@ -470,6 +470,62 @@ def gridding(pcd, resolution=64, bounds=(-0.5, 0.5), lengths=None):
     return _Gridding.apply(_cloud_tensor(pcd), int(resolution), lo, hi, lengths)
 
 
+class _CubicFeatureSampling(torch.autograd.Function):
+    """rf_cubic_feature_sampling / rf_cubic_feature_sampling_grad: only the volume carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, xyz, vol, lo, hi, lengths):
+        feat, _ = _raw.cubic_feature_sampling(xyz, vol, lo, hi, lengths)
+        ctx.save_for_backward(xyz)
+        ctx.box, ctx.lengths = (vol.shape[2], lo, hi), lengths
+        return feat
+
+    @staticmethod
+    def backward(ctx, grad_feat):
+        (xyz,) = ctx.saved_tensors
+        gv = _raw.cubic_feature_sampling_grad(xyz, grad_feat.contiguous(), *ctx.box, lengths=ctx.lengths)
+        return None, gv, None, None, None
+
+
+def cubic_feature_sampling(pcd, volume, bounds=(-0.5, 0.5), lengths=None):
+    """GRNet's Cubic Feature Sampling: for every point of pcd (b, n, 3) the feature vectors of volume (b, c, R, R, R) at the
+    eight vertices of its cell of the grid over [bounds[0], bounds[1]]^3 (the geometry of `gridding`) -> (b, n, 8, c), the
+    corners with z fastest; zeros for points outside the cube and padded rows (`lengths`: per-sample point counts).  Autograd
+    goes to `volume` only (rf_cubic_feature_sampling_grad: double sums in LDS, no float atomics in memory); the op is piecewise
+    constant in the points."""
+    lo, hi = _grid_bounds(bounds)
+    vol = volume if isinstance(volume, torch.Tensor) else torch.as_tensor(volume)
+    return _CubicFeatureSampling.apply(_cloud_tensor(pcd).detach(), vol.to(torch.float32).contiguous(), lo, hi, lengths)
+
+
+class _GriddingReverse(torch.autograd.Function):
+    """rf_gridding_reverse / rf_gridding_reverse_grad: the points carry a gradient to the grid; the counts do not."""
+
+    @staticmethod
+    def forward(ctx, grid, lo, hi, eps, compact):
+        points, row, count = _raw.gridding_reverse(grid, lo, hi, eps, compact)
+        ctx.save_for_backward(grid, row)
+        ctx.box = (lo, hi)
+        ctx.mark_non_differentiable(count)
+        return points, count
+
+    @staticmethod
+    def backward(ctx, grad_points, _):
+        grid, row = ctx.saved_tensors
+        return _raw.gridding_reverse_grad(grid, row, grad_points.contiguous(), *ctx.box), None, None, None, None
+
+
+def gridding_reverse(grid, bounds=(-0.5, 0.5), eps=1e-6, compact=True):
+    """GRNet's Gridding Reverse: the grid (b, R, R, R) back to a cloud -> (points (b, (R - 1)^3, 3), lengths (b,) int32 on the
+    device).  Every cell whose eight corner weights sum to at least `eps` gives one point, the weighted mean of its corners.
+    `compact`: the valid cells fill the first lengths[i] rows in cell order and the rest is zeros, so the pair is a padded batch
+    for every `lengths=` argument of this library -- no boolean mask, no host sync, capturable in a graph; otherwise cell c stays
+    in row c and invalid rows are zeros.  Differentiable in grid (rf_gridding_reverse_grad)."""
+    lo, hi = _grid_bounds(bounds)
+    g = grid if isinstance(grid, torch.Tensor) else torch.as_tensor(grid)
+    return _GriddingReverse.apply(g.to(torch.float32).contiguous(), lo, hi, float(eps), bool(compact))
+
+
 class _EmdAssign(torch.autograd.Function):
     """rf_emd_assign / rf_emd_assign_grad: the exact assignment; only the cost (b,) carries a gradient, under the
     fixed assignment."""
