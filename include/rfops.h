@@ -602,6 +602,75 @@ int rf_emd_assign(int b, int n, const float *xyz1, const float *xyz2, const int 
 int rf_emd_assign_grad(int b, int n, const float *xyz1, const float *xyz2, const int *match12, const int *match21,
                        const int *len, const float *gcost, float *grad1, float *grad2, rf_stream_t stream);
 
+/* ---- the expansion penalty and minimum density sampling (the ops of MSN-style completion networks) -- */
+/* rf_expansion_penalty: the surface is generated as P patches of S points; every patch gets its minimum spanning tree,
+ * and the tree edges longer than alpha times the patch's mean edge are the penalty.  xyz (b, n, 3) fp32, n = P S, patch
+ * p of a sample is rows [p S, (p + 1) S); 2 <= S <= RF_XP_MAX_PATCH; alpha finite and >= 0.  One launch, no workspace,
+ * no atomics, no host synchronisation: a call can be captured in a HIP graph.  One workgroup works on a patch; ragged
+ * counts per patch and patches above RF_XP_MAX_PATCH are out of scope.  Per patch, as a pure function of its S rows
+ * (indices below are local to the patch, root = 0):
+ *
+ *   1. Status.  If any of the 3 S coordinates is NaN or +-Inf (exponent bits all ones): status RF_XP_NONFINITE,
+ *      father[v] = v, length = dist = +0, mean = 0; the other patches are unaffected and no address depends on a data
+ *      value.  Otherwise status RF_XP_OK.
+ *   2. Distances.  d2(u, v) = ((dx dx) + (dy dy)) + (dz dz), unfused fp32 -- rf_emd_assign's d_ij without the root;
+ *      symmetric bit for bit, >= 0 or +inf, never NaN.  Nothing of size S^2 is stored.
+ *   3. Tree.  Prim from vertex 0: key[v] = d2(0, v), father[v] = 0.  S - 1 times: the next vertex u minimises
+ *      (bits(key[v]), v) lexicographically over the vertices outside the tree (the unsigned bit order is the float
+ *      order); then, for every v still outside, key[v] and father[v] are replaced by d2(u, v) and u only where
+ *      d2(u, v) < key[v] -- strictly, so the earliest tree vertex keeps a tie.  Ties, duplicates and lattices give one
+ *      defined tree.
+ *   4. Lengths.  length[v] = sqrtf(key[v]) with the key v joined with, correctly rounded; length[0] = +0, father[0] = 0.
+ *   5. Mean.  mean64 = (sum over v = 1 .. S - 1 ascending of (double)length[v]) / (double)(S - 1); mean = (float)mean64.
+ *   6. Penalty.  dist[v] = length[v] where (double)length[v] > (double)alpha * mean64, else +0.
+ *
+ * Outputs: dist (b, n), length (b, n) fp32; father (b, n) int32 as CLOUD-level row indices (p S + local: inside the own
+ * patch); mean (b, P) fp32; info (b, P) int32 status.  Two calls return identical bits; a sample's outputs are those of
+ * the call on [i : i + 1], a patch's those of the call on the patch alone (n = S) with father shifted by p S.
+ *
+ * rf_expansion_penalty_grad: the gradient of sum_v gdist[v] dist[v] with the tree, the mean and the indicator held
+ * constant.  For v with dist[v] != 0: f = father[v] - p S clamped into [0, S), l_v = sqrtf(d2(v, f)) recomputed,
+ * t_v = gdist[v] * ((x_v - x_f) / l_v) per component in fp32 (0 where l_v == 0).  grad[w] = (float)(0.0 + [dist[w] != 0]
+ * t_w - sum over v with dist[v] != 0 and f(v) = w, ascending v, of t_v), summed in double in that order and rounded once:
+ * exactly +0 where nothing contributes.  No atomics.  grad (b, n, 3) fully overwritten.
+ *
+ * rf_mds: minimum density sampling.  xyz (b, n, 3), 1 <= n <= RF_MDS_MAX_POINTS; m >= 1 samples per cloud; sigma (b)
+ * fp32 on the device; len: device int32 (b) or NULL with rf_nn_distance_lengths' conventions (clamped into [1, n] by the
+ * kernel), L the clamped count.  One launch, no workspace, capturable.  Per sample:
+ *
+ *   1. Scale.  c64 = 1.4426950408889634 / (2.0 * (double)sigma * (double)sigma), c = (float)c64.  If !(sigma > 0), or
+ *      c is 0 or inf: status RF_MDS_BADSIGMA and out[j] = j for j < mo.  Otherwise RF_MDS_OK.
+ *   2. Count.  mo = min(m, L).  out[0] = 0.  Slots j >= mo are 0 (coordinates +0).
+ *   3. Density.  dens[v] = +0 in fp32.  After choosing u, every valid v gets dens[v] += w(d2(u, v)), in the order of
+ *      the choices; d2 as above.  w: s = d2 * c; w = 0 if !(s < 64.0f) (NaN and inf included); else k = floorf(s),
+ *      f = s - k (exact), p = the degree-5 polynomial for 2^-f of rfnet_amd/csrc/msn_poly.hpp in Horner form,
+ *      p = p * f + c_i with a separate fp32 multiply and add at every step from c5 down to c0, and w = ldexpf(p, -k)
+ *      (exact).
+ *   4. Choice.  The next sample minimises (bits(dens[v]), v) over the valid v not chosen yet.
+ *
+ * Outputs: out (b, m) int32; info (b) int32 status; new_xyz (b, m, 3) or NULL: the chosen rows of xyz (gather_point
+ * fused).  Two calls return identical bits; a sample's outputs are those of the call on [i : i + 1].
+ *
+ * Argument rules, all checked before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for
+ * S outside [2, RF_XP_MAX_PATCH], n < S or n % S != 0, alpha negative or not finite, b (n / S) above 2^31 - 1; for n
+ * outside [1, RF_MDS_MAX_POINTS] or m < 1; for a NULL tensor (len and new_xyz may be NULL) or a tensor or count array
+ * not 4-byte aligned.  All index arithmetic is in size_t.  rf_expansion_penalty_supported(n, S) and rf_mds_supported(n)
+ * return 1 for sizes inside these ranges, else 0. */
+#define RF_XP_MAX_PATCH 4096
+#define RF_XP_OK 0
+#define RF_XP_NONFINITE 1
+#define RF_MDS_MAX_POINTS 16384
+#define RF_MDS_OK 0
+#define RF_MDS_BADSIGMA 1
+int rf_expansion_penalty_supported(int n, int S);
+int rf_expansion_penalty(int b, int n, int S, float alpha, const float *xyz, float *dist, int *father, float *length,
+                         float *mean, int *info, rf_stream_t stream);
+int rf_expansion_penalty_grad(int b, int n, int S, const float *xyz, const int *father, const float *dist,
+                              const float *gdist, float *grad, rf_stream_t stream);
+int rf_mds_supported(int n);
+int rf_mds(int b, int n, int m, const float *xyz, const float *sigma, const int *len, int *out, int *info,
+           float *new_xyz, rf_stream_t stream);
+
 /* ----------------------------------------------------------- EMD (pc_distance) ---------- */
 /* Replaces approxmatchLauncher(b,n,m,xyz1,xyz2,match,temp) (pc_distance/tf_approxmatch.cpp:141,
  * tf_approxmatch.cu:180-182).  xyz1 (b,n,3) "dataset", xyz2 (b,m,3) "query" (b <= 65535 for

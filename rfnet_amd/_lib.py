@@ -82,6 +82,11 @@ SIGNATURES = {
     "rf_emd_assign_workspace_bytes": (_sz, [_i, _i]),
     "rf_emd_assign": (_i, [_i, _i, _vp, _vp, _vp, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_emd_assign_grad": (_i, [_i, _i] + [_vp] * 9),
+    "rf_expansion_penalty_supported": (_i, [_i, _i]),
+    "rf_expansion_penalty": (_i, [_i, _i, _i, _f] + [_vp] * 7),
+    "rf_expansion_penalty_grad": (_i, [_i, _i, _i] + [_vp] * 6),
+    "rf_mds_supported": (_i, [_i]),
+    "rf_mds": (_i, [_i, _i, _i] + [_vp] * 7),
     "rf_merge_layer_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_merge_layer": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_merge_layer_grad": (_i, [_i, _i, _i] + [_vp] * 9),

@@ -884,6 +884,115 @@ def emd_assign_grad(xyz1, xyz2, match12, match21, grad_cost, lengths=None):
     return st.give(g1), st.give(g2)
 
 
+XP_MAX_PATCH = 4096  # RF_XP_MAX_PATCH (include/rfops.h)
+XP_OK, XP_NONFINITE = 0, 1  # RF_XP_* status values
+MDS_MAX_POINTS = 16384  # RF_MDS_MAX_POINTS
+MDS_OK, MDS_BADSIGMA = 0, 1  # RF_MDS_* status values
+
+
+def _xp_inputs(st, xyz, primitive_size, what):
+    a = st.take(xyz, F32)
+    if a.dim() != 3 or a.shape[2] != 3:
+        raise H.invalid(f"{what} requires xyz be of shape (batch,#points,3)")
+    S = int(primitive_size)
+    if S < 2 or S > XP_MAX_PATCH:
+        raise H.invalid(f"{what} takes a primitive size in [2, {XP_MAX_PATCH}]")
+    b, n = a.shape[0], a.shape[1]
+    if n < S or n % S != 0:
+        raise H.invalid(f"{what} expects #points to be a positive multiple of the primitive size")
+    if b * (n // S) > 2 ** 31 - 1:
+        raise H.invalid(f"{what} takes up to 2^31 - 1 patches per call: split the batch")
+    return a, S
+
+
+@H.on_input_device
+def expansion_penalty(xyz, primitive_size, alpha=1.5):
+    """rf_expansion_penalty: xyz (b, n, 3) as n / primitive_size patches of consecutive rows; per patch the minimum
+    spanning tree (Prim from the patch's first row, ties to the smallest index), its edges longer than alpha times the
+    patch's mean edge penalised -> (dist (b, n), father (b, n) int32 cloud-level rows, length (b, n), mean (b, P),
+    info (b, P) int32 status: 0 ok, 1 a non-finite coordinate in the patch)."""
+    st = H.Staged()
+    a, S = _xp_inputs(st, xyz, primitive_size, "expansion_penalty")
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 3.4028234663852886e38:  # (a finite fp32)
+        raise H.invalid("expansion_penalty expects a finite alpha >= 0")
+    b, n = a.shape[0], a.shape[1]
+    dev = st.device_()
+    (a,) = st.up(a)
+    dist, father, length = H.empty((b, n), F32, dev), H.empty((b, n), I32, dev), H.empty((b, n), F32, dev)
+    mean, info = H.empty((b, n // S), F32, dev), H.empty((b, n // S), I32, dev)
+    if b > 0:
+        check(lib.rf_expansion_penalty(b, n, S, alpha, H.ptr(a), H.ptr(dist), H.ptr(father), H.ptr(length), H.ptr(mean),
+                                       H.ptr(info), H.stream(dev)), "rf_expansion_penalty")
+    return tuple(st.give(t) for t in (dist, father, length, mean, info))
+
+
+@H.on_input_device
+def expansion_penalty_grad(xyz, primitive_size, father, dist, grad_dist):
+    """rf_expansion_penalty_grad -> grad_xyz (b, n, 3): the gradient of sum(grad_dist * dist) under the fixed tree, mean
+    and indicator; summed in double in index order, exactly 0 where nothing contributes."""
+    st = H.Staged()
+    a, S = _xp_inputs(st, xyz, primitive_size, "expansion_penalty_grad")
+    b, n = a.shape[0], a.shape[1]
+    fa, d, g = st.take(father, I32), st.take(dist, F32), st.take(grad_dist, F32)
+    if tuple(fa.shape) != (b, n) or tuple(d.shape) != (b, n):
+        raise H.invalid("expansion_penalty_grad requires father and dist be of shape (batch,#points)")
+    if tuple(g.shape) != (b, n):
+        raise H.invalid("expansion_penalty_grad requires grad_dist be of shape (batch,#points)")
+    dev = st.device_()
+    a, fa, d, g = st.up(a, fa, d, g)
+    out = H.empty((b, n, 3), F32, dev)
+    if b > 0:
+        check(lib.rf_expansion_penalty_grad(b, n, S, H.ptr(a), H.ptr(fa), H.ptr(d), H.ptr(g), H.ptr(out), H.stream(dev)),
+              "rf_expansion_penalty_grad")
+    return st.give(out)
+
+
+@H.on_input_device
+def minimum_density_sample(xyz, npoint, sigma, lengths=None, return_xyz=False):
+    """rf_mds: thin xyz (b, n, 3), n <= 16384, to npoint rows; every step takes the valid row whose Gaussian density
+    (scale sigma) under the rows chosen so far is smallest, ties to the smallest index; the first is row 0
+    -> (idx (b, npoint) int32, info (b,) int32 status: 0 ok, 1 a sigma that is not positive or whose scale leaves fp32)
+    and, with return_xyz, the chosen rows (b, npoint, 3).  sigma: a float, or (b,) values -- a CUDA tensor is used where
+    it is.  `lengths` (b,): per-sample point counts; slots behind min(npoint, count) are zeros."""
+    st = H.Staged()
+    a = st.take(xyz, F32)
+    if a.dim() != 3 or a.shape[2] != 3:
+        raise H.invalid("minimum_density_sample requires xyz be of shape (batch,#points,3)")
+    b, n = a.shape[0], a.shape[1]
+    m = int(npoint)
+    if b > 0 and n < 1:
+        raise H.invalid("minimum_density_sample requires at least one point per cloud")
+    if n > MDS_MAX_POINTS:
+        raise H.invalid(f"minimum_density_sample takes clouds of up to {MDS_MAX_POINTS} points")
+    if m < 1:
+        raise H.invalid("minimum_density_sample expects npoint >= 1")
+    if isinstance(sigma, (int, float)):
+        sg = None  # filled on the device below: no host-to-device copy, so the call stays capturable
+    else:
+        sg = sigma.detach() if isinstance(sigma, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(sigma)))
+        if sg.dim() == 0:
+            sg = sg.reshape(1).expand(b)
+        if sg.dim() != 1 or sg.shape[0] != b:
+            raise H.invalid("minimum_density_sample requires sigma be a number or of shape (batch,)")
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    (a,) = st.up(a)
+    if sg is None:
+        sg = torch.full((b,), float(sigma), dtype=F32, device=dev)
+    elif sg.is_cuda and sg.device != dev:
+        raise ValueError(f"all GPU inputs of one op must live on the same device: got {dev} and {sg.device}")
+    sg = sg.to(device=dev, dtype=F32).contiguous()
+    ln = _lengths_up(ln, dev, n)
+    out, info = H.empty((b, m), I32, dev), H.empty((b,), I32, dev)
+    new_xyz = H.empty((b, m, 3), F32, dev) if return_xyz else None
+    if b > 0:
+        check(lib.rf_mds(b, n, m, H.ptr(a), H.ptr(sg), H.ptr(ln), H.ptr(out), H.ptr(info), H.ptr(new_xyz), H.stream(dev)),
+              "rf_mds")
+    res = (st.give(out), st.give(info))
+    return res + (st.give(new_xyz),) if return_xyz else res
+
+
 @H.on_input_device
 def chamfer_metrics_grad(xyz1, xyz2, dist1, idx1, dist2, idx2, count1, count2, alpha, grad_metrics, lengths1=None,
                          lengths2=None):

@@ -572,6 +572,53 @@ def emd_exact(pcd1, pcd2, lengths=None):
     return (cost / ln.to(device=cost.device, dtype=cost.dtype).clamp(1, n)).mean()
 
 
+class _ExpansionPenalty(torch.autograd.Function):
+    """rf_expansion_penalty / rf_expansion_penalty_grad: only dist carries a gradient, under the fixed tree, mean and
+    indicator (a penalty on the long edges, not on the mean)."""
+
+    @staticmethod
+    def forward(ctx, xyz, primitive_size, alpha):
+        dist, father, length, mean, info = _raw.expansion_penalty(xyz, primitive_size, alpha)
+        ctx.save_for_backward(xyz, father, dist)
+        ctx.primitive_size = primitive_size
+        ctx.mark_non_differentiable(father, length, mean, info)
+        return dist, father, length, mean, info
+
+    @staticmethod
+    def backward(ctx, grad_dist, *_):
+        xyz, father, dist = ctx.saved_tensors
+        return _raw.expansion_penalty_grad(xyz, ctx.primitive_size, father, dist, grad_dist.contiguous()), None, None
+
+
+def expansion_penalty(pcd, primitive_size, alpha=1.5, return_info=False):
+    """MSN's expansion penalty: pcd (b, n, 3) is n / primitive_size surface patches of consecutive rows, each of 2 to 4096
+    points.  Every patch gets its minimum spanning tree; a tree edge longer than alpha times the patch's mean edge is
+    penalised with its length -> (dist (b, n): the penalised length of the edge that joined each point, else 0;
+    father (b, n) int32: the row each point hangs on; mean_mst (b, P): the mean edge per patch).  dist is differentiable
+    in pcd with the tree, the mean and the indicator held constant.  return_info: also length (b, n), every tree edge,
+    and info (b, P) (0 ok, 1: the patch holds a non-finite coordinate and is all zeros).  One launch, no host
+    synchronisation: capturable in a graph."""
+    dist, father, length, mean, info = _ExpansionPenalty.apply(pcd.contiguous(), int(primitive_size), float(alpha))
+    return (dist, father, mean, length, info) if return_info else (dist, father, mean)
+
+
+def expansion_loss(pcd, primitive_size, alpha=1.5):
+    """The mean of expansion_penalty's dist over all points: MSN's reduction."""
+    return expansion_penalty(pcd, primitive_size, alpha)[0].mean()
+
+
+def minimum_density_sample(pcd, npoint, sigma, lengths=None, return_xyz=False):
+    """MSN's minimum density sampling: thin pcd (b, n, 3), n <= 16384, to npoint rows -- FPS's sibling, even density where
+    FPS gives even coverage.  The first sample is row 0; every further one is the row whose Gaussian density
+    sum exp(-d^2 / (2 sigma^2)) under the rows chosen so far is smallest (ties to the smallest index) -> idx (b, npoint)
+    int32, and with return_xyz also the rows themselves (b, npoint, 3), not differentiable (gather_point(pcd, idx) is).
+    sigma: a float, or a (b,) tensor that stays on the device (expansion_penalty's mean_mst.mean(1) flows in without a
+    sync); a sample whose sigma is not positive gets the first npoint rows.  lengths (b,): per-sample point counts; slots
+    behind min(npoint, count) are zeros."""
+    res = _raw.minimum_density_sample(pcd.detach(), npoint, sigma, lengths=lengths, return_xyz=return_xyz)
+    return (res[0], res[2]) if return_xyz else res[0]
+
+
 def earth_mover(pcd1, pcd2, lengths1=None, lengths2=None):
     """mean over the batch of cost_i / #points (vv_recon.py:392-399).  lengths1 / lengths2: per-sample point counts of a
     ragged batch (rf_earth_mover_lengths): the mean of cost_i / lengths1[i], the ragged form of the division by
