@@ -485,7 +485,7 @@ int rf_gridding_grad(int b, int n, int res, float lo, float hi, const float *xyz
  * sum's own roundings -- and two calls may differ within that.  The points get no gradient: the op is piecewise constant
  * in xyz, as in GRNet.  The backward takes xyz and len again and recomputes the cells; it takes no index tensor, so no
  * corrupt index can move a store.  Only GRNet's neighborhood_size = 1 (the eight vertices of the cell) is provided: larger
- * neighbourhoods and trilinear (PVCNN-style) devoxelisation are out of scope.
+ * neighbourhoods are out of scope; trilinear (PVCNN-style) devoxelisation is rf_trilinear_devoxelize, in the next section.
  *
  * rf_gridding_reverse: grid (b, R, R, R) fp32, eps fp32 finite and > 0, compact 0 or 1.  There are M = (R - 1)^3 cells,
  * cell = (ix (R - 1) + iy) (R - 1) + iz with its first vertex v = (ix R + iy) R + iz.  Per cell, all in double:
@@ -532,6 +532,92 @@ int rf_gridding_reverse(int b, int res, float lo, float hi, float eps, int compa
                         int *row, int *count, void *workspace, size_t workspace_bytes, rf_stream_t stream);
 int rf_gridding_reverse_grad(int b, int res, float lo, float hi, const float *grid, const int *row,
                              const float *grad_points, float *grad_grid, rf_stream_t stream);
+
+/* ---- the point-voxel pair: average voxelization and trilinear devoxelization, with gradients -- */
+/* The two ops of the point-voxel networks (PVCNN blocks, Point-Voxel Diffusion, SPVCNN-style refiners): per-point feature
+ * vectors are averaged into the voxel nearest to each point, a 3-D CNN works on the volume, and the volume is interpolated
+ * back at every point.  The grid geometry is the gridding section's, verbatim: R = res vertices per axis,
+ * 2 <= R <= RF_GR_MAX_RES, the box [lo, hi]^3, inv_h = (float)((double)(R - 1) / ((double)hi - (double)lo)) formed on the
+ * host, per axis u = (x - lo) * inv_h in fp32, inside iff 0 <= u <= (float)(R - 1) on all three axes (a NaN fails), the
+ * cell i = min((int)floorf(u), R - 2), t = u - (float)i exact in [0, 1], the vertex index v = (ix R + iy) R + iz, the corners
+ * d in {0, 1}^3 with dz fastest: v + d = v + (dx R + dy) R + dz.  The lattice points of PVCNN's voxel grid are these
+ * vertices.  New here: the NEAREST VERTEX of an inside point is k_a = i_a + (t_a >= 0.5f ? 1 : 0) per axis, always in
+ * 0 ... R - 1 (a tie goes up), k = (kx R + ky) R + kz.
+ *
+ * Layout: point features are (b, n, c) fp32, as in rf_group_point; volumes are channel-first (b, c, R, R, R) fp32 and
+ * contiguous (what a 3-D convolution takes and returns); 1 <= c <= RF_CFS_MAX_CHANNELS, 1 <= n <= RF_GR_MAX_POINTS.  Counts
+ * are device int32 (b) or NULL with rf_nn_distance_lengths' conventions, clamped into [1, n] by the kernels.  The library is
+ * built with -ffp-contract=off: the double arithmetic below has exactly the roundings written.  No host synchronisation, no
+ * hipMemset, no float atomics in global memory, a fixed number of launches on `stream` (rf_voxelize_mean 2, its backward 1;
+ * rf_trilinear_devoxelize 1, its backward 2, and 3 with grad_xyz): every call can be captured in a HIP graph.
+ *
+ * rf_voxelize_mean: from xyz (b, n, 3), len and feat (b, n, c):
+ *   cnt (b, R, R, R) int32: cnt[k] = the number of inside points below the count whose nearest vertex is k.
+ *   vol (b, c, R, R, R): vol[ch][k] = (float)(S / (double)cnt[k]) with S a DOUBLE sum of (double)feat[i][ch] over those
+ *   points; +0 where cnt[k] = 0.
+ *   inside (b) int32: how many points of the sample are inside; it is the sum of cnt.
+ * Every element of all three outputs is written exactly once.  THE ORDER OF THE ADDITIONS IS NOT FIXED (it is the order in
+ * which the points arrive at a workgroup), as for rf_cubic_feature_sampling_grad, and the promise is the same: identical
+ * bits, for every call and batch, whenever the double sum is exact (for instance integer-valued features with sums below
+ * 2^53); otherwise, with exact = (sum of the terms) / cnt in real arithmetic,
+ *   |got - exact| <= 2^-23 |exact| + 2^-52 sum |terms|                    (results in fp32's normal range)
+ * and two calls may differ within that.  Derivation: the double sum of cnt terms makes cnt - 1 roundings, so it is off by at
+ * most (cnt - 1) u (1 + O(cnt u)) sum |terms| with u = 2^-53; divided by cnt that is below u sum |terms|.  The double division
+ * adds at most u |exact| (1 + ...) and the rounding to fp32 at most 2^-24 of the quotient.  Together: at most
+ * (2^-24 + 2 u + O(u 2^-24)) |exact| + (1 + 2^-24 + O(cnt u)) u sum |terms|, and both parentheses are below twice their
+ * leading term for every cnt <= 2^16: hence 2^-23 and 2^-52.
+ *
+ * rf_voxelize_mean_grad: grad_feat (b, n, c) from grad_vol (b, c, R, R, R), xyz, len and the forward's cnt:
+ *   grad_feat[i][ch] = (float)((double)grad_vol[ch][k_i] / (double)cnt[k_i])   for an inside point below the count with
+ *   cnt[k_i] >= 1, and +0 for every other element.  A pure gather with prescribed bits: two calls return identical bits.  k_i
+ * is recomputed from xyz; there is no index tensor, and whatever cnt holds moves no access.  The points get no gradient:
+ * the op is piecewise constant in xyz.
+ *
+ * rf_trilinear_devoxelize: from xyz, len and vol (b, c, R, R, R).  With w_a(0) = 1.0f - t_a and w_a(1) = t_a in fp32 and
+ *   W_d = ((double)w_x(d_x) * (double)w_y(d_y)) * (double)w_z(d_z)          (the first product is exact, the second rounds)
+ *   feat[i][ch] = (float)(sum_{d = 0..7 ascending} W_d * (double)vol[ch][v_i + d])
+ * the sum in double from +0, one rounding per product and per addition, rounded once to fp32; +0 for points outside the
+ * box and rows behind the count.  feat (b, n, c), every element written; inside (b) int32.  A pure function with every
+ * rounding written down: a float64 restatement matches it bit for bit on arbitrary finite inputs.
+ *
+ * rf_trilinear_devoxelize_grad: from xyz, len, vol and grad_feat gf (b, n, c).
+ *   grad_vol (b, c, R, R, R): grad_vol[ch][v] is the fp32 rounding of a DOUBLE sum of the terms W_d(i) * (double)gf[i][ch]
+ *   (each term rounded once, as a double product) over the (i, d) with v_i + d = v, i inside and below the count.  Every
+ *   element is stored exactly once, +0 where nothing fell.  The order of the additions is not fixed; the promise is
+ *   rf_cubic_feature_sampling_grad's: identical bits whenever the sum of the terms is exact, otherwise
+ *   |got - exact| <= 2^-23 |exact| + k 2^-52 sum |terms| for k terms, exact being the exact sum of the prescribed terms.
+ *   grad_xyz (b, n, 3) or NULL (then it is not computed and one launch fewer is made): with
+ *     g_d = sum_{ch ascending} (double)gf[i][ch] * (double)vol[ch][v_i + d]         (every product exact, the sum from +0)
+ *     grad_xyz[i][a] = (float)((double)inv_h * sum_{d ascending} (sigma_a(d) g_d) * (prod_{k != a} (double)w_k(d_k)))
+ *   sigma_a(d) = +1 if d_a = 1 else -1, the sum in double from +0 as in rf_gridding_grad; +0 for points outside the box and
+ *   rows behind the count.  A gather with prescribed bits.
+ *
+ * Guarantees: sample i is the call on [i : i + 1], a ragged call is the call on the sliced clouds, and rows behind a count
+ * are never read -- bit for bit for the prescribed outputs, and as far as the promises above go for vol and grad_vol.  A
+ * non-finite coordinate never moves a memory access: it is simply outside.  Every loop bound is a count.
+ *
+ * Workspace, each part rounded up to 256 bytes, with nb = ceil(R / 16), for rf_voxelize_mean and
+ * rf_trilinear_devoxelize_grad alike:  4 b (nb^3 + 1)  list starts  + 8 b n  one record per point (its vertex or cell and
+ * its index).
+ *
+ * Argument rules, all checked before any HIP call, as for rf_gridding: RF_EINVAL for a negative size; then b == 0 is RF_OK;
+ * RF_EINVAL for n outside 1 ... RF_GR_MAX_POINTS, c outside 1 ... RF_CFS_MAX_CHANNELS, res outside 2 ... RF_GR_MAX_RES, b
+ * above 65535, a non-finite lo or hi or lo >= hi, a NULL tensor (len and grad_xyz may be NULL), a tensor or count array not
+ * 4-byte aligned, a workspace that is NULL or not 16-byte aligned; RF_EWORKSPACE for a workspace smaller than the
+ * _workspace_bytes function states (0 for non-positive or unsupported sizes, positive otherwise).  All index arithmetic is
+ * in size_t.  Out of scope: PVCNN's coordinate normalisation (torch ops in front of the call), non-cubic boxes, and bit
+ * parity with PVCNN's CUDA ops (torch.round's ties to even, float atomics). */
+size_t rf_voxelize_mean_workspace_bytes(int b, int n, int res);
+int rf_voxelize_mean(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len, const float *feat,
+                     float *vol, int *cnt, int *inside, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+int rf_voxelize_mean_grad(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len, const int *cnt,
+                          const float *grad_vol, float *grad_feat, rf_stream_t stream);
+int rf_trilinear_devoxelize(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len,
+                            const float *vol, float *feat, int *inside, rf_stream_t stream);
+size_t rf_trilinear_devoxelize_grad_workspace_bytes(int b, int n, int res);
+int rf_trilinear_devoxelize_grad(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len,
+                                 const float *vol, const float *grad_feat, float *grad_vol, float *grad_xyz,
+                                 void *workspace, size_t workspace_bytes, rf_stream_t stream);
 
 /* ---- the exact earth mover's distance: optimal assignment with a certificate and gradients -- */
 /* The one-to-one assignment of minimal total distance between two clouds of EQUAL counts, by a deterministic Jacobi

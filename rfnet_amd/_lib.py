@@ -78,6 +78,12 @@ SIGNATURES = {
     "rf_gridding_reverse_workspace_bytes": (_sz, [_i, _i]),
     "rf_gridding_reverse": (_i, [_i, _i, _f, _f, _f, _i] + [_vp] * 5 + [_sz, _vp]),
     "rf_gridding_reverse_grad": (_i, [_i, _i, _f, _f] + [_vp] * 5),
+    "rf_voxelize_mean_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_voxelize_mean": (_i, [_i, _i, _i, _i, _f, _f] + [_vp] * 7 + [_sz, _vp]),
+    "rf_voxelize_mean_grad": (_i, [_i, _i, _i, _i, _f, _f] + [_vp] * 6),
+    "rf_trilinear_devoxelize": (_i, [_i, _i, _i, _i, _f, _f] + [_vp] * 6),
+    "rf_trilinear_devoxelize_grad_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_trilinear_devoxelize_grad": (_i, [_i, _i, _i, _i, _f, _f] + [_vp] * 7 + [_sz, _vp]),
     "rf_emd_assign_supported": (_i, [_i]),
     "rf_emd_assign_workspace_bytes": (_sz, [_i, _i]),
     "rf_emd_assign": (_i, [_i, _i, _vp, _vp, _vp, _i] + [_vp] * 7 + [_sz, _vp]),

@@ -812,6 +812,116 @@ def gridding_reverse_grad(grid, row, grad_points, lo, hi):
     return st.give(out)
 
 
+PV_BRICK, PV_CHUNK = 8, 8  # point_voxel.hip: a scatter workgroup's sub-brick edge in vertices, and its channels
+
+
+def _pv_features(op, st, t, name, b, n):
+    f = st.take(t, F32)
+    if f.dim() != 3 or tuple(f.shape[:2]) != (b, n):
+        raise H.invalid(f"{op} requires {name} be of shape (batch,#points,channels)")
+    if f.shape[2] < 1 or f.shape[2] > CFS_MAX_CHANNELS:
+        raise H.invalid(f"{op} takes 1 to {CFS_MAX_CHANNELS} channels")
+    return f
+
+
+@H.on_input_device
+def avg_voxelize(xyz, feat, res, lo, hi, lengths=None):
+    """rf_voxelize_mean: average voxelization -> (vol (b, c, res, res, res) fp32, cnt (b, res, res, res) int32, inside (b,)
+    int32): the feature vectors feat (b, n, c) of the points of xyz (b, n, 3) inside [lo, hi]^3, averaged per nearest vertex of
+    the grid (a tie goes up); fp32 roundings of double sums divided by the count, +0 where no point fell, no float atomics."""
+    st = H.Staged()
+    a = _gr_cloud("avg_voxelize", st, xyz, "xyz")
+    res, lo, hi = _gr_box("avg_voxelize", res, lo, hi)
+    b, n = a.shape[0], a.shape[1]
+    f = _pv_features("avg_voxelize", st, feat, "feat", b, n)
+    c = f.shape[2]
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    a, f = st.up(a, f)
+    ln = _lengths_up(ln, dev, n)
+    vol, cnt = H.empty((b, c, res, res, res), F32, dev), H.empty((b, res, res, res), I32, dev)
+    inside = H.empty((b,), I32, dev)
+    if b > 0:
+        ws, wsz = H.workspace(lib.rf_voxelize_mean_workspace_bytes(b, n, res), dev, "point_voxel")
+        check(lib.rf_voxelize_mean(b, n, c, res, lo, hi, H.ptr(a), H.ptr(ln), H.ptr(f), H.ptr(vol), H.ptr(cnt), H.ptr(inside),
+                                   H.ptr(ws), wsz, H.stream(dev)), "rf_voxelize_mean")
+    return st.give(vol), st.give(cnt), st.give(inside)
+
+
+@H.on_input_device
+def avg_voxelize_grad(xyz, cnt, grad_vol, lo, hi, lengths=None):
+    """rf_voxelize_mean_grad: the backward of avg_voxelize -> grad_feat (b, n, c) from the forward's cnt (b, res, res, res)
+    and grad_vol (b, c, res, res, res): grad_vol at the point's nearest vertex over that vertex's count, +0 for points outside the
+    box and rows behind the count.  The vertices are recomputed from xyz."""
+    st = H.Staged()
+    a = _gr_cloud("avg_voxelize_grad", st, xyz, "xyz")
+    b, n = a.shape[0], a.shape[1]
+    gv = _cfs_volume("avg_voxelize_grad", st, grad_vol, "grad_vol", b)
+    c = gv.shape[1]
+    res, lo, hi = _gr_box("avg_voxelize_grad", gv.shape[2], lo, hi)
+    k = st.take(cnt, I32)
+    if tuple(k.shape) != (b, res, res, res):
+        raise H.invalid("avg_voxelize_grad requires cnt be of shape (batch,res,res,res)")
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    a, k, gv = st.up(a, k, gv)
+    ln = _lengths_up(ln, dev, n)
+    out = H.empty((b, n, c), F32, dev)
+    if b > 0:
+        check(lib.rf_voxelize_mean_grad(b, n, c, res, lo, hi, H.ptr(a), H.ptr(ln), H.ptr(k), H.ptr(gv), H.ptr(out),
+                                        H.stream(dev)), "rf_voxelize_mean_grad")
+    return st.give(out)
+
+
+@H.on_input_device
+def trilinear_devoxelize(xyz, vol, lo, hi, lengths=None):
+    """rf_trilinear_devoxelize: trilinear devoxelization -> (feat (b, n, c) fp32, inside (b,) int32): vol (b, c, R, R, R)
+    interpolated at every point of xyz (b, n, 3) inside [lo, hi]^3 from the eight vertices of its cell, in double with every
+    rounding prescribed; +0 for points outside the box and rows behind the count."""
+    st = H.Staged()
+    a = _gr_cloud("trilinear_devoxelize", st, xyz, "xyz")
+    b, n = a.shape[0], a.shape[1]
+    v = _cfs_volume("trilinear_devoxelize", st, vol, "vol", b)
+    c = v.shape[1]
+    res, lo, hi = _gr_box("trilinear_devoxelize", v.shape[2], lo, hi)
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    a, v = st.up(a, v)
+    ln = _lengths_up(ln, dev, n)
+    feat, inside = H.empty((b, n, c), F32, dev), H.empty((b,), I32, dev)
+    if b > 0:
+        check(lib.rf_trilinear_devoxelize(b, n, c, res, lo, hi, H.ptr(a), H.ptr(ln), H.ptr(v), H.ptr(feat), H.ptr(inside),
+                                          H.stream(dev)), "rf_trilinear_devoxelize")
+    return st.give(feat), st.give(inside)
+
+
+@H.on_input_device
+def trilinear_devoxelize_grad(xyz, vol, grad_feat, lo, hi, lengths=None, want_xyz=True):
+    """rf_trilinear_devoxelize_grad: the backward of trilinear_devoxelize -> (grad_vol (b, c, R, R, R), grad_xyz (b, n, 3) or
+    None without `want_xyz`) from grad_feat (b, n, c): grad_vol as fp32 roundings of double sums, every element written once, no
+    float atomics in memory; grad_xyz a gather in double.  The cells and weights are recomputed from xyz."""
+    st = H.Staged()
+    a = _gr_cloud("trilinear_devoxelize_grad", st, xyz, "xyz")
+    b, n = a.shape[0], a.shape[1]
+    v = _cfs_volume("trilinear_devoxelize_grad", st, vol, "vol", b)
+    c = v.shape[1]
+    res, lo, hi = _gr_box("trilinear_devoxelize_grad", v.shape[2], lo, hi)
+    gf = st.take(grad_feat, F32)
+    if tuple(gf.shape) != (b, n, c):
+        raise H.invalid("trilinear_devoxelize_grad requires grad_feat be of shape (batch,#points,channels)")
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    a, v, gf = st.up(a, v, gf)
+    ln = _lengths_up(ln, dev, n)
+    gv = H.empty((b, c, res, res, res), F32, dev)
+    gx = H.empty((b, n, 3), F32, dev) if want_xyz else None
+    if b > 0:
+        ws, wsz = H.workspace(lib.rf_trilinear_devoxelize_grad_workspace_bytes(b, n, res), dev, "point_voxel")
+        check(lib.rf_trilinear_devoxelize_grad(b, n, c, res, lo, hi, H.ptr(a), H.ptr(ln), H.ptr(v), H.ptr(gf), H.ptr(gv),
+                                               H.ptr(gx), H.ptr(ws), wsz, H.stream(dev)), "rf_trilinear_devoxelize_grad")
+    return st.give(gv), (st.give(gx) if want_xyz else None)
+
+
 EA_MAX_POINTS = 4096  # RF_EA_MAX_POINTS (include/rfops.h)
 EA_OK, EA_CAPPED, EA_NONFINITE = 0, 1, 2  # RF_EA_* status values
 EA_TPB, EA_WAVE = 1024, 64  # emd_assign.hip's tiles: threads of the one workgroup per sample; lanes a bidder's scan strides by

@@ -1,0 +1,579 @@
+// point_voxel.hip -- the point-voxel pair of PVCNN-style networks: average voxelization (per-point feature vectors averaged into
+// the voxel nearest to each point) and trilinear devoxelization (a (b, c, R, R, R) feature volume interpolated back at every
+// point), both with gradients.  include/rfops.h states the contract, DESIGN.md 5.3o the layout and the measurements.  The geometry
+// is gridding.hpp's, shared with gridding.hip and grnet_layers.hip; the lattice points of PVCNN's voxel grid are its vertices.
+//
+//   voxelize        no float atomics in memory and no memset: the inside points are counting-sorted by the brick (GR_E^3
+//                   vertices) of their NEAREST vertex, the record carrying that vertex and the point index; one workgroup per
+//                   (sample, sub-brick of PV_E^3 vertices, chunk of PV_CHUNK channels) walks its own brick's list only, compacts
+//                   the records of its sub-brick through LDS, and a wave then takes eight of them per step with a lane per
+//                   (record, channel) -- eight reads of PV_CHUNK contiguous floats of feat -- adding into LDS doubles and LDS
+//                   integer counts; every element of vol is stored once as sum / count, the chunk-0 workgroup stores cnt.
+//   voxelize grad   the plain gather: grad_vol[ch][k_i] / cnt[k_i], k_i recomputed from xyz.
+//   devoxelize      the plain gather, cfs_gather_kernel's shape: a workgroup takes PV_PTS points, cell and t go through LDS, the
+//                   threads run over the (point, channel) elements of the output in memory order; eight plane reads, a double sum.
+//   devoxelize grad grad_vol is cfs_brick_kernel's walk of up to eight lists over a sort by the brick of the CELL, a record per
+//                   step with a lane per (corner, channel), the weight recomputed from xyz[i] and one read of grad_feat[i][ch];
+//                   grad_xyz is a gather with eight lanes per point, lane d summing g_d over the channels in ascending order.
+//
+// Every kernel with a (tile, sample) grid takes its logical place from pv_place: the workgroups of a sample share one XCD's L2.
+// The counting sort is cfs_bin_kernel's with another key.  It is restated here rather than shared: moving it into a header
+// would change what grnet_layers.hip compiles to.
+#include "gridding.hpp"
+
+namespace {
+
+constexpr int PV_TPB = 256, PV_PTS = 32;
+constexpr int PV_BIN_TPB = 1024, PV_MAX_NB3 = 4096;
+constexpr int PV_E = 8, PV_E3 = PV_E * PV_E * PV_E;  // vertices per sub-brick edge
+constexpr int PV_CHUNK = 8;                          // channels per workgroup: 8 records (or corners) x 8 channels = one wave per step
+static_assert(PV_MAX_NB3 == (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E) && PV_MAX_NB3 == 4 * PV_BIN_TPB, "");
+static_assert(GR_E == 2 * PV_E && 8 * PV_CHUNK == 64 && PV_E3 * PV_CHUNK * sizeof(double) == 32768, "");
+static_assert(RF_GR_MAX_POINTS <= 65536 && PV_E3 <= 65536 && RF_GR_MAX_RES <= 256, "a record holds 3 x 8 bits of vertex and 16 bits of index");
+
+struct PvPoint {
+    int ix, iy, iz;  // the cell
+    float tx, ty, tz;
+};
+
+// the point's cell and t, false for a point outside the box (its fields are then not to be used)
+__device__ __forceinline__ bool pv_point(const float *__restrict__ x, const GrBox &g, PvPoint &p) {
+    const bool inx = gr_axis(x[0], g, p.ix, p.tx), iny = gr_axis(x[1], g, p.iy, p.ty), inz = gr_axis(x[2], g, p.iz, p.tz);
+    return inx & iny & inz;
+}
+
+// the nearest vertex: i + (t >= 0.5f), in 0 ... R - 1 because i <= R - 2
+__device__ __forceinline__ void pv_nearest(const PvPoint &p, int &kx, int &ky, int &kz) {
+    kx = p.ix + (p.tx >= 0.5f ? 1 : 0), ky = p.iy + (p.ty >= 0.5f ? 1 : 0), kz = p.iz + (p.tz >= 0.5f ? 1 : 0);
+}
+
+// W_d = ((double)w_x(d_x) * (double)w_y(d_y)) * (double)w_z(d_z) with w(0) = 1.0f - t and w(1) = t in fp32
+__device__ __forceinline__ double pv_weight(const PvPoint &p, int dx, int dy, int dz) {
+    const float wx = dx ? p.tx : 1.0f - p.tx, wy = dy ? p.ty : 1.0f - p.ty, wz = dz ? p.tz : 1.0f - p.tz;
+    return ((double)wx * (double)wy) * (double)wz;
+}
+
+// The workgroup's logical place in its (x, sample) grid.  Workgroup ids go round the 8 XCDs; rf::xcd_contiguous gives every XCD a
+// contiguous run of the logical order, so that the workgroups of one sample -- which read the same volume, and in the scatter
+// kernels the chunk workgroups of one sub-brick, which read the same rows of features -- share one L2 (profiles/point_voxel_ab.txt).
+__device__ __forceinline__ void pv_place(int &x, int &s) {
+    const unsigned pos = rf::xcd_contiguous(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
+    s = (int)(pos / gridDim.x), x = (int)(pos - (unsigned)s * gridDim.x);
+}
+
+// ------------------------------------------------------------------------------------------------ the counting sort
+struct PvBin {
+    int n;
+    GrBox g;
+    const float *xyz;
+    const int *len;
+    unsigned *starts;          // (b, nb^3 + 1): where every brick's list begins; the last entry is the inside count
+    unsigned long long *recs;  // (b, n): the key (3 x 8 bits) and the point index (16 bits, from bit 24)
+};
+
+// cfs_bin_kernel for one cloud; the key is the cell, or with NEAREST the nearest vertex.  grid (b)
+template <bool NEAREST>
+__global__ __launch_bounds__(PV_BIN_TPB) void pv_bin_kernel(PvBin a) {
+    __shared__ unsigned hist[PV_MAX_NB3];
+    __shared__ unsigned wtot[PV_BIN_TPB / 64];
+    const int s = blockIdx.x, tid = threadIdx.x, n = a.n;
+    const int L = rf::ragged_count(a.len, s, n);
+    const float *__restrict__ xyz = a.xyz + (size_t)s * n * 3;
+    const GrBox g = a.g;
+    const int nb = gr_nb(g.R), nb3 = nb * nb * nb;
+    unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
+    unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
+
+    auto key = [&](int i, int &kx, int &ky, int &kz) {
+        PvPoint p;
+        const bool in = pv_point(xyz + (size_t)i * 3, g, p);
+        if (NEAREST)
+            pv_nearest(p, kx, ky, kz);
+        else
+            kx = p.ix, ky = p.iy, kz = p.iz;
+        return in;
+    };
+    for (int k = tid; k < nb3; k += PV_BIN_TPB) hist[k] = 0;
+    __syncthreads();
+    for (int i = tid; i < L; i += PV_BIN_TPB) {
+        int kx, ky, kz;
+        if (key(i, kx, ky, kz)) atomicAdd(&hist[((kx / GR_E) * nb + ky / GR_E) * nb + kz / GR_E], 1u);  // k <= R - 1: a brick < nb
+    }
+    __syncthreads();
+    unsigned cn[4], tsum = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int idx = tid * 4 + k;
+        cn[k] = idx < nb3 ? hist[idx] : 0u;
+        tsum += cn[k];
+    }
+    const unsigned incl = rf::wave_incl_scan(tsum);
+    if ((tid & 63) == 63) wtot[tid >> 6] = incl;
+    __syncthreads();
+    unsigned run = incl - tsum;
+    for (int w = 0; w < (tid >> 6); w++) run += wtot[w];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int idx = tid * 4 + k;
+        if (idx < nb3) hist[idx] = run, st[idx] = run;  // the bin's cursor and its start
+        run += cn[k];
+    }
+    if (tid == PV_BIN_TPB - 1) st[nb3] = run;
+    __syncthreads();
+    for (int i = tid; i < L; i += PV_BIN_TPB) {
+        int kx, ky, kz;
+        if (key(i, kx, ky, kz)) {
+            const unsigned pos = atomicAdd(&hist[((kx / GR_E) * nb + ky / GR_E) * nb + kz / GR_E], 1u);
+            rec[pos] = (unsigned long long)((unsigned)kx | (unsigned)ky << 8 | (unsigned)kz << 16) |
+                       (unsigned long long)(unsigned)i << 24;  // pos < the inside count <= L; i < 65536
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ average voxelization
+struct PvVox {
+    int n, c, R;
+    const unsigned *starts;
+    const unsigned long long *recs;
+    const float *feat;  // (b, n, c)
+    float *vol;         // (b, c, R, R, R)
+    int *cnt;           // (b, R, R, R)
+    int *inside;        // (b)
+};
+
+// grid (ceil(R / PV_E)^3 * ceil(c / PV_CHUNK), b), the channel chunk fastest
+__global__ __launch_bounds__(PV_TPB) void pv_vox_kernel(PvVox a) {
+    __shared__ double acc[PV_E3 * PV_CHUNK];  // [vertex][channel]
+    __shared__ unsigned num[PV_E3];
+    __shared__ unsigned slot[PV_TPB];  // a wave's 64: the records of this sub-brick among the 64 it has just read
+    int s, bx;
+    pv_place(bx, s);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int R = a.R, c = a.c, n = a.n;
+    const int nsb = (R + PV_E - 1) / PV_E, nchunk = (c + PV_CHUNK - 1) / PV_CHUNK;
+    const int nb = gr_nb(R), nb3 = nb * nb * nb;
+    const int sbi = bx / nchunk, ch0 = (bx - sbi * nchunk) * PV_CHUNK;
+    const int sz = sbi % nsb, sy = (sbi / nsb) % nsb, sx = sbi / (nsb * nsb);
+    const unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
+    const size_t R3 = (size_t)R * R * R;
+    if (bx == 0 && tid == 0) a.inside[s] = (int)st[nb3];
+
+    // the key of the sort is the vertex: the records that reach this sub-brick are in its own brick's list
+    const int q = ((sx >> 1) * nb + (sy >> 1)) * nb + (sz >> 1);
+    const unsigned lo = st[q], hi = st[q + 1];
+    const bool any = hi > lo;  // (uniform over the workgroup)
+    if (any) {
+        for (int l = tid; l < PV_E3 * PV_CHUNK; l += PV_TPB) acc[l] = 0.0;
+        for (int l = tid; l < PV_E3; l += PV_TPB) num[l] = 0u;
+        __syncthreads();
+        const unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
+        const float *__restrict__ feat = a.feat + (size_t)s * n * c;
+        const int grp = lane >> 3, ch = lane & 7;
+        const bool chok = ch0 + ch < c;
+        unsigned *__restrict__ mine = slot + wave * 64;
+        for (unsigned r0 = lo + wave * 64; r0 < hi; r0 += PV_TPB) {  // uniform over the wave
+            const unsigned r = r0 + lane;
+            const unsigned long long w = r < hi ? rec[r] : 0ull;
+            const int lx = (int)((unsigned)w & 255u) - sx * PV_E, ly = (int)((unsigned)(w >> 8) & 255u) - sy * PV_E,
+                      lz = (int)((unsigned)(w >> 16) & 255u) - sz * PV_E;
+            const bool keep = r < hi && (unsigned)lx < (unsigned)PV_E && (unsigned)ly < (unsigned)PV_E && (unsigned)lz < (unsigned)PV_E;
+            const unsigned long long mask = __ballot(keep);
+            const int kept = __popcll(mask);
+            const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+            // the local vertex (< PV_E3) and the point index (< n: written by the bin kernel from a row below the count)
+            if (keep) mine[rank] = ((unsigned)(w >> 24) & 0xFFFFu) | (unsigned)((lx * PV_E + ly) * PV_E + lz) << 16;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int j = grp; j < kept; j += 8) {  // eight records per step, a lane per (record, channel)
+                const unsigned k = mine[j];
+                const int i = (int)(k & 0xFFFFu), v = (int)(k >> 16) & (PV_E3 - 1);
+                if (ch == 0) atomicAdd(&num[v], 1u);
+                if (chok) atomicAdd(&acc[v * PV_CHUNK + ch], (double)feat[(size_t)i * c + ch0 + ch]);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+        __syncthreads();
+    }
+    float *__restrict__ vol = a.vol + ((size_t)s * c + ch0) * R3;
+    for (int e = tid; e < PV_E3 * PV_CHUNK; e += PV_TPB) {
+        const int chh = e / PV_E3, l = e % PV_E3;
+        const int gx = sx * PV_E + l / (PV_E * PV_E), gy = sy * PV_E + (l / PV_E) % PV_E, gz = sz * PV_E + l % PV_E;
+        if (ch0 + chh < c && gx < R && gy < R && gz < R) {
+            const unsigned k = any ? num[l] : 0u;
+            vol[(size_t)chh * R3 + ((size_t)gx * R + gy) * R + gz] = k ? (float)(acc[l * PV_CHUNK + chh] / (double)k) : 0.f;
+        }
+    }
+    if (ch0 == 0) {
+        int *__restrict__ cnt = a.cnt + (size_t)s * R3;
+        for (int l = tid; l < PV_E3; l += PV_TPB) {
+            const int gx = sx * PV_E + l / (PV_E * PV_E), gy = sy * PV_E + (l / PV_E) % PV_E, gz = sz * PV_E + l % PV_E;
+            if (gx < R && gy < R && gz < R) cnt[((size_t)gx * R + gy) * R + gz] = any ? (int)num[l] : 0;
+        }
+    }
+}
+
+struct PvVoxGrad {
+    int n, c;
+    GrBox g;
+    const float *xyz;
+    const int *len;
+    const int *cnt;   // (b, R, R, R): the forward's
+    const float *gv;  // (b, c, R, R, R)
+    float *gf;        // (b, n, c)
+};
+
+// grid (ceil(n / PV_PTS), b)
+__global__ __launch_bounds__(PV_TPB) void pv_vox_grad_kernel(PvVoxGrad a) {
+    __shared__ int vtx[PV_PTS];
+    __shared__ int num[PV_PTS];
+    int s, bx;
+    pv_place(bx, s);
+    const int tid = threadIdx.x, n = a.n, c = a.c;
+    const GrBox g = a.g;
+    const int R = g.R, L = rf::ragged_count(a.len, s, n);
+    const size_t R3 = (size_t)R * R * R;
+    const int p0 = bx * PV_PTS;
+    if (tid < PV_PTS) {
+        const int i = p0 + tid;
+        int v = -1, k = 0;
+        if (i < L) {
+            PvPoint p;
+            if (pv_point(a.xyz + ((size_t)s * n + i) * 3, g, p)) {
+                int kx, ky, kz;
+                pv_nearest(p, kx, ky, kz);
+                v = (kx * R + ky) * R + kz;
+                k = a.cnt[(size_t)s * R3 + v];
+            }
+        }
+        vtx[tid] = v, num[tid] = k;
+    }
+    __syncthreads();
+    const int np = n - p0 < PV_PTS ? n - p0 : PV_PTS, total = np * c;
+    const float *__restrict__ gv = a.gv + (size_t)s * c * R3;
+    float *__restrict__ gf = a.gf + ((size_t)s * n + p0) * c;
+#pragma unroll 4
+    for (int e = tid; e < total; e += PV_TPB) {
+        const int p = e / c, ch = e - p * c;
+        const int v = vtx[p], k = num[p];
+        const bool ok = v >= 0 && k >= 1;
+        const float w = gv[(size_t)ch * R3 + (size_t)(ok ? v : 0)];  // an unconditional load, so that several are in flight
+        gf[e] = ok ? (float)((double)w / (double)k) : 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ trilinear devoxelization
+struct PvDevox {
+    int n, c;
+    GrBox g;
+    const float *xyz;
+    const int *len;
+    const float *vol;  // (b, c, R, R, R)
+    float *feat;       // (b, n, c)
+    int *inside;
+};
+
+// grid (ceil(n / PV_PTS), b)
+__global__ __launch_bounds__(PV_TPB) void pv_devox_kernel(PvDevox a) {
+    __shared__ int vtx[PV_PTS];
+    __shared__ float tt[PV_PTS * 3];
+    __shared__ unsigned wcnt[PV_TPB / 64];
+    int s, bx;
+    pv_place(bx, s);
+    const int tid = threadIdx.x, n = a.n, c = a.c;
+    const GrBox g = a.g;
+    const int R = g.R, L = rf::ragged_count(a.len, s, n);
+    const float *__restrict__ xyz = a.xyz + (size_t)s * n * 3;
+    const int p0 = bx * PV_PTS;
+    if (tid < PV_PTS) {
+        const int i = p0 + tid;
+        PvPoint p;
+        const bool in = i < L && pv_point(xyz + (size_t)i * 3, g, p);
+        vtx[tid] = in ? (p.ix * R + p.iy) * R + p.iz : -1;
+        tt[tid * 3] = in ? p.tx : 0.f, tt[tid * 3 + 1] = in ? p.ty : 0.f, tt[tid * 3 + 2] = in ? p.tz : 0.f;
+    }
+    if (bx == 0) {  // the inside count of the sample
+        unsigned cnt = 0;
+        for (int i = tid; i < L; i += PV_TPB) {
+            PvPoint p;
+            cnt += pv_point(xyz + (size_t)i * 3, g, p);
+        }
+        cnt = rf::wave_add_u32(cnt);
+        if ((tid & 63) == 0) wcnt[tid >> 6] = cnt;
+    }
+    __syncthreads();
+    if (bx == 0 && tid == 0) a.inside[s] = (int)((wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]));
+    const int np = n - p0 < PV_PTS ? n - p0 : PV_PTS, total = np * c;
+    const size_t R3 = (size_t)R * R * R;
+    const float *__restrict__ vol = a.vol + (size_t)s * c * R3;
+    float *__restrict__ feat = a.feat + ((size_t)s * n + p0) * c;
+    for (int e = tid; e < total; e += PV_TPB) {
+        const int p = e / c, ch = e - p * c;
+        const int v = vtx[p];
+        float o = 0.f;
+        if (v >= 0) {
+            PvPoint q;
+            q.tx = tt[p * 3], q.ty = tt[p * 3 + 1], q.tz = tt[p * 3 + 2];
+            const float *__restrict__ pl = vol + (size_t)ch * R3 + (size_t)v;
+            double sum = 0.0;
+#pragma unroll
+            for (int d = 0; d < 8; d++) {
+                const int dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
+                sum += pv_weight(q, dx, dy, dz) * (double)pl[((size_t)dx * R + dy) * R + dz];
+            }
+            o = (float)sum;
+        }
+        feat[e] = o;
+    }
+}
+
+struct PvBrick {
+    int n, c;
+    GrBox g;
+    const unsigned *starts;
+    const unsigned long long *recs;
+    const float *xyz;
+    const float *gf;  // (b, n, c)
+    float *gv;        // (b, c, R, R, R)
+};
+
+// cfs_brick_kernel with a weight.  grid (ceil(R / PV_E)^3 * ceil(c / PV_CHUNK), b), the channel chunk fastest
+__global__ __launch_bounds__(PV_TPB) void pv_devox_brick_kernel(PvBrick a) {
+    __shared__ double acc[PV_E3 * PV_CHUNK];  // [vertex][channel]
+    int s, bx;
+    pv_place(bx, s);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const GrBox g = a.g;
+    const int R = g.R, c = a.c, n = a.n;
+    const int nsb = (R + PV_E - 1) / PV_E, nchunk = (c + PV_CHUNK - 1) / PV_CHUNK;
+    const int nb = gr_nb(R), nb3 = nb * nb * nb;
+    const int sbi = bx / nchunk, ch0 = (bx - sbi * nchunk) * PV_CHUNK;
+    const int sz = sbi % nsb, sy = (sbi / nsb) % nsb, sx = sbi / (nsb * nsb);
+    const unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
+    const size_t R3 = (size_t)R * R * R;
+    float *__restrict__ gv = a.gv + ((size_t)s * c + ch0) * R3;
+
+    // The cells that reach this sub-brick's vertices are those of its own brick and, where the sub-brick is the lower half of its
+    // brick along an axis, of the lower neighbour along that axis: at most eight lists.
+    auto list = [&](int d, unsigned &lo, unsigned &hi) {
+        const int dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
+        const int nx = (sx >> 1) - dx, ny = (sy >> 1) - dy, nz = (sz >> 1) - dz;
+        const bool skip = (dx && ((sx & 1) || nx < 0)) || (dy && ((sy & 1) || ny < 0)) || (dz && ((sz & 1) || nz < 0));
+        const int q = skip ? 0 : (nx * nb + ny) * nb + nz;
+        lo = st[q], hi = skip ? lo : st[q + 1];
+    };
+    unsigned any = 0;
+#pragma unroll
+    for (int d = 0; d < 8; d++) {
+        unsigned lo, hi;
+        list(d, lo, hi);
+        any |= hi - lo;
+    }
+    if (any) {  // (uniform over the workgroup)
+        for (int l = tid; l < PV_E3 * PV_CHUNK; l += PV_TPB) acc[l] = 0.0;
+        __syncthreads();
+        const unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
+        const float *__restrict__ xyz = a.xyz + (size_t)s * n * 3;
+        const float *__restrict__ gf = a.gf + (size_t)s * n * c;
+        const int d = lane >> 3, ch = lane & 7, dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
+        const bool chok = ch0 + ch < c;
+#pragma unroll 1
+        for (int q = 0; q < 8; q++) {
+            unsigned lo, hi;
+            list(q, lo, hi);
+            for (unsigned r0 = lo + wave * 64; r0 < hi; r0 += PV_TPB) {  // uniform over the wave
+                const unsigned r = r0 + lane;
+                const unsigned long long w = r < hi ? rec[r] : 0ull;
+                // the cell relative to this sub-brick's first vertex: kept iff -1 ... 7 on every axis
+                const int cx = (int)((unsigned)w & 255u) - sx * PV_E + 1, cy = (int)((unsigned)(w >> 8) & 255u) - sy * PV_E + 1,
+                          cz = (int)((unsigned)(w >> 16) & 255u) - sz * PV_E + 1;
+                const bool keep = r < hi && (unsigned)cx <= (unsigned)PV_E && (unsigned)cy <= (unsigned)PV_E &&
+                                  (unsigned)cz <= (unsigned)PV_E;
+                const unsigned key = ((unsigned)(w >> 24) & 0xFFFFu) | (unsigned)cx << 16 | (unsigned)cy << 20 | (unsigned)cz << 24;
+                unsigned long long mask = __ballot(keep);
+                while (mask) {  // a record per step, a lane per (corner, channel)
+                    const int j = __ffsll((long long)mask) - 1;
+                    mask &= mask - 1;
+                    const unsigned k = (unsigned)__shfl((int)key, j, 64);
+                    const int i = (int)(k & 0xFFFFu);  // < n: written by the bin kernel from a row below the count
+                    const int lx = (int)((k >> 16) & 15u) - 1 + dx, ly = (int)((k >> 20) & 15u) - 1 + dy,
+                              lz = (int)((k >> 24) & 15u) - 1 + dz;
+                    if ((unsigned)lx < (unsigned)PV_E && (unsigned)ly < (unsigned)PV_E && (unsigned)lz < (unsigned)PV_E && chok) {
+                        PvPoint p;
+                        pv_point(xyz + (size_t)i * 3, g, p);  // inside: the bin kernel kept it; only t is used
+                        atomicAdd(&acc[((lx * PV_E + ly) * PV_E + lz) * PV_CHUNK + ch],
+                                  pv_weight(p, dx, dy, dz) * (double)gf[(size_t)i * c + ch0 + ch]);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < PV_E3 * PV_CHUNK; e += PV_TPB) {
+        const int chh = e / PV_E3, l = e % PV_E3;
+        const int gx = sx * PV_E + l / (PV_E * PV_E), gy = sy * PV_E + (l / PV_E) % PV_E, gz = sz * PV_E + l % PV_E;
+        if (ch0 + chh < c && gx < R && gy < R && gz < R)
+            gv[(size_t)chh * R3 + ((size_t)gx * R + gy) * R + gz] = any ? (float)acc[l * PV_CHUNK + chh] : 0.f;
+    }
+}
+
+struct PvXyzGrad {
+    int n, c;
+    GrBox g;
+    const float *xyz;
+    const int *len;
+    const float *vol;  // (b, c, R, R, R)
+    const float *gf;   // (b, n, c)
+    float *out;        // (b, n, 3)
+};
+
+// grid (ceil(n / PV_PTS), b): eight lanes per point, lane d sums g_d over the channels; lanes 0 ... 2 then form one axis each
+__global__ __launch_bounds__(PV_TPB) void pv_devox_xyz_kernel(PvXyzGrad a) {
+    int s, bx;
+    pv_place(bx, s);
+    const int tid = threadIdx.x, n = a.n, c = a.c;
+    const int i = bx * PV_PTS + (tid >> 3), d = tid & 7;
+    const GrBox g = a.g;
+    const int R = g.R, L = rf::ragged_count(a.len, s, n);
+    const size_t R3 = (size_t)R * R * R;
+    PvPoint p;
+    p.ix = p.iy = p.iz = 0, p.tx = p.ty = p.tz = 0.f;
+    bool in = false;
+    if (i < L) in = pv_point(a.xyz + ((size_t)s * n + i) * 3, g, p);
+    double gd = 0.0;
+    if (in) {
+        const float *__restrict__ pl = a.vol + (size_t)s * c * R3 + ((size_t)(p.ix + (d >> 2)) * R + (p.iy + ((d >> 1) & 1))) * R + (p.iz + (d & 1));
+        const float *__restrict__ gf = a.gf + ((size_t)s * n + i) * c;
+        for (int ch = 0; ch < c; ch++) gd += (double)gf[ch] * (double)pl[(size_t)ch * R3];
+    }
+    const double wx[2] = {(double)(1.0f - p.tx), (double)p.tx}, wy[2] = {(double)(1.0f - p.ty), (double)p.ty},
+                 wz[2] = {(double)(1.0f - p.tz), (double)p.tz};
+    double acc = 0.0;
+#pragma unroll
+    for (int e = 0; e < 8; e++) {  // (every lane takes part in the shuffles)
+        const int ex = e >> 2, ey = (e >> 1) & 1, ez = e & 1;
+        const double v = __shfl(gd, (tid & 56) + e, 64);
+        const bool up = d == 0 ? ex : (d == 1 ? ey : ez);
+        const double w = d == 0 ? wy[ey] * wz[ez] : (d == 1 ? wx[ex] * wz[ez] : wx[ex] * wy[ey]);
+        acc += (up ? v : -v) * w;
+    }
+    if (i < n && d < 3) a.out[((size_t)s * n + i) * 3 + d] = in ? (float)((double)g.inv_h * acc) : 0.f;
+}
+
+struct PvLayout {
+    size_t starts, recs, total;
+};
+
+PvLayout pv_layout(int b, int n, int res) {
+    const size_t nb = gr_nb(res), nb3 = nb * nb * nb;
+    PvLayout l;
+    l.starts = 0;
+    l.recs = l.starts + rf::align256((size_t)b * (nb3 + 1) * sizeof(unsigned));
+    l.total = l.recs + rf::align256((size_t)b * (size_t)n * sizeof(unsigned long long));
+    return l;
+}
+
+bool pv_sizes_ok(int b, int n, int c, int res) { return gr_sizes_ok(b, n, res) && c >= 1 && c <= RF_CFS_MAX_CHANNELS; }
+
+}  // namespace
+
+extern "C" {
+
+size_t rf_voxelize_mean_workspace_bytes(int b, int n, int res) {
+    if (!gr_sizes_ok(b, n, res)) return 0;
+    return pv_layout(b, n, res).total;
+}
+
+int rf_voxelize_mean(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len, const float *feat, float *vol,
+                     int *cnt, int *inside, void *workspace, size_t workspace_bytes, rf_stream_t stream) {
+    if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (!pv_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_box_ok(lo, hi)) return RF_EINVAL;
+    if (!xyz || !feat || !vol || !cnt || !inside) return RF_EINVAL;
+    if (!rf::aligned4(xyz) || !rf::aligned4(feat) || !rf::aligned4(vol) || !rf::aligned4(cnt) || !rf::aligned4(inside) || !rf::aligned4(len))
+        return RF_EINVAL;
+    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    const PvLayout l = pv_layout(b, n, res);
+    if (workspace_bytes < l.total) return RF_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+
+    char *w = (char *)workspace;
+    unsigned *starts = (unsigned *)(w + l.starts);
+    unsigned long long *recs = (unsigned long long *)(w + l.recs);
+    const PvBin bin{n, gr_box(res, lo, hi), xyz, len, starts, recs};
+    RF_LAUNCH("voxelize_bin", pv_bin_kernel<true>, dim3(b), dim3(PV_BIN_TPB), 0, st, bin);
+    const int nsb = rf::ceil_div(res, PV_E), nchunk = rf::ceil_div(c, PV_CHUNK);
+    const PvVox vx{n, c, res, starts, recs, feat, vol, cnt, inside};
+    RF_LAUNCH("voxelize_brick", pv_vox_kernel, dim3(nsb * nsb * nsb * nchunk, b), dim3(PV_TPB), 0, st, vx);
+    return RF_OK;
+}
+
+int rf_voxelize_mean_grad(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len, const int *cnt,
+                          const float *grad_vol, float *grad_feat, rf_stream_t stream) {
+    if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (!pv_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_box_ok(lo, hi)) return RF_EINVAL;
+    if (!xyz || !cnt || !grad_vol || !grad_feat) return RF_EINVAL;
+    if (!rf::aligned4(xyz) || !rf::aligned4(cnt) || !rf::aligned4(grad_vol) || !rf::aligned4(grad_feat) || !rf::aligned4(len)) return RF_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const PvVoxGrad a{n, c, gr_box(res, lo, hi), xyz, len, cnt, grad_vol, grad_feat};
+    RF_LAUNCH("voxelize_grad", pv_vox_grad_kernel, dim3(rf::ceil_div(n, PV_PTS), b), dim3(PV_TPB), 0, st, a);
+    return RF_OK;
+}
+
+int rf_trilinear_devoxelize(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len, const float *vol,
+                            float *feat, int *inside, rf_stream_t stream) {
+    if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (!pv_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_box_ok(lo, hi)) return RF_EINVAL;
+    if (!xyz || !vol || !feat || !inside) return RF_EINVAL;
+    if (!rf::aligned4(xyz) || !rf::aligned4(vol) || !rf::aligned4(feat) || !rf::aligned4(inside) || !rf::aligned4(len)) return RF_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const PvDevox a{n, c, gr_box(res, lo, hi), xyz, len, vol, feat, inside};
+    RF_LAUNCH("devoxelize", pv_devox_kernel, dim3(rf::ceil_div(n, PV_PTS), b), dim3(PV_TPB), 0, st, a);
+    return RF_OK;
+}
+
+size_t rf_trilinear_devoxelize_grad_workspace_bytes(int b, int n, int res) {
+    if (!gr_sizes_ok(b, n, res)) return 0;
+    return pv_layout(b, n, res).total;
+}
+
+int rf_trilinear_devoxelize_grad(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len, const float *vol,
+                                 const float *grad_feat, float *grad_vol, float *grad_xyz, void *workspace, size_t workspace_bytes,
+                                 rf_stream_t stream) {
+    if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
+    if (b == 0) return RF_OK;
+    if (!pv_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_box_ok(lo, hi)) return RF_EINVAL;
+    if (!xyz || !vol || !grad_feat || !grad_vol) return RF_EINVAL;  // (grad_xyz may be NULL: it is then not computed)
+    if (!rf::aligned4(xyz) || !rf::aligned4(vol) || !rf::aligned4(grad_feat) || !rf::aligned4(grad_vol) || !rf::aligned4(grad_xyz) ||
+        !rf::aligned4(len))
+        return RF_EINVAL;
+    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    const PvLayout l = pv_layout(b, n, res);
+    if (workspace_bytes < l.total) return RF_EWORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+
+    char *w = (char *)workspace;
+    unsigned *starts = (unsigned *)(w + l.starts);
+    unsigned long long *recs = (unsigned long long *)(w + l.recs);
+    const GrBox g = gr_box(res, lo, hi);
+    const PvBin bin{n, g, xyz, len, starts, recs};
+    RF_LAUNCH("devoxelize_bin", pv_bin_kernel<false>, dim3(b), dim3(PV_BIN_TPB), 0, st, bin);
+    const int nsb = rf::ceil_div(res, PV_E), nchunk = rf::ceil_div(c, PV_CHUNK);
+    const PvBrick br{n, c, g, starts, recs, xyz, grad_feat, grad_vol};
+    RF_LAUNCH("devoxelize_brick", pv_devox_brick_kernel, dim3(nsb * nsb * nsb * nchunk, b), dim3(PV_TPB), 0, st, br);
+    if (grad_xyz) {
+        const PvXyzGrad xg{n, c, g, xyz, len, vol, grad_feat, grad_xyz};
+        RF_LAUNCH("devoxelize_xyz_grad", pv_devox_xyz_kernel, dim3(rf::ceil_div(n, PV_PTS), b), dim3(PV_TPB), 0, st, xg);
+    }
+    return RF_OK;
+}
+
+}  // extern "C"

@@ -526,6 +526,70 @@ def gridding_reverse(grid, bounds=(-0.5, 0.5), eps=1e-6, compact=True):
     return _GriddingReverse.apply(g.to(torch.float32).contiguous(), lo, hi, float(eps), bool(compact))
 
 
+class _AvgVoxelize(torch.autograd.Function):
+    """rf_voxelize_mean / rf_voxelize_mean_grad: only the features carry a gradient."""
+
+    @staticmethod
+    def forward(ctx, xyz, feat, res, lo, hi, lengths):
+        vol, cnt, inside = _raw.avg_voxelize(xyz, feat, res, lo, hi, lengths)
+        ctx.save_for_backward(xyz, cnt)
+        ctx.box, ctx.lengths = (lo, hi), lengths
+        ctx.mark_non_differentiable(cnt, inside)
+        return vol, cnt, inside
+
+    @staticmethod
+    def backward(ctx, grad_vol, *_):
+        xyz, cnt = ctx.saved_tensors
+        gf = _raw.avg_voxelize_grad(xyz, cnt, grad_vol.contiguous(), *ctx.box, lengths=ctx.lengths)
+        return None, gf, None, None, None, None
+
+
+def avg_voxelize(pcd, feat, resolution=32, bounds=(-0.5, 0.5), lengths=None, return_counts=False):
+    """PVCNN's average voxelization: the feature vectors feat (b, n, c) of the points pcd (b, n, 3), averaged per nearest
+    vertex of the grid of `resolution` vertices per axis over the cube [bounds[0], bounds[1]]^3 (the geometry of `gridding`;
+    the vertices are PVCNN's voxel lattice) -> a volume (b, c, R, R, R), zeros where no point fell.  Points outside the cube and
+    padded rows (`lengths`: per-sample point counts) contribute nothing.  Double sums in LDS, no float atomics in memory
+    (rf_voxelize_mean).  Differentiable in feat (rf_voxelize_mean_grad); the op is piecewise constant in the points.
+    PVCNN's coordinate normalisation (mean-centre, scale by the largest norm) is torch code in front of this call.
+    return_counts: also (cnt (b, R, R, R) int32, inside (b,) int32)."""
+    lo, hi = _grid_bounds(bounds)
+    f = feat if isinstance(feat, torch.Tensor) else torch.as_tensor(feat)
+    vol, cnt, inside = _AvgVoxelize.apply(_cloud_tensor(pcd).detach(), f.to(torch.float32).contiguous(), int(resolution), lo, hi,
+                                          lengths)
+    if return_counts:
+        return vol, cnt, inside
+    return vol
+
+
+class _TrilinearDevoxelize(torch.autograd.Function):
+    """rf_trilinear_devoxelize / rf_trilinear_devoxelize_grad: the volume and the points carry gradients."""
+
+    @staticmethod
+    def forward(ctx, xyz, vol, lo, hi, lengths):
+        feat, _ = _raw.trilinear_devoxelize(xyz, vol, lo, hi, lengths)
+        ctx.save_for_backward(xyz, vol)
+        ctx.box, ctx.lengths = (lo, hi), lengths
+        return feat
+
+    @staticmethod
+    def backward(ctx, grad_feat):
+        xyz, vol = ctx.saved_tensors
+        gv, gx = _raw.trilinear_devoxelize_grad(xyz, vol, grad_feat.contiguous(), *ctx.box, lengths=ctx.lengths,
+                                                want_xyz=ctx.needs_input_grad[0])
+        return gx, (gv if ctx.needs_input_grad[1] else None), None, None, None
+
+
+def trilinear_devoxelize(pcd, volume, bounds=(-0.5, 0.5), lengths=None):
+    """PVCNN's trilinear devoxelization: volume (b, c, R, R, R) interpolated at every point of pcd (b, n, 3) from the eight
+    vertices of its cell of the grid over [bounds[0], bounds[1]]^3 (the geometry of `gridding`) -> (b, n, c); zeros for points
+    outside the cube and padded rows (`lengths`: per-sample point counts).  Every rounding is prescribed
+    (rf_trilinear_devoxelize).  Differentiable in volume (double sums in LDS, no float atomics in memory) and in pcd; the
+    gradient to the points is computed only when pcd requires it (rf_trilinear_devoxelize_grad)."""
+    lo, hi = _grid_bounds(bounds)
+    vol = volume if isinstance(volume, torch.Tensor) else torch.as_tensor(volume)
+    return _TrilinearDevoxelize.apply(_cloud_tensor(pcd), vol.to(torch.float32).contiguous(), lo, hi, lengths)
+
+
 class _EmdAssign(torch.autograd.Function):
     """rf_emd_assign / rf_emd_assign_grad: the exact assignment; only the cost (b,) carries a gradient, under the
     fixed assignment."""
