@@ -619,6 +619,93 @@ int rf_trilinear_devoxelize_grad(int b, int n, int c, int res, float lo, float h
                                  const float *vol, const float *grad_feat, float *grad_vol, float *grad_xyz,
                                  void *workspace, size_t workspace_bytes, rf_stream_t stream);
 
+/* ---- the vector attention pair: neighbour subtraction and neighbour aggregation, with gradients -- */
+/* The two ops that transformer-style point networks (Point Transformer, SnowflakeNet's skip-transformer, PoinTr / AdaPoinTr,
+ * SeedFormer) run on their neighbourhoods behind a kNN search -- pointops' `subtraction` and `aggregation`, here padded-batch
+ * with counts instead of packed with offsets:
+ *   sub[i][t][:] = q[i][:] - src[idx[i][t]][:]                                        (b, m, k, c)
+ *   out[i][ch]   = sum_t (value[idx[i][t]][ch] + pos[i][t][ch]) * weight[i][t][ch mod cw]   (b, m, c); share_planes = c / cw
+ * Everything is fp32, channel-last and contiguous.  idx is (b, m, k) int32: m queries with k slots each, naming rows of a
+ * (b, n, c) tensor.  len1 (b) = valid source rows, len2 (b) = valid queries: device int32 arrays or NULL (= n, m), clamped into
+ * [1, n] and [1, m] by the kernels as every count of this header.
+ *
+ * LIVENESS, one rule for all four entries: slot (i, t) is live iff i < len2', t < len1' and 0 <= idx[i][t] < len1' (the
+ * primes: the clamped counts).  It is the rule of rf_knn_grad_lengths, so the idx of a ragged rf_knn_lengths -- zeros behind
+ * a short sample's len1' neighbours, zero rows for padded queries -- and its two count arrays pass through unchanged.  A dead
+ * slot's pos, weight, grad_out and whatever row its idx names never enter a result (they are dropped by a select, never by
+ * a product: NaN there reaches nothing), and every output element that a dead slot or a padded row owns is written as +0.0.
+ * Any int32 is allowed in idx.  A live non-finite input gives non-finite results in the same places; NaN payloads are not
+ * promised.  The library is built with -ffp-contract=off: the arithmetic below has exactly the roundings written.
+ *
+ * rf_neighbor_sub: out (b, m, k, c): one fp32 subtraction per element of a live slot.  Bit for bit.
+ *
+ * rf_neighbor_sub_grad, from grad_out g (b, m, k, c); the features themselves are not needed:
+ *   grad_q (b, m, c) or NULL:   grad_q[i][ch] = (float)(sum over the live t, ascending, of (double)g[i][t][ch]), the sum in double
+ *   from +0.0.  Prescribed, bit for bit.
+ *   grad_src (b, n, c) or NULL: grad_src[r][ch] = (float)(the double sum from +0.0 of the terms -(double)g[i][t][ch] over the live
+ *   slots with idx[i][t] = r).  ORDER-FREE (below).  Every row is stored exactly once; rows nobody names are +0.0, and so is an
+ *   exact zero.
+ *
+ * rf_neighbor_aggregate: 1 <= cw, cw divides c.  pos (b, m, k, c) or NULL, weight (b, m, k, cw).  Per live slot
+ *   s = fl32(value[idx[i][t]][ch] + pos[i][t][ch])  (value[...] itself when pos is NULL),   acc = acc + (double)s * (double)w
+ *   with w = weight[i][t][ch mod cw]: the product of two floats is exact in double, so there is one rounding per addition; t
+ *   ascending from acc = +0.0; out[i][ch] = (float)acc.  A pure function with every rounding written down: a float64
+ *   restatement matches it bit for bit.
+ *
+ * rf_neighbor_aggregate_grad, from grad_out g (b, m, c) and the forward's inputs; each output may be NULL and is then not computed:
+ *   grad_pos (b, m, k, c):     grad_pos[i][t][ch] = fl32(g[i][ch] * w[i][t][ch mod cw]), one fp32 product.  Bit for bit.
+ *   grad_weight (b, m, k, cw): grad_weight[i][t][j] = (float)(sum over q = 0 ... c / cw - 1, ascending, of
+ *   (double)g[i][j + q cw] * (double)s[i][t][j + q cw]), s as in the forward, the sum in double from +0.0.  Bit for bit.
+ *   grad_value (b, n, c):      grad_value[r][ch] = (float)(the double sum from +0.0 of the exact products
+ *   (double)g[i][ch] * (double)w[i][t][ch mod cw] over the live slots with idx[i][t] = r).  ORDER-FREE.  Every row is stored
+ *   exactly once, rows nobody names are +0.0.
+ *
+ * The ORDER-FREE sums (grad_src, grad_value): the order of the additions is the order in which a counting sort leaves the
+ * slots of a row, which is not fixed.  Promise: identical bits, for every call and batch, whenever the double sum is exact
+ * (for instance integer-valued terms with sums below 2^53); otherwise, for an element with K terms,
+ *   |got - exact| <= 2^-23 |exact| + K 2^-52 sum |terms|                    (results in fp32's normal range)
+ * with exact the sum of the prescribed terms in real arithmetic, and two calls may differ within that.  Derivation: a recursive
+ * double sum of K terms makes K - 1 roundings, each of at most u = 2^-53 of a partial sum that is itself at most
+ * (1 + (K - 1) u) sum |terms|: the sum is off by at most (K - 1) u (1 + O(K u)) sum |terms|, below K 2^-53 sum |terms| with room
+ * to spare for every K <= 2^22 (m k at its largest), and the statement doubles it.  The rounding to fp32 adds at most 2^-24 of
+ * the computed sum, that is 2^-24 |exact| + 2^-24 K 2^-53 sum |terms|; 2^-23 |exact| and the doubled second term cover both.
+ *
+ * Guarantees: sample i is the call on [i : i + 1]; a ragged call is the call on each sample's slices [: len1'], [: len2'],
+ * with +0.0 in every element beyond (bit for bit for the prescribed outputs, as far as the promise goes for the order-free
+ * ones); rows and slots behind a count are never used.  No host synchronisation, no hipMemset, no float atomics in
+ * global memory, a fixed number of launches on `stream` for a given set of NULL outputs (rf_neighbor_sub 1;
+ * rf_neighbor_sub_grad 1 for grad_q + 2 for grad_src; rf_neighbor_aggregate 1; rf_neighbor_aggregate_grad 1 for grad_pos
+ * + 1 for grad_weight + 2 for grad_value): every call can be captured in a HIP graph.
+ *
+ * Workspace of the two _grad entries, needed only when grad_src / grad_value is asked for (otherwise no sort runs, and
+ * `workspace` is not looked at), each part rounded up to 256 bytes:
+ *   4 b (n + 1)  the rows' list starts  +  4 b m k  the slots in row order.
+ * The two _workspace_bytes functions return that, and 0 outside the domain of (b, n, m, k).
+ *
+ * Domain: 1 <= b <= 65535, 1 <= n, m <= 65536, 1 <= k <= RF_VA_MAX_K, 1 <= c <= RF_VA_MAX_CHANNELS, cw >= 1 with c % cw == 0,
+ * m k c < 2^31 and n c < 2^31 (32-bit offsets inside a sample).  Argument rules, all checked before any HIP call: RF_EINVAL for
+ * a negative size; then b == 0 is RF_OK; RF_EINVAL for sizes outside the domain, a NULL tensor (len1, len2, pos and the
+ * outputs of the _grad entries may be NULL), a tensor or count array not 4-byte aligned, and, where grad_src / grad_value is
+ * asked for, a workspace that is NULL or not 16-byte aligned; RF_EWORKSPACE for a workspace smaller than stated.  Tensors at
+ * 16-byte alignment with c % 4 == 0 take the float4 kernels; the results do not depend on it.  Out of scope: the softmax over
+ * k in front of the aggregation (torch code, as in pointops), bf16 / fp16 channels, and packed (offset) batches. */
+#define RF_VA_MAX_K 64
+#define RF_VA_MAX_CHANNELS 1024
+int rf_neighbor_sub(int b, int n, int m, int k, int c, const float *feat_q, const float *feat_src, const int *idx,
+                    const int *len1, const int *len2, float *out, rf_stream_t stream);
+size_t rf_neighbor_sub_grad_workspace_bytes(int b, int n, int m, int k);
+int rf_neighbor_sub_grad(int b, int n, int m, int k, int c, const int *idx, const int *len1, const int *len2,
+                         const float *grad_out, float *grad_q, float *grad_src, void *workspace, size_t workspace_bytes,
+                         rf_stream_t stream);
+int rf_neighbor_aggregate(int b, int n, int m, int k, int c, int cw, const float *value, const float *pos,
+                          const float *weight, const int *idx, const int *len1, const int *len2, float *out,
+                          rf_stream_t stream);
+size_t rf_neighbor_aggregate_grad_workspace_bytes(int b, int n, int m, int k);
+int rf_neighbor_aggregate_grad(int b, int n, int m, int k, int c, int cw, const float *value, const float *pos,
+                               const float *weight, const int *idx, const int *len1, const int *len2, const float *grad_out,
+                               float *grad_value, float *grad_pos, float *grad_weight, void *workspace,
+                               size_t workspace_bytes, rf_stream_t stream);
+
 /* ---- the exact earth mover's distance: optimal assignment with a certificate and gradients -- */
 /* The one-to-one assignment of minimal total distance between two clouds of EQUAL counts, by a deterministic Jacobi
  * auction with eps-scaling on an integer cost grid: a pure function of its inputs with a machine-checkable optimality

@@ -84,6 +84,12 @@ SIGNATURES = {
     "rf_trilinear_devoxelize": (_i, [_i, _i, _i, _i, _f, _f] + [_vp] * 6),
     "rf_trilinear_devoxelize_grad_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_trilinear_devoxelize_grad": (_i, [_i, _i, _i, _i, _f, _f] + [_vp] * 7 + [_sz, _vp]),
+    "rf_neighbor_sub": (_i, [_i] * 5 + [_vp] * 7),
+    "rf_neighbor_sub_grad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "rf_neighbor_sub_grad": (_i, [_i] * 5 + [_vp] * 7 + [_sz, _vp]),
+    "rf_neighbor_aggregate": (_i, [_i] * 6 + [_vp] * 8),
+    "rf_neighbor_aggregate_grad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "rf_neighbor_aggregate_grad": (_i, [_i] * 6 + [_vp] * 11 + [_sz, _vp]),
     "rf_emd_assign_supported": (_i, [_i]),
     "rf_emd_assign_workspace_bytes": (_sz, [_i, _i]),
     "rf_emd_assign": (_i, [_i, _i, _vp, _vp, _vp, _i] + [_vp] * 7 + [_sz, _vp]),

@@ -922,6 +922,167 @@ def trilinear_devoxelize_grad(xyz, vol, grad_feat, lo, hi, lengths=None, want_xy
     return st.give(gv), (st.give(gx) if want_xyz else None)
 
 
+# ---- the vector attention pair (include/rfops.h): neighbour subtraction and neighbour aggregation
+VA_MAX_K, VA_MAX_CHANNELS = 64, 1024  # RF_VA_MAX_K, RF_VA_MAX_CHANNELS
+
+
+def _va_index(op, st, idx):
+    ix = st.take(idx, I32)
+    if ix.dim() != 3:
+        raise H.invalid(f"{op} requires idx be of shape (batch,#queries,k)")
+    b, m, k = (int(v) for v in ix.shape)
+    if not 1 <= k <= VA_MAX_K:
+        raise H.invalid(f"{op} takes 1 to {VA_MAX_K} neighbours")
+    if not 1 <= m <= 65536:
+        raise H.invalid(f"{op} takes 1 to 65536 queries")
+    if b > 65535:
+        raise H.invalid(f"{op} takes at most 65535 samples")
+    return ix, b, m, k
+
+
+def _va_rows(op, st, t, name, b, rows=None, c=None, what="#points"):
+    """a (batch, rows, channels) tensor; rows / c: what they must be where another argument has fixed them"""
+    f = st.take(t, F32)
+    if f.dim() != 3 or f.shape[0] != b or (rows is not None and f.shape[1] != rows) or (c is not None and f.shape[2] != c):
+        raise H.invalid(f"{op} requires {name} be of shape (batch,{what},channels)")
+    if not 1 <= f.shape[1] <= 65536:
+        raise H.invalid(f"{op} takes 1 to 65536 points")
+    if not 1 <= f.shape[2] <= VA_MAX_CHANNELS:
+        raise H.invalid(f"{op} takes 1 to {VA_MAX_CHANNELS} channels")
+    return f
+
+
+def _va_slots(op, st, t, name, b, m, k, c=None):
+    f = st.take(t, F32)
+    if f.dim() != 4 or tuple(f.shape[:3]) != (b, m, k) or (c is not None and f.shape[3] != c):
+        raise H.invalid(f"{op} requires {name} be of shape (batch,#queries,k,channels)")
+    return f
+
+
+def _va_sizes(op, n, m, k, c):
+    if m * k * c >= 1 << 31 or n * c >= 1 << 31:
+        raise H.invalid(f"{op} takes #queries * k * channels and #points * channels below 2^31")
+
+
+def _va_weight(op, st, weight, b, m, k, c):
+    w = _va_slots(op, st, weight, "weight", b, m, k)
+    cw = int(w.shape[3])
+    if cw < 1 or c % cw:
+        raise H.invalid(f"{op} requires the channels of weight to divide those of value")
+    return w, cw
+
+
+@H.on_input_device
+def neighbor_subtraction(feat_q, feat_src, idx, lengths1=None, lengths2=None):
+    """rf_neighbor_sub (pointops' subtraction on padded batches) -> (b, m, k, c) fp32: feat_q (b, m, c) less the rows of feat_src
+    (b, n, c) that idx (b, m, k) int32 names; +0 in dead slots -- queries behind lengths2, slots t >= lengths1 of a query, and
+    slots naming a row outside [0, lengths1): the idx of a ragged knn_point and its two counts pass through unchanged."""
+    op = "neighbor_subtraction"
+    st = H.Staged()
+    ix, b, m, k = _va_index(op, st, idx)
+    q = _va_rows(op, st, feat_q, "feat_q", b, rows=m, what="#queries")
+    c = int(q.shape[2])
+    s = _va_rows(op, st, feat_src, "feat_src", b, c=c)
+    n = int(s.shape[1])
+    _va_sizes(op, n, m, k, c)
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    q, s, ix = st.up(q, s, ix)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    out = H.empty((b, m, k, c), F32, dev)
+    if b > 0:
+        check(lib.rf_neighbor_sub(b, n, m, k, c, H.ptr(q), H.ptr(s), H.ptr(ix), H.ptr(l1), H.ptr(l2), H.ptr(out), H.stream(dev)),
+              "rf_neighbor_sub")
+    return st.give(out)
+
+
+@H.on_input_device
+def neighbor_subtraction_grad(idx, grad_out, n, lengths1=None, lengths2=None, want_q=True, want_src=True):
+    """rf_neighbor_sub_grad -> (grad_q (b, m, c) or None, grad_src (b, n, c) or None) from grad_out (b, m, k, c): grad_q the double
+    sum over a query's live slots in ascending order, grad_src minus the double sum over the live slots naming a row -- a sort of
+    the slots by row and a gather that stores every row once, no float atomics.  What is not wanted is not computed."""
+    op = "neighbor_subtraction_grad"
+    st = H.Staged()
+    ix, b, m, k = _va_index(op, st, idx)
+    g = _va_slots(op, st, grad_out, "grad_out", b, m, k)
+    c, n = int(g.shape[3]), int(n)
+    if not 1 <= c <= VA_MAX_CHANNELS:
+        raise H.invalid(f"{op} takes 1 to {VA_MAX_CHANNELS} channels")
+    if not 1 <= n <= 65536:
+        raise H.invalid(f"{op} takes 1 to 65536 points")
+    _va_sizes(op, n, m, k, c)
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    ix, g = st.up(ix, g)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    gq = H.empty((b, m, c), F32, dev) if want_q else None
+    gs = H.empty((b, n, c), F32, dev) if want_src else None
+    if b > 0 and (want_q or want_src):
+        ws, wsz = H.workspace(lib.rf_neighbor_sub_grad_workspace_bytes(b, n, m, k), dev, "vector_attention") if want_src else (None, 0)
+        check(lib.rf_neighbor_sub_grad(b, n, m, k, c, H.ptr(ix), H.ptr(l1), H.ptr(l2), H.ptr(g), H.ptr(gq), H.ptr(gs), H.ptr(ws), wsz,
+                                       H.stream(dev)), "rf_neighbor_sub_grad")
+    return (st.give(gq) if want_q else None), (st.give(gs) if want_src else None)
+
+
+def _va_agg_inputs(op, st, value, weight, idx, pos):
+    ix, b, m, k = _va_index(op, st, idx)
+    v = _va_rows(op, st, value, "value", b)
+    n, c = int(v.shape[1]), int(v.shape[2])
+    w, cw = _va_weight(op, st, weight, b, m, k, c)
+    p = None if pos is None else _va_slots(op, st, pos, "pos", b, m, k, c)
+    _va_sizes(op, n, m, k, c)
+    return ix, v, w, p, (b, n, m, k, c, cw)
+
+
+@H.on_input_device
+def neighbor_aggregation(value, weight, idx, pos=None, lengths1=None, lengths2=None):
+    """rf_neighbor_aggregate (pointops' aggregation on padded batches) -> (b, m, c) fp32: the sum over a query's live slots, in
+    ascending order and in double, of (value[idx] + pos) * weight[..., ch mod cw]; value (b, n, c), weight (b, m, k, cw) with cw
+    dividing c (share_planes = c / cw), pos (b, m, k, c) or None.  Dead slots (neighbor_subtraction's rule) add nothing, whatever
+    they hold; padded queries are +0."""
+    op = "neighbor_aggregation"
+    st = H.Staged()
+    ix, v, w, p, (b, n, m, k, c, cw) = _va_agg_inputs(op, st, value, weight, idx, pos)
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    ix, v, w = st.up(ix, v, w)
+    p = None if p is None else st.up(p)[0]
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    out = H.empty((b, m, c), F32, dev)
+    if b > 0:
+        check(lib.rf_neighbor_aggregate(b, n, m, k, c, cw, H.ptr(v), H.ptr(p), H.ptr(w), H.ptr(ix), H.ptr(l1), H.ptr(l2), H.ptr(out),
+                                        H.stream(dev)), "rf_neighbor_aggregate")
+    return st.give(out)
+
+
+@H.on_input_device
+def neighbor_aggregation_grad(value, weight, idx, grad_out, pos=None, lengths1=None, lengths2=None, want_value=True, want_pos=True,
+                              want_weight=True):
+    """rf_neighbor_aggregate_grad -> (grad_value (b, n, c), grad_pos (b, m, k, c), grad_weight (b, m, k, cw)), None for each that
+    is not wanted (it is then not computed), from grad_out (b, m, c): grad_pos one fp32 product per element, grad_weight a double
+    sum over the channel groups in ascending order, grad_value a sort of the slots by row and a gather that forms its terms from
+    grad_out and weight on the fly and stores every row once -- no float atomics."""
+    op = "neighbor_aggregation_grad"
+    st = H.Staged()
+    ix, v, w, p, (b, n, m, k, c, cw) = _va_agg_inputs(op, st, value, weight, idx, pos)
+    g = _va_rows(op, st, grad_out, "grad_out", b, rows=m, c=c, what="#queries")
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    ix, v, w, g = st.up(ix, v, w, g)
+    p = None if p is None else st.up(p)[0]
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    gv = H.empty((b, n, c), F32, dev) if want_value else None
+    gp = H.empty((b, m, k, c), F32, dev) if want_pos else None
+    gw = H.empty((b, m, k, cw), F32, dev) if want_weight else None
+    if b > 0 and (want_value or want_pos or want_weight):
+        ws, wsz = (H.workspace(lib.rf_neighbor_aggregate_grad_workspace_bytes(b, n, m, k), dev, "vector_attention")
+                   if want_value else (None, 0))
+        check(lib.rf_neighbor_aggregate_grad(b, n, m, k, c, cw, H.ptr(v), H.ptr(p), H.ptr(w), H.ptr(ix), H.ptr(l1), H.ptr(l2),
+                                             H.ptr(g), H.ptr(gv), H.ptr(gp), H.ptr(gw), H.ptr(ws), wsz, H.stream(dev)),
+              "rf_neighbor_aggregate_grad")
+    return tuple(st.give(t) if t is not None else None for t in (gv, gp, gw))
+
+
 EA_MAX_POINTS = 4096  # RF_EA_MAX_POINTS (include/rfops.h)
 EA_OK, EA_CAPPED, EA_NONFINITE = 0, 1, 2  # RF_EA_* status values
 EA_TPB, EA_WAVE = 1024, 64  # emd_assign.hip's tiles: threads of the one workgroup per sample; lanes a bidder's scan strides by

@@ -9,6 +9,7 @@ are small elementwise / reduction tensor ops that autograd differentiates.
   groupin_near    vv_recon.py:410-414    zero_groupnear vv_recon.py:415-419
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _raw
 from .pc_distance.tf_approxmatch import earth_mover_cost
@@ -588,6 +589,75 @@ def trilinear_devoxelize(pcd, volume, bounds=(-0.5, 0.5), lengths=None):
     lo, hi = _grid_bounds(bounds)
     vol = volume if isinstance(volume, torch.Tensor) else torch.as_tensor(volume)
     return _TrilinearDevoxelize.apply(_cloud_tensor(pcd), vol.to(torch.float32).contiguous(), lo, hi, lengths)
+
+
+class _NeighborSubtraction(torch.autograd.Function):
+    """rf_neighbor_sub / rf_neighbor_sub_grad: both feature tensors carry gradients, idx does not."""
+
+    @staticmethod
+    def forward(ctx, feat_q, feat_src, idx, lengths1, lengths2):
+        ctx.save_for_backward(idx)
+        ctx.n, ctx.lengths = feat_src.shape[1], (lengths1, lengths2)
+        return _raw.neighbor_subtraction(feat_q, feat_src, idx, lengths1, lengths2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        (idx,) = ctx.saved_tensors
+        gq, gs = _raw.neighbor_subtraction_grad(idx, grad_out.contiguous(), ctx.n, *ctx.lengths, want_q=ctx.needs_input_grad[0],
+                                                want_src=ctx.needs_input_grad[1])
+        return gq, gs, None, None, None
+
+
+def _feature_tensor(x):
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(x)
+    return t.to(torch.float32).contiguous()
+
+
+def _index_tensor(idx):
+    t = idx if isinstance(idx, torch.Tensor) else torch.as_tensor(idx)
+    return t.detach().to(torch.int32).contiguous()
+
+
+def neighbor_subtraction(feat_q, feat_src, idx, lengths1=None, lengths2=None):
+    """The relative features in front of a vector attention's MLP (pointops' `subtraction`, on padded batches):
+    feat_q (b, m, c) less the rows of feat_src (b, n, c) that idx (b, m, k) names -> (b, m, k, c).  idx is what `knn_point`
+    returns, and a ragged batch passes knn_point's own lengths1 / lengths2 (source rows / queries per sample): its padded slots
+    and rows are zeros here and receive no gradient (rf_neighbor_sub).  Differentiable in both feature tensors: the gradient
+    to feat_src is a sort of the slots by row and a gather in double, no float atomics (rf_neighbor_sub_grad); only the
+    gradients that are needed are computed."""
+    return _NeighborSubtraction.apply(_feature_tensor(feat_q), _feature_tensor(feat_src), _index_tensor(idx), lengths1, lengths2)
+
+
+class _NeighborAggregation(torch.autograd.Function):
+    """rf_neighbor_aggregate / rf_neighbor_aggregate_grad: value, weight and pos carry gradients, idx does not."""
+
+    @staticmethod
+    def forward(ctx, value, weight, idx, pos, lengths1, lengths2):
+        ctx.save_for_backward(value, weight, idx, pos)
+        ctx.lengths = (lengths1, lengths2)
+        return _raw.neighbor_aggregation(value, weight, idx, pos, lengths1, lengths2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        value, weight, idx, pos = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gv, gp, gw = _raw.neighbor_aggregation_grad(value, weight, idx, grad_out.contiguous(), pos, *ctx.lengths, want_value=need[0],
+                                                    want_pos=pos is not None and need[3], want_weight=need[1])
+        return gv, gw, None, gp, None, None
+
+
+def neighbor_aggregation(value, weight, idx, pos=None, lengths1=None, lengths2=None):
+    """Vector attention's weighted sum (pointops' `aggregation`, on padded batches): out[i, ch] = the sum over the k
+    neighbours t of (value[idx[i, t], ch] + pos[i, t, ch]) * weight[i, t, ch mod cw] -> (b, m, c); value (b, n, c), weight
+    (b, m, k, cw) with cw dividing c (Point Transformer's share_planes = c / cw), pos (b, m, k, c) or None, idx (b, m, k) from
+    `knn_point`.  The softmax over k stays torch code in front of this call.  Nothing of size (b, m, k, c) is formed or kept for
+    autograd; sums in double in ascending neighbour order (rf_neighbor_aggregate).  lengths1 / lengths2 as in
+    `neighbor_subtraction`.  Differentiable in value, weight and pos; only the gradients that are needed are computed, the one
+    to value without float atomics (rf_neighbor_aggregate_grad)."""
+    p = None if pos is None else _feature_tensor(pos)
+    return _NeighborAggregation.apply(_feature_tensor(value), _feature_tensor(weight), _index_tensor(idx), p, lengths1, lengths2)
 
 
 class _EmdAssign(torch.autograd.Function):
