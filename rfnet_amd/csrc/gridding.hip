@@ -22,16 +22,14 @@
 //
 // No float atomics, no hipMemset, no sum whose order is left open.  Every loop bound is a count or a list length that the bin
 // kernel derived from counts; a non-finite coordinate fails the inside test and never moves a memory access.
-#include "gridding.hpp"  // GrBox, gr_axis, gr_nb, GR_E: shared with grnet_layers.hip
+#include "brick_sort.hpp"  // gr_brick_sort and the sort's constants and layout; gridding.hpp's GrBox, gr_axis, gr_nb, GR_E
 
 namespace {
 
 constexpr int GR_E3 = GR_E * GR_E * GR_E;
-constexpr int GR_MAX_NB3 = 4096;         // (RF_GR_MAX_RES / GR_E)^3 bricks per sample at most
-constexpr int GR_BIN_TPB = 1024, GR_BRICK_TPB = 256, GR_PT_TPB = 256;
+constexpr int GR_BRICK_TPB = 256, GR_PT_TPB = 256;
 constexpr double GR_Q3 = 134217728.0;    // RF_GR_Q^3
-static_assert(RF_GR_Q == 512 && RF_GR_MAX_RES == 256 && GR_MAX_NB3 == (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E), "");
-static_assert(GR_MAX_NB3 == 4 * GR_BIN_TPB, "the scan of gr_bin_kernel gives a thread four bins");
+static_assert(RF_GR_Q == 512, "a record holds three q1 of 10 bits");
 
 __device__ __forceinline__ unsigned gr_q1(float t) { return (unsigned)(int)rintf(t * 512.0f); }
 
@@ -46,11 +44,9 @@ struct GrBin {
     int *inside;                 // (b, clouds)
 };
 
-// grid (clouds, b)
+// gr_brick_sort by the cell, the record carrying the three q1.  grid (clouds, b)
 __global__ __launch_bounds__(GR_BIN_TPB) void gr_bin_kernel(GrBin a) {
-    __shared__ unsigned hist[GR_MAX_NB3];
-    __shared__ unsigned wtot[GR_BIN_TPB / 64];
-    const int cloud = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    const int cloud = blockIdx.x, s = blockIdx.y;
     const int np = cloud ? a.m : a.n;
     const int L = rf::ragged_count(cloud ? a.len2 : a.len1, s, np);
     const float *__restrict__ xyz = (cloud ? a.xyz2 : a.xyz1) + (size_t)s * np * 3;
@@ -58,54 +54,17 @@ __global__ __launch_bounds__(GR_BIN_TPB) void gr_bin_kernel(GrBin a) {
     const int nb = gr_nb(g.R), nb3 = nb * nb * nb;
     unsigned *__restrict__ st = a.starts + ((size_t)s * a.clouds + cloud) * (nb3 + 1);
     unsigned long long *__restrict__ rec = a.recs + (size_t)s * ((size_t)a.n + a.m) + (cloud ? a.n : 0);
-
-    for (int k = tid; k < nb3; k += GR_BIN_TPB) hist[k] = 0;
-    __syncthreads();
-    for (int i = tid; i < L; i += GR_BIN_TPB) {
-        int ix, iy, iz;
+    int *inside = a.inside + ((size_t)s * a.clouds + cloud);
+    gr_brick_sort(L, g.R, st, rec, inside, [&](int i, int &ix, int &iy, int &iz, unsigned long long &word) {
         float tx, ty, tz;
         const bool in = gr_axis(xyz[(size_t)i * 3], g, ix, tx) & gr_axis(xyz[(size_t)i * 3 + 1], g, iy, ty) &
                         gr_axis(xyz[(size_t)i * 3 + 2], g, iz, tz);
-        if (in) atomicAdd(&hist[((ix / GR_E) * nb + iy / GR_E) * nb + iz / GR_E], 1u);
-    }
-    __syncthreads();
-    // exclusive scan over the bins: a thread owns four consecutive bins, a wave by DPP, the waves in order
-    unsigned c[4], tsum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int idx = tid * 4 + k;
-        c[k] = idx < nb3 ? hist[idx] : 0u;
-        tsum += c[k];
-    }
-    const unsigned incl = rf::wave_incl_scan(tsum);
-    if ((tid & 63) == 63) wtot[tid >> 6] = incl;
-    __syncthreads();
-    unsigned run = incl - tsum;
-    for (int w = 0; w < (tid >> 6); w++) run += wtot[w];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int idx = tid * 4 + k;
-        if (idx < nb3) hist[idx] = run, st[idx] = run;  // the bin's cursor and its start
-        run += c[k];
-    }
-    if (tid == GR_BIN_TPB - 1) {
-        st[nb3] = run;
-        a.inside[(size_t)s * a.clouds + cloud] = (int)run;
-    }
-    __syncthreads();
-    for (int i = tid; i < L; i += GR_BIN_TPB) {
-        int ix, iy, iz;
-        float tx, ty, tz;
-        const bool in = gr_axis(xyz[(size_t)i * 3], g, ix, tx) & gr_axis(xyz[(size_t)i * 3 + 1], g, iy, ty) &
-                        gr_axis(xyz[(size_t)i * 3 + 2], g, iz, tz);
-        if (in) {
-            const unsigned pos = atomicAdd(&hist[((ix / GR_E) * nb + iy / GR_E) * nb + iz / GR_E], 1u);
-            const unsigned lo = (unsigned)ix | (unsigned)iy << 8 | (unsigned)iz << 16 | gr_q1(tx) << 24;  // (q1x: bits 24 .. 33)
-            const unsigned long long hi = (unsigned long long)(gr_q1(tx) >> 8) | (unsigned long long)gr_q1(ty) << 2 |
-                                          (unsigned long long)gr_q1(tz) << 12;
-            rec[pos] = (unsigned long long)lo | hi << 32;  // pos < the inside count <= L
-        }
-    }
+        const unsigned lo = (unsigned)ix | (unsigned)iy << 8 | (unsigned)iz << 16 | gr_q1(tx) << 24;  // (q1x: bits 24 .. 33)
+        const unsigned long long hi = (unsigned long long)(gr_q1(tx) >> 8) | (unsigned long long)gr_q1(ty) << 2 |
+                                      (unsigned long long)gr_q1(tz) << 12;
+        word = (unsigned long long)lo | hi << 32;
+        return in;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ brick
@@ -323,10 +282,11 @@ struct GrLayout {
 // clouds 2: the loss (partials, and the sign grid with gradients); clouds 1: the layer (m = 0, neither)
 GrLayout gr_layout(int b, int n, int m, int res, int clouds, bool want_grad) {
     const size_t nb = gr_nb(res), nb3 = nb * nb * nb;
+    const GrSortLayout sort = gr_sort_layout((size_t)b * clouds, (size_t)b * ((size_t)n + (size_t)m), res);
     GrLayout l;
-    l.starts = 0;
-    l.recs = l.starts + rf::align256((size_t)b * clouds * (nb3 + 1) * sizeof(unsigned));
-    l.partial = l.recs + rf::align256((size_t)b * ((size_t)n + (size_t)m) * sizeof(unsigned long long));
+    l.starts = sort.starts;
+    l.recs = sort.recs;
+    l.partial = sort.total;
     l.sign = l.partial + (clouds == 2 ? rf::align256((size_t)b * nb3 * sizeof(long long)) : 0);
     l.total = l.sign + (clouds == 2 && want_grad ? rf::align256((size_t)b * res * res * res) : 0);
     return l;

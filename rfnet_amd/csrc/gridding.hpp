@@ -1,5 +1,6 @@
 // gridding.hpp -- the grid geometry of include/rfops.h's gridding section, ONCE: the box, the per-axis cell rule and the brick
-// count.  gridding.hip (the Gridding layer and loss) and grnet_layers.hip (Gridding Reverse, Cubic Feature Sampling) share it.
+// count.  gridding.hip (the Gridding layer and loss), grnet_layers.hip (Gridding Reverse, Cubic Feature Sampling) and
+// point_voxel.hip (average voxelize, trilinear devoxelize) share it through brick_sort.hpp, which adds their common sort and scatter.
 #pragma once
 #include "common.hpp"
 

@@ -1,30 +1,25 @@
 // grnet_layers.hip -- the two GRNet layers that bring a voxel grid back to points: Gridding Reverse (a (b, R, R, R) occupancy
 // volume -> one point per cell, as a padded batch with device counts) and Cubic Feature Sampling (the feature vectors at the
 // eight vertices of every point's cell, from a (b, c, R, R, R) volume).  include/rfops.h states the contract, DESIGN.md 5.3m the
-// layout and the measurements.  The geometry is gridding.hpp's, shared with gridding.hip.
+// layout and the measurements.  The geometry is gridding.hpp's; the sort and the scatter of the backward are brick_sort.hpp's.
 //
 //   cfs forward   the plain gather: a workgroup takes CFS_FWD_PTS points, their vertices go through LDS, and the threads run over
 //                 the (point, corner, channel) elements of the output in memory order -- coalesced stores, strided plane reads.
-//   cfs backward  no float atomics in memory and no memset: the points are sorted by the brick (GR_E^3 vertices) of their cell as
-//                 in gridding.hip, the record now carrying the point index; one workgroup per (sample, sub-brick of CFS_E^3
-//                 vertices, chunk of CFS_CHUNK channels) walks the lists that can reach its vertices, a wave takes one record per
-//                 step with a lane per (corner, channel) -- eight reads of CFS_CHUNK contiguous floats of grad_feat -- and adds into
-//                 LDS doubles (ds_add_f64); every element of grad_vol is then stored once, zeros where nothing fell.  The order of
-//                 the additions is the order of arrival: the contract says what that leaves open.
+//   cfs backward  no float atomics in memory and no memset: gr_brick_sort sorts the points by the brick (GR_E^3 vertices) of their
+//                 cell, the record carrying the point index; one workgroup per (sample, sub-brick of GR_SUB_E^3 vertices, chunk
+//                 of GR_CHUNK channels) runs gr_subbrick_scatter over the lists that can reach its vertices, a wave taking one
+//                 record per step with a lane per (corner, channel) -- eight reads of GR_CHUNK contiguous floats of grad_feat --
+//                 and adding into LDS doubles (ds_add_f64); every element of grad_vol is then stored once, zeros where nothing
+//                 fell.  The order of the additions is the order of arrival: the contract says what that leaves open.
 //   reverse       count the valid cells per tile of GV_TILE cells, scan the tile counts of a sample in one workgroup, write: the
 //                 valid cells keep their cell order, so the placement is a pure function of the grid.  Three launches, no atomics.
 //   reverse grad  a gather per vertex over its up to eight cells, in double.
-#include "gridding.hpp"
+#include "brick_sort.hpp"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ cubic feature sampling
 constexpr int CFS_FWD_PTS = 32, CFS_TPB = 256;
-constexpr int CFS_BIN_TPB = 1024, CFS_MAX_NB3 = 4096;
-constexpr int CFS_E = 8, CFS_E3 = CFS_E * CFS_E * CFS_E;  // vertices per sub-brick edge
-constexpr int CFS_CHUNK = 8;                              // channels per workgroup: 8 corners x 8 channels = one wave per record
-static_assert(CFS_MAX_NB3 == (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E) && CFS_MAX_NB3 == 4 * CFS_BIN_TPB, "");
-static_assert(GR_E == 2 * CFS_E && 8 * CFS_CHUNK == 64 && CFS_E3 * CFS_CHUNK * sizeof(double) == 32768, "");
 
 struct CfsFwd {
     int n, c;
@@ -78,68 +73,22 @@ __global__ __launch_bounds__(CFS_TPB) void cfs_gather_kernel(CfsFwd a) {
     }
 }
 
-struct CfsBin {
-    int n;
-    GrBox g;
-    const float *xyz;
-    const int *len;
-    unsigned *starts;          // (b, nb^3 + 1): where every brick's list begins; the last entry is the inside count
-    unsigned long long *recs;  // (b, n): the cell (3 x 8 bits) and the point index (16 bits, from bit 24)
-};
-
-// gr_bin_kernel's counting sort for one cloud, with the point index in the record.  grid (b)
-__global__ __launch_bounds__(CFS_BIN_TPB) void cfs_bin_kernel(CfsBin a) {
-    __shared__ unsigned hist[CFS_MAX_NB3];
-    __shared__ unsigned wtot[CFS_BIN_TPB / 64];
-    const int s = blockIdx.x, tid = threadIdx.x, n = a.n;
+// gr_brick_sort by the cell, the record carrying the point index.  grid (b)
+__global__ __launch_bounds__(GR_BIN_TPB) void cfs_bin_kernel(GrSortCloud a) {
+    const int s = blockIdx.x, n = a.n;
     const int L = rf::ragged_count(a.len, s, n);
     const float *__restrict__ xyz = a.xyz + (size_t)s * n * 3;
     const GrBox g = a.g;
     const int nb = gr_nb(g.R), nb3 = nb * nb * nb;
     unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
     unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
-
-    for (int k = tid; k < nb3; k += CFS_BIN_TPB) hist[k] = 0;
-    __syncthreads();
-    for (int i = tid; i < L; i += CFS_BIN_TPB) {
-        int ix, iy, iz;
+    gr_brick_sort(L, g.R, st, rec, nullptr, [&](int i, int &ix, int &iy, int &iz, unsigned long long &word) {
         float tx, ty, tz;
         const bool in = gr_axis(xyz[(size_t)i * 3], g, ix, tx) & gr_axis(xyz[(size_t)i * 3 + 1], g, iy, ty) &
                         gr_axis(xyz[(size_t)i * 3 + 2], g, iz, tz);
-        if (in) atomicAdd(&hist[((ix / GR_E) * nb + iy / GR_E) * nb + iz / GR_E], 1u);
-    }
-    __syncthreads();
-    unsigned cn[4], tsum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int idx = tid * 4 + k;
-        cn[k] = idx < nb3 ? hist[idx] : 0u;
-        tsum += cn[k];
-    }
-    const unsigned incl = rf::wave_incl_scan(tsum);
-    if ((tid & 63) == 63) wtot[tid >> 6] = incl;
-    __syncthreads();
-    unsigned run = incl - tsum;
-    for (int w = 0; w < (tid >> 6); w++) run += wtot[w];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int idx = tid * 4 + k;
-        if (idx < nb3) hist[idx] = run, st[idx] = run;  // the bin's cursor and its start
-        run += cn[k];
-    }
-    if (tid == CFS_BIN_TPB - 1) st[nb3] = run;
-    __syncthreads();
-    for (int i = tid; i < L; i += CFS_BIN_TPB) {
-        int ix, iy, iz;
-        float tx, ty, tz;
-        const bool in = gr_axis(xyz[(size_t)i * 3], g, ix, tx) & gr_axis(xyz[(size_t)i * 3 + 1], g, iy, ty) &
-                        gr_axis(xyz[(size_t)i * 3 + 2], g, iz, tz);
-        if (in) {
-            const unsigned pos = atomicAdd(&hist[((ix / GR_E) * nb + iy / GR_E) * nb + iz / GR_E], 1u);
-            rec[pos] = (unsigned long long)((unsigned)ix | (unsigned)iy << 8 | (unsigned)iz << 16) |
-                       (unsigned long long)(unsigned)i << 24;  // pos < the inside count <= L; i < 65536
-        }
-    }
+        word = gr_index_record(ix, iy, iz, i);
+        return in;
+    });
 }
 
 struct CfsBrick {
@@ -150,93 +99,19 @@ struct CfsBrick {
     float *gv;        // (b, c, R, R, R)
 };
 
-// grid (ceil(R / CFS_E)^3 * ceil(c / CFS_CHUNK), b), the channel chunk fastest
-__global__ __launch_bounds__(CFS_TPB) void cfs_brick_kernel(CfsBrick a) {
-    __shared__ double acc[CFS_E3 * CFS_CHUNK];  // [vertex][channel]
-    const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// gr_subbrick_scatter of grad_feat's (corner, channel) elements.  grid (ceil(R / GR_SUB_E)^3 * ceil(c / GR_CHUNK), b), the channel
+// chunk fastest
+__global__ __launch_bounds__(GR_SUB_TPB) void cfs_brick_kernel(CfsBrick a) {
+    const int s = blockIdx.y;
     const int R = a.R, c = a.c, n = a.n;
-    const int nsb = (R + CFS_E - 1) / CFS_E, nchunk = (c + CFS_CHUNK - 1) / CFS_CHUNK;
     const int nb = gr_nb(R), nb3 = nb * nb * nb;
-    const int sbi = blockIdx.x / nchunk, ch0 = (blockIdx.x - sbi * nchunk) * CFS_CHUNK;
-    const int sz = sbi % nsb, sy = (sbi / nsb) % nsb, sx = sbi / (nsb * nsb);
-    const unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
     const size_t R3 = (size_t)R * R * R;
-    float *__restrict__ gv = a.gv + ((size_t)s * c + ch0) * R3;
-
-    // The cells that reach this sub-brick's vertices are those of its own brick and, where the sub-brick is the lower half of its
-    // brick along an axis, of the lower neighbour along that axis: at most eight lists.
-    auto list = [&](int d, unsigned &lo, unsigned &hi) {
-        const int dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
-        const int nx = (sx >> 1) - dx, ny = (sy >> 1) - dy, nz = (sz >> 1) - dz;
-        const bool skip = (dx && ((sx & 1) || nx < 0)) || (dy && ((sy & 1) || ny < 0)) || (dz && ((sz & 1) || nz < 0));
-        const int q = skip ? 0 : (nx * nb + ny) * nb + nz;
-        lo = st[q], hi = skip ? lo : st[q + 1];
-    };
-    unsigned any = 0;
-#pragma unroll
-    for (int d = 0; d < 8; d++) {
-        unsigned lo, hi;
-        list(d, lo, hi);
-        any |= hi - lo;
-    }
-    if (any) {  // (uniform over the workgroup)
-        for (int l = tid; l < CFS_E3 * CFS_CHUNK; l += CFS_TPB) acc[l] = 0.0;
-        __syncthreads();
-        const unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
-        const float *__restrict__ gf = a.gf + (size_t)s * n * 8 * c;
-        const int d = lane >> 3, ch = lane & 7, dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
-        const bool chok = ch0 + ch < c;
-#pragma unroll 1
-        for (int q = 0; q < 8; q++) {
-            unsigned lo, hi;
-            list(q, lo, hi);
-            for (unsigned r0 = lo + wave * 64; r0 < hi; r0 += CFS_TPB) {  // uniform over the wave
-                const unsigned r = r0 + lane;
-                const unsigned long long w = r < hi ? rec[r] : 0ull;
-                // the cell relative to this sub-brick's first vertex: kept iff -1 ... 7 on every axis
-                const int cx = (int)((unsigned)w & 255u) - sx * CFS_E + 1, cy = (int)((unsigned)(w >> 8) & 255u) - sy * CFS_E + 1,
-                          cz = (int)((unsigned)(w >> 16) & 255u) - sz * CFS_E + 1;
-                const bool keep = r < hi && (unsigned)cx <= (unsigned)CFS_E && (unsigned)cy <= (unsigned)CFS_E &&
-                                  (unsigned)cz <= (unsigned)CFS_E;
-                const unsigned key = ((unsigned)(w >> 24) & 0xFFFFu) | (unsigned)cx << 16 | (unsigned)cy << 20 | (unsigned)cz << 24;
-                unsigned long long mask = __ballot(keep);
-                while (mask) {  // a record per step, a lane per (corner, channel)
-                    const int j = __ffsll((long long)mask) - 1;
-                    mask &= mask - 1;
-                    const unsigned k = (unsigned)__shfl((int)key, j, 64);
-                    const int i = (int)(k & 0xFFFFu);  // < n: written by the bin kernel from a row below the count
-                    const int lx = (int)((k >> 16) & 15u) - 1 + dx, ly = (int)((k >> 20) & 15u) - 1 + dy,
-                              lz = (int)((k >> 24) & 15u) - 1 + dz;
-                    if ((unsigned)lx < (unsigned)CFS_E && (unsigned)ly < (unsigned)CFS_E && (unsigned)lz < (unsigned)CFS_E && chok)
-                        atomicAdd(&acc[((lx * CFS_E + ly) * CFS_E + lz) * CFS_CHUNK + ch],
-                                  (double)gf[((size_t)i * 8 + d) * c + ch0 + ch]);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    for (int e = tid; e < CFS_E3 * CFS_CHUNK; e += CFS_TPB) {
-        const int chh = e / CFS_E3, l = e % CFS_E3;
-        const int gx = sx * CFS_E + l / (CFS_E * CFS_E), gy = sy * CFS_E + (l / CFS_E) % CFS_E, gz = sz * CFS_E + l % CFS_E;
-        if (ch0 + chh < c && gx < R && gy < R && gz < R)
-            gv[(size_t)chh * R3 + ((size_t)gx * R + gy) * R + gz] = any ? (float)acc[l * CFS_CHUNK + chh] : 0.f;
-    }
+    const unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
+    const unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
+    const float *__restrict__ gf = a.gf + (size_t)s * n * 8 * c;
+    gr_subbrick_scatter(blockIdx.x, R, c, st, rec, a.gv + (size_t)s * c * R3,
+                        [&](int i, int d, int ch) { return (double)gf[((size_t)i * 8 + d) * c + ch]; });
 }
-
-struct CfsLayout {
-    size_t starts, recs, total;
-};
-
-CfsLayout cfs_layout(int b, int n, int res) {
-    const size_t nb = gr_nb(res), nb3 = nb * nb * nb;
-    CfsLayout l;
-    l.starts = 0;
-    l.recs = l.starts + rf::align256((size_t)b * (nb3 + 1) * sizeof(unsigned));
-    l.total = l.recs + rf::align256((size_t)b * (size_t)n * sizeof(unsigned long long));
-    return l;
-}
-
-bool cfs_sizes_ok(int b, int n, int c, int res) { return gr_sizes_ok(b, n, res) && c >= 1 && c <= RF_CFS_MAX_CHANNELS; }
 
 // ------------------------------------------------------------------------------------------------ gridding reverse
 constexpr int GV_TILE = 256, GV_TPB = GV_TILE, GV_SCAN_TPB = 1024;
@@ -409,7 +284,7 @@ int rf_cubic_feature_sampling(int b, int n, int c, int res, float lo, float hi, 
                               float *feat, int *inside, rf_stream_t stream) {
     if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (!cfs_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
     if (!xyz || !vol || !feat || !inside) return RF_EINVAL;
     if (!rf::aligned4(xyz) || !rf::aligned4(vol) || !rf::aligned4(feat) || !rf::aligned4(inside) || !rf::aligned4(len)) return RF_EINVAL;
@@ -421,7 +296,7 @@ int rf_cubic_feature_sampling(int b, int n, int c, int res, float lo, float hi, 
 
 size_t rf_cubic_feature_sampling_grad_workspace_bytes(int b, int n, int res) {
     if (!gr_sizes_ok(b, n, res)) return 0;
-    return cfs_layout(b, n, res).total;
+    return gr_sort_layout(b, n, res).total;
 }
 
 int rf_cubic_feature_sampling_grad(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len,
@@ -429,23 +304,23 @@ int rf_cubic_feature_sampling_grad(int b, int n, int c, int res, float lo, float
                                    rf_stream_t stream) {
     if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (!cfs_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
     if (!xyz || !grad_feat || !grad_vol) return RF_EINVAL;
     if (!rf::aligned4(xyz) || !rf::aligned4(grad_feat) || !rf::aligned4(grad_vol) || !rf::aligned4(len)) return RF_EINVAL;
     if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
-    const CfsLayout l = cfs_layout(b, n, res);
+    const GrSortLayout l = gr_sort_layout(b, n, res);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
 
     char *w = (char *)workspace;
     unsigned *starts = (unsigned *)(w + l.starts);
     unsigned long long *recs = (unsigned long long *)(w + l.recs);
-    const CfsBin bin{n, gr_box(res, lo, hi), xyz, len, starts, recs};
-    RF_LAUNCH("cfs_bin", cfs_bin_kernel, dim3(b), dim3(CFS_BIN_TPB), 0, st, bin);
-    const int nsb = rf::ceil_div(res, CFS_E), nchunk = rf::ceil_div(c, CFS_CHUNK);
+    const GrSortCloud bin{n, gr_box(res, lo, hi), xyz, len, starts, recs};
+    RF_LAUNCH("cfs_bin", cfs_bin_kernel, dim3(b), dim3(GR_BIN_TPB), 0, st, bin);
+    const int nsb = rf::ceil_div(res, GR_SUB_E), nchunk = rf::ceil_div(c, GR_CHUNK);
     const CfsBrick br{n, c, res, starts, recs, grad_feat, grad_vol};
-    RF_LAUNCH("cfs_brick", cfs_brick_kernel, dim3(nsb * nsb * nsb * nchunk, b), dim3(CFS_TPB), 0, st, br);
+    RF_LAUNCH("cfs_brick", cfs_brick_kernel, dim3(nsb * nsb * nsb * nchunk, b), dim3(GR_SUB_TPB), 0, st, br);
     return RF_OK;
 }
 

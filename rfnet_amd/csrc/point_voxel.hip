@@ -5,31 +5,25 @@
 //
 //   voxelize        no float atomics in memory and no memset: the inside points are counting-sorted by the brick (GR_E^3
 //                   vertices) of their NEAREST vertex, the record carrying that vertex and the point index; one workgroup per
-//                   (sample, sub-brick of PV_E^3 vertices, chunk of PV_CHUNK channels) walks its own brick's list only, compacts
+//                   (sample, sub-brick of GR_SUB_E^3 vertices, chunk of GR_CHUNK channels) walks its own brick's list only, compacts
 //                   the records of its sub-brick through LDS, and a wave then takes eight of them per step with a lane per
-//                   (record, channel) -- eight reads of PV_CHUNK contiguous floats of feat -- adding into LDS doubles and LDS
+//                   (record, channel) -- eight reads of GR_CHUNK contiguous floats of feat -- adding into LDS doubles and LDS
 //                   integer counts; every element of vol is stored once as sum / count, the chunk-0 workgroup stores cnt.
 //   voxelize grad   the plain gather: grad_vol[ch][k_i] / cnt[k_i], k_i recomputed from xyz.
 //   devoxelize      the plain gather, cfs_gather_kernel's shape: a workgroup takes PV_PTS points, cell and t go through LDS, the
 //                   threads run over the (point, channel) elements of the output in memory order; eight plane reads, a double sum.
-//   devoxelize grad grad_vol is cfs_brick_kernel's walk of up to eight lists over a sort by the brick of the CELL, a record per
+//   devoxelize grad grad_vol is gr_subbrick_scatter's walk of up to eight lists over a sort by the brick of the CELL, a record per
 //                   step with a lane per (corner, channel), the weight recomputed from xyz[i] and one read of grad_feat[i][ch];
 //                   grad_xyz is a gather with eight lanes per point, lane d summing g_d over the channels in ascending order.
 //
 // Every kernel with a (tile, sample) grid takes its logical place from pv_place: the workgroups of a sample share one XCD's L2.
-// The counting sort is cfs_bin_kernel's with another key.  It is restated here rather than shared: moving it into a header
-// would change what grnet_layers.hip compiles to.
-#include "gridding.hpp"
+// Both sorts are brick_sort.hpp's gr_brick_sort, the one that grnet_layers.hip runs, with the vertex or the cell as the key; the
+// devoxelize backward's scatter is its gr_subbrick_scatter, placed by pv_place.
+#include "brick_sort.hpp"
 
 namespace {
 
 constexpr int PV_TPB = 256, PV_PTS = 32;
-constexpr int PV_BIN_TPB = 1024, PV_MAX_NB3 = 4096;
-constexpr int PV_E = 8, PV_E3 = PV_E * PV_E * PV_E;  // vertices per sub-brick edge
-constexpr int PV_CHUNK = 8;                          // channels per workgroup: 8 records (or corners) x 8 channels = one wave per step
-static_assert(PV_MAX_NB3 == (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E) * (RF_GR_MAX_RES / GR_E) && PV_MAX_NB3 == 4 * PV_BIN_TPB, "");
-static_assert(GR_E == 2 * PV_E && 8 * PV_CHUNK == 64 && PV_E3 * PV_CHUNK * sizeof(double) == 32768, "");
-static_assert(RF_GR_MAX_POINTS <= 65536 && PV_E3 <= 65536 && RF_GR_MAX_RES <= 256, "a record holds 3 x 8 bits of vertex and 16 bits of index");
 
 struct PvPoint {
     int ix, iy, iz;  // the cell
@@ -62,72 +56,26 @@ __device__ __forceinline__ void pv_place(int &x, int &s) {
 }
 
 // ------------------------------------------------------------------------------------------------ the counting sort
-struct PvBin {
-    int n;
-    GrBox g;
-    const float *xyz;
-    const int *len;
-    unsigned *starts;          // (b, nb^3 + 1): where every brick's list begins; the last entry is the inside count
-    unsigned long long *recs;  // (b, n): the key (3 x 8 bits) and the point index (16 bits, from bit 24)
-};
-
-// cfs_bin_kernel for one cloud; the key is the cell, or with NEAREST the nearest vertex.  grid (b)
+// gr_brick_sort, the record carrying the point index; the key is the cell, or with NEAREST the nearest vertex.  grid (b)
 template <bool NEAREST>
-__global__ __launch_bounds__(PV_BIN_TPB) void pv_bin_kernel(PvBin a) {
-    __shared__ unsigned hist[PV_MAX_NB3];
-    __shared__ unsigned wtot[PV_BIN_TPB / 64];
-    const int s = blockIdx.x, tid = threadIdx.x, n = a.n;
+__global__ __launch_bounds__(GR_BIN_TPB) void pv_bin_kernel(GrSortCloud a) {
+    const int s = blockIdx.x, n = a.n;
     const int L = rf::ragged_count(a.len, s, n);
     const float *__restrict__ xyz = a.xyz + (size_t)s * n * 3;
     const GrBox g = a.g;
     const int nb = gr_nb(g.R), nb3 = nb * nb * nb;
     unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
     unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
-
-    auto key = [&](int i, int &kx, int &ky, int &kz) {
+    gr_brick_sort(L, g.R, st, rec, nullptr, [&](int i, int &kx, int &ky, int &kz, unsigned long long &word) {
         PvPoint p;
         const bool in = pv_point(xyz + (size_t)i * 3, g, p);
         if (NEAREST)
             pv_nearest(p, kx, ky, kz);
         else
             kx = p.ix, ky = p.iy, kz = p.iz;
+        word = gr_index_record(kx, ky, kz, i);
         return in;
-    };
-    for (int k = tid; k < nb3; k += PV_BIN_TPB) hist[k] = 0;
-    __syncthreads();
-    for (int i = tid; i < L; i += PV_BIN_TPB) {
-        int kx, ky, kz;
-        if (key(i, kx, ky, kz)) atomicAdd(&hist[((kx / GR_E) * nb + ky / GR_E) * nb + kz / GR_E], 1u);  // k <= R - 1: a brick < nb
-    }
-    __syncthreads();
-    unsigned cn[4], tsum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int idx = tid * 4 + k;
-        cn[k] = idx < nb3 ? hist[idx] : 0u;
-        tsum += cn[k];
-    }
-    const unsigned incl = rf::wave_incl_scan(tsum);
-    if ((tid & 63) == 63) wtot[tid >> 6] = incl;
-    __syncthreads();
-    unsigned run = incl - tsum;
-    for (int w = 0; w < (tid >> 6); w++) run += wtot[w];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int idx = tid * 4 + k;
-        if (idx < nb3) hist[idx] = run, st[idx] = run;  // the bin's cursor and its start
-        run += cn[k];
-    }
-    if (tid == PV_BIN_TPB - 1) st[nb3] = run;
-    __syncthreads();
-    for (int i = tid; i < L; i += PV_BIN_TPB) {
-        int kx, ky, kz;
-        if (key(i, kx, ky, kz)) {
-            const unsigned pos = atomicAdd(&hist[((kx / GR_E) * nb + ky / GR_E) * nb + kz / GR_E], 1u);
-            rec[pos] = (unsigned long long)((unsigned)kx | (unsigned)ky << 8 | (unsigned)kz << 16) |
-                       (unsigned long long)(unsigned)i << 24;  // pos < the inside count <= L; i < 65536
-        }
-    }
+    });
 }
 
 // ------------------------------------------------------------------------------------------------ average voxelization
@@ -141,18 +89,18 @@ struct PvVox {
     int *inside;        // (b)
 };
 
-// grid (ceil(R / PV_E)^3 * ceil(c / PV_CHUNK), b), the channel chunk fastest
+// grid (ceil(R / GR_SUB_E)^3 * ceil(c / GR_CHUNK), b), the channel chunk fastest
 __global__ __launch_bounds__(PV_TPB) void pv_vox_kernel(PvVox a) {
-    __shared__ double acc[PV_E3 * PV_CHUNK];  // [vertex][channel]
-    __shared__ unsigned num[PV_E3];
+    __shared__ double acc[GR_SUB_E3 * GR_CHUNK];  // [vertex][channel]
+    __shared__ unsigned num[GR_SUB_E3];
     __shared__ unsigned slot[PV_TPB];  // a wave's 64: the records of this sub-brick among the 64 it has just read
     int s, bx;
     pv_place(bx, s);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int R = a.R, c = a.c, n = a.n;
-    const int nsb = (R + PV_E - 1) / PV_E, nchunk = (c + PV_CHUNK - 1) / PV_CHUNK;
+    const int nsb = (R + GR_SUB_E - 1) / GR_SUB_E, nchunk = (c + GR_CHUNK - 1) / GR_CHUNK;
     const int nb = gr_nb(R), nb3 = nb * nb * nb;
-    const int sbi = bx / nchunk, ch0 = (bx - sbi * nchunk) * PV_CHUNK;
+    const int sbi = bx / nchunk, ch0 = (bx - sbi * nchunk) * GR_CHUNK;
     const int sz = sbi % nsb, sy = (sbi / nsb) % nsb, sx = sbi / (nsb * nsb);
     const unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
     const size_t R3 = (size_t)R * R * R;
@@ -163,8 +111,8 @@ __global__ __launch_bounds__(PV_TPB) void pv_vox_kernel(PvVox a) {
     const unsigned lo = st[q], hi = st[q + 1];
     const bool any = hi > lo;  // (uniform over the workgroup)
     if (any) {
-        for (int l = tid; l < PV_E3 * PV_CHUNK; l += PV_TPB) acc[l] = 0.0;
-        for (int l = tid; l < PV_E3; l += PV_TPB) num[l] = 0u;
+        for (int l = tid; l < GR_SUB_E3 * GR_CHUNK; l += PV_TPB) acc[l] = 0.0;
+        for (int l = tid; l < GR_SUB_E3; l += PV_TPB) num[l] = 0u;
         __syncthreads();
         const unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
         const float *__restrict__ feat = a.feat + (size_t)s * n * c;
@@ -174,22 +122,22 @@ __global__ __launch_bounds__(PV_TPB) void pv_vox_kernel(PvVox a) {
         for (unsigned r0 = lo + wave * 64; r0 < hi; r0 += PV_TPB) {  // uniform over the wave
             const unsigned r = r0 + lane;
             const unsigned long long w = r < hi ? rec[r] : 0ull;
-            const int lx = (int)((unsigned)w & 255u) - sx * PV_E, ly = (int)((unsigned)(w >> 8) & 255u) - sy * PV_E,
-                      lz = (int)((unsigned)(w >> 16) & 255u) - sz * PV_E;
-            const bool keep = r < hi && (unsigned)lx < (unsigned)PV_E && (unsigned)ly < (unsigned)PV_E && (unsigned)lz < (unsigned)PV_E;
+            const int lx = (int)((unsigned)w & 255u) - sx * GR_SUB_E, ly = (int)((unsigned)(w >> 8) & 255u) - sy * GR_SUB_E,
+                      lz = (int)((unsigned)(w >> 16) & 255u) - sz * GR_SUB_E;
+            const bool keep = r < hi && (unsigned)lx < (unsigned)GR_SUB_E && (unsigned)ly < (unsigned)GR_SUB_E && (unsigned)lz < (unsigned)GR_SUB_E;
             const unsigned long long mask = __ballot(keep);
             const int kept = __popcll(mask);
             const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
-            // the local vertex (< PV_E3) and the point index (< n: written by the bin kernel from a row below the count)
-            if (keep) mine[rank] = ((unsigned)(w >> 24) & 0xFFFFu) | (unsigned)((lx * PV_E + ly) * PV_E + lz) << 16;
+            // the local vertex (< GR_SUB_E3) and the point index (< n: written by the bin kernel from a row below the count)
+            if (keep) mine[rank] = ((unsigned)(w >> 24) & 0xFFFFu) | (unsigned)((lx * GR_SUB_E + ly) * GR_SUB_E + lz) << 16;
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             for (int j = grp; j < kept; j += 8) {  // eight records per step, a lane per (record, channel)
                 const unsigned k = mine[j];
-                const int i = (int)(k & 0xFFFFu), v = (int)(k >> 16) & (PV_E3 - 1);
+                const int i = (int)(k & 0xFFFFu), v = (int)(k >> 16) & (GR_SUB_E3 - 1);
                 if (ch == 0) atomicAdd(&num[v], 1u);
-                if (chok) atomicAdd(&acc[v * PV_CHUNK + ch], (double)feat[(size_t)i * c + ch0 + ch]);
+                if (chok) atomicAdd(&acc[v * GR_CHUNK + ch], (double)feat[(size_t)i * c + ch0 + ch]);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -198,18 +146,18 @@ __global__ __launch_bounds__(PV_TPB) void pv_vox_kernel(PvVox a) {
         __syncthreads();
     }
     float *__restrict__ vol = a.vol + ((size_t)s * c + ch0) * R3;
-    for (int e = tid; e < PV_E3 * PV_CHUNK; e += PV_TPB) {
-        const int chh = e / PV_E3, l = e % PV_E3;
-        const int gx = sx * PV_E + l / (PV_E * PV_E), gy = sy * PV_E + (l / PV_E) % PV_E, gz = sz * PV_E + l % PV_E;
+    for (int e = tid; e < GR_SUB_E3 * GR_CHUNK; e += PV_TPB) {
+        const int chh = e / GR_SUB_E3, l = e % GR_SUB_E3;
+        const int gx = sx * GR_SUB_E + l / (GR_SUB_E * GR_SUB_E), gy = sy * GR_SUB_E + (l / GR_SUB_E) % GR_SUB_E, gz = sz * GR_SUB_E + l % GR_SUB_E;
         if (ch0 + chh < c && gx < R && gy < R && gz < R) {
             const unsigned k = any ? num[l] : 0u;
-            vol[(size_t)chh * R3 + ((size_t)gx * R + gy) * R + gz] = k ? (float)(acc[l * PV_CHUNK + chh] / (double)k) : 0.f;
+            vol[(size_t)chh * R3 + ((size_t)gx * R + gy) * R + gz] = k ? (float)(acc[l * GR_CHUNK + chh] / (double)k) : 0.f;
         }
     }
     if (ch0 == 0) {
         int *__restrict__ cnt = a.cnt + (size_t)s * R3;
-        for (int l = tid; l < PV_E3; l += PV_TPB) {
-            const int gx = sx * PV_E + l / (PV_E * PV_E), gy = sy * PV_E + (l / PV_E) % PV_E, gz = sz * PV_E + l % PV_E;
+        for (int l = tid; l < GR_SUB_E3; l += PV_TPB) {
+            const int gx = sx * GR_SUB_E + l / (GR_SUB_E * GR_SUB_E), gy = sy * GR_SUB_E + (l / GR_SUB_E) % GR_SUB_E, gz = sz * GR_SUB_E + l % GR_SUB_E;
             if (gx < R && gy < R && gz < R) cnt[((size_t)gx * R + gy) * R + gz] = any ? (int)num[l] : 0;
         }
     }
@@ -339,84 +287,24 @@ struct PvBrick {
     float *gv;        // (b, c, R, R, R)
 };
 
-// cfs_brick_kernel with a weight.  grid (ceil(R / PV_E)^3 * ceil(c / PV_CHUNK), b), the channel chunk fastest
-__global__ __launch_bounds__(PV_TPB) void pv_devox_brick_kernel(PvBrick a) {
-    __shared__ double acc[PV_E3 * PV_CHUNK];  // [vertex][channel]
+// gr_subbrick_scatter of grad_feat times the corner's weight, recomputed from xyz.  grid (ceil(R / GR_SUB_E)^3 *
+// ceil(c / GR_CHUNK), b), the channel chunk fastest
+__global__ __launch_bounds__(GR_SUB_TPB) void pv_devox_brick_kernel(PvBrick a) {
     int s, bx;
     pv_place(bx, s);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const GrBox g = a.g;
     const int R = g.R, c = a.c, n = a.n;
-    const int nsb = (R + PV_E - 1) / PV_E, nchunk = (c + PV_CHUNK - 1) / PV_CHUNK;
     const int nb = gr_nb(R), nb3 = nb * nb * nb;
-    const int sbi = bx / nchunk, ch0 = (bx - sbi * nchunk) * PV_CHUNK;
-    const int sz = sbi % nsb, sy = (sbi / nsb) % nsb, sx = sbi / (nsb * nsb);
-    const unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
     const size_t R3 = (size_t)R * R * R;
-    float *__restrict__ gv = a.gv + ((size_t)s * c + ch0) * R3;
-
-    // The cells that reach this sub-brick's vertices are those of its own brick and, where the sub-brick is the lower half of its
-    // brick along an axis, of the lower neighbour along that axis: at most eight lists.
-    auto list = [&](int d, unsigned &lo, unsigned &hi) {
-        const int dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
-        const int nx = (sx >> 1) - dx, ny = (sy >> 1) - dy, nz = (sz >> 1) - dz;
-        const bool skip = (dx && ((sx & 1) || nx < 0)) || (dy && ((sy & 1) || ny < 0)) || (dz && ((sz & 1) || nz < 0));
-        const int q = skip ? 0 : (nx * nb + ny) * nb + nz;
-        lo = st[q], hi = skip ? lo : st[q + 1];
-    };
-    unsigned any = 0;
-#pragma unroll
-    for (int d = 0; d < 8; d++) {
-        unsigned lo, hi;
-        list(d, lo, hi);
-        any |= hi - lo;
-    }
-    if (any) {  // (uniform over the workgroup)
-        for (int l = tid; l < PV_E3 * PV_CHUNK; l += PV_TPB) acc[l] = 0.0;
-        __syncthreads();
-        const unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
-        const float *__restrict__ xyz = a.xyz + (size_t)s * n * 3;
-        const float *__restrict__ gf = a.gf + (size_t)s * n * c;
-        const int d = lane >> 3, ch = lane & 7, dx = d >> 2, dy = (d >> 1) & 1, dz = d & 1;
-        const bool chok = ch0 + ch < c;
-#pragma unroll 1
-        for (int q = 0; q < 8; q++) {
-            unsigned lo, hi;
-            list(q, lo, hi);
-            for (unsigned r0 = lo + wave * 64; r0 < hi; r0 += PV_TPB) {  // uniform over the wave
-                const unsigned r = r0 + lane;
-                const unsigned long long w = r < hi ? rec[r] : 0ull;
-                // the cell relative to this sub-brick's first vertex: kept iff -1 ... 7 on every axis
-                const int cx = (int)((unsigned)w & 255u) - sx * PV_E + 1, cy = (int)((unsigned)(w >> 8) & 255u) - sy * PV_E + 1,
-                          cz = (int)((unsigned)(w >> 16) & 255u) - sz * PV_E + 1;
-                const bool keep = r < hi && (unsigned)cx <= (unsigned)PV_E && (unsigned)cy <= (unsigned)PV_E &&
-                                  (unsigned)cz <= (unsigned)PV_E;
-                const unsigned key = ((unsigned)(w >> 24) & 0xFFFFu) | (unsigned)cx << 16 | (unsigned)cy << 20 | (unsigned)cz << 24;
-                unsigned long long mask = __ballot(keep);
-                while (mask) {  // a record per step, a lane per (corner, channel)
-                    const int j = __ffsll((long long)mask) - 1;
-                    mask &= mask - 1;
-                    const unsigned k = (unsigned)__shfl((int)key, j, 64);
-                    const int i = (int)(k & 0xFFFFu);  // < n: written by the bin kernel from a row below the count
-                    const int lx = (int)((k >> 16) & 15u) - 1 + dx, ly = (int)((k >> 20) & 15u) - 1 + dy,
-                              lz = (int)((k >> 24) & 15u) - 1 + dz;
-                    if ((unsigned)lx < (unsigned)PV_E && (unsigned)ly < (unsigned)PV_E && (unsigned)lz < (unsigned)PV_E && chok) {
-                        PvPoint p;
-                        pv_point(xyz + (size_t)i * 3, g, p);  // inside: the bin kernel kept it; only t is used
-                        atomicAdd(&acc[((lx * PV_E + ly) * PV_E + lz) * PV_CHUNK + ch],
-                                  pv_weight(p, dx, dy, dz) * (double)gf[(size_t)i * c + ch0 + ch]);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    for (int e = tid; e < PV_E3 * PV_CHUNK; e += PV_TPB) {
-        const int chh = e / PV_E3, l = e % PV_E3;
-        const int gx = sx * PV_E + l / (PV_E * PV_E), gy = sy * PV_E + (l / PV_E) % PV_E, gz = sz * PV_E + l % PV_E;
-        if (ch0 + chh < c && gx < R && gy < R && gz < R)
-            gv[(size_t)chh * R3 + ((size_t)gx * R + gy) * R + gz] = any ? (float)acc[l * PV_CHUNK + chh] : 0.f;
-    }
+    const unsigned *__restrict__ st = a.starts + (size_t)s * (nb3 + 1);
+    const unsigned long long *__restrict__ rec = a.recs + (size_t)s * n;
+    const float *__restrict__ xyz = a.xyz + (size_t)s * n * 3;
+    const float *__restrict__ gf = a.gf + (size_t)s * n * c;
+    gr_subbrick_scatter(bx, R, c, st, rec, a.gv + (size_t)s * c * R3, [&](int i, int d, int ch) {
+        PvPoint p;
+        pv_point(xyz + (size_t)i * 3, g, p);  // inside: the bin kernel kept it; only t is used
+        return pv_weight(p, d >> 2, (d >> 1) & 1, d & 1) * (double)gf[(size_t)i * c + ch];
+    });
 }
 
 struct PvXyzGrad {
@@ -462,50 +350,35 @@ __global__ __launch_bounds__(PV_TPB) void pv_devox_xyz_kernel(PvXyzGrad a) {
     if (i < n && d < 3) a.out[((size_t)s * n + i) * 3 + d] = in ? (float)((double)g.inv_h * acc) : 0.f;
 }
 
-struct PvLayout {
-    size_t starts, recs, total;
-};
-
-PvLayout pv_layout(int b, int n, int res) {
-    const size_t nb = gr_nb(res), nb3 = nb * nb * nb;
-    PvLayout l;
-    l.starts = 0;
-    l.recs = l.starts + rf::align256((size_t)b * (nb3 + 1) * sizeof(unsigned));
-    l.total = l.recs + rf::align256((size_t)b * (size_t)n * sizeof(unsigned long long));
-    return l;
-}
-
-bool pv_sizes_ok(int b, int n, int c, int res) { return gr_sizes_ok(b, n, res) && c >= 1 && c <= RF_CFS_MAX_CHANNELS; }
-
 }  // namespace
 
 extern "C" {
 
 size_t rf_voxelize_mean_workspace_bytes(int b, int n, int res) {
     if (!gr_sizes_ok(b, n, res)) return 0;
-    return pv_layout(b, n, res).total;
+    return gr_sort_layout(b, n, res).total;
 }
 
 int rf_voxelize_mean(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len, const float *feat, float *vol,
                      int *cnt, int *inside, void *workspace, size_t workspace_bytes, rf_stream_t stream) {
     if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (!pv_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
     if (!xyz || !feat || !vol || !cnt || !inside) return RF_EINVAL;
     if (!rf::aligned4(xyz) || !rf::aligned4(feat) || !rf::aligned4(vol) || !rf::aligned4(cnt) || !rf::aligned4(inside) || !rf::aligned4(len))
         return RF_EINVAL;
     if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
-    const PvLayout l = pv_layout(b, n, res);
+    const GrSortLayout l = gr_sort_layout(b, n, res);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
 
     char *w = (char *)workspace;
     unsigned *starts = (unsigned *)(w + l.starts);
     unsigned long long *recs = (unsigned long long *)(w + l.recs);
-    const PvBin bin{n, gr_box(res, lo, hi), xyz, len, starts, recs};
-    RF_LAUNCH("voxelize_bin", pv_bin_kernel<true>, dim3(b), dim3(PV_BIN_TPB), 0, st, bin);
-    const int nsb = rf::ceil_div(res, PV_E), nchunk = rf::ceil_div(c, PV_CHUNK);
+    const GrSortCloud bin{n, gr_box(res, lo, hi), xyz, len, starts, recs};
+    RF_LAUNCH("voxelize_bin", pv_bin_kernel<true>, dim3(b), dim3(GR_BIN_TPB), 0, st, bin);
+    const int nsb = rf::ceil_div(res, GR_SUB_E), nchunk = rf::ceil_div(c, GR_CHUNK);
     const PvVox vx{n, c, res, starts, recs, feat, vol, cnt, inside};
     RF_LAUNCH("voxelize_brick", pv_vox_kernel, dim3(nsb * nsb * nsb * nchunk, b), dim3(PV_TPB), 0, st, vx);
     return RF_OK;
@@ -515,7 +388,7 @@ int rf_voxelize_mean_grad(int b, int n, int c, int res, float lo, float hi, cons
                           const float *grad_vol, float *grad_feat, rf_stream_t stream) {
     if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (!pv_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
     if (!xyz || !cnt || !grad_vol || !grad_feat) return RF_EINVAL;
     if (!rf::aligned4(xyz) || !rf::aligned4(cnt) || !rf::aligned4(grad_vol) || !rf::aligned4(grad_feat) || !rf::aligned4(len)) return RF_EINVAL;
@@ -529,7 +402,7 @@ int rf_trilinear_devoxelize(int b, int n, int c, int res, float lo, float hi, co
                             float *feat, int *inside, rf_stream_t stream) {
     if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (!pv_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
     if (!xyz || !vol || !feat || !inside) return RF_EINVAL;
     if (!rf::aligned4(xyz) || !rf::aligned4(vol) || !rf::aligned4(feat) || !rf::aligned4(inside) || !rf::aligned4(len)) return RF_EINVAL;
@@ -541,7 +414,7 @@ int rf_trilinear_devoxelize(int b, int n, int c, int res, float lo, float hi, co
 
 size_t rf_trilinear_devoxelize_grad_workspace_bytes(int b, int n, int res) {
     if (!gr_sizes_ok(b, n, res)) return 0;
-    return pv_layout(b, n, res).total;
+    return gr_sort_layout(b, n, res).total;
 }
 
 int rf_trilinear_devoxelize_grad(int b, int n, int c, int res, float lo, float hi, const float *xyz, const int *len, const float *vol,
@@ -549,14 +422,14 @@ int rf_trilinear_devoxelize_grad(int b, int n, int c, int res, float lo, float h
                                  rf_stream_t stream) {
     if (b < 0 || n < 0 || c < 0 || res < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (!pv_sizes_ok(b, n, c, res)) return RF_EINVAL;
+    if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
     if (!xyz || !vol || !grad_feat || !grad_vol) return RF_EINVAL;  // (grad_xyz may be NULL: it is then not computed)
     if (!rf::aligned4(xyz) || !rf::aligned4(vol) || !rf::aligned4(grad_feat) || !rf::aligned4(grad_vol) || !rf::aligned4(grad_xyz) ||
         !rf::aligned4(len))
         return RF_EINVAL;
     if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
-    const PvLayout l = pv_layout(b, n, res);
+    const GrSortLayout l = gr_sort_layout(b, n, res);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
 
@@ -564,11 +437,11 @@ int rf_trilinear_devoxelize_grad(int b, int n, int c, int res, float lo, float h
     unsigned *starts = (unsigned *)(w + l.starts);
     unsigned long long *recs = (unsigned long long *)(w + l.recs);
     const GrBox g = gr_box(res, lo, hi);
-    const PvBin bin{n, g, xyz, len, starts, recs};
-    RF_LAUNCH("devoxelize_bin", pv_bin_kernel<false>, dim3(b), dim3(PV_BIN_TPB), 0, st, bin);
-    const int nsb = rf::ceil_div(res, PV_E), nchunk = rf::ceil_div(c, PV_CHUNK);
+    const GrSortCloud bin{n, g, xyz, len, starts, recs};
+    RF_LAUNCH("devoxelize_bin", pv_bin_kernel<false>, dim3(b), dim3(GR_BIN_TPB), 0, st, bin);
+    const int nsb = rf::ceil_div(res, GR_SUB_E), nchunk = rf::ceil_div(c, GR_CHUNK);
     const PvBrick br{n, c, g, starts, recs, xyz, grad_feat, grad_vol};
-    RF_LAUNCH("devoxelize_brick", pv_devox_brick_kernel, dim3(nsb * nsb * nsb * nchunk, b), dim3(PV_TPB), 0, st, br);
+    RF_LAUNCH("devoxelize_brick", pv_devox_brick_kernel, dim3(nsb * nsb * nsb * nchunk, b), dim3(GR_SUB_TPB), 0, st, br);
     if (grad_xyz) {
         const PvXyzGrad xg{n, c, g, xyz, len, vol, grad_feat, grad_xyz};
         RF_LAUNCH("devoxelize_xyz_grad", pv_devox_xyz_kernel, dim3(rf::ceil_div(n, PV_PTS), b), dim3(PV_TPB), 0, st, xg);

@@ -11,7 +11,7 @@ import pytest
 
 from test_gridding_host import BOUNDS, CORNERS, F32, F64, family, gr_grid_ref, gr_points, gr_spread, pair, vertex_coord
 
-BRICK, CHUNK = 8, 8  # grnet_layers.hip: CFS_E, the sub-brick edge of the sampling's backward in vertices, and CFS_CHUNK, its channels
+BRICK, CHUNK = 8, 8  # brick_sort.hpp: GR_SUB_E, the sub-brick edge of the sampling's backward in vertices, and GR_CHUNK, its channels
 TILE = 256           # grnet_layers.hip: GV_TILE, the cells per tile of Gridding Reverse's compaction
 MAX_CHANNELS = 1024
 U32, I32 = np.uint32, np.int32
@@ -288,7 +288,9 @@ def test_entries_are_declared_exported_and_bound():
     assert f"#define RF_CFS_MAX_CHANNELS {_raw.CFS_MAX_CHANNELS}\n" in header and _raw.CFS_MAX_CHANNELS == MAX_CHANNELS
     assert (_raw.CFS_BRICK, _raw.CFS_CHUNK, _raw.GREV_TILE) == (BRICK, CHUNK, TILE)
     src = open(_lib._PKG + "/csrc/grnet_layers.hip").read()
-    assert f"CFS_E = {BRICK}," in src and f"CFS_CHUNK = {CHUNK};" in src and f"GV_TILE = {TILE}," in src
+    shared = open(_lib._PKG + "/csrc/brick_sort.hpp").read()
+    assert '#include "brick_sort.hpp"' in src and f"GR_SUB_E = {BRICK}," in shared and f"GR_CHUNK = {CHUNK};" in shared
+    assert f"GV_TILE = {TILE}," in src
 
 
 def test_workspace_sizes():

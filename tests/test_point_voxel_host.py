@@ -13,7 +13,7 @@ import pytest
 from test_gridding_host import BOUNDS, CORNERS, F32, F64, gr_gather, gr_points, gr_spread, inv_h_of
 from test_grnet_layers_host import cloud
 
-BRICK, CHUNK = 8, 8  # point_voxel.hip: PV_E, the sub-brick edge of the two scatter kernels in vertices, and PV_CHUNK, their channels
+BRICK, CHUNK = 8, 8  # brick_sort.hpp: GR_SUB_E, the sub-brick edge of the two scatter kernels in vertices, and GR_CHUNK, their channels
 MAX_CHANNELS = 1024
 U32, I32, I64 = np.uint32, np.int32, np.int64
 
@@ -315,8 +315,9 @@ def test_entries_are_declared_exported_and_bound():
         assert hasattr(raw, name), f"librfops.so lacks {name}"
         assert name in _lib.SIGNATURES, f"ctypes binding lacks {name}"
     assert (_raw.PV_BRICK, _raw.PV_CHUNK) == (BRICK, CHUNK) and _raw.CFS_MAX_CHANNELS == MAX_CHANNELS
-    src = open(_lib._PKG + "/csrc/point_voxel.hip").read()
-    assert f"PV_E = {BRICK}," in src and f"PV_CHUNK = {CHUNK};" in src
+    src = open(_lib._PKG + "/csrc/brick_sort.hpp").read()
+    assert f"GR_SUB_E = {BRICK}," in src and f"GR_CHUNK = {CHUNK};" in src
+    assert '#include "brick_sort.hpp"' in open(_lib._PKG + "/csrc/point_voxel.hip").read()
     for name in ("avg_voxelize", "avg_voxelize_grad", "trilinear_devoxelize", "trilinear_devoxelize_grad"):
         assert callable(getattr(_raw, name))
     assert callable(glue.avg_voxelize) and callable(glue.trilinear_devoxelize)
