@@ -1262,11 +1262,15 @@ int rf_merge_layer_grad_lengths(int b, int n, int m, const float *rawpts, const 
  * y (b,n,c): the GEMM of the wide per-point inputs, or NULL; p (b,n,kp), w (kp,c): a narrow
  * per-point input (the coordinates: kp = 3; kp <= 16) applied on the fly, or kp = 0; r: bias + code
  * word term, (b,c) with r_per_sample != 0, (c) otherwise; act: 0 none, 1 relu, 2 tanh.
- * c % 4 == 0, c <= 1024 (rf_point_affine_supported).  out may alias y. */
+ * c % 4 == 0, c <= 1024 (rf_point_affine_supported).  out may alias y.
+ * Non-finite values pass through as the tensor ops pass them: with no activation and with relu a NaN in y, p or r
+ * gives NaN (relu is `v < 0 ? 0 : v`, torch.relu's and tf.nn.relu's rule, not fmaxf, which would turn NaN into 0), +inf
+ * stays +inf, relu(-inf) = 0; tanh(+-inf) = +-1 and tanh(NaN) = NaN.  relu(-0.0) may be either zero. */
 /* tf.reduce_max(axis=1) of a (b, n, c) feature tensor -> (b, c) (global_mlp / encode_cell /
  * recover_cell / init_move_layer / refine_layer, vv_recon.py:90,107,129,151,286).  c % 4 == 0,
  * c <= 1024.  Two launches (strips, fold); exact and deterministic (max in any order).  NaNs are
- * ignored (fmaxf), which the graph never produces after a ReLU. */
+ * skipped (fmaxf): a channel's maximum runs over its numbers, and a channel that holds nothing above -inf gives -inf.
+ * (rf_point_affine's relu lets a NaN through, so a NaN can reach this pooling; it is skipped here all the same.) */
 size_t rf_maxpool_points_workspace_bytes(int b, int n, int c);
 int rf_maxpool_points(int b, int n, int c, const float *x, float *out, void *workspace,
                       size_t workspace_bytes, rf_stream_t stream);

@@ -21,7 +21,7 @@ constexpr int PA_STRIP = 64;  // points per workgroup
 
 template <int ACT>
 __device__ __forceinline__ float pa_act(float v) {
-    if (ACT == 1) return fmaxf(v, 0.f);
+    if (ACT == 1) return v < 0.f ? 0.f : v;  // not fmaxf: a NaN stays a NaN, as in torch.relu and tf.nn.relu
     if (ACT == 2) return tanhf(v);
     return v;
 }
