@@ -70,17 +70,7 @@ def nn_distance(xyz1, xyz2, mode="auto", stats=None, lengths1=None, lengths2=Non
     if lengths1 is not None or lengths2 is not None:
         return _nn_distance_lengths(xyz1, xyz2, mode, stats, lengths1, lengths2)
     st = H.Staged()
-    a, b_ = st.take(xyz1, F32), st.take(xyz2, F32)
-    if a.dim() != 3:
-        raise H.invalid("NnDistance requires xyz1 be of shape (batch,#points,3)")
-    if a.shape[2] != 3:
-        raise H.invalid("NnDistance only accepts 3d point set xyz1")
-    if b_.dim() != 3:
-        raise H.invalid("NnDistance requires xyz2 be of shape (batch,#points,3)")
-    if b_.shape[2] != 3:
-        raise H.invalid("NnDistance only accepts 3d point set xyz2")
-    if b_.shape[0] != a.shape[0]:
-        raise H.invalid("NnDistance expects xyz1 and xyz2 have same batch size")
+    a, b_ = _nn_inputs(st, xyz1, xyz2)
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
     dev = st.device_()
     a, b_ = st.up(a, b_)
@@ -178,6 +168,15 @@ def _nn_inputs(st, xyz1, xyz2, op="NnDistance"):
     return a, b_
 
 
+def _nn_outputs(b, n, m, dev, want1, want2):
+    """(dist1, idx1, dist2, idx2) buffers of the wanted directions, None for a skipped one."""
+    d1 = H.empty((b, n), F32, dev) if want1 else None
+    i1 = H.empty((b, n), I32, dev) if want1 else None
+    d2 = H.empty((b, m), F32, dev) if want2 else None
+    i2 = H.empty((b, m), I32, dev) if want2 else None
+    return d1, i1, d2, i2
+
+
 @H.on_input_device
 def nn_distance_dir(xyz1, xyz2, want1=True, want2=True):
     """nn_distance with only the direction(s) the caller uses (rf_nn_distance_dir): the reference's
@@ -190,10 +189,7 @@ def nn_distance_dir(xyz1, xyz2, want1=True, want2=True):
     b, n, m = a.shape[0], a.shape[1], b_.shape[1]
     dev = st.device_()
     a, b_ = st.up(a, b_)
-    d1 = H.empty((b, n), F32, dev) if want1 else None
-    i1 = H.empty((b, n), I32, dev) if want1 else None
-    d2 = H.empty((b, m), F32, dev) if want2 else None
-    i2 = H.empty((b, m), I32, dev) if want2 else None
+    d1, i1, d2, i2 = _nn_outputs(b, n, m, dev, want1, want2)
     ws, wsz = H.workspace(lib.rf_nn_distance_dir_workspace_bytes(b, n, m, int(want1), int(want2)), dev, "nn")
     check(lib.rf_nn_distance_dir(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(d1), H.ptr(i1), H.ptr(d2), H.ptr(i2),
                                  H.ptr(ws), wsz, H.stream(dev), int(want1), int(want2)), "rf_nn_distance_dir")
@@ -241,10 +237,7 @@ def nn_distance_sorted(s1, s2, want1=True, want2=True):
         raise H.invalid("nn_distance_sorted needs at least one direction")
     dev, b, n, m = s1.device, s1.b, s1.n, s2.n
     with torch.cuda.device(dev):
-        d1 = H.empty((b, n), F32, dev) if want1 else None
-        i1 = H.empty((b, n), I32, dev) if want1 else None
-        d2 = H.empty((b, m), F32, dev) if want2 else None
-        i2 = H.empty((b, m), I32, dev) if want2 else None
+        d1, i1, d2, i2 = _nn_outputs(b, n, m, dev, want1, want2)
         check(lib.rf_nn_distance_sorted(b, n, m, H.ptr(s1.buf), H.ptr(s2.buf), H.ptr(d1), H.ptr(i1), H.ptr(d2),
                                         H.ptr(i2), H.stream(dev)), "rf_nn_distance_sorted")
     return d1, i1, d2, i2
@@ -303,10 +296,7 @@ def chamfer_loss(xyz1, xyz2, sorted1=None, sorted2=None, want1=True, want2=True,
     dev = st.device_()
     a, b_ = st.up(a, b_)
     loss = H.empty((b, 2), F32, dev)
-    d1 = H.empty((b, n), F32, dev) if want1 else None
-    i1 = H.empty((b, n), I32, dev) if want1 else None
-    d2 = H.empty((b, m), F32, dev) if want2 else None
-    i2 = H.empty((b, m), I32, dev) if want2 else None
+    d1, i1, d2, i2 = _nn_outputs(b, n, m, dev, want1, want2)
     p1, p2 = _sorted_ptr(sorted1, b, n, dev), _sorted_ptr(sorted2, b, m, dev)
     ws, wsz = H.workspace(lib.rf_chamfer_loss_workspace_bytes(b, n, m, int(want1), int(want2), int(p1 is not None),
                                                               int(p2 is not None)), dev, "nn")
@@ -327,10 +317,7 @@ def _chamfer_loss_lengths(xyz1, xyz2, sorted1, sorted2, want1, want2, lengths1, 
     a, b_ = st.up(a, b_)
     l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
     loss = H.empty((b, 2), F32, dev)
-    d1 = H.empty((b, n), F32, dev) if want1 else None
-    i1 = H.empty((b, n), I32, dev) if want1 else None
-    d2 = H.empty((b, m), F32, dev) if want2 else None
-    i2 = H.empty((b, m), I32, dev) if want2 else None
+    d1, i1, d2, i2 = _nn_outputs(b, n, m, dev, want1, want2)
     ws, wsz = H.workspace(lib.rf_chamfer_loss_lengths_workspace_bytes(b, n, m, int(want1), int(want2)), dev, "nn")
     check(lib.rf_chamfer_loss_lengths(b, n, m, H.ptr(a), H.ptr(b_), H.ptr(l1), H.ptr(l2), H.ptr(loss), H.ptr(d1),
                                       H.ptr(i1), H.ptr(d2), H.ptr(i2), H.ptr(ws), wsz, H.stream(dev)),
@@ -1694,15 +1681,7 @@ def query_ball_point(radius, nsample, xyz1, xyz2, sorted1=None, form="auto", len
     d, q = st.up(d, q)
     idx = H.zeros((b, m, nsample), I32, dev)
     cnt = H.empty((b, m), I32, dev)
-    rt = None
-    if isinstance(radius, torch.Tensor) and radius.is_cuda:
-        # the reference's form: radius is an op input tensor on the device (tf_grouping.cpp:18,93-95)
-        if radius.device != dev:
-            raise ValueError(f"all GPU inputs of one op must live on the same device: got {dev} and {radius.device}")
-        rt = radius.detach().reshape(-1)[:1].to(F32).contiguous()
-        r = 0.0
-    else:
-        r = float(np.float32(float(radius)))
+    r, rt = _radius_arg(radius, dev)
     wsz = lib.rf_queryballpoint_boxes_workspace_bytes(b, n) if nsample <= 64 and b <= 65535 else 0
     boxes = form == "boxes" or (form == "auto" and n >= QB_BOXES_MIN_N)
     if form == "boxes" and not wsz:
@@ -2141,27 +2120,33 @@ def point_affine(y, p, w, r, act="relu", out=None):
     return out
 
 
-def maxpool_points_idx(x, lengths=None):
-    """rf_maxpool_points_idx: max over the points axis of a (b, n, c) GPU tensor -> values (b, 1, c) and
-    the point index of each maximum (b, c) int32 (lowest index among ties).  `lengths`: per-sample row counts of a
-    ragged batch (rf_maxpool_points_idx_lengths): sample i pools x[i, :lengths[i]], idx < lengths[i]."""
+def _maxpool_points(x, lengths, want_idx):
+    """The four rf_maxpool_points* entries: `lengths` picks the ragged ones, want_idx the ones that also give positions."""
     b, n, c = x.shape
     ln = _check_lengths(lengths, b, n, "lengths")
     dev = x.device
     x_ = x.contiguous()
-    out, idx = H.empty((b, 1, c), F32, dev), H.empty((b, c), I32, dev)
-    if ln is not None:
-        with torch.cuda.device(dev):
-            ln = _lengths_up(ln, dev, n)
-            ws, wsz = H.workspace(lib.rf_maxpool_points_idx_lengths_workspace_bytes(b, n, c), dev, "maxpool")
-            check(lib.rf_maxpool_points_idx_lengths(b, n, c, H.ptr(x_), H.ptr(ln), H.ptr(out), H.ptr(idx), H.ptr(ws), wsz,
-                                                    H.stream(dev)), "rf_maxpool_points_idx_lengths")
-        return out, idx
+    out = H.empty((b, 1, c), F32, dev)
+    idx = H.empty((b, c), I32, dev) if want_idx else None
+    name = "rf_maxpool_points" + ("_idx" if want_idx else "") + ("_lengths" if ln is not None else "")
     with torch.cuda.device(dev):
-        ws, wsz = H.workspace(lib.rf_maxpool_points_idx_workspace_bytes(b, n, c), dev, "maxpool")
-        check(lib.rf_maxpool_points_idx(b, n, c, H.ptr(x_), H.ptr(out), H.ptr(idx), H.ptr(ws), wsz, H.stream(dev)),
-              "rf_maxpool_points_idx")
-    return out, idx
+        args = [b, n, c, H.ptr(x_)]
+        if ln is not None:
+            ln = _lengths_up(ln, dev, n)
+            args.append(H.ptr(ln))
+        args.append(H.ptr(out))
+        if want_idx:
+            args.append(H.ptr(idx))
+        ws, wsz = H.workspace(getattr(lib, name + "_workspace_bytes")(b, n, c), dev, "maxpool")
+        check(getattr(lib, name)(*args, H.ptr(ws), wsz, H.stream(dev)), name)
+    return (out, idx) if want_idx else out
+
+
+def maxpool_points_idx(x, lengths=None):
+    """rf_maxpool_points_idx: max over the points axis of a (b, n, c) GPU tensor -> values (b, 1, c) and
+    the point index of each maximum (b, c) int32 (lowest index among ties).  `lengths`: per-sample row counts of a
+    ragged batch (rf_maxpool_points_idx_lengths): sample i pools x[i, :lengths[i]], idx < lengths[i]."""
+    return _maxpool_points(x, lengths, True)
 
 
 _ACT_GRAD = {None: 0, "none": 0, "relu": 1, "tanh": 2, "leaky_relu": 3}
@@ -2192,19 +2177,4 @@ def act_grad_colsum(grad, out, act, inplace=False):
 def maxpool_points(x, lengths=None):
     """rf_maxpool_points: max over the points axis of a (b, n, c) GPU tensor -> (b, 1, c) (keepdim).  `lengths`:
     per-sample row counts of a ragged batch (rf_maxpool_points_lengths): sample i pools x[i, :lengths[i]]."""
-    b, n, c = x.shape
-    ln = _check_lengths(lengths, b, n, "lengths")
-    dev = x.device
-    x_ = x.contiguous()
-    out = H.empty((b, 1, c), F32, dev)
-    if ln is not None:
-        with torch.cuda.device(dev):
-            ln = _lengths_up(ln, dev, n)
-            ws, wsz = H.workspace(lib.rf_maxpool_points_lengths_workspace_bytes(b, n, c), dev, "maxpool")
-            check(lib.rf_maxpool_points_lengths(b, n, c, H.ptr(x_), H.ptr(ln), H.ptr(out), H.ptr(ws), wsz, H.stream(dev)),
-                  "rf_maxpool_points_lengths")
-        return out
-    with torch.cuda.device(dev):
-        ws, wsz = H.workspace(lib.rf_maxpool_points_workspace_bytes(b, n, c), dev, "maxpool")
-        check(lib.rf_maxpool_points(b, n, c, H.ptr(x_), H.ptr(out), H.ptr(ws), wsz, H.stream(dev)), "rf_maxpool_points")
-    return out
+    return _maxpool_points(x, lengths, False)

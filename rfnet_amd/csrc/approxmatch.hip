@@ -2318,15 +2318,14 @@ struct AmLayout {
 #endif
 constexpr double ROWSORT_MIN_PAIRS = RFA_ROWSORT_MIN_PAIRS;
 
-int round_up_i(int v, int q) { return (v + q - 1) / q * q; }
 
 // mode (include/rfops.h): RF_EMD_AUTO -- the routes by the size of the whole batch (below); RF_EMD_SWEPT -- every level as a
 // dense sweep over the clouds in the caller's order and every launch shape taken as for b = 1: a sample's bits do not depend on
 // the batch it is called in (the reference is batch-independent per sample, tf_approxmatch.cu:13).
 AmLayout am_layout(int b, int n, int m, int nlevels, int mode = RF_EMD_AUTO) {
     AmLayout L;
-    L.npad = round_up_i(n, CPAD);
-    L.mpad = round_up_i(m, CPAD);
+    L.npad = rf::round_up(n, CPAD);
+    L.mpad = rf::round_up(m, CPAD);
     L.V = (size_t)L.npad + L.mpad;
     L.bstride = L.V * (size_t)(1 + nlevels);
     size_t off = (size_t)b * L.bstride + 64;  // + slack: scalar prefetch runs SUB entries ahead
@@ -2748,7 +2747,6 @@ int mcg_tile_launch(int b, int n, int m, const float *xyz1, const float *xyz2, c
     return RF_OK;
 }
 
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 }  // namespace
 
 extern "C" {
@@ -2822,7 +2820,7 @@ int rf_approxmatch_lengths(int b, int n, int m, const float *xyz1, const float *
         if (!(levels_host[v] <= 0.f) || !isfinite(levels_host[v])) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
-    if (!xyz1 || !xyz2 || !match || !workspace || !rf::aligned16(workspace) || !aligned4(len1) || !aligned4(len2))
+    if (!xyz1 || !xyz2 || !match || !workspace || !rf::aligned16(workspace) || !rf::aligned4(len1) || !rf::aligned4(len2))
         return RF_EINVAL;
     if (workspace_bytes < rf_approxmatch_lengths_workspace_bytes(b, n, m, nlevels)) return RF_EWORKSPACE;
     return am_approxmatch<true>(b, n, m, xyz1, xyz2, match, levels_host, nlevels, workspace, (hipStream_t)stream, RF_EMD_SWEPT,
@@ -2836,7 +2834,7 @@ int rf_matchcost_lengths(int b, int n, int m, const float *xyz1, const float *xy
     if (b < 0 || b > MAX_BATCH || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !match || !cost || !workspace || !rf::aligned16(workspace) || !aligned4(len1) || !aligned4(len2))
+    if (!xyz1 || !xyz2 || !match || !cost || !workspace || !rf::aligned16(workspace) || !rf::aligned4(len1) || !rf::aligned4(len2))
         return RF_EINVAL;
     if (workspace_bytes < rf_matchcost_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     return mc_launch<true>(b, n, m, xyz1, xyz2, match, cost, workspace, (hipStream_t)stream, len1, len2);
@@ -2847,7 +2845,7 @@ int rf_matchcost_grad_lengths(int b, int n, int m, const float *xyz1, const floa
     if (b < 0 || b > MAX_BATCH || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !match || !grad1 || !grad2 || !aligned4(len1) || !aligned4(len2)) return RF_EINVAL;
+    if (!xyz1 || !xyz2 || !match || !grad1 || !grad2 || !rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     RF_ZERO(grad1, sizeof(float) * 3 * (size_t)b * n, s);
     RF_ZERO(grad2, sizeof(float) * 3 * (size_t)b * m, s);
@@ -2884,7 +2882,7 @@ EmdLayout emd_layout(int b, int n, int m, int mode = RF_EMD_AUTO) {
     while (lsplit < 64 && base * lsplit < 4096 && L.mpad / (lsplit * 2) >= 2 * MG_TL) lsplit *= 2;
     // (the spans cover the class-sorted records of the cost-only form: up to mpad + one padding record per class)
     E.rstride = (size_t)L.mpad + 64;
-    E.lspan = round_up_i(rf::ceil_div(L.mpad + 2 * EF_NCLS, lsplit), MG_TL);
+    E.lspan = rf::round_up(rf::ceil_div(L.mpad + 2 * EF_NCLS, lsplit), MG_TL);
     E.lsplit = rf::ceil_div(L.mpad + 2 * EF_NCLS, E.lspan);
     E.off_rec = L.total;
     E.off_partial = E.off_rec + (size_t)b * E.rstride * EF_REC + 64;
@@ -3013,7 +3011,7 @@ int rf_earth_mover_lengths(int b, int n, int m, const float *xyz1, const float *
     if ((grad1 == nullptr) != (grad2 == nullptr)) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
-    if (!xyz1 || !xyz2 || !cost || !workspace || !rf::aligned16(workspace) || !aligned4(len1) || !aligned4(len2))
+    if (!xyz1 || !xyz2 || !cost || !workspace || !rf::aligned16(workspace) || !rf::aligned4(len1) || !rf::aligned4(len2))
         return RF_EINVAL;
     if (workspace_bytes < rf_earth_mover_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;

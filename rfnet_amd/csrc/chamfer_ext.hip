@@ -20,13 +20,30 @@
 // The arithmetic of the Chamfer itself is the sweeps' (bit-exact dist / idx); the glue arithmetic
 // follows the TensorFlow graph's expression order (unfused products and sums) and is held to the
 // glue tolerance (rel 1e-5) against a numpy restatement of the reference's glue in the tests.
+#include <type_traits>
+
 #include "common.hpp"
 #include "nn_dense.hpp"
 #include "nn_pruned.hpp"
 
 namespace {
 
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+// Sum of acc over a workgroup of TPB threads, valid in thread 0 only: the butterfly inside each wave, then thread 0 adds the
+// waves' sums in ascending order -- a fixed order, so the float result is deterministic.
+template <int TPB>
+__device__ __forceinline__ float block_sum(float acc) {
+    __shared__ float part[TPB / 64];
+    acc = rf::wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    float t = 0.f;
+    if (threadIdx.x == 0) {
+        t = part[0];
+#pragma unroll
+        for (int w = 1; w < TPB / 64; w++) t += part[w];
+    }
+    return t;
+}
 
 // loss[bi][dir] = mean_j sqrt(dist_dir[bi][j]): one workgroup per (sample, direction), fixed
 // summation order (strided per-thread partials, DPP inside the wave, waves in order): deterministic.
@@ -44,7 +61,6 @@ __global__ __launch_bounds__(LR_TPB) void chamfer_loss_reduce_kernel(int n, int 
                                                                      float *__restrict__ pad_d1, int *__restrict__ pad_i1,
                                                                      float *__restrict__ pad_d2,
                                                                      int *__restrict__ pad_i2) {
-    __shared__ float part[LR_TPB / 64];
     const int bi = blockIdx.x >> 1, dir = blockIdx.x & 1;
     const float *__restrict__ d = dir ? dist2 : dist1;
     int cnt = dir ? m : n;
@@ -75,28 +91,35 @@ __global__ __launch_bounds__(LR_TPB) void chamfer_loss_reduce_kernel(int n, int 
         a0 += sqrtf(v0); a1 += sqrtf(v1); a2 += sqrtf(v2); a3 += sqrtf(v3);
     }
     for (; j < cnt; j += LR_TPB) a0 += sqrtf(d[j]);
-    float acc = (a0 + a1) + (a2 + a3);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = part[0];
-#pragma unroll
-        for (int w = 1; w < LR_TPB / 64; w++) t += part[w];
-        loss[bi * 2 + dir] = t / (float)cnt;
-    }
+    const float t = block_sum<LR_TPB>((a0 + a1) + (a2 + a3));
+    if (threadIdx.x == 0) loss[bi * 2 + dir] = t / (float)cnt;
 }
 
 // merge_layer's tail (vv_recon.py:135-138): g = raw[idx2]; diff = g - q;
 // ratio = exp(-sum(diff^2) / (1e-8 + dec^2)); out = q + ratio * diff.  TensorFlow's expression
 // order, nothing contracted (the file is compiled with -ffp-contract=off).
+// RAGGED (rf_merge_layer_lengths / rf_merge_layer_grad_lengths, here and in the backward below): sample bi has len_raw[bi] raw
+// points and len_new[bi] new points (device counts, clamped into [1, n] / [1, m] here; NULL = all).  Valid new rows get the
+// dense arithmetic; a padded new row gets idx2 = 0 and refined = +0.0 whatever the sweep left in its slot ((0, -1) on the
+// dense route, nothing on the culled one), so that gathers downstream need no special case.  Only that form writes idx2.
+template <bool RAGGED>
 __global__ void merge_pull_kernel(int n, int m, long total, const float *__restrict__ raw,
-                                  const float *__restrict__ newpts, const int *__restrict__ idx2,
-                                  const float *__restrict__ decfactor, float *__restrict__ out) {
+                                  const float *__restrict__ newpts,
+                                  std::conditional_t<RAGGED, int, const int> *__restrict__ idx2,
+                                  const float *__restrict__ decfactor, float *__restrict__ out,
+                                  const int *__restrict__ len_new) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= total) return;
     const long bi = e / m;
+    if constexpr (RAGGED) {
+        if ((int)(e - bi * m) >= rf::ragged_count(len_new, (int)bi, m)) {
+            idx2[e] = 0;
+            out[e * 3 + 0] = 0.f;
+            out[e * 3 + 1] = 0.f;
+            out[e * 3 + 2] = 0.f;
+            return;
+        }
+    }
     const float dec = decfactor[0];
     const float c = 1e-8f + dec * dec;
     const float *g = raw + (bi * n + idx2[e]) * 3;
@@ -114,7 +137,12 @@ __global__ void merge_pull_kernel(int n, int m, long total, const float *__restr
 //   grad_newpts = go - g_diff;   grad_raw[idx2] += g_diff  (optional, atomics on a zero-filled buffer)
 //   grad_dec[bi] = sum_points g_ratio * ratio * s / c^2 * 2 dec     (fixed order: deterministic)
 // idx2 carries no gradient (NnDistance's index outputs have none, tf_nndistance.py:26-32).
+// RAGGED: the same strided loop and the same reduction over the sample's len_new valid rows (the order the dense form takes on
+// that slice alone); padded rows get grad_newpts = 0 without their grad_out or idx2 being read.  A stored index is held inside
+// [0, len_raw) before it addresses raw / grad_raw (the forward never leaves one outside), so grad_raw stays 0 behind the count
+// whatever the caller kept in idx2.
 constexpr int MG_TPB = 1024;
+template <bool RAGGED>
 __global__ __launch_bounds__(MG_TPB) void merge_pull_grad_kernel(int n, int m, const float *__restrict__ raw,
                                                                  const float *__restrict__ newpts,
                                                                  const int *__restrict__ idx2,
@@ -122,103 +150,22 @@ __global__ __launch_bounds__(MG_TPB) void merge_pull_grad_kernel(int n, int m, c
                                                                  const float *__restrict__ grad_out,
                                                                  float *__restrict__ grad_newpts,
                                                                  float *__restrict__ grad_dec,
-                                                                 float *__restrict__ grad_raw) {
-    __shared__ float part[MG_TPB / 64];
+                                                                 float *__restrict__ grad_raw,
+                                                                 const int *__restrict__ len_raw,
+                                                                 const int *__restrict__ len_new) {
     const int bi = blockIdx.x;
-    const float dec = decfactor[0];
-    const float c = 1e-8f + dec * dec;
-    float acc = 0.f;
-    for (int j = threadIdx.x; j < m; j += MG_TPB) {
-        const size_t e = (size_t)bi * m + j;
-        const int k = idx2[e];
-        const float *g = raw + ((size_t)bi * n + k) * 3;
-        const float qx = newpts[e * 3 + 0], qy = newpts[e * 3 + 1], qz = newpts[e * 3 + 2];
-        const float dx = g[0] - qx, dy = g[1] - qy, dz = g[2] - qz;
-        const float s = (dx * dx + dy * dy) + dz * dz;
-        const float ratio = expf(-s / c);
-        const float gx = grad_out[e * 3 + 0], gy = grad_out[e * 3 + 1], gz = grad_out[e * 3 + 2];
-        const float g_ratio = (gx * dx + gy * dy) + gz * dz;
-        const float k2 = 2.f * ratio * g_ratio / c;
-        const float fx = ratio * gx - k2 * dx, fy = ratio * gy - k2 * dy, fz = ratio * gz - k2 * dz;
-        grad_newpts[e * 3 + 0] = gx - fx;
-        grad_newpts[e * 3 + 1] = gy - fy;
-        grad_newpts[e * 3 + 2] = gz - fz;
-        if (grad_raw) {
-            float *gr = grad_raw + ((size_t)bi * n + k) * 3;
-            atomicAdd(gr + 0, fx);
-            atomicAdd(gr + 1, fy);
-            atomicAdd(gr + 2, fz);
-        }
-        acc += g_ratio * ratio * s / (c * c);
+    int nl = n, ml = m;
+    if constexpr (RAGGED) {
+        nl = rf::ragged_count(len_raw, bi, n);
+        ml = rf::ragged_count(len_new, bi, m);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = part[0];
-#pragma unroll
-        for (int w = 1; w < MG_TPB / 64; w++) t += part[w];
-        grad_dec[bi] = t * (2.f * dec);
-    }
-}
-
-// The tail and its backward over a ragged batch (rf_merge_layer_lengths / rf_merge_layer_grad_lengths): sample bi has
-// len_raw[bi] raw points and len_new[bi] new points (device counts, clamped into [1, n] / [1, m] here; NULL = all).  Valid new
-// rows get merge_pull_kernel's arithmetic, expression for expression; a padded new row gets idx2 = 0 and refined = +0.0
-// whatever the sweep left in its slot ((0, -1) on the dense route, nothing on the culled one), so that gathers downstream
-// need no special case.
-
-__global__ void merge_pull_len_kernel(int n, int m, long total, const float *__restrict__ raw,
-                                      const float *__restrict__ newpts, int *__restrict__ idx2,
-                                      const float *__restrict__ decfactor, float *__restrict__ out,
-                                      const int *__restrict__ len_new) {
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= total) return;
-    const long bi = e / m;
-    if ((int)(e - bi * m) >= rf::ragged_count(len_new, (int)bi, m)) {
-        idx2[e] = 0;
-        out[e * 3 + 0] = 0.f;
-        out[e * 3 + 1] = 0.f;
-        out[e * 3 + 2] = 0.f;
-        return;
-    }
-    const float dec = decfactor[0];
-    const float c = 1e-8f + dec * dec;
-    const float *g = raw + (bi * n + idx2[e]) * 3;
-    const float qx = newpts[e * 3 + 0], qy = newpts[e * 3 + 1], qz = newpts[e * 3 + 2];
-    const float dx = g[0] - qx, dy = g[1] - qy, dz = g[2] - qz;
-    const float s = (dx * dx + dy * dy) + dz * dz;
-    const float ratio = expf(-s / c);
-    out[e * 3 + 0] = qx + ratio * dx;
-    out[e * 3 + 1] = qy + ratio * dy;
-    out[e * 3 + 2] = qz + ratio * dz;
-}
-
-// One sample per workgroup, as merge_pull_grad_kernel: the same strided loop and the same reduction over the sample's
-// len_new valid rows (the order the dense kernel takes on that slice alone); padded rows get grad_newpts = 0 without their
-// grad_out or idx2 being read.  A stored index is held inside [0, len_raw) before it addresses raw / grad_raw (the forward
-// never leaves one outside), so grad_raw stays 0 behind the count whatever the caller kept in idx2.
-__global__ __launch_bounds__(MG_TPB) void merge_pull_grad_len_kernel(int n, int m, const float *__restrict__ raw,
-                                                                     const float *__restrict__ newpts,
-                                                                     const int *__restrict__ idx2,
-                                                                     const float *__restrict__ decfactor,
-                                                                     const float *__restrict__ grad_out,
-                                                                     float *__restrict__ grad_newpts,
-                                                                     float *__restrict__ grad_dec,
-                                                                     float *__restrict__ grad_raw,
-                                                                     const int *__restrict__ len_raw,
-                                                                     const int *__restrict__ len_new) {
-    __shared__ float part[MG_TPB / 64];
-    const int bi = blockIdx.x;
-    const int nl = rf::ragged_count(len_raw, bi, n), ml = rf::ragged_count(len_new, bi, m);
     const float dec = decfactor[0];
     const float c = 1e-8f + dec * dec;
     float acc = 0.f;
     for (int j = threadIdx.x; j < ml; j += MG_TPB) {
         const size_t e = (size_t)bi * m + j;
         int k = idx2[e];
-        k = k < 0 ? 0 : (k >= nl ? nl - 1 : k);
+        if constexpr (RAGGED) k = k < 0 ? 0 : (k >= nl ? nl - 1 : k);
         const float *g = raw + ((size_t)bi * n + k) * 3;
         const float qx = newpts[e * 3 + 0], qy = newpts[e * 3 + 1], qz = newpts[e * 3 + 2];
         const float dx = g[0] - qx, dy = g[1] - qy, dz = g[2] - qz;
@@ -239,17 +186,11 @@ __global__ __launch_bounds__(MG_TPB) void merge_pull_grad_len_kernel(int n, int 
         }
         acc += g_ratio * ratio * s / (c * c);
     }
-    for (int j = ml * 3 + threadIdx.x; j < m * 3; j += MG_TPB) grad_newpts[(size_t)bi * m * 3 + j] = 0.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = part[0];
-#pragma unroll
-        for (int w = 1; w < MG_TPB / 64; w++) t += part[w];
-        grad_dec[bi] = t * (2.f * dec);
+    if constexpr (RAGGED) {
+        for (int j = ml * 3 + threadIdx.x; j < m * 3; j += MG_TPB) grad_newpts[(size_t)bi * m * 3 + j] = 0.f;
     }
+    const float t = block_sum<MG_TPB>(acc);
+    if (threadIdx.x == 0) grad_dec[bi] = t * (2.f * dec);
 }
 
 int dirs_of(int want1, int want2) { return (want1 ? 1 : 0) | (want2 ? 2 : 0); }
@@ -295,6 +236,27 @@ int run_forward(int b, int n, int m, const float *xyz1, const float *xyz2, const
 }
 
 bool bad_sizes(int b, int n, int m) { return b < 0 || n < 0 || m < 0; }
+
+// merge_layer's workspace starts with the b * m distances of direction 2 (they are not an output); the sweep's own follows
+size_t merge_dist_bytes(int b, int m) { return rf::align256((size_t)b * m * sizeof(float)); }
+
+// the tail of both merge_layer entries, once the sweep has left idx2
+template <bool RAGGED>
+int merge_pull(const char *name, int b, int n, int m, const float *rawpts, const float *newpts, int *idx2,
+               const float *decfactor_dev, float *refined, const int *len_new, hipStream_t s) {
+    const long total = (long)b * m;
+    RF_LAUNCH(name, merge_pull_kernel<RAGGED>, dim3(rf::ceil_div(total, 256)), dim3(256), 0, s, n, m, total, rawpts, newpts,
+              idx2, decfactor_dev, refined, len_new);
+    return RF_OK;
+}
+
+// what both merge_layer gradients zero before their kernel: grad_raw (the kernel adds into it), and grad_dec where there is
+// no pair to pull (`empty`: the caller returns then)
+int merge_grad_zero(int b, int n, bool empty, float *grad_dec, float *grad_raw, hipStream_t s) {
+    if (grad_raw && n) RF_ZERO(grad_raw, sizeof(float) * 3 * (size_t)b * n, s);
+    if (empty) RF_ZERO(grad_dec, sizeof(float) * (size_t)b, s);
+    return RF_OK;
+}
 
 }  // namespace
 
@@ -416,7 +378,7 @@ int rf_chamfer_loss_lengths(int b, int n, int m, const float *xyz1, const float 
     if (n == 0 || m == 0 || !xyz1 || !xyz2 || !loss || !workspace) return RF_EINVAL;
     const int dirs = dirs_of(dist1 && idx1, dist2 && idx2);
     if (!dirs) return RF_EINVAL;
-    if (!rf::aligned16(workspace) || !aligned4(len1) || !aligned4(len2)) return RF_EINVAL;
+    if (!rf::aligned16(workspace) || !rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
     if (workspace_bytes < rfd::ragged_workspace_bytes(b, n, m, RF_NN_AUTO, dirs)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float *d1 = (dirs & 1) ? dist1 : nullptr, *d2 = (dirs & 2) ? dist2 : nullptr;
@@ -439,7 +401,7 @@ int rf_chamfer_loss_grad_lengths(int b, int n, int m, const float *xyz1, const f
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0 || !grad_loss) return RF_EINVAL;
-    if (!aligned4(len1) || !aligned4(len2)) return RF_EINVAL;
+    if (!rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
     const rfd::GradSource g{nullptr, nullptr, dist1, dist2, grad_loss};
     // both count arrays NULL: the kernel of rf_chamfer_loss_grad, same results
     return rfd::nn_distance_grad(b, n, m, xyz1, xyz2, g, dist1 ? idx1 : nullptr, dist2 ? idx2 : nullptr, grad_xyz1,
@@ -449,7 +411,7 @@ int rf_chamfer_loss_grad_lengths(int b, int n, int m, const float *xyz1, const f
 // ------------------------------------------------------------------ merge_layer ------------
 size_t rf_merge_layer_workspace_bytes(int b, int n, int m, int have_sorted_raw) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
-    return rf::align256((size_t)b * m * sizeof(float)) + plan_forward(b, n, m, 2, have_sorted_raw != 0, false).bytes;
+    return merge_dist_bytes(b, m) + plan_forward(b, n, m, 2, have_sorted_raw != 0, false).bytes;
 }
 
 int rf_merge_layer(int b, int n, int m, const float *rawpts, const float *newpts, const void *sorted_raw,
@@ -458,17 +420,14 @@ int rf_merge_layer(int b, int n, int m, const float *rawpts, const float *newpts
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0 || m == 0) return RF_OK;
     if (n == 0 || !rawpts || !newpts || !decfactor_dev || !refined || !idx2 || !workspace) return RF_EINVAL;
-    const size_t dbytes = rf::align256((size_t)b * m * sizeof(float));
+    const size_t dbytes = merge_dist_bytes(b, m);
     if (workspace_bytes < dbytes) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float *dist2 = (float *)workspace;  // the distances themselves are not an output of merge_layer
     if (int e = run_forward(b, n, m, rawpts, newpts, sorted_raw, nullptr, nullptr, nullptr, dist2, idx2, 2,
                             (char *)workspace + dbytes, workspace_bytes - dbytes, s))
         return e;
-    const long total = (long)b * m;
-    RF_LAUNCH("merge_pull", merge_pull_kernel, dim3(rf::ceil_div(total, 256)), dim3(256), 0, s, n, m, total, rawpts,
-              newpts, (const int *)idx2, decfactor_dev, refined);
-    return RF_OK;
+    return merge_pull<false>("merge_pull", b, n, m, rawpts, newpts, idx2, decfactor_dev, refined, nullptr, s);
 }
 
 int rf_merge_layer_grad(int b, int n, int m, const float *rawpts, const float *newpts, const float *decfactor_dev,
@@ -478,21 +437,19 @@ int rf_merge_layer_grad(int b, int n, int m, const float *rawpts, const float *n
     if (b == 0) return RF_OK;
     if (!grad_dec) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (grad_raw && n) RF_ZERO(grad_raw, sizeof(float) * 3 * (size_t)b * n, s);
-    if (m == 0 || n == 0) {
-        RF_ZERO(grad_dec, sizeof(float) * (size_t)b, s);
-        return RF_OK;
-    }
+    const bool empty = m == 0 || n == 0;
+    if (int e = merge_grad_zero(b, n, empty, grad_dec, grad_raw, s)) return e;
+    if (empty) return RF_OK;
     if (!rawpts || !newpts || !decfactor_dev || !idx2 || !grad_refined || !grad_newpts) return RF_EINVAL;
-    RF_LAUNCH("merge_pull_grad", merge_pull_grad_kernel, dim3(b), dim3(MG_TPB), 0, s, n, m, rawpts, newpts, idx2,
-              decfactor_dev, grad_refined, grad_newpts, grad_dec, grad_raw);
+    RF_LAUNCH("merge_pull_grad", merge_pull_grad_kernel<false>, dim3(b), dim3(MG_TPB), 0, s, n, m, rawpts, newpts, idx2,
+              decfactor_dev, grad_refined, grad_newpts, grad_dec, grad_raw, nullptr, nullptr);
     return RF_OK;
 }
 
 // ------------------------------------------------------------------ merge_layer, ragged ----
 size_t rf_merge_layer_lengths_workspace_bytes(int b, int n, int m) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
-    return rf::align256((size_t)b * m * sizeof(float)) + rfd::ragged_workspace_bytes(b, n, m, RF_NN_AUTO, 2);
+    return merge_dist_bytes(b, m) + rfd::ragged_workspace_bytes(b, n, m, RF_NN_AUTO, 2);
 }
 
 int rf_merge_layer_lengths(int b, int n, int m, const float *rawpts, const float *newpts, const int *len_raw,
@@ -501,8 +458,8 @@ int rf_merge_layer_lengths(int b, int n, int m, const float *rawpts, const float
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0 || m == 0) return RF_OK;
     if (n == 0 || !rawpts || !newpts || !decfactor_dev || !refined || !idx2 || !workspace) return RF_EINVAL;
-    if (!rf::aligned16(workspace) || !aligned4(len_raw) || !aligned4(len_new)) return RF_EINVAL;
-    const size_t dbytes = rf::align256((size_t)b * m * sizeof(float));
+    if (!rf::aligned16(workspace) || !rf::aligned4(len_raw) || !rf::aligned4(len_new)) return RF_EINVAL;
+    const size_t dbytes = merge_dist_bytes(b, m);
     if (workspace_bytes < rf_merge_layer_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float *dist2 = (float *)workspace;  // the distances themselves are not an output of merge_layer
@@ -510,10 +467,7 @@ int rf_merge_layer_lengths(int b, int n, int m, const float *rawpts, const float
     if (int e = rfd::ragged_nn_distance(b, n, m, rawpts, newpts, len_raw, len_new, nullptr, nullptr, dist2, idx2,
                                         (char *)workspace + dbytes, workspace_bytes - dbytes, s, RF_NN_AUTO, 2, false))
         return e;
-    const long total = (long)b * m;
-    RF_LAUNCH("merge_pull_len", merge_pull_len_kernel, dim3(rf::ceil_div(total, 256)), dim3(256), 0, s, n, m, total,
-              rawpts, newpts, idx2, decfactor_dev, refined, len_new);
-    return RF_OK;
+    return merge_pull<true>("merge_pull_len", b, n, m, rawpts, newpts, idx2, decfactor_dev, refined, len_new, s);
 }
 
 int rf_merge_layer_grad_lengths(int b, int n, int m, const float *rawpts, const float *newpts, const int *len_raw,
@@ -522,16 +476,13 @@ int rf_merge_layer_grad_lengths(int b, int n, int m, const float *rawpts, const 
                                 rf_stream_t stream) {
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (!grad_dec || !aligned4(len_raw) || !aligned4(len_new)) return RF_EINVAL;
+    if (!grad_dec || !rf::aligned4(len_raw) || !rf::aligned4(len_new)) return RF_EINVAL;
     const bool empty = m == 0 || n == 0;
     if (!empty && (!rawpts || !newpts || !decfactor_dev || !idx2 || !grad_refined || !grad_newpts)) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    if (grad_raw && n) RF_ZERO(grad_raw, sizeof(float) * 3 * (size_t)b * n, s);
-    if (empty) {
-        RF_ZERO(grad_dec, sizeof(float) * (size_t)b, s);
-        return RF_OK;
-    }
-    RF_LAUNCH("merge_pull_grad_len", merge_pull_grad_len_kernel, dim3(b), dim3(MG_TPB), 0, s, n, m, rawpts, newpts, idx2,
+    if (int e = merge_grad_zero(b, n, empty, grad_dec, grad_raw, s)) return e;
+    if (empty) return RF_OK;
+    RF_LAUNCH("merge_pull_grad_len", merge_pull_grad_kernel<true>, dim3(b), dim3(MG_TPB), 0, s, n, m, rawpts, newpts, idx2,
               decfactor_dev, grad_refined, grad_newpts, grad_dec, grad_raw, len_raw, len_new);
     return RF_OK;
 }

@@ -21,6 +21,8 @@ __device__ __forceinline__ float d2_fma(float dx, float dy, float dz) {
 }
 
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+// v rounded up to a multiple of q, in long arithmetic (callers pass int and long counts; the result fits an int)
+inline int round_up(long v, int q) { return (int)((v + q - 1) / q * q); }
 
 // ---- profiling hook (rf_profile_enable / rf_profile_collect) --------------------------
 struct ProfScope {

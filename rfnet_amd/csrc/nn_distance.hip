@@ -64,9 +64,13 @@ struct Sweep {
 
 // Re-pack both clouds in ONE launch: blocks [0, nblk_own) pack the own set (padded with -inf),
 // the rest the candidate set (padded with +inf).
+// LEN (ragged batches, rf_nn_distance_lengths): sample bi uses the first rf::ragged_count(len, bi, n) points of its row, so
+// each sample is padded from its OWN length and every point beyond it is a pad of the sweep, as the alignment padding is.
+template <bool LEN>
 __global__ void pack_kernel(int b, int n_own, int n_own_pad, const float *__restrict__ src_own,
-                            float *__restrict__ dst_own, int nblk_own, int n_cand, int n_cand_pad,
-                            const float *__restrict__ src_cand, float *__restrict__ dst_cand) {
+                            const int *__restrict__ len_own, float *__restrict__ dst_own, int nblk_own, int n_cand,
+                            int n_cand_pad, const float *__restrict__ src_cand, const int *__restrict__ len_cand,
+                            float *__restrict__ dst_cand) {
     const bool is_cand = (int)blockIdx.x >= nblk_own;
     const int n = is_cand ? n_cand : n_own, n_pad = is_cand ? n_cand_pad : n_own_pad;
     const float *__restrict__ src = is_cand ? src_cand : src_own;
@@ -77,35 +81,10 @@ __global__ void pack_kernel(int b, int n_own, int n_own_pad, const float *__rest
     if (g >= total) return;
     long bi = g / n_pad;
     int j = (int)(g - bi * n_pad);
+    int cnt = n;
+    if constexpr (LEN) cnt = rf::ragged_count(is_cand ? len_cand : len_own, (int)bi, n);
     float x = padval, y = 0.f, z = 0.f;
-    if (j < n) {
-        const float *p = src + (bi * n + j) * 3;
-        x = p[0]; y = p[1]; z = p[2];
-    }
-    dst[g * 3 + 0] = x;
-    dst[g * 3 + 1] = y;
-    dst[g * 3 + 2] = z;
-}
-
-// Ragged batches (rf_nn_distance_lengths): sample bi uses the first rf::ragged_count(len, bi, n) points of its row.
-// pack_kernel for ragged batches: each sample padded from its OWN length (own -inf, candidates +inf,
-// as the alignment padding above), so every point beyond a sample's length is a pad of the sweep.
-__global__ void pack_len_kernel(int b, int n_own, int n_own_pad, const float *__restrict__ src_own,
-                                const int *__restrict__ len_own, float *__restrict__ dst_own, int nblk_own,
-                                int n_cand, int n_cand_pad, const float *__restrict__ src_cand,
-                                const int *__restrict__ len_cand, float *__restrict__ dst_cand) {
-    const bool is_cand = (int)blockIdx.x >= nblk_own;
-    const int n = is_cand ? n_cand : n_own, n_pad = is_cand ? n_cand_pad : n_own_pad;
-    const float *__restrict__ src = is_cand ? src_cand : src_own;
-    float *__restrict__ dst = is_cand ? dst_cand : dst_own;
-    const float padval = is_cand ? INFINITY : -INFINITY;
-    long g = (long)(blockIdx.x - (is_cand ? nblk_own : 0)) * blockDim.x + threadIdx.x;
-    long total = (long)b * n_pad;
-    if (g >= total) return;
-    long bi = g / n_pad;
-    int j = (int)(g - bi * n_pad);
-    float x = padval, y = 0.f, z = 0.f;
-    if (j < rf::ragged_count(is_cand ? len_cand : len_own, (int)bi, n)) {
+    if (j < cnt) {
         const float *p = src + (bi * n + j) * 3;
         x = p[0]; y = p[1]; z = p[2];
     }
@@ -689,8 +668,6 @@ struct Plan {
     size_t off_own, off_cand, off_rowd, off_rowi, off_col, off_coll, bytes;
 };
 
-int round_up(long v, int q) { return (int)((v + q - 1) / q * q); }
-
 // dirs: bit 0 = direction 1 (nearest neighbour of every xyz1 point in xyz2 -> dist1/idx1), bit 1 =
 // direction 2.  With one direction the wanted set is the "own" side whatever its size (the own side
 // is the per-point minimum over all candidates) and the column half of the sweep is compiled out.
@@ -699,8 +676,8 @@ Plan make_plan(int b, int n, int m, int dirs = 3) {
     p.swap = dirs == 3 ? m > n : dirs == 2;
     p.no = p.swap ? m : n;
     p.nc = p.swap ? n : m;
-    p.no_pad = round_up(p.no, PADQ);
-    p.nc_pad = round_up(p.nc, PADQ);
+    p.no_pad = rf::round_up(p.no, PADQ);
+    p.nc_pad = rf::round_up(p.nc, PADQ);
     p.oblocks = rf::ceil_div(p.no, 64 * RR);
     // Split the candidate range so that (measured in round 1 with an environment-knob A/B tool, one device; the knobs are compile-time now: tools/build_variant.py + tools/ab_variants.py):
     //   * at least one residency round exists: 4096 waves (118 VGPRs -> 4 per SIMD x 1024 SIMDs);
@@ -712,7 +689,7 @@ Plan make_plan(int b, int n, int m, int dirs = 3) {
     if (want < rf::ceil_div(p.nc, 1024)) want = rf::ceil_div(p.nc, 1024);
     int maxs = p.nc / 128 > 0 ? p.nc / 128 : 1;
     int s = want < 1 ? 1 : (want > maxs ? maxs : want);
-    p.span = round_up(rf::ceil_div(p.nc, s), CG);
+    p.span = rf::round_up(rf::ceil_div(p.nc, s), CG);
     p.nsplit = rf::ceil_div(p.nc, p.span);
     p.wgm = (p.nsplit % (TPB / 64) == 0) ? 1 : 0;
     p.rslots = p.wgm ? p.nsplit / (TPB / 64) : p.nsplit;
@@ -787,14 +764,15 @@ int dense_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2,
         cand_p = const_cast<float *>(cand_src);
         p.no_pad = p.no;
         p.nc_pad = p.nc;
-    } else if (ragged) {
-        const int nb_own = rf::ceil_div((long)b * p.no_pad, 256), nb_cand = rf::ceil_div((long)b * p.nc_pad, 256);
-        RF_LAUNCH("nn_pack_len", pack_len_kernel, dim3(nb_own + nb_cand), dim3(256), 0, s, b, p.no, p.no_pad, own_src,
-                  own_len, own_p, nb_own, p.nc, p.nc_pad, cand_src, cand_len, cand_p);
     } else {
         const int nb_own = rf::ceil_div((long)b * p.no_pad, 256), nb_cand = rf::ceil_div((long)b * p.nc_pad, 256);
-        RF_LAUNCH("nn_pack", pack_kernel, dim3(nb_own + nb_cand), dim3(256), 0, s, b, p.no, p.no_pad, own_src,
-                  own_p, nb_own, p.nc, p.nc_pad, cand_src, cand_p);
+        if (ragged) {
+            RF_LAUNCH("nn_pack_len", pack_kernel<true>, dim3(nb_own + nb_cand), dim3(256), 0, s, b, p.no, p.no_pad, own_src,
+                      own_len, own_p, nb_own, p.nc, p.nc_pad, cand_src, cand_len, cand_p);
+        } else {
+            RF_LAUNCH("nn_pack", pack_kernel<false>, dim3(nb_own + nb_cand), dim3(256), 0, s, b, p.no, p.no_pad, own_src,
+                      nullptr, own_p, nb_own, p.nc, p.nc_pad, cand_src, nullptr, cand_p);
+        }
     }
 
     Sweep a;
@@ -918,7 +896,6 @@ int rf_nn_distance_mode(int b, int n, int m, const float *xyz1, const float *xyz
 
 // ------------------------------------------------------------------ ragged batches -------
 namespace {
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 }  // namespace
 
 size_t rf_nn_distance_lengths_workspace_bytes(int b, int n, int m, int mode) {
@@ -943,8 +920,8 @@ int rf_nn_distance_lengths(int b, int n, int m, const float *xyz1, const float *
     const int dirs = ((dist1 || idx1) ? 1 : 0) | ((dist2 || idx2) ? 2 : 0);
     if (!dirs || ((dirs & 1) && (!dist1 || !idx1)) || ((dirs & 2) && (!dist2 || !idx2))) return RF_EINVAL;
     if (!xyz1 || !xyz2 || !workspace) return RF_EINVAL;
-    if (!aligned4(xyz1) || !aligned4(xyz2) || !aligned4(len1) || !aligned4(len2) || !aligned4(dist1) ||
-        !aligned4(idx1) || !aligned4(dist2) || !aligned4(idx2) || !rf::aligned16(workspace))
+    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(dist1) ||
+        !rf::aligned4(idx1) || !rf::aligned4(dist2) || !rf::aligned4(idx2) || !rf::aligned16(workspace))
         return RF_EINVAL;
     if (rfd::resolve_mode(b, n, m, mode) == RF_NN_CULLED && !rfp::pruned_supported(b, n, m)) return RF_EINVAL;
     if (workspace_bytes < rfd::ragged_workspace_bytes(b, n, m, mode, dirs)) return RF_EWORKSPACE;
@@ -959,7 +936,7 @@ int rf_nn_distance_grad_lengths(int b, int n, int m, const float *xyz1, const fl
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;
     if (!xyz1 || !xyz2 || !grad_dist1 || !idx1 || !grad_dist2 || !idx2 || !grad_xyz1 || !grad_xyz2) return RF_EINVAL;
-    if (!aligned4(len1) || !aligned4(len2)) return RF_EINVAL;
+    if (!rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
     const rfd::GradSource g{grad_dist1, grad_dist2, nullptr, nullptr, nullptr};
     // (a NULL count array stands for "all": with both NULL this is rf_nn_distance_grad's kernel)
     return rfd::nn_distance_grad(b, n, m, xyz1, xyz2, g, idx1, idx2, grad_xyz1, grad_xyz2, (hipStream_t)stream, len1,

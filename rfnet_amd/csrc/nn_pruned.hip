@@ -2318,12 +2318,11 @@ __global__ __launch_bounds__(GS_TPB) void nnp_grad_sorted_kernel(GradSArgs a) {
     grad_tile(a, bi, logical - bi * wpc, (gs_acc_t *)acc_dyn, list, &nlist);
 }
 
-int round_up(long v, int q) { return (int)((v + q - 1) / q * q); }
 
 // workgroups sorting one cloud of n points, and the padded record count of a sorted set: a split
 // cloud carries one more superblock (half 0's segment is padded to a multiple of 64 on its own)
 int sort_split_of(int n) { return (RFP_SORT_SPLIT > 1 && n > RFP_SORT_SPLIT_ABOVE && n <= RPT * STPB) ? RFP_SORT_SPLIT : 1; }
-size_t npad_of(int n) { return (size_t)round_up(n, SB) + (size_t)(sort_split_of(n) - 1) * SB; }
+size_t npad_of(int n) { return (size_t)rf::round_up(n, SB) + (size_t)(sort_split_of(n) - 1) * SB; }
 
 }  // namespace
 

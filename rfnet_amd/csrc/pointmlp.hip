@@ -81,39 +81,8 @@ __device__ __forceinline__ float4 max4(float4 a, float4 b) {
     return make_float4(fmaxf(a.x, b.x), fmaxf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
 }
 
-__global__ __launch_bounds__(MP_TPB) void maxpool_stage1_kernel(int n, int c, int nstrips, const float *__restrict__ x,
-                                                                float *__restrict__ part) {
-    __shared__ float4 red[MP_TPB];
-    const int quads = c >> 2, ppi = MP_TPB / quads;
-    const int cq = threadIdx.x % quads, pl = threadIdx.x / quads;
-    const int bi = blockIdx.y, strip = blockIdx.x;
-    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    if (pl < ppi) {
-        const int n1 = min(n, (strip + 1) * MP_STRIP);
-        for (int j = strip * MP_STRIP + pl; j < n1; j += ppi)
-            m = max4(m, *(const float4 *)(x + ((size_t)bi * n + j) * c + cq * 4));
-    }
-    red[threadIdx.x] = m;
-    __syncthreads();
-    if (pl == 0) {
-        for (int k = 1; k < ppi; k++) m = max4(m, red[k * quads + cq]);
-        *(float4 *)(part + ((size_t)bi * nstrips + strip) * c + cq * 4) = m;
-    }
-}
-
-__global__ __launch_bounds__(MP_TPB) void maxpool_stage2_kernel(int c, int nstrips, const float *__restrict__ part,
-                                                                float *__restrict__ out) {
-    const int bi = blockIdx.x;
-    for (int ch = threadIdx.x; ch < c; ch += MP_TPB) {
-        float m = -INFINITY;
-        for (int s = 0; s < nstrips; s++) m = fmaxf(m, part[((size_t)bi * nstrips + s) * c + ch]);
-        out[(size_t)bi * c + ch] = m;
-    }
-}
-
-// The same with the position of the maximum (the lowest point index among ties; NaN entries are
-// skipped, as fmaxf skips them): what the backward of the pooling needs.  part holds the strip maxima,
-// parti (same shape) their point indices.
+// The position of the maximum (IDX; the lowest point index among ties; NaN entries are skipped, as fmaxf skips them) is what
+// the backward of the pooling needs.  part holds the strip maxima, parti (IDX, same shape) their point indices.
 __device__ __forceinline__ void amax1(float v, int j, float &m, int &mj) {
     if (v > m || (v == m && j < mj)) {
         m = v;
@@ -121,79 +90,25 @@ __device__ __forceinline__ void amax1(float v, int j, float &m, int &mj) {
     }
 }
 
-__global__ __launch_bounds__(MP_TPB) void maxpool_idx_stage1_kernel(int n, int c, int nstrips,
-                                                                    const float *__restrict__ x,
-                                                                    float *__restrict__ part, int *__restrict__ parti) {
-    __shared__ float4 red[MP_TPB];
-    __shared__ int4 redi[MP_TPB];
-    const int quads = c >> 2, ppi = MP_TPB / quads;
-    const int cq = threadIdx.x % quads, pl = threadIdx.x / quads;
-    const int bi = blockIdx.y, strip = blockIdx.x;
-    float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    const int jfirst = strip * MP_STRIP;
-    int4 mi = make_int4(jfirst, jfirst, jfirst, jfirst);
-    if (pl < ppi) {
-        const int n1 = min(n, (strip + 1) * MP_STRIP);
-        for (int j = jfirst + pl; j < n1; j += ppi) {
-            const float4 v = *(const float4 *)(x + ((size_t)bi * n + j) * c + cq * 4);
-            amax1(v.x, j, m.x, mi.x);
-            amax1(v.y, j, m.y, mi.y);
-            amax1(v.z, j, m.z, mi.z);
-            amax1(v.w, j, m.w, mi.w);
-        }
-    }
-    red[threadIdx.x] = m;
-    redi[threadIdx.x] = mi;
-    __syncthreads();
-    if (pl == 0) {
-        for (int k = 1; k < ppi; k++) {
-            const float4 v = red[k * quads + cq];
-            const int4 vi = redi[k * quads + cq];
-            amax1(v.x, vi.x, m.x, mi.x);
-            amax1(v.y, vi.y, m.y, mi.y);
-            amax1(v.z, vi.z, m.z, mi.z);
-            amax1(v.w, vi.w, m.w, mi.w);
-        }
-        const size_t o = ((size_t)bi * nstrips + strip) * c + cq * 4;
-        *(float4 *)(part + o) = m;
-        *(int4 *)(parti + o) = mi;
-    }
-}
-
-__global__ __launch_bounds__(MP_TPB) void maxpool_idx_stage2_kernel(int c, int nstrips, const float *__restrict__ part,
-                                                                    const int *__restrict__ parti,
-                                                                    float *__restrict__ out, int *__restrict__ idx) {
-    const int bi = blockIdx.x;
-    for (int ch = threadIdx.x; ch < c; ch += MP_TPB) {
-        float m = -INFINITY;
-        int mj = 0;
-        for (int s = 0; s < nstrips; s++) {
-            const size_t o = ((size_t)bi * nstrips + s) * c + ch;
-            amax1(part[o], parti[o], m, mj);  // strips ascend: a tie keeps the earlier strip's index
-        }
-        out[(size_t)bi * c + ch] = m;
-        idx[(size_t)bi * c + ch] = mj;
-    }
-}
-
-// ---- the same two poolings over a ragged batch (rf_maxpool_points_lengths / rf_maxpool_points_idx_lengths): sample bi pools
-// its rows [0, len[bi]) only (len: device counts, clamped into [1, n] here; NULL = all rows).  Grid and partial layout are the
-// dense kernels'; a workgroup whose strip starts at or behind the count leaves at once (the count is uniform over the
-// workgroup: all of it leaves, before the barrier, having read nothing), the strip that holds the count stops its point loop
-// there, and the fold walks the ceil(len / MP_STRIP) strips that were written -- the other partials are never read, so the
-// workspace needs no initial value.  Per sample this is the dense kernels' arithmetic on x[bi, :len[bi]]: same strips, same
-// point-lane order, same tie rule.
-
-template <bool IDX>
-__global__ __launch_bounds__(MP_TPB) void maxpool_len_stage1_kernel(int n, int c, int nstrips, const float *__restrict__ x,
-                                                                    const int *__restrict__ len, float *__restrict__ part,
-                                                                    int *__restrict__ parti) {
+// RAGGED (rf_maxpool_points_lengths / rf_maxpool_points_idx_lengths): sample bi pools its rows [0, len[bi]) only (len: device
+// counts, clamped into [1, n] here; NULL = all rows).  Grid and partial layout are the dense form's; a workgroup whose strip
+// starts at or behind the count leaves at once (the count is uniform over the workgroup: all of it leaves, before the barrier,
+// having read nothing), the strip that holds the count stops its point loop there, and the fold walks the
+// ceil(len / MP_STRIP) strips that were written -- the other partials are never read, so the workspace needs no initial
+// value.  Per sample this is the dense arithmetic on x[bi, :len[bi]]: same strips, same point-lane order, same tie rule.
+template <bool IDX, bool RAGGED>
+__global__ __launch_bounds__(MP_TPB) void maxpool_stage1_kernel(int n, int c, int nstrips, const float *__restrict__ x,
+                                                                const int *__restrict__ len, float *__restrict__ part,
+                                                                int *__restrict__ parti) {
     __shared__ float4 red[MP_TPB];
     __shared__ int4 redi[IDX ? MP_TPB : 1];
     const int bi = blockIdx.y, strip = blockIdx.x;
-    const int cnt = rf::ragged_count(len, bi, n);
     const int jfirst = strip * MP_STRIP;
-    if (jfirst >= cnt) return;
+    int cnt = n;
+    if constexpr (RAGGED) {
+        cnt = rf::ragged_count(len, bi, n);
+        if (jfirst >= cnt) return;
+    }
     const int quads = c >> 2, ppi = MP_TPB / quads;
     const int cq = threadIdx.x % quads, pl = threadIdx.x / quads;
     float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
@@ -234,20 +149,21 @@ __global__ __launch_bounds__(MP_TPB) void maxpool_len_stage1_kernel(int n, int c
     }
 }
 
-template <bool IDX>
-__global__ __launch_bounds__(MP_TPB) void maxpool_len_stage2_kernel(int n, int c, int nstrips, const int *__restrict__ len,
-                                                                    const float *__restrict__ part,
-                                                                    const int *__restrict__ parti, float *__restrict__ out,
-                                                                    int *__restrict__ idx) {
+template <bool IDX, bool RAGGED>
+__global__ __launch_bounds__(MP_TPB) void maxpool_stage2_kernel(int n, int c, int nstrips, const int *__restrict__ len,
+                                                                const float *__restrict__ part,
+                                                                const int *__restrict__ parti, float *__restrict__ out,
+                                                                int *__restrict__ idx) {
     const int bi = blockIdx.x;
-    const int written = (rf::ragged_count(len, bi, n) + MP_STRIP - 1) / MP_STRIP;  // strips stage 1 wrote for this sample
+    int written = nstrips;  // strips stage 1 wrote for this sample
+    if constexpr (RAGGED) written = (rf::ragged_count(len, bi, n) + MP_STRIP - 1) / MP_STRIP;
     for (int ch = threadIdx.x; ch < c; ch += MP_TPB) {
         float m = -INFINITY;
         int mj = 0;
         for (int s = 0; s < written; s++) {
             const size_t o = ((size_t)bi * nstrips + s) * c + ch;
             if constexpr (IDX) {
-                amax1(part[o], parti[o], m, mj);
+                amax1(part[o], parti[o], m, mj);  // strips ascend: a tie keeps the earlier strip's index
             } else {
                 m = fmaxf(m, part[o]);
             }
@@ -335,6 +251,32 @@ __global__ __launch_bounds__(MP_TPB) void colsum_fold_kernel(int c, int nstrips,
     }
 }
 
+// The four rf_maxpool_points* entries: validation, workspace split and the two launches.  len (RAGGED) and idx (IDX) are NULL
+// where the entry has no such argument; a NULL len of a ragged entry means all rows.  An IDX workspace is twice the plain one:
+// the strip maxima, then their point indices.
+template <bool IDX, bool RAGGED>
+int maxpool_run(int b, int n, int c, const float *x, const int *len, float *out, int *idx, void *workspace,
+                size_t workspace_bytes, rf_stream_t stream, const char *name, const char *fold_name) {
+    if (b < 0 || n < 0 || c < 0) return RF_EINVAL;
+    if ((size_t)b * c == 0) return RF_OK;
+    if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
+    if (!x || !out || (IDX && !idx) || !workspace) return RF_EINVAL;
+    // x, workspace: float4 rows
+    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out) || !rf::aligned4(idx) || !rf::aligned4(len))
+        return RF_EINVAL;
+    const int nstrips = rf::ceil_div(n, MP_STRIP);
+    const size_t floats = (size_t)b * nstrips * c;
+    if (workspace_bytes < (IDX ? 2 : 1) * floats * sizeof(float)) return RF_EWORKSPACE;
+    float *part = (float *)workspace;
+    int *parti = IDX ? (int *)(part + floats) : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    RF_LAUNCH(name, (maxpool_stage1_kernel<IDX, RAGGED>), dim3(nstrips, b), dim3(MP_TPB), 0, s, n, c, nstrips, x, len, part,
+              parti);
+    RF_LAUNCH(fold_name, (maxpool_stage2_kernel<IDX, RAGGED>), dim3(b), dim3(MP_TPB), 0, s, n, c, nstrips, len,
+              (const float *)part, (const int *)parti, out, idx);
+    return RF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -346,19 +288,8 @@ size_t rf_maxpool_points_workspace_bytes(int b, int n, int c) {
 
 int rf_maxpool_points(int b, int n, int c, const float *x, float *out, void *workspace, size_t workspace_bytes,
                       rf_stream_t stream) {
-    if (b < 0 || n < 0 || c < 0) return RF_EINVAL;
-    if ((size_t)b * c == 0) return RF_OK;
-    if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
-    if (!x || !out || !workspace) return RF_EINVAL;
-    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out)) return RF_EINVAL;  // x, workspace: float4 rows
-    if (workspace_bytes < rf_maxpool_points_workspace_bytes(b, n, c)) return RF_EWORKSPACE;
-    const int nstrips = rf::ceil_div(n, MP_STRIP);
-    hipStream_t s = (hipStream_t)stream;
-    RF_LAUNCH("maxpool_points", maxpool_stage1_kernel, dim3(nstrips, b), dim3(MP_TPB), 0, s, n, c, nstrips, x,
-              (float *)workspace);
-    RF_LAUNCH("maxpool_points_fold", maxpool_stage2_kernel, dim3(b), dim3(MP_TPB), 0, s, c, nstrips,
-              (const float *)workspace, out);
-    return RF_OK;
+    return maxpool_run<false, false>(b, n, c, x, nullptr, out, nullptr, workspace, workspace_bytes, stream, "maxpool_points",
+                                     "maxpool_points_fold");
 }
 
 size_t rf_maxpool_points_idx_workspace_bytes(int b, int n, int c) {
@@ -367,40 +298,16 @@ size_t rf_maxpool_points_idx_workspace_bytes(int b, int n, int c) {
 
 int rf_maxpool_points_idx(int b, int n, int c, const float *x, float *out, int *idx, void *workspace,
                           size_t workspace_bytes, rf_stream_t stream) {
-    if (b < 0 || n < 0 || c < 0) return RF_EINVAL;
-    if ((size_t)b * c == 0) return RF_OK;
-    if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
-    if (!x || !out || !idx || !workspace) return RF_EINVAL;
-    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out) || !rf::aligned4(idx)) return RF_EINVAL;
-    if (workspace_bytes < rf_maxpool_points_idx_workspace_bytes(b, n, c)) return RF_EWORKSPACE;
-    const int nstrips = rf::ceil_div(n, MP_STRIP);
-    float *part = (float *)workspace;
-    int *parti = (int *)(part + (size_t)b * nstrips * c);
-    hipStream_t s = (hipStream_t)stream;
-    RF_LAUNCH("maxpool_points_idx", maxpool_idx_stage1_kernel, dim3(nstrips, b), dim3(MP_TPB), 0, s, n, c, nstrips,
-              x, part, parti);
-    RF_LAUNCH("maxpool_points_idx_fold", maxpool_idx_stage2_kernel, dim3(b), dim3(MP_TPB), 0, s, c, nstrips,
-              (const float *)part, (const int *)parti, out, idx);
-    return RF_OK;
+    return maxpool_run<true, false>(b, n, c, x, nullptr, out, idx, workspace, workspace_bytes, stream, "maxpool_points_idx",
+                                    "maxpool_points_idx_fold");
 }
 
 size_t rf_maxpool_points_lengths_workspace_bytes(int b, int n, int c) { return rf_maxpool_points_workspace_bytes(b, n, c); }
 
 int rf_maxpool_points_lengths(int b, int n, int c, const float *x, const int *len, float *out, void *workspace,
                               size_t workspace_bytes, rf_stream_t stream) {
-    if (b < 0 || n < 0 || c < 0) return RF_EINVAL;
-    if ((size_t)b * c == 0) return RF_OK;
-    if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
-    if (!x || !out || !workspace) return RF_EINVAL;
-    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out) || !rf::aligned4(len)) return RF_EINVAL;
-    if (workspace_bytes < rf_maxpool_points_lengths_workspace_bytes(b, n, c)) return RF_EWORKSPACE;
-    const int nstrips = rf::ceil_div(n, MP_STRIP);
-    hipStream_t s = (hipStream_t)stream;
-    RF_LAUNCH("maxpool_points_len", maxpool_len_stage1_kernel<false>, dim3(nstrips, b), dim3(MP_TPB), 0, s, n, c, nstrips,
-              x, len, (float *)workspace, (int *)nullptr);
-    RF_LAUNCH("maxpool_points_len_fold", maxpool_len_stage2_kernel<false>, dim3(b), dim3(MP_TPB), 0, s, n, c, nstrips, len,
-              (const float *)workspace, (const int *)nullptr, out, (int *)nullptr);
-    return RF_OK;
+    return maxpool_run<false, true>(b, n, c, x, len, out, nullptr, workspace, workspace_bytes, stream, "maxpool_points_len",
+                                    "maxpool_points_len_fold");
 }
 
 size_t rf_maxpool_points_idx_lengths_workspace_bytes(int b, int n, int c) {
@@ -409,22 +316,8 @@ size_t rf_maxpool_points_idx_lengths_workspace_bytes(int b, int n, int c) {
 
 int rf_maxpool_points_idx_lengths(int b, int n, int c, const float *x, const int *len, float *out, int *idx,
                                   void *workspace, size_t workspace_bytes, rf_stream_t stream) {
-    if (b < 0 || n < 0 || c < 0) return RF_EINVAL;
-    if ((size_t)b * c == 0) return RF_OK;
-    if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
-    if (!x || !out || !idx || !workspace) return RF_EINVAL;
-    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out) || !rf::aligned4(idx) || !rf::aligned4(len))
-        return RF_EINVAL;
-    if (workspace_bytes < rf_maxpool_points_idx_lengths_workspace_bytes(b, n, c)) return RF_EWORKSPACE;
-    const int nstrips = rf::ceil_div(n, MP_STRIP);
-    float *part = (float *)workspace;
-    int *parti = (int *)(part + (size_t)b * nstrips * c);
-    hipStream_t s = (hipStream_t)stream;
-    RF_LAUNCH("maxpool_points_idx_len", maxpool_len_stage1_kernel<true>, dim3(nstrips, b), dim3(MP_TPB), 0, s, n, c,
-              nstrips, x, len, part, parti);
-    RF_LAUNCH("maxpool_points_idx_len_fold", maxpool_len_stage2_kernel<true>, dim3(b), dim3(MP_TPB), 0, s, n, c, nstrips,
-              len, (const float *)part, (const int *)parti, out, idx);
-    return RF_OK;
+    return maxpool_run<true, true>(b, n, c, x, len, out, idx, workspace, workspace_bytes, stream, "maxpool_points_idx_len",
+                                   "maxpool_points_idx_len_fold");
 }
 
 size_t rf_act_grad_colsum_workspace_bytes(int b, int n, int c) { return rf_maxpool_points_workspace_bytes(b, n, c); }

@@ -17,7 +17,6 @@
 #include "nn_pruned.hpp"
 
 namespace {
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // The chain on checked arguments.  ragged (rf_sample_and_group_lengths): the sort, FPS and the ball query take the counts -- len
 // (b) points per cloud for all three, len_out (b) samples per cloud as FPS's row length and the ball query's query count --
@@ -124,8 +123,9 @@ int rf_sample_and_group_lengths(int b, int n, int npoint, float radius, const fl
     if (npoint == 0) return RF_EINVAL;  // counts are at least 1
     if (n < 64 || nsample > 64 || b > 65535 || !rfp::pruned_supported(b, n, n)) return RF_EINVAL;
     if (!xyz || !fps_idx || !new_xyz || !idx || !pts_cnt || !grouped_xyz || !workspace) return RF_EINVAL;
-    if (!aligned4(xyz) || !aligned4(len) || !aligned4(len_out) || !aligned4(fps_idx) || !aligned4(new_xyz) || !aligned4(idx) ||
-        !aligned4(pts_cnt) || !aligned4(grouped_xyz) || !aligned4(radius_dev) || !rf::aligned16(workspace))
+    if (!rf::aligned4(xyz) || !rf::aligned4(len) || !rf::aligned4(len_out) || !rf::aligned4(fps_idx) || !rf::aligned4(new_xyz) ||
+        !rf::aligned4(idx) || !rf::aligned4(pts_cnt) || !rf::aligned4(grouped_xyz) || !rf::aligned4(radius_dev) ||
+        !rf::aligned16(workspace))
         return RF_EINVAL;
     if (workspace_bytes < rf_sample_and_group_lengths_workspace_bytes(b, n)) return RF_EWORKSPACE;
     return chain(b, n, npoint, radius, radius_dev, nsample, xyz, true, len, len_out, fps_idx, new_xyz, idx, pts_cnt, grouped_xyz,

@@ -785,7 +785,6 @@ int fps_sorted_lengths(int b, int n, int m, const float *inp, const int *len, co
 }  // namespace rfi
 
 namespace {
-bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 }  // namespace
 
 extern "C" {
@@ -851,7 +850,7 @@ int rf_farthestpointsampling_lengths(int b, int n, int m, const float *inp, cons
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
     if (!inp || !out) return RF_EINVAL;
-    if (!aligned4(inp) || !aligned4(len) || !aligned4(len_out) || !aligned4(out) || !aligned4(new_xyz) ||
+    if (!rf::aligned4(inp) || !rf::aligned4(len) || !rf::aligned4(len_out) || !rf::aligned4(out) || !rf::aligned4(new_xyz) ||
         !rf::aligned16(workspace))
         return RF_EINVAL;
     const size_t need = rf_farthestpointsampling_lengths_workspace_bytes(b, n, m);

@@ -98,8 +98,7 @@ __global__ __launch_bounds__(CB_TPB) void rows_csr_build_kernel(int n, int S, in
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) low += __shfl_xor(low, o, 64);
+    low = rf::wave_sum(low);
     if (lane == 0) lowsum[wave] = low;
     __syncthreads();
     // exclusive scan of the nbl counters: thread t owns the `per` consecutive bins [t * per, (t + 1) * per)

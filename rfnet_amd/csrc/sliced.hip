@@ -169,8 +169,7 @@ __global__ __launch_bounds__(SW_MERGE_MAX) void sliced_merge_kernel(int b, int n
             if (grad) coef2[row2 + idx2[row2 + j]] = s1 / den;
         }
     // fixed order: butterfly inside the wave, then the waves in order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+    part = rf::wave_sum(part);
     if ((tid & 63) == 0) wsum[tid >> 6] = part;
     __syncthreads();
     if (tid == 0) {

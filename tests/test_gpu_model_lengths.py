@@ -2,7 +2,8 @@
 earlier ragged operators did not bring: the poolings over the points axis (rf_maxpool_points_lengths /
 rf_maxpool_points_idx_lengths) and merge_layer (rf_merge_layer_lengths / rf_merge_layer_grad_lengths).
 
-The reference of every kernel check is the DENSE entry called on that sample's slice alone, bit for bit; rows behind a count
+The reference of every kernel check is the DENSE entry called on that sample's slice alone, bit for bit (the ragged merge_layer
+is held to the float64 formula and torch autograd as well, since both forms are one kernel template); rows behind a count
 are filled with values that would win if they were read (+inf / NaN for a max, copies of the query points for a nearest
 neighbour search).  The network is checked against the float64 restatement oracle run per sample on the unpadded slice
 (the bars of tests/test_rfnet_model.py) and against its own dense B = 1 call on the slice."""
@@ -231,6 +232,48 @@ def test_merge_layer_gradient_equals_the_dense_entry_on_slices(shape, len_new, s
         assert not gr[i, lr[i]:].any() and not gn[i, ln[i]:].any(), i
     gn2, gd2, none = _raw.merge_layer_grad(raw, new, dec, idx_in, go, lengths=lr, lengths_new=len_new)
     assert none is None and torch.equal(gn2, gn) and torch.equal(gd2, gd)
+
+
+def test_merge_layer_ragged_against_the_float64_formula(orc):
+    """The ragged entries against references that share no kernel with them (the two tests above compare one instantiation
+    of the pull kernels with the other): per sample, on the slice, idx2 from the oracle's nn_distance, the reference's
+    formula (vv_recon.py:132-139) in numpy float64, gradients from glue.merge_layer_unfused under torch autograd.  The bars
+    are those of tests/test_gpu_chamfer_ext.py::test_merge_layer_fused_vs_reference_formula.  The new counts sit on both
+    sides of the backward's 1024-thread stride and leave a zero-fill tail; padding is NaN on every input."""
+    from rfnet_amd import _raw, glue
+    b, n, m = 4, 300, 1100
+    len_raw, len_new = [1, 64, 299, 300], [1, 1024, 1025, 1100]
+    rng = np.random.RandomState(b * n + m)
+    raw = (rng.rand(b, n, 3) - 0.5).astype(np.float32)
+    new = (rng.rand(b, m, 3) - 0.5).astype(np.float32)
+    w = rng.randn(b, m, 3).astype(np.float32)
+    dec = np.float32(0.07)
+    for i in range(b):
+        raw[i, len_raw[i]:] = np.nan
+        new[i, len_new[i]:] = np.nan
+        w[i, len_new[i]:] = np.nan
+    traw, tnew, tw = cu(raw), cu(new), cu(w)
+    tdec = torch.tensor([dec], device="cuda")
+    refined, idx2 = _raw.merge_layer(traw, tnew, tdec, lengths=len_raw, lengths_new=len_new)
+    gn, gd, gr = _raw.merge_layer_grad(traw, tnew, tdec, idx2, tw, want_raw=True, lengths=len_raw, lengths_new=len_new)
+    for i in range(b):
+        lr, ln = len_raw[i], len_new[i]
+        sraw, snew = raw[i:i + 1, :lr], new[i:i + 1, :ln]
+        i2 = orc.nn_distance(sraw, snew)[3]
+        assert np.array_equal(idx2[i:i + 1, :ln].cpu().numpy(), i2), i
+        g = np.take_along_axis(sraw, i2[..., None].astype(np.int64), 1).astype(np.float64)
+        diff = g - snew
+        ratio = np.exp(-(diff * diff).sum(-1, keepdims=True) / (1e-8 + float(dec) ** 2))
+        assert np.allclose(refined[i:i + 1, :ln].cpu().numpy(), snew + ratio * diff, rtol=1e-5, atol=1e-6), i
+        # padded new rows: index 0 and refined with all bits zero
+        assert not idx2[i, ln:].any() and not refined[i, ln:].view(torch.int32).any(), i
+        uraw, unew = cu(sraw).requires_grad_(True), cu(snew).requires_grad_(True)
+        udec = torch.tensor([dec], device="cuda", requires_grad=True)
+        (glue.merge_layer_unfused(uraw, unew, udec) * tw[i:i + 1, :ln]).sum().backward()
+        assert torch.allclose(gn[i:i + 1, :ln], unew.grad, rtol=1e-4, atol=1e-5 * float(unew.grad.abs().max())), i
+        assert torch.allclose(gr[i:i + 1, :lr], uraw.grad, rtol=1e-4, atol=1e-5 * float(uraw.grad.abs().max())), i
+        assert torch.allclose(gd[i:i + 1], udec.grad, rtol=1e-3, atol=1e-4 * float(udec.grad.abs().max()) + 1e-6), i
+        assert not gn[i, ln:].any() and not gr[i, lr:].any(), i  # exactly zero behind the counts
 
 
 def test_glue_merge_layer_and_sampling_take_the_counts():
