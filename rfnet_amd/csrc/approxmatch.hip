@@ -2300,7 +2300,7 @@ int default_levels(float *lv) {
     return c;
 }
 
-struct AmLayout {
+struct AmLayout {  // (tests/test_gpu_emd_levels.py reads the vector region -- slots of V floats from the workspace's start -- as laid out here)
     int npad, mpad;
     size_t V;        // floats per vector pair [L: npad | R: mpad]
     size_t bstride;  // floats per batch element in the vector region: (1 + nlevels) * V

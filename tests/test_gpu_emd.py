@@ -55,7 +55,8 @@ def test_emd_random_shapes(orc, b, n, m):
 
 def test_c4_config_full_size(orc):
     """BASELINE.json configs[3]: B=32, 2048 vs 2048, reference 10-level schedule.  Oracle on one
-    batch element (1.3e8 exp evaluations), properties on all 32."""
+    batch element (1.3e8 exp evaluations), properties on all 32.
+    (Per launch, against a float64 replay of the kernels' own stored vectors with derived bounds per element: tests/test_gpu_emd_levels.py -- that is where the sweeps are held; the stray count here is a bar on the whole ill-conditioned chain.)"""
     from pc_distance.tf_approxmatch import approx_match, match_cost
     rng = np.random.RandomState(100)
     a = (rng.random_sample((32, 2048, 3)) - 0.5).astype(np.float32)
@@ -345,11 +346,12 @@ def test_exp2_is_exactly_zero_below_the_cull_argument():
 
 
 @pytest.mark.parametrize("b,n,m", [(1, 4096, 4096), (1, 4096, 5000), (2, 6000, 4100)])
-def test_earth_mover_culled_sharp_levels(orc, b, n, m):
+def test_earth_mover_large_clouds_vs_oracle(orc, b, n, m):
     """rf_earth_mover on clouds of >= 4096 points: cost against the oracle's chain (approx_match -> match_cost, tf_approxmatch.cu
-    restated) within 1e-5, with and without gradients, and the unfused chain.  (The name is rounds 3-5's, when the cost-only form ran
-    its three sharpest levels CULLED over sorted copies, sums in sorted order; round 6 took that route out -- a soak found its cost
-    1e-5 .. 3e-5 off the oracle's on rare large shapes: tools/experiments/emd_cull_route.patch.txt.)"""
+    restated) within 1e-5, with and without gradients, and the unfused chain.  (Until round 6 this test was named after the route
+    rounds 3-5 had here: the cost-only form ran its three sharpest levels CULLED over sorted copies, sums in sorted order; round 6
+    took that route out -- a soak found its cost 1e-5 .. 3e-5 off the oracle's on rare large shapes:
+    tools/experiments/emd_cull_route.patch.txt.)"""
     from rfnet_amd import _raw as R
     rng = np.random.RandomState(n + m)
     a = (rng.random_sample((b, n, 3)) - 0.5).astype(np.float32)
@@ -402,12 +404,14 @@ def test_sharp_level_sweeps_with_sorted_rows_keep_every_bit():
 
 
 @pytest.mark.parametrize("scale,what", [(1.0, "unit cube"), (4.0, "clouds four times the unit cube"), (float("nan"), "a NaN coordinate in one sample")])
-def test_broad_levels_by_expansion_and_its_refusal(orc, scale, what):
+def test_large_batch_sorted_and_live_sweeps_vs_oracle(orc, scale, what):
     """A large batch (8.4e7 pairs: sorted rows at the sharp levels, live-column sweeps from the third level on) against the oracle's
     chain on its first and last sample; with clouds four times the unit cube (every level sixteen-fold sharper: the strays are the
     sharp levels' cancellations, 2485 of 8e6 on every build since round 4); with a NaN in ANOTHER sample of the batch (that sample is
-    garbage by contract, the others must be what they are without the NaN next door).  (The name is round 5's, when the three
-    broadest levels of such a batch came from a Taylor expansion that refused the last two cases: tools/experiments/emd_fgt_route.patch.txt.)"""
+    garbage by contract, the others must be what they are without the NaN next door).  (Round 5 took the three broadest levels of
+    such a batch from a Taylor expansion that refused the last two cases, and this test was named after it:
+    tools/experiments/emd_fgt_route.patch.txt.)
+    (Per launch, against a float64 replay of the kernels' own stored vectors with derived bounds per element: tests/test_gpu_emd_levels.py -- that is where the sweeps are held; the stray count here is a bar on the whole ill-conditioned chain.)"""
     from pc_distance.tf_approxmatch import approx_match, match_cost
     rng = np.random.RandomState(31)
     B, N = 21, 2000  # 8.4e7 pairs: past the expansion's threshold (approxmatch.hip FGT_MIN_PAIRS = 8e7)
@@ -459,10 +463,11 @@ def test_match_cost_grad_whole_row_form_shapes(orc, b, n, m):
     assert torch.allclose(h1, g1, rtol=1e-4, atol=2e-6) and torch.allclose(h2, g2, rtol=1e-4, atol=2e-6)
 
 
-def test_broad_levels_by_expansion_ragged_sizes(orc):
+def test_large_batch_sorted_and_live_sweeps_unequal_sizes(orc):
     """A large batch with clouds of different sizes (multiL / multiR != 1; the live sets of the two sides' sweeps of different
     capacities, last chunks that are mostly padding): 24 x 2400 x 1500 = 8.6e7 pairs, first and last sample against the
-    oracle's chain; the fused earth_mover cost on the same route."""
+    oracle's chain; the fused earth_mover cost on the same route.
+    (Per launch, against a float64 replay of the kernels' own stored vectors with derived bounds per element: tests/test_gpu_emd_levels.py -- that is where the sweeps are held; the stray count here is a bar on the whole ill-conditioned chain.)"""
     from pc_distance.tf_approxmatch import approx_match, match_cost
     from rfnet_amd import _raw as R
     rng = np.random.RandomState(47)
@@ -554,7 +559,8 @@ def test_live_column_sweeps_on_lopsided_clouds(orc, kind):
     box nearly all columns are used up by the sharp levels (C4: 3 % left at level -1); two clusters in opposite corners match
     nothing until the broad levels, so every column stays live to the end; a partial shape against a complete one sits in
     between.  All of them against the oracle at the C4 bars, the cost at rel 1e-5, the fused cost, and against the pinned swept
-    route (which sweeps every column at every level)."""
+    route (which sweeps every column at every level).
+    (Per launch, against a float64 replay of the kernels' own stored vectors with derived bounds per element: tests/test_gpu_emd_levels.py -- that is where the sweeps are held; the stray count here is a bar on the whole ill-conditioned chain.)"""
     from rfnet_amd import _raw as R
     rng = np.random.RandomState(11)
     B, N = 2, 1536
@@ -584,7 +590,8 @@ def test_live_column_sweeps_on_lopsided_clouds(orc, kind):
 @pytest.mark.parametrize("n,m", [(512, 512), (513, 700), (2048, 640), (640, 2048), (5000, 3000)])
 def test_live_column_sweeps_shapes(orc, n, m):
     """The live-column route at the edges of its domain (it starts at 512 points per cloud): ragged sizes, multiL / multiR != 1,
-    a set 2 larger or smaller than set 1, more entries than one thread of the packing kernels holds in registers."""
+    a set 2 larger or smaller than set 1, more entries than one thread of the packing kernels holds in registers.
+    (Per launch, against a float64 replay of the kernels' own stored vectors with derived bounds per element: tests/test_gpu_emd_levels.py -- that is where the sweeps are held; the stray count here is a bar on the whole ill-conditioned chain.)"""
     from rfnet_amd import _raw as R
     rng = np.random.RandomState(n + m)
     b = 2
