@@ -1076,6 +1076,32 @@ int rf_knn_grad_lengths(int b, int n, int m, int k, const float *xyz1, const flo
                         const int *idx, const float *grad_val, float *grad_xyz1, float *grad_xyz2, void *workspace,
                         size_t workspace_bytes, rf_stream_t stream);
 
+/* ---- k-nearest neighbours in FEATURE space: the dynamic graph of DGCNN's EdgeConv ------------
+ * knn_point's argument order in c dimensions: feat1 (b,n,c) candidates, feat2 (b,m,c) queries; val (b,m,k) float32 and
+ * idx (b,m,k) int32.  No (b,m,n) tensor is formed: the inner products come from the fp32-input matrix instruction
+ * (v_mfma_f32_32x32x2_f32, an fp32 fmaf chain in ascending k) and every query keeps its k best in registers (knn_feature.hip).
+ * The distance is the formula DGCNN uses, |q|^2 + |x|^2 - 2 q.x, every operation prescribed, all in fp32:
+ *   ip[j][i]: acc = +0; for ch = 0 .. c-1 ascending: acc = fmaf(feat2[j][ch], feat1[i][ch], acc);
+ *             the matrix instruction's K is 2, so an odd c is padded with one channel of zeros: acc = fmaf(+0, +0, acc);
+ *   sq1[i], sq2[j]: acc = +0; for ch ascending: acc = fmaf(x[ch], x[ch], acc);
+ *   d[j][i] = fmaf(-2, ip[j][i], sq2[j] + sq1[i]), the sum rounded to fp32 first.
+ * d is NOT the rounded squared distance: under cancellation it can be slightly negative, so a row that queries itself is not
+ * guaranteed slot 0 among near-duplicates (the formula's property, DGCNN's included).  d is never -0 (the sum is >= +0).
+ * Result: per query the k smallest by (d, index), ascending -- ties go to the lower index; -0 orders as +0; a NaN distance
+ * ranks before everything (knn_point's rule), -inf before the finite values and +inf after them.  val = -d, -NaN for a NaN.
+ * Ragged batches, knn_point's rule exactly: len1 = candidates per sample, len2 = queries, device arrays of b ints clamped into
+ * [1, n] / [1, m] (either may be NULL; both NULL: a dense batch), read on the device with no host synchronisation.  The list is
+ * opened for kv = min(k, len1[i]); slots [kv, k) and the rows of padded queries are zeros (+0.0f, index 0); rows behind a count
+ * may hold anything, NaN included.  The result is a pure function of a sample's own valid rows: two calls return the same bits, a
+ * sample does not depend on its batch, a ragged call equals the call on the slices.
+ * Domain: 1 <= k <= min(n, 64), 1 <= n, m <= 65536, 1 <= b <= 65535, 1 <= c <= 2048; anything else is RF_EINVAL before any HIP
+ * call, as is a NULL tensor, a tensor or count array not 4-byte aligned and a NULL or not 16-byte aligned workspace.  workspace:
+ * rf_knn_feature_workspace_bytes(b, n, m, c, k) bytes (the squared norms; 0 = outside the domain); a shorter one is
+ * RF_EWORKSPACE and nothing is touched.  Two launches on `stream`. */
+size_t rf_knn_feature_workspace_bytes(int b, int n, int m, int c, int k);
+int rf_knn_feature(int b, int n, int m, int c, int k, const float *feat1, const float *feat2, const int *len1, const int *len2,
+                   float *val, int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+
 /* -------------------------------------------------- interpolation (tf_ops/interpolation) - */
 /* Replace threenn_cpu / threeinterpolate_cpu / threeinterpolate_grad_cpu
  * (tf_interpolate.cpp:60-153; CPU-only ops in the reference).  xyz1 (b,n,3) unknown,

@@ -146,6 +146,8 @@ SIGNATURES = {
     "rf_knn_grad_lengths": (_i, [_i, _i, _i, _i] + [_vp] * 9 + [_sz, _vp]),
     "rf_knn_grad_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_knn_grad": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
+    "rf_knn_feature_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "rf_knn_feature": (_i, [_i, _i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_threenn": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_threenn_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_threenn_lengths": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp, _i]),

@@ -1945,6 +1945,44 @@ def knn_point(k, xyz1, xyz2, form="auto", sorted1=None, sorted2=None, lengths1=N
     return st.give(val), st.give(idx)
 
 
+KNN_FEATURE_MAX_CHANNELS = 2048
+
+
+@H.on_input_device
+def knn_feature(k, feat1, feat2, lengths1=None, lengths2=None):
+    """rf_knn_feature: knn_point in feature space (DGCNN's dynamic graph) -> val (b,m,k) = -d, idx (b,m,k) int32: per row of
+    feat2 (b,m,c) the k rows of feat1 (b,n,c) of smallest d = |q|^2 + |x|^2 - 2 q.x, ascending by (d, index), ties to the lower
+    index, a NaN distance first.  Every fp32 operation of d is prescribed (include/rfops.h) and the inner products come from the
+    fp32 matrix instruction; no (b,m,n) tensor is formed.  d is the formula's value, not the rounded squared distance: it can be
+    slightly negative, so a row that queries itself is not guaranteed slot 0 among near-duplicates.
+    lengths1 / lengths2: a ragged batch, knn_point's rule -- candidates / queries per sample; rows of padded queries come back as
+    zeros, a sample with fewer candidates than k gets its lengths1[i] neighbours and zeros behind them."""
+    op = "KnnFeature"
+    k = int(k)
+    st = H.Staged()
+    a, q = st.take(feat1, F32), st.take(feat2, F32)
+    if not _shape3(a):
+        raise H.invalid(f"{op} expects (b,n,c) feat1 shape")
+    if not (_shape3(q, a.shape[2]) and q.shape[0] == a.shape[0]):
+        raise H.invalid(f"{op} expects (b,m,c) feat2 shape, and batch_size and channels must match")
+    b, n, c, m = a.shape[0], a.shape[1], a.shape[2], q.shape[1]
+    if not 1 <= k <= min(n, KNN_MAX_K):
+        raise H.invalid(f"{op} takes 1 <= k <= min(n, {KNN_MAX_K})")
+    if not (1 <= b <= 65535 and 1 <= n <= 65536 and 1 <= m <= 65536):
+        raise H.invalid(f"{op} takes 1 <= b <= 65535 and 1..65536 rows")
+    if not 1 <= c <= KNN_FEATURE_MAX_CHANNELS:
+        raise H.invalid(f"{op} takes 1 to {KNN_FEATURE_MAX_CHANNELS} channels")
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, q = st.up(a, q)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    val, idx = H.empty((b, m, k), F32, dev), H.empty((b, m, k), I32, dev)
+    ws, wsz = H.workspace(lib.rf_knn_feature_workspace_bytes(b, n, m, c, k), dev, "knn_feature")
+    check(lib.rf_knn_feature(b, n, m, c, k, H.ptr(a), H.ptr(q), H.ptr(l1), H.ptr(l2), H.ptr(val), H.ptr(idx), H.ptr(ws), wsz,
+                             H.stream(dev)), "rf_knn_feature")
+    return st.give(val), st.give(idx)
+
+
 @H.on_input_device
 def knn_point_grad(xyz1, xyz2, idx, grad_val, lengths1=None, lengths2=None):
     """The gradient of knn_point's val -> (grad_xyz1 (b,n,3), grad_xyz2 (b,m,3)) (rf_knn_grad).  lengths1 / lengths2: the counts

@@ -36,12 +36,10 @@
 #include "nn_pruned.hpp"
 #include "box_bound.hpp"
 #include "group_internal.hpp"
+#include "knn_list.hpp"  // u64, KN_MAXK, kn_insert, kn_zero, KN_DISPATCH: shared with knn_feature.hip
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int KN_MAXK = 64;
 constexpr int KN_TPB = 256;
 
 __device__ __forceinline__ u64 kn_key(float d, unsigned i) {
@@ -59,16 +57,6 @@ __device__ __forceinline__ float kn_val(u64 key) {
 }
 
 template <int KB>
-__device__ __forceinline__ void kn_insert(u64 (&L)[KB], u64 key) {
-    bool c[KB];
-#pragma unroll
-    for (int t = 0; t < KB; t++) c[t] = key < L[t];
-#pragma unroll
-    for (int t = KB - 1; t > 0; t--) L[t] = c[t - 1] ? L[t - 1] : (c[t] ? key : L[t]);
-    L[0] = c[0] ? key : L[0];
-}
-
-template <int KB>
 __device__ __forceinline__ void kn_write(const u64 (&L)[KB], int k, float *__restrict__ val, int *__restrict__ idx) {
 #pragma unroll
     for (int t = 0; t < KB; t++) {
@@ -78,11 +66,6 @@ __device__ __forceinline__ void kn_write(const u64 (&L)[KB], int k, float *__res
         }
     }
 }
-// slots [from, k) of a row as zeros (ragged batches: behind a sample's neighbours, and the whole row of a padded query)
-__device__ __forceinline__ void kn_zero(int from, int k, float *__restrict__ val, int *__restrict__ idx) {
-    for (int t = from; t < k; t++) val[t] = 0.f, idx[t] = 0;
-}
-
 // Candidates that pass the pre-test are not inserted at once: each lane appends them to a buffer of its own in LDS, and the wave
 // inserts only when some lane's buffer is full (or at the end of a run of candidates).  Inserting at once makes the whole wave run
 // the KB-slot insertion whenever ANY of its 64 lanes admits a candidate -- nearly every candidate of the first 64 k -- while a
@@ -298,15 +281,6 @@ bool kn_supported(int b, int n, int m, int k) {
     return b > 0 && b <= 65535 && n > 0 && m > 0 && n <= rfp::kMaxPoints && m <= rfp::kMaxPoints && k >= 1 && k <= KN_MAXK &&
            k <= n;
 }
-
-#define KN_DISPATCH(k, GO)                   \
-    do {                                     \
-        if ((k) <= 4) { GO(4); }             \
-        else if ((k) <= 8) { GO(8); }        \
-        else if ((k) <= 16) { GO(16); }      \
-        else if ((k) <= 32) { GO(32); }      \
-        else { GO(64); }                     \
-    } while (0)
 
 }  // namespace
 

@@ -629,6 +629,66 @@ def neighbor_subtraction(feat_q, feat_src, idx, lengths1=None, lengths2=None):
     return _NeighborSubtraction.apply(_feature_tensor(feat_q), _feature_tensor(feat_src), _index_tensor(idx), lengths1, lengths2)
 
 
+class _KnnFeature(torch.autograd.Function):
+    """rf_knn_feature; the backward has no kernel of its own: it recomputes the relative features and goes through
+    rf_neighbor_sub_grad."""
+
+    @staticmethod
+    def forward(ctx, feat1, feat2, k, lengths1, lengths2):
+        val, idx = _raw.knn_feature(k, feat1, feat2, lengths1, lengths2)
+        ctx.save_for_backward(feat1, feat2, idx)
+        ctx.lengths = (lengths1, lengths2)
+        ctx.mark_non_differentiable(idx)
+        return val, idx
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_val, _):
+        feat1, feat2, idx = ctx.saved_tensors
+        diff = _raw.neighbor_subtraction(feat2, feat1, idx, *ctx.lengths)  # f2[j] - f1[idx[j, t]], +0 in dead slots
+        grad_diff = (-2.0 * grad_val.unsqueeze(-1) * diff).contiguous()
+        g2, g1 = _raw.neighbor_subtraction_grad(idx, grad_diff, feat1.shape[1], *ctx.lengths, want_q=ctx.needs_input_grad[1],
+                                                want_src=ctx.needs_input_grad[0])
+        return g1, g2, None, None, None
+
+
+def knn_feature(k, feat1, feat2, lengths1=None, lengths2=None):
+    """k-nearest neighbours in feature space, the graph DGCNN's EdgeConv rebuilds at every layer: per row of feat2 (b, m, c)
+    the k rows of feat1 (b, n, c) of smallest d = |q|^2 + |x|^2 - 2 q.x -> (val (b, m, k) = -d, idx (b, m, k) int32), ascending
+    by (d, index); `knn_point`'s argument order, tie rule and ragged rule (lengths1 / lengths2: candidate / query rows per
+    sample; padded rows and slots are zeros).  No (b, m, n) matrix is formed (rf_knn_feature).  d is the formula's fp32 value and
+    can be slightly negative under cancellation, so a row that queries itself is not guaranteed slot 0 among near-duplicates.
+    idx is non-differentiable.  val is differentiable in both inputs, as -|feat2[j] - feat1[idx[j, t]]|^2 at fixed idx: the
+    backward recomputes the differences (rf_neighbor_sub) and scatters -2 g diff through rf_neighbor_sub_grad -- the derivative
+    of the squared distance itself, not of the rounded three-term formula."""
+    return _KnnFeature.apply(_feature_tensor(feat1), _feature_tensor(feat2), int(k), lengths1, lengths2)
+
+
+def edge_feature(feat_q, feat_src, idx, lengths1=None, lengths2=None):
+    """DGCNN's get_graph_feature: cat(f_j - f_i, f_i) -> (b, m, k, 2c), f_i = feat_q (b, m, c) the centre rows and f_j the rows
+    of feat_src (b, n, c) that idx (b, m, k) names -- what `knn_feature(k, feat_src, feat_q)` returns.  Torch glue over
+    `neighbor_subtraction`, whose gradients it inherits; with lengths1 / lengths2 (source rows / queries per sample) padded rows
+    and slots are zeros in both halves."""
+    fq = _feature_tensor(feat_q)
+    ix = _index_tensor(idx)
+    fs = _feature_tensor(feat_src)
+    rel = 0.0 - neighbor_subtraction(fq, fs, ix, lengths1, lengths2)  # f_j - f_i exactly; dead slots stay +0
+    b, m, k = ix.shape
+    n, dev = int(fs.shape[1]), rel.device
+    centre = fq.to(dev).unsqueeze(2).expand(b, m, k, fq.shape[2])
+    if lengths1 is not None or lengths2 is not None:  # the dead slots of rf_neighbor_sub, from the counts on the device
+        live = torch.ones((b, m, k), dtype=torch.bool, device=dev)
+        if lengths1 is not None:
+            l1 = _raw._lengths_up(_raw._check_lengths(lengths1, b, n, "lengths1"), dev, n).clamp(1, n)[:, None, None]
+            jx = ix.to(dev)
+            live = live & (torch.arange(k, device=dev)[None, None, :] < l1) & (jx >= 0) & (jx < l1)
+        if lengths2 is not None:
+            l2 = _raw._lengths_up(_raw._check_lengths(lengths2, b, m, "lengths2"), dev, m).clamp(1, m)[:, None, None]
+            live = live & (torch.arange(m, device=dev)[None, :, None] < l2)
+        centre = torch.where(live.unsqueeze(-1), centre, torch.zeros((), dtype=centre.dtype, device=dev))
+    return torch.cat((rel, centre), dim=-1)
+
+
 class _NeighborAggregation(torch.autograd.Function):
     """rf_neighbor_aggregate / rf_neighbor_aggregate_grad: value, weight and pos carry gradients, idx does not."""
 
