@@ -2257,7 +2257,8 @@ __device__ __forceinline__ void grad_tile(const GradSArgs &a, const int bi, int 
             // instruction whatever the addresses: tools/ubench/lds_atomic_rate.hip), which is what this kernel was bound by
             // (16.3 -> 12.8 us, step 84 -> 80.5 us).  RFP_GS_SEG: the pre-reduction that made the fp32 atomics bearable -- runs of
             // equal destination inside a 16-lane row summed in registers (segmented scan by DPP row shifts), only the last lane
-            // of a run touching LDS; it changes nothing any more and is off.
+            // of a run touching LDS.  It is still compiled in (RFP_GS_SEG defaults to 1): a run's terms meet in four levels of
+            // fp32 adds before they reach the double (tests/chamfer_grad_ref.py k_sorted counts them).
             const int j = w[i] - j0;
             const int key = (unsigned)j < (unsigned)jn ? j : -1;
             float sx = -v[i][0], sy = -v[i][1], sz = -v[i][2];
