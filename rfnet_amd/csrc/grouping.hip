@@ -23,9 +23,8 @@
 //   end, so no slot is written twice.
 #include <stdlib.h>
 
-#include <type_traits>
-
 #include "common.hpp"
+#include "lane_rows.hpp"
 #include "nn_pruned.hpp"
 #include "group_internal.hpp"
 #include "scatter_rows.hpp"
@@ -535,19 +534,17 @@ __global__ void group_point3_kernel(int n, int per_batch, const float *__restric
 // ELEMENT; they remain for what does not fit 32 bits).  GRAD: the same walk, adding grad_out into grad_points.
 constexpr int GPR_TPB = 256;
 constexpr int GPR_PP = 4;  // slots per thread row and block
-typedef float gpr_v4f __attribute__((ext_vector_type(4)));
 template <int VEC, bool GRAD>
 __global__ __launch_bounds__(GPR_TPB) void group_point_rows_kernel(int n, int c, int per_batch, int tx_log2, int bpb /* blocks per sample */,
                                                                    const float *__restrict__ src /* points | grad_out */,
                                                                    const int *__restrict__ idx,
                                                                    float *__restrict__ dst /* out | grad_points */) {
-    typedef typename std::conditional<VEC == 4, gpr_v4f, float>::type V;
+    typedef typename rf::LaneVec<VEC>::T V;
     // (a sample's blocks on ONE XCD: the rows it gathers cross the fabric once instead of eight times)
-    const unsigned logical = rf::xcd_contiguous(blockIdx.x, gridDim.x);  // a sample's workgroups on one XCD
-    const size_t bi = logical / bpb;
-    const int bx = logical - (unsigned)bi * bpb;
-    const int TX = 1 << tx_log2, TY = GPR_TPB >> tx_log2;
-    const int lx = threadIdx.x & (TX - 1), ly = threadIdx.x >> tx_log2;
+    size_t bi;
+    int bx;
+    rf::place_1d(bpb, bi, bx);
+    const rf::LaneRows<GPR_TPB> g(tx_log2);
     const int cv = c / VEC;
     const int *__restrict__ I = idx + bi * per_batch;
     const float *__restrict__ P = GRAD ? src + bi * per_batch * c : src + bi * n * c;  // rows of slots | rows of points
@@ -555,10 +552,10 @@ __global__ __launch_bounds__(GPR_TPB) void group_point_rows_kernel(int n, int c,
     int js[GPR_PP], row[GPR_PP];
 #pragma unroll
     for (int u = 0; u < GPR_PP; u++) {
-        js[u] = (bx * GPR_PP + u) * TY + ly;
+        js[u] = (bx * GPR_PP + u) * g.TY + g.ly;
         row[u] = I[min(js[u], per_batch - 1)];
     }
-    for (int l = lx; l < cv; l += TX) {
+    for (int l = g.lx; l < cv; l += g.TX) {
         V v[GPR_PP];
 #pragma unroll
         for (int u = 0; u < GPR_PP; u++) v[u] = ((const V *)P)[(size_t)(GRAD ? min(js[u], per_batch - 1) : row[u]) * cv + l];
@@ -568,13 +565,9 @@ __global__ __launch_bounds__(GPR_TPB) void group_point_rows_kernel(int n, int c,
             if (!GRAD) {
                 __builtin_nontemporal_store(v[u], &((V *)O)[(size_t)js[u] * cv + l]);
             } else {
-                float *g = O + ((size_t)row[u] * cv + l) * VEC;
-                if constexpr (VEC == 4) {
+                float *go = O + ((size_t)row[u] * cv + l) * VEC;
 #pragma unroll
-                    for (int k = 0; k < 4; k++) atomicAdd(g + k, v[u][k]);
-                } else {
-                    atomicAdd(g, v[u]);
-                }
+                for (int k = 0; k < VEC; k++) atomicAdd(go + k, rf::lane_at(v[u], k));
             }
         }
     }
@@ -585,10 +578,8 @@ static int group_rows_launch(int b, int n, int c, long per_batch, const float *s
                              hipStream_t s) {
     // (the gradient one channel per lane: a wave's atomic instruction then covers whole cache lines -- four adds per lane at a stride
     // of 16 bytes across the lanes measured 0.91 ms against 0.24 for 32 x 1024 x 32 slots of 64 channels)
-    const bool vec = !GRAD && c % 4 == 0 && rf::aligned16(src) && rf::aligned16(dst);
-    const int cv = vec ? c / 4 : c;
-    int tx_log2 = 0;
-    while ((1 << tx_log2) < cv && tx_log2 < 6) tx_log2++;
+    const bool vec = !GRAD && rf::lane_rows_vec_ok(c, {src, dst});
+    const int tx_log2 = rf::lane_rows_tx_log2(vec ? c / 4 : c);
     const int spb = (GPR_TPB >> tx_log2) * GPR_PP;  // slots per block
     const long bpb = (per_batch + spb - 1) / spb;
     const dim3 grid((unsigned)(bpb * b));
@@ -661,7 +652,6 @@ int ball_boxes(int b, int n, int m, float radius, const float *radius_dev, int n
 }
 }  // namespace rfi
 
-static bool qb_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 template <bool RAGGED>
 static int queryball_impl(int b, int n, int m, float radius, const float *radius_dev, int nsample, const float *xyz1,
@@ -774,8 +764,8 @@ int rf_queryballpoint_lengths(int b, int n, int m, float radius, const float *ra
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
     if (!xyz1 || !xyz2 || !idx || !pts_cnt) return RF_EINVAL;
-    if (!qb_aligned4(xyz1) || !qb_aligned4(xyz2) || !qb_aligned4(len1) || !qb_aligned4(len2) || !qb_aligned4(idx) ||
-        !qb_aligned4(pts_cnt) || !qb_aligned4(radius_dev) || !rf::aligned16(workspace))
+    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(idx) ||
+        !rf::aligned4(pts_cnt) || !rf::aligned4(radius_dev) || !rf::aligned16(workspace))
         return RF_EINVAL;
     const int route = qb_lengths_form(b, n, nsample, form);
     if (route < 0) return RF_EINVAL;

@@ -19,6 +19,7 @@
 // index order and inserts on strict '<': its result is the three smallest by (distance, index); the boxed form visits them in
 // any order and inserts by that pair -- the same triple, ties included.
 #include "common.hpp"
+#include "lane_rows.hpp"
 #include "scatter_rows.hpp"
 #include "nn_pruned.hpp"
 #include "box_bound.hpp"
@@ -170,36 +171,17 @@ __global__ __launch_bounds__(64 * TB_WAVES) void three_nn_boxes_kernel(
 constexpr int TI_TPB = 256;
 constexpr int TI_PP = 4;  // points per thread row and block
 
-typedef float ti_v4f __attribute__((ext_vector_type(4)));
-template <int VEC>
-struct TiVec;
-template <>
-struct TiVec<4> {
-    typedef ti_v4f T;
-    static __device__ __forceinline__ T mul(T a, float w) { return a * w; }  // (per component, every product rounded)
-    static __device__ __forceinline__ T add(T a, T b) { return a + b; }
-    static __device__ __forceinline__ float at(T a, int v) { return a[v]; }
-};
-template <>
-struct TiVec<1> {
-    typedef float T;
-    static __device__ __forceinline__ T mul(T a, float w) { return a * w; }
-    static __device__ __forceinline__ T add(T a, T b) { return a + b; }
-    static __device__ __forceinline__ float at(T a, int) { return a; }
-};
-
 template <int VEC>
 __global__ __launch_bounds__(TI_TPB) void three_interpolate_rows_kernel(int m, int c, int n, int tx_log2, int bpb /* blocks per sample */,
                                                                         const float *__restrict__ points,
                                                                         const int *__restrict__ idx,
                                                                         const float *__restrict__ weight,
                                                                         float *__restrict__ out) {
-    typedef typename TiVec<VEC>::T V;
+    typedef typename rf::LaneVec<VEC>::T V;
     // (a sample's blocks on ONE XCD: its rows of `points` then cross the fabric once instead of eight times -- FETCH_SIZE 71 -> 14 MB, 68 -> 57 us)
-    const unsigned logical = rf::xcd_contiguous(blockIdx.x, gridDim.x);  // a sample's workgroups on one XCD
-    const int bi = logical / bpb, bx = logical - bi * bpb;
-    const int TX = 1 << tx_log2, TY = TI_TPB >> tx_log2;
-    const int lx = threadIdx.x & (TX - 1), ly = threadIdx.x >> tx_log2;
+    int bi, bx;
+    rf::place_1d(bpb, bi, bx);
+    const rf::LaneRows<TI_TPB> g(tx_log2);
     const int cv = c / VEC;
     const V *__restrict__ P = (const V *)(points + (size_t)bi * m * c);
     V *__restrict__ O = (V *)(out + (size_t)bi * n * c);
@@ -210,7 +192,7 @@ __global__ __launch_bounds__(TI_TPB) void three_interpolate_rows_kernel(int m, i
     int jj[TI_PP];
 #pragma unroll
     for (int u = 0; u < TI_PP; u++) {
-        jj[u] = (bx * TI_PP + u) * TY + ly;
+        jj[u] = (bx * TI_PP + u) * g.TY + g.ly;
         const int j = min(jj[u], n - 1);
 #pragma unroll
         for (int t = 0; t < 3; t++) {
@@ -218,15 +200,14 @@ __global__ __launch_bounds__(TI_TPB) void three_interpolate_rows_kernel(int m, i
             w[u][t] = W[j * 3 + t];
         }
     }
-    for (int l = lx; l < cv; l += TX) {
+    for (int l = g.lx; l < cv; l += g.TX) {
         V a[TI_PP], b2[TI_PP], d[TI_PP];
 #pragma unroll
         for (int u = 0; u < TI_PP; u++) a[u] = P[r[u][0] + l], b2[u] = P[r[u][1] + l], d[u] = P[r[u][2] + l];
 #pragma unroll
         for (int u = 0; u < TI_PP; u++) {
             if (jj[u] < n)  // (written once, read by another kernel: past the caches)
-                __builtin_nontemporal_store(TiVec<VEC>::add(TiVec<VEC>::add(TiVec<VEC>::mul(a[u], w[u][0]), TiVec<VEC>::mul(b2[u], w[u][1])),
-                                                            TiVec<VEC>::mul(d[u], w[u][2])), &O[(size_t)jj[u] * cv + l]);
+                __builtin_nontemporal_store((a[u] * w[u][0] + b2[u] * w[u][1]) + d[u] * w[u][2], &O[(size_t)jj[u] * cv + l]);
         }
     }
 }
@@ -248,15 +229,14 @@ __global__ __launch_bounds__(TG_TPB) void three_interpolate_grad_tile_kernel(int
                                                                              const int *__restrict__ idx,
                                                                              const float *__restrict__ weight,
                                                                              float *__restrict__ grad_points) {
-    typedef typename TiVec<VEC>::T V;
+    typedef typename rf::LaneVec<VEC>::T V;
     extern __shared__ __attribute__((aligned(16))) double ti_tile[];  // [m * cs]; cs = VEC << tx_log2, or (VEC == 1) any cs <= 1 << tx_log2
     // (a sample's slices and parts on ONE XCD: neighbouring slices share the cache lines of grad_out's rows)
-    const unsigned logical = rf::xcd_contiguous(blockIdx.x, gridDim.x);  // a sample's workgroups on one XCD
-    const int wps = nslices * parts;  // workgroups per sample
-    const int bi = logical / wps, bx = logical - bi * wps;
+    int bi, bx;
+    rf::place_1d(nslices * parts /* workgroups per sample */, bi, bx);
     const int slice = bx % nslices, part = bx / nslices;
-    const int TX = 1 << tx_log2, TY = TG_TPB >> tx_log2;
-    const int lx = threadIdx.x & (TX - 1), ly = threadIdx.x >> tx_log2;
+    const rf::LaneRows<TG_TPB> lr(tx_log2);
+    const int TY = lr.TY, lx = lr.lx, ly = lr.ly;
     const bool lane_on = POW2 || lx * VEC < cs;  // (a slice of 3 or 13 channels leaves the last lanes of its rows idle)
     const int csl = POW2 ? 31 - __clz(cs) : 0;
     for (int e = threadIdx.x; e < m * cs; e += TG_TPB) ti_tile[e] = 0.0;
@@ -300,9 +280,9 @@ __global__ __launch_bounds__(TG_TPB) void three_interpolate_grad_tile_kernel(int
         for (int u = 0; u < TG_U; u++)
 #pragma unroll
             for (int k = 0; k < VEC; k++) {
-                float x = TiVec<VEC>::at(g[u], k);
+                float x = rf::lane_at(g[u], k);
                 if (VEC == 4) {
-                    const float y = TiVec<VEC>::at(g[u], (k + 1) & 3), z = TiVec<VEC>::at(g[u], (k + 2) & 3), q = TiVec<VEC>::at(g[u], (k + 3) & 3);
+                    const float y = rf::lane_at(g[u], (k + 1) & 3), z = rf::lane_at(g[u], (k + 2) & 3), q = rf::lane_at(g[u], (k + 3) & 3);
                     x = rot == 0 ? x : (rot == 1 ? y : (rot == 2 ? z : q));
                 }
                 gr[u][k] = x;
@@ -422,7 +402,6 @@ static int tn_lengths_form(int b, int n, int m, int form) {  // -> RF_GROUP_SCAN
     const bool pays = n >= 1024 && m >= 512 && (pairs >= (small ? 1e8 : 4e9) || (m >= 1536 && n >= 4096 && small));
     return domain && pays ? RF_GROUP_BOXES : RF_GROUP_SCAN;
 }
-static bool tn_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 size_t rf_threenn_lengths_workspace_bytes(int b, int n, int m, int form) {
     if (b <= 0 || b > 65535 || n <= 0 || m <= 0) return 0;
@@ -435,8 +414,8 @@ int rf_threenn_lengths(int b, int n, int m, const float *xyz1, const float *xyz2
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
     if (!xyz1 || !xyz2 || !dist || !idx) return RF_EINVAL;
-    if (!tn_aligned4(xyz1) || !tn_aligned4(xyz2) || !tn_aligned4(len1) || !tn_aligned4(len2) || !tn_aligned4(dist) ||
-        !tn_aligned4(idx) || !rf::aligned16(workspace))
+    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(dist) ||
+        !rf::aligned4(idx) || !rf::aligned16(workspace))
         return RF_EINVAL;
     const int route = tn_lengths_form(b, n, m, form);
     if (route < 0) return RF_EINVAL;
@@ -467,10 +446,8 @@ int rf_threeinterpolate(int b, int m, int c, int n, const float *points, const i
     if (total == 0) return RF_OK;
     if (!points || !idx || !weight || !out) return RF_EINVAL;
     if (b <= 65535 && (long)n * c < (1L << 31) && (long)m * c < (1L << 31) && (long)n * 3 < (1L << 31)) {
-        const bool vec = c % 4 == 0 && rf::aligned16(points) && rf::aligned16(out);
-        const int cv = vec ? c / 4 : c;
-        int tx_log2 = 0;
-        while ((1 << tx_log2) < cv && tx_log2 < 6) tx_log2++;
+        const bool vec = rf::lane_rows_vec_ok(c, {points, out});
+        const int tx_log2 = rf::lane_rows_tx_log2(vec ? c / 4 : c);
         const int ppb = (TI_TPB >> tx_log2) * TI_PP;  // points per block
         const long bpb = rf::ceil_div(n, ppb);
         if (bpb * b <= 0x7FFFFFFF) {
@@ -534,8 +511,7 @@ int rf_threeinterpolate_grad_ws(int b, int n, int c, int m, const float *grad_ou
         const bool pow2 = (cs & (cs - 1)) == 0 && cs >= 8;
         const bool vec = pow2 && rf::aligned16(grad_out);  // (rows of a slice start 16-byte aligned when the tensor does)
         const int nslices = c / cs;
-        int tx_log2 = 0;
-        while ((1 << tx_log2) < (vec ? cs / 4 : cs)) tx_log2++;
+        const int tx_log2 = rf::lane_rows_tx_log2(vec ? cs / 4 : cs);  // (cs <= 64: the rows cover the slice in one pass)
         // parts of the unknown points: a workgroup per CU (the tile leaves room for one), every part still thousands of points
         int parts = 1;
         while ((long)b * nslices * parts < RFI_TG_WGS && n / (parts * 2) >= 2048) parts *= 2;

@@ -344,7 +344,6 @@ int rf_knn_grad(int b, int n, int m, int k, const float *xyz1, const float *xyz2
 
 // ---- ragged batches (include/rfops.h).  auto: the boxed form where the Python wrapper takes it for the plain op
 // (KNN_BOXES_* of rfnet_amd/_raw.py), by the PADDED sizes.
-static bool kn_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 static int kn_lengths_form(int n, int m, int k, int form) {  // -> RF_GROUP_SCAN / RF_GROUP_BOXES, or -1
     if (form == RF_GROUP_SCAN || form == RF_GROUP_BOXES) return form;
     if (form != RF_GROUP_AUTO) return -1;
@@ -361,8 +360,8 @@ int rf_knn_lengths(int b, int n, int m, int k, const float *xyz1, const float *x
     if (b == 0 && n >= 0 && m >= 0 && k >= 0) return RF_OK;
     if (!kn_supported(b, n, m, k)) return RF_EINVAL;
     if (!xyz1 || !xyz2 || !val || !idx) return RF_EINVAL;
-    if (!kn_aligned4(xyz1) || !kn_aligned4(xyz2) || !kn_aligned4(len1) || !kn_aligned4(len2) || !kn_aligned4(val) ||
-        !kn_aligned4(idx) || !rf::aligned16(workspace))
+    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(val) ||
+        !rf::aligned4(idx) || !rf::aligned16(workspace))
         return RF_EINVAL;
     const int route = kn_lengths_form(n, m, k, form);
     if (route < 0) return RF_EINVAL;
@@ -401,7 +400,7 @@ int rf_knn_grad_lengths(int b, int n, int m, int k, const float *xyz1, const flo
     if (!kn_supported(b, n, m, k)) return RF_EINVAL;
     if (!xyz1 || !xyz2 || !idx || !grad_val || !grad_xyz1 || !grad_xyz2 || !workspace || !rf::aligned16(workspace))
         return RF_EINVAL;
-    if (!kn_aligned4(len1) || !kn_aligned4(len2)) return RF_EINVAL;
+    if (!rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
     if (workspace_bytes < rf_knn_grad_lengths_workspace_bytes(b, n, m, k)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     RF_LAUNCH("knn_grad_query_lengths", knn_grad_query_kernel<true>, dim3(rf::ceil_div(m, KG_TPB), b), dim3(KG_TPB), 0, s, n, m, k,

@@ -16,10 +16,13 @@
 //                   step with a lane per (corner, channel), the weight recomputed from xyz[i] and one read of grad_feat[i][ch];
 //                   grad_xyz is a gather with eight lanes per point, lane d summing g_d over the channels in ascending order.
 //
-// Every kernel with a (tile, sample) grid takes its logical place from pv_place: the workgroups of a sample share one XCD's L2.
+// Every kernel with a (tile, sample) grid takes its logical place from rf::place_2d (lane_rows.hpp): the workgroups of one sample --
+// which read the same volume, and in the scatter kernels the chunk workgroups of one sub-brick, which read the same rows of
+// features -- share one XCD's L2 (profiles/point_voxel_ab.txt).
 // Both sorts are brick_sort.hpp's gr_brick_sort, the one that grnet_layers.hip runs, with the vertex or the cell as the key; the
-// devoxelize backward's scatter is its gr_subbrick_scatter, placed by pv_place.
+// devoxelize backward's scatter is its gr_subbrick_scatter, placed by rf::place_2d.
 #include "brick_sort.hpp"
+#include "lane_rows.hpp"
 
 namespace {
 
@@ -45,14 +48,6 @@ __device__ __forceinline__ void pv_nearest(const PvPoint &p, int &kx, int &ky, i
 __device__ __forceinline__ double pv_weight(const PvPoint &p, int dx, int dy, int dz) {
     const float wx = dx ? p.tx : 1.0f - p.tx, wy = dy ? p.ty : 1.0f - p.ty, wz = dz ? p.tz : 1.0f - p.tz;
     return ((double)wx * (double)wy) * (double)wz;
-}
-
-// The workgroup's logical place in its (x, sample) grid.  Workgroup ids go round the 8 XCDs; rf::xcd_contiguous gives every XCD a
-// contiguous run of the logical order, so that the workgroups of one sample -- which read the same volume, and in the scatter
-// kernels the chunk workgroups of one sub-brick, which read the same rows of features -- share one L2 (profiles/point_voxel_ab.txt).
-__device__ __forceinline__ void pv_place(int &x, int &s) {
-    const unsigned pos = rf::xcd_contiguous(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-    s = (int)(pos / gridDim.x), x = (int)(pos - (unsigned)s * gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------ the counting sort
@@ -95,7 +90,7 @@ __global__ __launch_bounds__(PV_TPB) void pv_vox_kernel(PvVox a) {
     __shared__ unsigned num[GR_SUB_E3];
     __shared__ unsigned slot[PV_TPB];  // a wave's 64: the records of this sub-brick among the 64 it has just read
     int s, bx;
-    pv_place(bx, s);
+    rf::place_2d<false>(bx, s);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int R = a.R, c = a.c, n = a.n;
     const int nsb = (R + GR_SUB_E - 1) / GR_SUB_E, nchunk = (c + GR_CHUNK - 1) / GR_CHUNK;
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(PV_TPB) void pv_vox_grad_kernel(PvVoxGrad a) {
     __shared__ int vtx[PV_PTS];
     __shared__ int num[PV_PTS];
     int s, bx;
-    pv_place(bx, s);
+    rf::place_2d<false>(bx, s);
     const int tid = threadIdx.x, n = a.n, c = a.c;
     const GrBox g = a.g;
     const int R = g.R, L = rf::ragged_count(a.len, s, n);
@@ -229,7 +224,7 @@ __global__ __launch_bounds__(PV_TPB) void pv_devox_kernel(PvDevox a) {
     __shared__ float tt[PV_PTS * 3];
     __shared__ unsigned wcnt[PV_TPB / 64];
     int s, bx;
-    pv_place(bx, s);
+    rf::place_2d<false>(bx, s);
     const int tid = threadIdx.x, n = a.n, c = a.c;
     const GrBox g = a.g;
     const int R = g.R, L = rf::ragged_count(a.len, s, n);
@@ -291,7 +286,7 @@ struct PvBrick {
 // ceil(c / GR_CHUNK), b), the channel chunk fastest
 __global__ __launch_bounds__(GR_SUB_TPB) void pv_devox_brick_kernel(PvBrick a) {
     int s, bx;
-    pv_place(bx, s);
+    rf::place_2d<false>(bx, s);
     const GrBox g = a.g;
     const int R = g.R, c = a.c, n = a.n;
     const int nb = gr_nb(R), nb3 = nb * nb * nb;
@@ -320,7 +315,7 @@ struct PvXyzGrad {
 // grid (ceil(n / PV_PTS), b): eight lanes per point, lane d sums g_d over the channels; lanes 0 ... 2 then form one axis each
 __global__ __launch_bounds__(PV_TPB) void pv_devox_xyz_kernel(PvXyzGrad a) {
     int s, bx;
-    pv_place(bx, s);
+    rf::place_2d<false>(bx, s);
     const int tid = threadIdx.x, n = a.n, c = a.c;
     const int i = bx * PV_PTS + (tid >> 3), d = tid & 7;
     const GrBox g = a.g;

@@ -15,6 +15,7 @@
 //                    rows nobody names as zeros: no zero-fill pass, no read-modify-write.
 // HBM traffic = the data: src once, dst once, 12 bytes of index per slot.
 #include "common.hpp"
+#include "lane_rows.hpp"
 #include "scatter_rows.hpp"
 #include "group_internal.hpp"
 
@@ -65,8 +66,8 @@ __global__ __launch_bounds__(CB_TPB) void rows_csr_build_kernel(int n, int S, in
     __shared__ unsigned wsum[CB_TPB / 64];
     __shared__ unsigned lowsum[CB_TPB / 64];
     __shared__ unsigned seg_end;  // where this workgroup's segment of perm ends
-    const unsigned logical = rf::xcd_contiguous(blockIdx.x, gridDim.x);
-    const int bi = logical / H, h = logical - bi * H;
+    int bi, h;
+    rf::place_1d(H, bi, h);
     const int lo = h * nbl, hi = min(n, lo + nbl);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr bool REG = CB_RPT > 0;
@@ -162,18 +163,6 @@ __global__ __launch_bounds__(CB_TPB) void rows_csr_build_kernel(int n, int S, in
     for (unsigned j = tid; j < cnt; j += CB_TPB) P[first + j] = (int)stage[j];
 }
 
-typedef float cg_v4f __attribute__((ext_vector_type(4)));
-template <int VEC>
-struct CgVec;
-template <>
-struct CgVec<4> {
-    typedef cg_v4f T;
-};
-template <>
-struct CgVec<1> {
-    typedef float T;
-};
-
 constexpr int CG_TPB = 256;
 // (same device, C3's gradient shapes, tools/ab_group_grad.py: 2 rows x 2 slots 84 us; 1 x 4 88, 2 x 4 83, 1 x 8 87, 4 x 2 101; the
 // source rows by non-temporal loads 97 -- and 84 instead of 52 for three_interpolate's, whose rows are read three times)
@@ -186,11 +175,10 @@ __global__ __launch_bounds__(CG_TPB) void rows_csr_gather_kernel(int n, int c, i
                                                                  const float *__restrict__ src, const float *__restrict__ weight,
                                                                  const int *__restrict__ row_start, const int *__restrict__ perm,
                                                                  float *__restrict__ dst) {
-    typedef typename CgVec<VEC>::T V;
-    const unsigned logical = rf::xcd_contiguous(blockIdx.x, gridDim.x);
-    const int bi = logical / bpb, bx = logical - bi * bpb;
-    const int TX = 1 << tx_log2, TY = CG_TPB >> tx_log2;
-    const int lx = threadIdx.x & (TX - 1), ly = threadIdx.x >> tx_log2;
+    typedef typename rf::LaneVec<VEC>::T V;
+    int bi, bx;
+    rf::place_1d(bpb, bi, bx);
+    const rf::LaneRows<CG_TPB> g(tx_log2);
     const int cv = c / VEC;
     const int *__restrict__ RS = row_start + (size_t)bi * (n + 1);
     const int *__restrict__ P = perm + (size_t)bi * S;
@@ -200,12 +188,12 @@ __global__ __launch_bounds__(CG_TPB) void rows_csr_gather_kernel(int n, int c, i
     int r[CG_RPT], beg[CG_RPT], end[CG_RPT];
 #pragma unroll
     for (int u = 0; u < CG_RPT; u++) {
-        r[u] = (bx * CG_RPT + u) * TY + ly;
+        r[u] = (bx * CG_RPT + u) * g.TY + g.ly;
         const int rr = min(r[u], n - 1);
         beg[u] = RS[rr];
         end[u] = r[u] < n ? RS[rr + 1] : beg[u];
     }
-    for (int l = lx; l < cv; l += TX) {
+    for (int l = g.lx; l < cv; l += g.TX) {
         double acc[CG_RPT][VEC];
 #pragma unroll
         for (int u = 0; u < CG_RPT; u++)
@@ -319,10 +307,8 @@ int rows_csr_scatter(int b, int n, int c, long S, int K, const float *src, const
     if (int e = rows_csr_sort(b, n, S, idx, workspace, build_name, s)) return e;
     const int *row_start = (const int *)workspace;
     const int *perm = rows_csr_perm(b, n, workspace);
-    const bool vec = c % 4 == 0 && rf::aligned16(src) && rf::aligned16(dst);
-    const int cv = vec ? c / 4 : c;
-    int tx_log2 = 0;
-    while ((1 << tx_log2) < cv && tx_log2 < 6) tx_log2++;
+    const bool vec = rf::lane_rows_vec_ok(c, {src, dst});
+    const int tx_log2 = rf::lane_rows_tx_log2(vec ? c / 4 : c);
     const int rpb = (CG_TPB >> tx_log2) * CG_RPT;
     const int bpb = rf::ceil_div(n, rpb);
     const dim3 grid((unsigned)((long)bpb * b));

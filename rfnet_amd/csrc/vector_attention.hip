@@ -4,7 +4,7 @@
 //   neighbour aggregation   out[i][ch]   = sum_t (value[idx[i][t]][ch] + pos[i][t][ch]) * weight[i][t][ch mod cw]
 // both with gradients.  include/rfops.h states the contract, DESIGN.md 5.3p the layout and the measurements.
 //
-// Three kernel shapes, all of them rows of lanes over the channels (float4 per lane where c % 4 == 0 and the pointers allow it):
+// Three kernel shapes, all of them lane rows over the channels (lane_rows.hpp has the geometry, the vector type and the placement):
 //   slot rows    a lane row per slot (i, t): the subtraction, grad_pos, grad_weight (there the lanes run over the WEIGHT channels
 //                and every lane walks the c / cw channel groups in ascending order: the prescribed order, coalesced loads);
 //   query rows   a lane row per query i walking its slots in ascending t with double accumulators: the aggregation and grad_q;
@@ -13,10 +13,11 @@
 //                stored once, nothing of size (b, m, k, c) is formed for the aggregation: its terms come from grad_out[i][:] and
 //                weight[i][t][:] on the fly.  No float atomics in memory and no memset anywhere.
 // The streamed (b, m, k, c) tensors go by non-temporal loads and stores, the gathered rows by plain loads (they are what the L2
-// holds), and va_place puts a sample's workgroups on one XCD.  A dead slot's operands are loaded from addresses that are the
+// holds), and rf::place_2d puts a sample's workgroups on one XCD.  A dead slot's operands are loaded from addresses that are the
 // call's own (its own slot of pos / weight / grad_out, row 0 of the gathered tensor) and dropped by a SELECT, never by a product:
 // a NaN there reaches nothing, and several loads stay in flight without a branch.
 #include "common.hpp"
+#include "lane_rows.hpp"
 #include "scatter_rows.hpp"
 
 namespace {
@@ -28,34 +29,6 @@ constexpr int VA_RPT = 2;   // source rows: rows per lane row (their chains run 
 constexpr int VA_Q = 4;     // ... and slots of each in flight
 constexpr int VA_MAXK = RF_VA_MAX_K, VA_MAXC = RF_VA_MAX_CHANNELS;
 static_assert(VA_MAXK == 64, "KN_MAXK (knn.hip): what rf_knn writes is what these entries take");
-
-typedef float va_v4f __attribute__((ext_vector_type(4)));
-template <int VEC>
-struct VaVec;
-template <>
-struct VaVec<4> {
-    typedef va_v4f T;
-};
-template <>
-struct VaVec<1> {
-    typedef float T;
-};
-__device__ __forceinline__ float va_at(float v, int) { return v; }
-__device__ __forceinline__ float va_at(const va_v4f &v, int j) { return v[j]; }
-__device__ __forceinline__ void va_set(float &v, int, float x) { v = x; }
-__device__ __forceinline__ void va_set(va_v4f &v, int j, float x) { v[j] = x; }
-
-// The workgroup's logical place in its (x, sample) grid: pv_place of point_voxel.hip.  Past 2^32 workgroups (sizes no memory
-// holds) the ids are taken as they are: any mapping is correct.
-__device__ __forceinline__ void va_place(int &x, int &s) {
-    const unsigned long long total = (unsigned long long)gridDim.x * gridDim.y;
-    if (total >> 32) {
-        x = (int)blockIdx.x, s = (int)blockIdx.y;
-        return;
-    }
-    const unsigned pos = rf::xcd_contiguous(blockIdx.y * gridDim.x + blockIdx.x, (unsigned)total);
-    s = (int)(pos / gridDim.x), x = (int)(pos - (unsigned)s * gridDim.x);
-}
 
 // the liveness rule of include/rfops.h, cb_key's of scatter_rows.hip: nv valid source rows, mv valid queries
 struct VaLive {
@@ -82,14 +55,14 @@ __device__ __forceinline__ VaWOff<VEC, WV> va_woff(int ch0, int cw) {
     return w;
 }
 template <int VEC, bool WV>
-__device__ __forceinline__ typename VaVec<VEC>::T va_wload(const float *__restrict__ row, const VaWOff<VEC, WV> &w) {
-    typedef typename VaVec<VEC>::T V;
+__device__ __forceinline__ typename rf::LaneVec<VEC>::T va_wload(const float *__restrict__ row, const VaWOff<VEC, WV> &w) {
+    typedef typename rf::LaneVec<VEC>::T V;
     if constexpr (WV || VEC == 1) {
         return __builtin_nontemporal_load((const V *)(row + w.o[0]));
     } else {
         V v;
 #pragma unroll
-        for (int j = 0; j < VEC; j++) va_set(v, j, __builtin_nontemporal_load(row + w.o[j]));
+        for (int j = 0; j < VEC; j++) rf::lane_set(v, j, __builtin_nontemporal_load(row + w.o[j]));
         return v;
     }
 }
@@ -105,17 +78,32 @@ struct VaArgs {
 };
 
 // ------------------------------------------------------------------------------------------------ slot rows
+// The PP slots of a lane row: js = (bx PP + u) TY + ly, clamped into the sample as jc (a slot behind the last loads the last
+// slot's operands and stores nothing), its query qi, whether it is live and the row it gathers (row 0 for a dead slot).
+// One text for va_slot_kernel and va_gweight_kernel, from their bx, L, I, k and S; a macro, because round an inlined function the
+// compiler places the kernels' address arithmetic elsewhere, and the code of seventeen tuned kernels is to stay what it is.
+#define VA_SLOTS(PP, G)                                            \
+    int js[PP], jc[PP], qi[PP], row[PP];                           \
+    bool live[PP];                                                 \
+    _Pragma("unroll") for (int u = 0; u < PP; u++) {               \
+        js[u] = (bx * PP + u) * G.TY + G.ly;                       \
+        jc[u] = min(js[u], S - 1);                                 \
+        qi[u] = jc[u] / k;                                         \
+        const int r = I[jc[u]];                                    \
+        live[u] = va_live(L, qi[u], jc[u] - qi[u] * k, r);         \
+        row[u] = live[u] ? r : 0;                                  \
+    }
+
 // What a lane row computes for its slot.  SUB: q - src.  GPOS: fl32(g * w).
 enum { VA_SUB = 0, VA_GPOS = 1 };
 
 // grid (ceil(m k / (TY VA_PP)), b)
 template <int VEC, int OP, bool WV>
 __global__ __launch_bounds__(VA_TPB) void va_slot_kernel(VaArgs a, int tx_log2) {
-    typedef typename VaVec<VEC>::T V;
+    typedef typename rf::LaneVec<VEC>::T V;
     int bx, s;
-    va_place(bx, s);
-    const int TX = 1 << tx_log2, TY = VA_TPB >> tx_log2;
-    const int lx = threadIdx.x & (TX - 1), ly = threadIdx.x >> tx_log2;
+    rf::place_2d<true>(bx, s);
+    const rf::LaneRows<VA_TPB> g(tx_log2);
     const int c = a.c, cv = c / VEC, k = a.k, S = a.m * k;
     const VaLive L{rf::ragged_count(a.len1, s, a.n), rf::ragged_count(a.len2, s, a.m)};
     const int *__restrict__ I = a.idx + (size_t)s * S;
@@ -123,18 +111,8 @@ __global__ __launch_bounds__(VA_TPB) void va_slot_kernel(VaArgs a, int tx_log2) 
     const V *__restrict__ P = (const V *)(a.src + (size_t)s * a.n * c);
     const float *__restrict__ W = a.weight + (size_t)s * S * a.cw;
     V *__restrict__ O = (V *)(a.out + (size_t)s * S * c);
-    int js[VA_PP], jc[VA_PP], qi[VA_PP], row[VA_PP];
-    bool live[VA_PP];
-#pragma unroll
-    for (int u = 0; u < VA_PP; u++) {
-        js[u] = (bx * VA_PP + u) * TY + ly;
-        jc[u] = min(js[u], S - 1);
-        qi[u] = jc[u] / k;
-        const int r = I[jc[u]];
-        live[u] = va_live(L, qi[u], jc[u] - qi[u] * k, r);
-        row[u] = live[u] ? r : 0;
-    }
-    for (int l = lx; l < cv; l += TX) {
+    VA_SLOTS(VA_PP, g)
+    for (int l = g.lx; l < cv; l += g.TX) {
         V x[VA_PP], y[VA_PP];
         if constexpr (OP == VA_SUB) {
 #pragma unroll
@@ -142,7 +120,8 @@ __global__ __launch_bounds__(VA_TPB) void va_slot_kernel(VaArgs a, int tx_log2) 
         } else {
             const VaWOff<VEC, WV> wo = va_woff<VEC, WV>(l * VEC, a.cw);
 #pragma unroll
-            for (int u = 0; u < VA_PP; u++) x[u] = Q[(size_t)qi[u] * cv + l], y[u] = va_wload<VEC, WV>(W + (size_t)jc[u] * a.cw, wo);
+            for (int u = 0; u < VA_PP; u++)
+                x[u] = Q[(size_t)qi[u] * cv + l], y[u] = va_wload<VEC, WV>(W + (size_t)jc[u] * a.cw, wo);
         }
 #pragma unroll
         for (int u = 0; u < VA_PP; u++) {
@@ -150,8 +129,8 @@ __global__ __launch_bounds__(VA_TPB) void va_slot_kernel(VaArgs a, int tx_log2) 
             V o;
 #pragma unroll
             for (int j = 0; j < VEC; j++) {
-                const float xa = va_at(x[u], j), ya = va_at(y[u], j);
-                va_set(o, j, live[u] ? (OP == VA_SUB ? xa - ya : xa * ya) : 0.f);
+                const float xa = rf::lane_at(x[u], j), ya = rf::lane_at(y[u], j);
+                rf::lane_set(o, j, live[u] ? (OP == VA_SUB ? xa - ya : xa * ya) : 0.f);
             }
             __builtin_nontemporal_store(o, &O[(size_t)js[u] * cv + l]);
         }
@@ -167,11 +146,10 @@ __global__ __launch_bounds__(VA_TPB) void va_slot_kernel(VaArgs a, int tx_log2) 
 // grid (ceil(m k / (TY PP)), b)
 template <int VEC, bool HAS_POS, int UQ, int PP>
 __global__ __launch_bounds__(VA_TPB) void va_gweight_kernel(VaArgs a, int tx_log2) {
-    typedef typename VaVec<VEC>::T V;
+    typedef typename rf::LaneVec<VEC>::T V;
     int bx, s;
-    va_place(bx, s);
-    const int TX = 1 << tx_log2, TY = VA_TPB >> tx_log2;
-    const int lx = threadIdx.x & (TX - 1), ly = threadIdx.x >> tx_log2;
+    rf::place_2d<true>(bx, s);
+    const rf::LaneRows<VA_TPB> lr(tx_log2);
     const int c = a.c, cv = c / VEC, cwv = a.cw / VEC, groups = c / a.cw, k = a.k, S = a.m * k;
     const VaLive L{rf::ragged_count(a.len1, s, a.n), rf::ragged_count(a.len2, s, a.m)};
     const int *__restrict__ I = a.idx + (size_t)s * S;
@@ -179,18 +157,8 @@ __global__ __launch_bounds__(VA_TPB) void va_gweight_kernel(VaArgs a, int tx_log
     const V *__restrict__ P = (const V *)(a.src + (size_t)s * a.n * c);
     const V *__restrict__ E = HAS_POS ? (const V *)(a.pos + (size_t)s * S * c) : nullptr;
     V *__restrict__ O = (V *)(a.out + (size_t)s * S * a.cw);
-    int js[PP], jc[PP], qi[PP], row[PP];
-    bool live[PP];
-#pragma unroll
-    for (int u = 0; u < PP; u++) {
-        js[u] = (bx * PP + u) * TY + ly;
-        jc[u] = min(js[u], S - 1);
-        qi[u] = jc[u] / k;
-        const int r = I[jc[u]];
-        live[u] = va_live(L, qi[u], jc[u] - qi[u] * k, r);
-        row[u] = live[u] ? r : 0;
-    }
-    for (int l = lx; l < cwv; l += TX) {
+    VA_SLOTS(PP, lr)
+    for (int l = lr.lx; l < cwv; l += lr.TX) {
         double acc[PP][VEC];
 #pragma unroll
         for (int u = 0; u < PP; u++)
@@ -215,8 +183,8 @@ __global__ __launch_bounds__(VA_TPB) void va_gweight_kernel(VaArgs a, int tx_log
                 for (int u = 0; u < PP; u++)
 #pragma unroll
                     for (int j = 0; j < VEC; j++) {
-                        const float sv = HAS_POS ? va_at(v[h][u], j) + va_at(e[h][u], j) : va_at(v[h][u], j);
-                        const double term = (double)va_at(g[h][u], j) * (double)sv;
+                        const float sv = HAS_POS ? rf::lane_at(v[h][u], j) + rf::lane_at(e[h][u], j) : rf::lane_at(v[h][u], j);
+                        const double term = (double)rf::lane_at(g[h][u], j) * (double)sv;
                         acc[u][j] += in ? term : 0.0;
                     }
             }
@@ -226,7 +194,7 @@ __global__ __launch_bounds__(VA_TPB) void va_gweight_kernel(VaArgs a, int tx_log
             if (js[u] >= S) continue;
             V o;
 #pragma unroll
-            for (int j = 0; j < VEC; j++) va_set(o, j, live[u] ? (float)acc[u][j] : 0.f);
+            for (int j = 0; j < VEC; j++) rf::lane_set(o, j, live[u] ? (float)acc[u][j] : 0.f);
             __builtin_nontemporal_store(o, &O[(size_t)js[u] * cwv + l]);
         }
     }
@@ -238,12 +206,11 @@ __global__ __launch_bounds__(VA_TPB) void va_gweight_kernel(VaArgs a, int tx_log
 // grid (ceil(m / TY), b)
 template <int VEC, bool AGG, bool HAS_POS, bool WV>
 __global__ __launch_bounds__(VA_TPB) void va_query_kernel(VaArgs a, int tx_log2) {
-    typedef typename VaVec<VEC>::T V;
+    typedef typename rf::LaneVec<VEC>::T V;
     int bx, s;
-    va_place(bx, s);
-    const int TX = 1 << tx_log2, TY = VA_TPB >> tx_log2;
-    const int lx = threadIdx.x & (TX - 1), ly = threadIdx.x >> tx_log2;
-    const int i = bx * TY + ly;
+    rf::place_2d<true>(bx, s);
+    const rf::LaneRows<VA_TPB> g(tx_log2);
+    const int i = bx * g.TY + g.ly;
     if (i >= a.m) return;
     const int c = a.c, cv = c / VEC, k = a.k;
     const VaLive L{rf::ragged_count(a.len1, s, a.n), rf::ragged_count(a.len2, s, a.m)};
@@ -253,7 +220,7 @@ __global__ __launch_bounds__(VA_TPB) void va_query_kernel(VaArgs a, int tx_log2)
     const V *__restrict__ E = (const V *)(a.pos + ((size_t)s * a.m + i) * k * c);  // (not formed into an address when pos is NULL)
     const float *__restrict__ W = a.weight + ((size_t)s * a.m + i) * k * a.cw;
     V *__restrict__ O = (V *)(a.out + ((size_t)s * a.m + i) * c);
-    for (int l = lx; l < cv; l += TX) {
+    for (int l = g.lx; l < cv; l += g.TX) {
         VaWOff<VEC, WV> wo;
         if constexpr (AGG) wo = va_woff<VEC, WV>(l * VEC, a.cw);
         double acc[VEC];
@@ -286,17 +253,17 @@ __global__ __launch_bounds__(VA_TPB) void va_query_kernel(VaArgs a, int tx_log2)
                 for (int j = 0; j < VEC; j++) {
                     double term;
                     if constexpr (AGG) {
-                        const float sv = HAS_POS ? va_at(v[u], j) + va_at(e[u], j) : va_at(v[u], j);
-                        term = (double)sv * (double)va_at(w[u], j);
+                        const float sv = HAS_POS ? rf::lane_at(v[u], j) + rf::lane_at(e[u], j) : rf::lane_at(v[u], j);
+                        term = (double)sv * (double)rf::lane_at(w[u], j);
                     } else {
-                        term = (double)va_at(e[u], j);
+                        term = (double)rf::lane_at(e[u], j);
                     }
                     acc[j] += live[u] ? term : 0.0;
                 }
         }
         V o;
 #pragma unroll
-        for (int j = 0; j < VEC; j++) va_set(o, j, (float)acc[j]);
+        for (int j = 0; j < VEC; j++) rf::lane_set(o, j, (float)acc[j]);
         O[(size_t)l] = o;
     }
 }
@@ -316,11 +283,10 @@ struct VaGather {
 // grid (ceil(n / (TY VA_RPT)), b)
 template <int VEC, bool AGG, bool WV>
 __global__ __launch_bounds__(VA_TPB) void va_rows_kernel(VaGather a, int tx_log2) {
-    typedef typename VaVec<VEC>::T V;
+    typedef typename rf::LaneVec<VEC>::T V;
     int bx, s;
-    va_place(bx, s);
-    const int TX = 1 << tx_log2, TY = VA_TPB >> tx_log2;
-    const int lx = threadIdx.x & (TX - 1), ly = threadIdx.x >> tx_log2;
+    rf::place_2d<true>(bx, s);
+    const rf::LaneRows<VA_TPB> g(tx_log2);
     const int n = a.n, c = a.c, cv = c / VEC, k = a.k, S = a.S;
     const int *__restrict__ RS = a.row_start + (size_t)s * (n + 1);
     const int *__restrict__ P = a.perm + (size_t)s * S;
@@ -330,12 +296,12 @@ __global__ __launch_bounds__(VA_TPB) void va_rows_kernel(VaGather a, int tx_log2
     int r[VA_RPT], beg[VA_RPT], end[VA_RPT];
 #pragma unroll
     for (int u = 0; u < VA_RPT; u++) {
-        r[u] = (bx * VA_RPT + u) * TY + ly;
+        r[u] = (bx * VA_RPT + u) * g.TY + g.ly;
         const int rr = min(r[u], n - 1);
         beg[u] = RS[rr];
         end[u] = r[u] < n ? RS[rr + 1] : beg[u];
     }
-    for (int l = lx; l < cv; l += TX) {
+    for (int l = g.lx; l < cv; l += g.TX) {
         VaWOff<VEC, WV> wo;
         if constexpr (AGG) wo = va_woff<VEC, WV>(l * VEC, a.cw);
         double acc[VA_RPT][VEC];
@@ -377,9 +343,9 @@ __global__ __launch_bounds__(VA_TPB) void va_rows_kernel(VaGather a, int tx_log2
                     for (int j = 0; j < VEC; j++) {
                         double term;
                         if constexpr (AGG) {
-                            term = (double)va_at(v[u][q], j) * (double)va_at(w[u][q], j);
+                            term = (double)rf::lane_at(v[u][q], j) * (double)rf::lane_at(w[u][q], j);
                         } else {
-                            term = -(double)va_at(v[u][q], j);
+                            term = -(double)rf::lane_at(v[u][q], j);
                         }
                         acc[u][j] += sl[u][q] < 0 ? 0.0 : term;
                     }
@@ -391,7 +357,7 @@ __global__ __launch_bounds__(VA_TPB) void va_rows_kernel(VaGather a, int tx_log2
             if (r[u] >= n) continue;
             V o;
 #pragma unroll
-            for (int j = 0; j < VEC; j++) va_set(o, j, (float)acc[u][j]);
+            for (int j = 0; j < VEC; j++) rf::lane_set(o, j, (float)acc[u][j]);
             __builtin_nontemporal_store(o, &O[(size_t)r[u] * cv + l]);
         }
     }
@@ -405,26 +371,14 @@ bool va_channels_ok(int n, int m, int k, int c, int cw) {
     return c >= 1 && c <= VA_MAXC && cw >= 1 && c % cw == 0 && (long)m * k * c < (1L << 31) && (long)n * c < (1L << 31);
 }
 
-int va_tx_log2(int lanes) {
-    int t = 0;
-    while ((1 << t) < lanes && t < 6) t++;
-    return t;
-}
-
-bool va_all16(std::initializer_list<const void *> ps) {
-    for (const void *p : ps)
-        if (p && !rf::aligned16(p)) return false;
-    return true;
-}
-
 // the sort by source row and the gather over it
 template <bool AGG>
 int va_rows(int b, int n, int m, int k, int c, int cw, const float *g, const float *weight, const int *idx, const int *len1,
             const int *len2, float *dst, void *workspace, const char *sort_name, const char *rows_name, hipStream_t st) {
     if (int e = rfs::rows_csr_sort_masked(b, n, m, k, idx, len1, len2, workspace, sort_name, st)) return e;
-    const bool vec = c % 4 == 0 && va_all16({g, dst});
-    const bool wv = vec && cw % 4 == 0 && va_all16({weight});
-    const int tx = va_tx_log2(vec ? c / 4 : c);
+    const bool vec = rf::lane_rows_vec_ok(c, {g, dst});
+    const bool wv = vec && rf::lane_rows_vec_ok(cw, {weight});
+    const int tx = rf::lane_rows_tx_log2(vec ? c / 4 : c);
     const dim3 grid(rf::ceil_div(n, (VA_TPB >> tx) * VA_RPT), b);
     const VaGather a{n, k, c, cw, m * k, g, weight, (const int *)workspace, rfs::rows_csr_perm(b, n, workspace), dst};
     if (!vec) {
@@ -460,8 +414,8 @@ int rf_neighbor_sub(int b, int n, int m, int k, int c, const float *feat_q, cons
         !rf::aligned4(out))
         return RF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = c % 4 == 0 && va_all16({feat_q, feat_src, out});
-    const int tx = va_tx_log2(vec ? c / 4 : c);
+    const bool vec = rf::lane_rows_vec_ok(c, {feat_q, feat_src, out});
+    const int tx = rf::lane_rows_tx_log2(vec ? c / 4 : c);
     const dim3 grid(rf::ceil_div((long)m * k, (VA_TPB >> tx) * VA_PP), b);
     const VaArgs a{n, m, k, c, 1, idx, len1, len2, feat_q, feat_src, nullptr, nullptr, out};
     if (vec) {
@@ -487,8 +441,8 @@ int rf_neighbor_sub_grad(int b, int n, int m, int k, int c, const int *idx, cons
     }
     hipStream_t st = (hipStream_t)stream;
     if (grad_q) {
-        const bool vec = c % 4 == 0 && va_all16({grad_out, grad_q});
-        const int tx = va_tx_log2(vec ? c / 4 : c);
+        const bool vec = rf::lane_rows_vec_ok(c, {grad_out, grad_q});
+        const int tx = rf::lane_rows_tx_log2(vec ? c / 4 : c);
         const dim3 grid(rf::ceil_div(m, VA_TPB >> tx), b);
         const VaArgs a{n, m, k, c, 1, idx, len1, len2, nullptr, nullptr, grad_out, nullptr, grad_q};
         if (vec) {
@@ -513,9 +467,9 @@ int rf_neighbor_aggregate(int b, int n, int m, int k, int c, int cw, const float
         !rf::aligned4(len2) || !rf::aligned4(out))
         return RF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = c % 4 == 0 && va_all16({value, pos, out});
-    const bool wv = vec && cw % 4 == 0 && va_all16({weight});
-    const int tx = va_tx_log2(vec ? c / 4 : c);
+    const bool vec = rf::lane_rows_vec_ok(c, {value, pos, out});
+    const bool wv = vec && rf::lane_rows_vec_ok(cw, {weight});
+    const int tx = rf::lane_rows_tx_log2(vec ? c / 4 : c);
     const dim3 grid(rf::ceil_div(m, VA_TPB >> tx), b);
     const VaArgs a{n, m, k, c, cw, idx, len1, len2, nullptr, value, pos, weight, out};
 #define VA_GO(VEC, POS, WV) RF_LAUNCH("neighbor_agg", (va_query_kernel<VEC, true, POS, WV>), grid, dim3(VA_TPB), 0, st, a, tx)
@@ -545,9 +499,9 @@ int rf_neighbor_aggregate_grad(int b, int n, int m, int k, int c, int cw, const 
     }
     hipStream_t st = (hipStream_t)stream;
     if (grad_pos) {
-        const bool vec = c % 4 == 0 && va_all16({grad_out, grad_pos});
-        const bool wv = vec && cw % 4 == 0 && va_all16({weight});
-        const int tx = va_tx_log2(vec ? c / 4 : c);
+        const bool vec = rf::lane_rows_vec_ok(c, {grad_out, grad_pos});
+        const bool wv = vec && rf::lane_rows_vec_ok(cw, {weight});
+        const int tx = rf::lane_rows_tx_log2(vec ? c / 4 : c);
         const dim3 grid(rf::ceil_div((long)m * k, (VA_TPB >> tx) * VA_PP), b);
         const VaArgs a{n, m, k, c, cw, idx, len1, len2, grad_out, nullptr, nullptr, weight, grad_pos};
         if (!vec) {
@@ -559,8 +513,8 @@ int rf_neighbor_aggregate_grad(int b, int n, int m, int k, int c, int cw, const 
         }
     }
     if (grad_weight) {
-        const bool vec = cw % 4 == 0 && va_all16({grad_out, value, pos, grad_weight});
-        const int tx = va_tx_log2(vec ? cw / 4 : cw);
+        const bool vec = rf::lane_rows_vec_ok(cw, {grad_out, value, pos, grad_weight});
+        const int tx = rf::lane_rows_tx_log2(vec ? cw / 4 : cw);
         const int uq = cw <= 4 ? 8 : (cw <= 8 ? 4 : (cw <= 16 ? 2 : 1));  // groups per 128-byte line, at most 8
         const int pp = uq == 8 ? 1 : 2;
         const dim3 grid(rf::ceil_div((long)m * k, (VA_TPB >> tx) * pp), b);

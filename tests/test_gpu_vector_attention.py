@@ -150,6 +150,14 @@ def test_families(kind):
         print(f"\n{kind}, n = {n}, m = {m}, k = {k}, c = {c}, cw = {cw}: scatters' worst error / bar {worst:.3f}")
 
 
+def test_second_pass_with_narrow_vector_weights():
+    """c = 260 is 65 float4s, a second pass of a lane row with one live lane; widths(260) has no cw = 4: one vector of weights that
+    65 channel groups share"""
+    n, m, k, c, cw = 65, 63, 3, 260, 4
+    worst = check(n, m, k, c, cw, "random", 401)
+    print(f"\nrandom, n = {n}, m = {m}, k = {k}, c = {c}, cw = {cw}: scatters' worst error / bar {worst:.3f}")
+
+
 def test_hub_of_a_large_sample():
     """a row named by every slot of 2048 queries (the walk of one lane row) next to rows nobody names"""
     n, m, k, c, cw = 257, 2048, 16, 8, 4
