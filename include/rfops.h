@@ -1102,6 +1102,60 @@ size_t rf_knn_feature_workspace_bytes(int b, int n, int m, int c, int k);
 int rf_knn_feature(int b, int n, int m, int c, int k, const float *feat1, const float *feat2, const int *len1, const int *len2,
                    float *val, int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream);
 
+/* ---- surface normals: PCA of every point's k-neighbourhood, and normal consistency -----------
+ * rf_local_pca: per query the eigen-decomposition of the covariance of the points its idx row names (normals.hip).
+ * xyz (b,n,3) the source points; idx (b,m,k) int32 what rf_knn* returned for m queries -- for one cloud knn_point of the
+ * cloud against itself, the point itself included.  The query coordinates are not an argument: the covariance is taken about
+ * the neighbourhood's own mean.  viewpoint (b,3) or NULL.  normals (b,m,3); eigenvalues (b,m,3) ascending; axes (b,m,3,3) or
+ * NULL: the three eigenvectors as rows, in the order of the eigenvalues.
+ * Ragged batches, knn_point's rule exactly: len1 = source points per sample, len2 = queries, device arrays of b ints clamped
+ * into [1, n] / [1, m] (either may be NULL), read on the device.  kv = min(k, len1[i]) slots of a row are live; a live slot
+ * whose index is outside [0, len1[i]) is skipped and does not count towards kv', the number of slots used; kv' == 0 is a
+ * non-finite neighbourhood (below).  Rows j >= len2[i] are written as zeros and their idx rows are not read; source rows
+ * behind len1[i] are not read.
+ * The arithmetic per query, everything in double, every product, sum, quotient and root one separately rounded operation,
+ * slots in ascending t:
+ *   1. mean        s = +0.0; s = s + (double)x_t per axis; mu = s / (double)kv'.
+ *   2. covariance  d_t = (double)x_t - mu; for the six entries of the upper triangle acc = +0.0; acc = acc + (d_a * d_b);
+ *                  C_ab = acc / (double)kv'.  If any of the six is not finite the neighbourhood is NON-FINITE: eigenvalues =
+ *                  three canonical quiet NaNs (0x7fc00000), normals and axes = +0, and nothing else is computed.
+ *   3. cyclic Jacobi, exactly 6 sweeps from A = C, V = I; a sweep rotates the pairs (p,q) = (0,1), (0,2), (1,2) in that
+ *      order; a pair with A_pq == 0 is skipped, otherwise
+ *        theta = (A_qq - A_pp) / (2.0 * A_pq);  t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0))
+ *        (no branch: theta * theta = inf gives t = +-0);  c = 1.0 / sqrt(t * t + 1.0);  s = t * c;  h = t * A_pq;
+ *        A_pp = A_pp - h;  A_qq = A_qq + h;  A_pq = 0;  with r the third index
+ *        (A_rp, A_rq) <- (c * A_rp - s * A_rq, s * A_rp + c * A_rq) from the old values, and for each row i of V
+ *        (V_ip, V_iq) <- (c * V_ip - s * V_iq, s * V_ip + c * V_iq).
+ *      (A numpy restatement leaves every off-diagonal entry exactly 0 after the sixth sweep on planes, lines, duplicates,
+ *      balls and clouds scaled by 1e18 and 1e-30: tests/test_normals_host.py.)
+ *   4. order       eigenvalue w is A_ww, its vector column w of V; ascending by (value, w).  A tiny negative smallest
+ *                  eigenvalue is returned as it is.
+ *   5. sign        every vector gets the canonical sign: its component of largest magnitude positive, a tie to the lowest
+ *                  axis, a zero vector as it is (negation only: no rounding).  With a viewpoint v the NORMAL ONLY (vector 0)
+ *                  is then negated when ((v_x - mu_x) * n_x + (v_y - mu_y) * n_y) + (v_z - mu_z) * n_z < 0; row 0 of axes
+ *                  follows it.
+ *   6. store       every output is the double rounded once to fp32.
+ * One launch, no workspace, no host synchronisation (capturable); two calls return the same bits, a sample does not depend
+ * on its batch, a ragged call equals the call on the slices.
+ * Domain: 1 <= k <= 64, 1 <= n, m <= 65536, 1 <= b <= 65535 (b == 0 is RF_OK); anything else is RF_EINVAL before any HIP
+ * call, as is a NULL tensor (len1, len2, viewpoint and axes may be NULL) and a tensor or count array not 4-byte aligned.
+ *
+ * rf_nn_normal_consistency: nrm1 (b,n,3) / nrm2 (b,m,3) the normals of two clouds, idx1 (b,n) / idx2 (b,m) the indices of
+ * rf_nn_distance_lengths; len1 / len2 as there.  out (b,4), L1 / L2 the clamped counts:
+ *   0  abs12    = (1/L1) sum_{j < L1} |n1[j] . n2[idx1[j]]|        1  abs21, the other direction (over L2)
+ *   2  signed12 = (1/L1) sum_{j < L1}  n1[j] . n2[idx1[j]]         3  signed21
+ * The dot is ((a_x b_x) + (a_y b_y)) + (a_z b_z) on the values widened to double; the sum is in double in one fixed order,
+ * divided once and rounded once to fp32: two calls return the same bits and a sample does not depend on its batch.  Slots
+ * behind a count are not read; a slot whose index is outside [0, L) of the other cloud contributes +0, and so does a pair
+ * in which either normal is all zeros (a degenerate or padded row).  No atomics, no workspace, one launch (capturable).
+ * Argument rules as rf_nn_metrics: b == 0 is RF_OK; RF_EINVAL for n < 1, m < 1, b > 65535, a NULL tensor (len1 / len2 may be
+ * NULL), a tensor or count array not 4-byte aligned; all before any HIP call. */
+#define RF_PCA_MAX_K 64
+int rf_local_pca(int b, int n, int m, int k, const float *xyz, const int *idx, const int *len1, const int *len2,
+                 const float *viewpoint, float *normals, float *eigenvalues, float *axes, rf_stream_t stream);
+int rf_nn_normal_consistency(int b, int n, int m, const float *nrm1, const float *nrm2, const int *idx1, const int *idx2,
+                             const int *len1, const int *len2, float *out, rf_stream_t stream);
+
 /* -------------------------------------------------- interpolation (tf_ops/interpolation) - */
 /* Replace threenn_cpu / threeinterpolate_cpu / threeinterpolate_grad_cpu
  * (tf_interpolate.cpp:60-153; CPU-only ops in the reference).  xyz1 (b,n,3) unknown,

@@ -148,6 +148,8 @@ SIGNATURES = {
     "rf_knn_grad": (_i, [_i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_knn_feature_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "rf_knn_feature": (_i, [_i, _i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
+    "rf_local_pca": (_i, [_i, _i, _i, _i] + [_vp] * 9),
+    "rf_nn_normal_consistency": (_i, [_i, _i, _i] + [_vp] * 8),
     "rf_threenn": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_threenn_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_threenn_lengths": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp, _i]),

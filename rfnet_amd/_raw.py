@@ -1983,6 +1983,70 @@ def knn_feature(k, feat1, feat2, lengths1=None, lengths2=None):
     return st.give(val), st.give(idx)
 
 
+PCA_MAX_K = 64  # RF_PCA_MAX_K (include/rfops.h)
+
+
+@H.on_input_device
+def local_pca(xyz, idx, lengths1=None, lengths2=None, viewpoint=None, want_axes=False):
+    """rf_local_pca: per row of idx (b,m,k) the eigen-decomposition of the covariance of the rows of xyz (b,n,3) it names ->
+    (normals (b,m,3), eigenvalues (b,m,3) ascending, axes (b,m,3,3) or None): cyclic Jacobi in double, every operation
+    prescribed (include/rfops.h).  idx is what knn_point returned; lengths1 / lengths2: knn_point's own counts (source points /
+    queries per sample) -- padded rows come back as zeros.  viewpoint (b,3): the normal is turned towards it."""
+    op = "LocalPca"
+    st = H.Staged()
+    a, ix = st.take(xyz, F32), st.take(idx, I32)
+    if not _shape3(a, 3):
+        raise H.invalid(f"{op} expects (b,n,3) xyz shape")
+    if not (_shape3(ix) and ix.shape[0] == a.shape[0]):
+        raise H.invalid(f"{op} expects (b,m,k) idx shape, and batch_size must match")
+    b, n, m, k = a.shape[0], a.shape[1], ix.shape[1], ix.shape[2]
+    if not 1 <= k <= PCA_MAX_K:
+        raise H.invalid(f"{op} takes 1 <= k <= {PCA_MAX_K}")
+    if not (1 <= b <= 65535 and 1 <= n <= 65536 and 1 <= m <= 65536):
+        raise H.invalid(f"{op} takes 1 <= b <= 65535 and 1..65536 points and queries")
+    vp = None
+    if viewpoint is not None:
+        vp = st.take(viewpoint, F32)
+        if tuple(vp.shape) != (b, 3):
+            raise H.invalid(f"{op} expects (b,3) viewpoint shape")
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, ix = st.up(a, ix)
+    if vp is not None:
+        vp, = st.up(vp)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    nrm, eig = H.empty((b, m, 3), F32, dev), H.empty((b, m, 3), F32, dev)
+    axes = H.empty((b, m, 3, 3), F32, dev) if want_axes else None
+    check(lib.rf_local_pca(b, n, m, k, H.ptr(a), H.ptr(ix), H.ptr(l1), H.ptr(l2), H.ptr(vp), H.ptr(nrm), H.ptr(eig), H.ptr(axes),
+                           H.stream(dev)), "rf_local_pca")
+    return st.give(nrm), st.give(eig), None if axes is None else st.give(axes)
+
+
+@H.on_input_device
+def nn_normal_consistency(normals1, normals2, idx1, idx2, lengths1=None, lengths2=None):
+    """rf_nn_normal_consistency: normals1 (b,n,3) / normals2 (b,m,3) and nn_distance's idx1 (b,n) / idx2 (b,m) -> (b,4):
+    the means of |n1 . n2[idx1]| and |n2 . n1[idx2]|, then the two signed means (include/rfops.h)."""
+    op = "NnNormalConsistency"
+    st = H.Staged()
+    a, c = st.take(normals1, F32), st.take(normals2, F32)
+    i1, i2 = st.take(idx1, I32), st.take(idx2, I32)
+    if not (_shape3(a, 3) and _shape3(c, 3) and a.shape[0] == c.shape[0]):
+        raise H.invalid(f"{op} expects (b,n,3) normals1 and (b,m,3) normals2")
+    b, n, m = a.shape[0], a.shape[1], c.shape[1]
+    if tuple(i1.shape) != (b, n) or tuple(i2.shape) != (b, m):
+        raise H.invalid(f"{op} expects (b,n) idx1 and (b,m) idx2")
+    if not (1 <= b <= 65535 and n >= 1 and m >= 1):
+        raise H.invalid(f"{op} takes 1 <= b <= 65535 and clouds of at least one point")
+    l1, l2 = _check_lengths(lengths1, b, n, "lengths1"), _check_lengths(lengths2, b, m, "lengths2")
+    dev = st.device_()
+    a, c, i1, i2 = st.up(a, c, i1, i2)
+    l1, l2 = _lengths_up(l1, dev, n), _lengths_up(l2, dev, m)
+    out = H.empty((b, 4), F32, dev)
+    check(lib.rf_nn_normal_consistency(b, n, m, H.ptr(a), H.ptr(c), H.ptr(i1), H.ptr(i2), H.ptr(l1), H.ptr(l2), H.ptr(out),
+                                       H.stream(dev)), "rf_nn_normal_consistency")
+    return st.give(out)
+
+
 @H.on_input_device
 def knn_point_grad(xyz1, xyz2, idx, grad_val, lengths1=None, lengths2=None):
     """The gradient of knn_point's val -> (grad_xyz1 (b,n,3), grad_xyz2 (b,m,3)) (rf_knn_grad).  lengths1 / lengths2: the counts

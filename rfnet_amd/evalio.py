@@ -137,6 +137,29 @@ def read_mmd_csv(path):
         return [(r[0], float(r[1]), int(r[2])) for r in rd]
 
 
+NORMALS_HEADER = ["id", "nc", "nc12", "nc21"]
+
+
+def write_normals_csv(path, rows):
+    """rows: iterable of (model_id, nc, nc12, nc21) -> normals.csv, the normal consistency of every completion with its
+    ground truth (evalrun.evaluate(normal_consistency=True)): nc12 from the completion's points, nc21 from the ground
+    truth's, nc their mean."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(NORMALS_HEADER)
+        for r in rows:
+            w.writerow([r[0]] + [repr(float(v)) for v in r[1:]])
+
+
+def read_normals_csv(path):
+    with open(path, newline="") as f:
+        rd = csv.reader(f)
+        header = next(rd)
+        assert header == NORMALS_HEADER, header
+        return [(r[0],) + tuple(float(v) for v in r[1:]) for r in rd]
+
+
 def read_results_csv(path):
     with open(path, newline="") as f:
         rd = csv.reader(f)

@@ -77,7 +77,8 @@ class GraphedForward:
 
 
 def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_pcd=False, graph=True, rng=None,
-             warm_models=10, extra_metrics=False, tau=0.01, alpha=1000.0, mmd_refs=None):
+             warm_models=10, extra_metrics=False, tau=0.01, alpha=1000.0, mmd_refs=None, normal_consistency=False,
+             normal_k=16):
     """recon_test.py's test(): returns the summary dict it prints (average time / CD / "EMD" and the
     per-category means) and writes <results_dir>/results.csv.
 
@@ -89,13 +90,17 @@ def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_
     `mmd_refs`: an (r, m, 3) array or tensor of reference clouds (a shelf of shapes, for scans without a ground
     truth).  The completions stay on the device, glue.minimal_matching (CD-L2 of the Chamfer matrix, one sort per
     cloud) runs after the loop, <results_dir>/mmd.csv gets id, mmd, ref_index and the summary `average_mmd`.  None
-    (the default): outputs exactly as before."""
+    (the default): outputs exactly as before.
+
+    `normal_consistency`: glue.normal_consistency(completion, gt, k=normal_k) per model -- both clouds' normals estimated
+    by PCA of their `normal_k` nearest neighbours -- into <results_dir>/normals.csv (id, nc, nc12, nc21) and, averaged, into
+    the summary as average_nc.  Off (the default): outputs exactly as before; on, every other file keeps its bytes."""
     dev = next(net.parameters()).device
     with open(list_path) as f:
         model_list = f.read().splitlines()
     os.makedirs(results_dir, exist_ok=True)
     fwd = None
-    rows, extra_rows, total_time = [], [], 0.0
+    rows, extra_rows, normal_rows, total_time = [], [], [], 0.0
     kept = []  # the completions, on the device (mmd_refs only)
     rng = rng if rng is not None else np.random.RandomState(0)
     for i, model_id in enumerate(model_list):
@@ -121,6 +126,9 @@ def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_
             else:
                 cd = float(glue.chamfer_big(completion, gt)[0])
             fd = float(glue.fidelity_loss(x, completion))
+            if normal_consistency:
+                nc = glue.normal_consistency(completion, gt, k=normal_k)
+                normal_rows.append((model_id, float(nc["nc"][0]), float(nc["nc12"][0]), float(nc["nc21"][0])))
         rows.append((model_id, cd, fd))
         if mmd_refs is not None:
             kept.append(completion[0].clone())  # (a replayed graph hands out the same buffer every time)
@@ -137,6 +145,9 @@ def evaluate(net, list_path, data_dir, results_dir, num_input_points=3000, save_
         evalio.write_metrics_csv(os.path.join(results_dir, "metrics.csv"), extra_rows)
         for col, key in ((3, "average_fscore"), (4, "average_hausdorff"), (5, "average_dcd")):
             extra[key] = float(np.mean([r[col] for r in extra_rows])) if extra_rows else 0.0
+    if normal_consistency:
+        evalio.write_normals_csv(os.path.join(results_dir, "normals.csv"), normal_rows)
+        extra["average_nc"] = float(np.mean([r[1] for r in normal_rows])) if normal_rows else 0.0
     if mmd_refs is not None:
         refs = torch.as_tensor(mmd_refs, dtype=torch.float32).to(dev)
         mmd_rows = []
@@ -180,6 +191,9 @@ def main(argv=None):
     ap.add_argument("--mmd_list", default=None,
                     help="a list of model ids whose complete/<id>.pcd files are the reference shelf: minimal matching "
                          "distance of every completion to it into mmd.csv (the clouds must have one size)")
+    ap.add_argument("--normal_consistency", action="store_true",
+                    help="normal consistency of every completion with its ground truth into normals.csv")
+    ap.add_argument("--normal_k", type=int, default=16, help="neighbours of the normal estimation")
     a = ap.parse_args(argv)
     from . import enable_graph_safe_runtime
     enable_graph_safe_runtime()  # before the HIP runtime starts
@@ -192,7 +206,8 @@ def main(argv=None):
             refs = np.stack([evalio.read_pcd(os.path.join(a.data_dir, "complete", "%s.pcd" % ref_id)).astype(np.float32)
                              for ref_id in f.read().splitlines() if ref_id])
     res = evaluate(net, a.list_path, a.data_dir, a.results_dir, save_pcd=a.save_pcd, graph=not a.no_graph,
-                   extra_metrics=a.extra_metrics, tau=a.tau, alpha=a.alpha, mmd_refs=refs)
+                   extra_metrics=a.extra_metrics, tau=a.tau, alpha=a.alpha, mmd_refs=refs,
+                   normal_consistency=a.normal_consistency, normal_k=a.normal_k)
     print("Average time: %f" % res["average_time_s"])
     print("Average Chamfer distance: %f" % res["average_cd"])
     print("Average Earth mover distance: %f" % res["average_emd"])
@@ -200,6 +215,8 @@ def main(argv=None):
         print("Average F-score@%g: %f" % (a.tau, res["average_fscore"]))
         print("Average Hausdorff distance: %f" % res["average_hausdorff"])
         print("Average density-aware Chamfer distance: %f" % res["average_dcd"])
+    if a.normal_consistency:
+        print("Average normal consistency (k = %d): %f" % (a.normal_k, res["average_nc"]))
     if refs is not None:
         print("Average minimal matching distance: %f" % res["average_mmd"])
     print("Chamfer distance per category")

@@ -689,6 +689,67 @@ def edge_feature(feat_q, feat_src, idx, lengths1=None, lengths2=None):
     return torch.cat((rel, centre), dim=-1)
 
 
+def _viewpoint_tensor(viewpoint, b, dev):
+    """A (3,) or (b, 3) viewpoint, tensor or sequence -> a contiguous (b, 3) fp32 tensor on `dev` (a tensor that is there stays)."""
+    if viewpoint is None:
+        return None
+    v = viewpoint if isinstance(viewpoint, torch.Tensor) else torch.as_tensor(viewpoint, dtype=torch.float32)
+    v = v.detach().to(device=dev, dtype=torch.float32)
+    if v.dim() == 1 and v.shape[0] == 3:
+        v = v.unsqueeze(0).expand(b, 3)
+    if tuple(v.shape) != (b, 3):
+        raise ValueError("viewpoint must be of shape (3,) or (batch, 3)")
+    return v.contiguous()
+
+
+def local_pca(pcd, idx, lengths1=None, lengths2=None, viewpoint=None, return_axes=False):
+    """The PCA of every neighbourhood that idx (b, m, k) names among the points of pcd (b, n, 3) -- idx is what
+    `knn_point(k, pcd, queries)` returned, and a ragged batch passes knn_point's own lengths1 / lengths2 (points / queries per
+    sample; padded rows are zeros).  Returns a dict: "normals" (b, m, 3), the unit eigenvector of the smallest eigenvalue;
+    "eigenvalues" (b, m, 3) of the neighbourhood's covariance, ascending (l0, l1, l2); with return_axes "axes" (b, m, 3, 3),
+    the three eigenvectors as rows in that order.  The surface variation of a point is l0 / (l0 + l1 + l2).
+    Every vector has a canonical sign (its largest component positive); with `viewpoint` ((3,) or (b, 3)) the normal is turned
+    towards the viewer.  A neighbourhood with a non-finite covariance gets NaN eigenvalues and a zero normal.  Cyclic Jacobi in
+    double with every operation prescribed (rf_local_pca): the same bits in every run, batch and shard.  Non-differentiable:
+    the inputs are detached."""
+    x = _cloud_tensor(pcd).detach()
+    vp = _viewpoint_tensor(viewpoint, x.shape[0], x.device)
+    nrm, eig, axes = _raw.local_pca(x, _index_tensor(idx), lengths1, lengths2, vp, want_axes=return_axes)
+    out = {"normals": nrm, "eigenvalues": eig}
+    if return_axes:
+        out["axes"] = axes
+    return out
+
+
+def estimate_normals(pcd, k=16, lengths=None, viewpoint=None):
+    """Surface normals of a cloud (b, n, 3) by PCA of every point's k nearest neighbours, the point itself included:
+    `knn_point` of the cloud against itself with its usual routing, then `local_pca` -> (normals (b, n, 3), eigenvalues
+    (b, n, 3) ascending).  k is capped at n.  lengths: points per sample of a ragged batch (rows behind a count are zeros);
+    viewpoint: (3,) or (b, 3), tensor or sequence -- normals are turned towards it, without one their largest component is
+    positive.  Non-differentiable: the cloud is detached."""
+    x = _cloud_tensor(pcd).detach()
+    _, idx = _raw.knn_point(min(int(k), int(x.shape[1])), x, x, lengths1=lengths, lengths2=lengths)
+    r = local_pca(x, idx, lengths, lengths, viewpoint)
+    return r["normals"], r["eigenvalues"]
+
+
+def normal_consistency(pcd1, pcd2, normals1=None, normals2=None, k=16, lengths1=None, lengths2=None):
+    """Normal consistency of two clouds, the third column of the reconstruction benchmarks next to Chamfer and F-score: every
+    point's normal against the normal of its nearest neighbour in the other cloud (`nn_distance_lengths`' indices).  normals1 /
+    normals2 (b, n, 3) / (b, m, 3): whichever is None is estimated with `estimate_normals(., k)`.  Returns a dict of (b,)
+    tensors: "nc12" = mean_j |n1[j] . n2[idx1[j]]|, "nc21" the other direction, "nc" = (nc12 + nc21) / 2 -- the unsigned
+    figures, for estimated normals whose sign means nothing -- and "signed12", "signed21", the means without the absolute
+    value, for clouds that carry oriented normals.  A zero normal contributes 0.  lengths1 / lengths2: points per sample of a
+    ragged batch.  Non-differentiable: the inputs are detached (rf_nn_normal_consistency)."""
+    x1, x2 = _cloud_tensor(pcd1).detach(), _cloud_tensor(pcd2).detach()
+    n1 = estimate_normals(x1, k, lengths1)[0] if normals1 is None else _cloud_tensor(normals1).detach()
+    n2 = estimate_normals(x2, k, lengths2)[0] if normals2 is None else _cloud_tensor(normals2).detach()
+    _, idx1, _, idx2 = _raw.nn_distance(x1, x2, lengths1=lengths1, lengths2=lengths2)
+    raw = _raw.nn_normal_consistency(n1, n2, idx1, idx2, lengths1, lengths2)
+    return {"nc12": raw[:, 0], "nc21": raw[:, 1], "nc": (raw[:, 0] + raw[:, 1]) / 2, "signed12": raw[:, 2],
+            "signed21": raw[:, 3]}
+
+
 class _NeighborAggregation(torch.autograd.Function):
     """rf_neighbor_aggregate / rf_neighbor_aggregate_grad: value, weight and pos carry gradients, idx does not."""
 
