@@ -2339,8 +2339,8 @@ AmLayout am_layout(int b, int n, int m, int nlevels, int mode = RF_EMD_AUTO) {
     L.nsa = L.nsb = 0;
     L.off_sa = L.off_sb = 0;
     if (L.rowsort_ok) {
-        L.nsa = rfp::sorted_view(b, n, nullptr).npad;
-        L.nsb = rfp::sorted_view(b, m, nullptr).npad;
+        L.nsa = rfp::sorted_npad(n);
+        L.nsb = rfp::sorted_npad(m);
         off = (off + 63) / 64 * 64;  // 256-byte alignment of the sorted sets
         L.off_sa = off;
         off += (rfp::sorted_bytes(b, n) + 3) / 4 + 64;
@@ -2701,7 +2701,7 @@ int rf_approxmatch_mode(int b, int n, int m, const float *xyz1, const float *xyz
     if (b < 0 || b > MAX_BATCH || n < 0 || m < 0 || nlevels <= 0 || nlevels > MAX_LEVELS || !levels_host || !emd_mode_ok(mode))
         return RF_EINVAL;
     if (b == 0 || n == 0 || m == 0) return RF_OK;
-    if (!xyz1 || !xyz2 || !match || !workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, match}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     if (workspace_bytes < rf_approxmatch_mode_workspace_bytes(b, n, m, nlevels, mode)) return RF_EWORKSPACE;
     return am_approxmatch<false>(b, n, m, xyz1, xyz2, match, levels_host, nlevels, workspace, (hipStream_t)stream, mode, nullptr,
                                  nullptr);
@@ -2760,7 +2760,7 @@ int rf_matchcost(int b, int n, int m, const float *xyz1, const float *xyz2, cons
         RF_ZERO(cost, sizeof(float) * b, s);
         return RF_OK;
     }
-    if (!xyz1 || !xyz2 || !match || !cost || !workspace) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, match, cost, workspace})) return RF_EINVAL;
     if (workspace_bytes < rf_matchcost_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     return mc_launch<false>(b, n, m, xyz1, xyz2, match, cost, workspace, s, nullptr, nullptr);
 }
@@ -2820,8 +2820,7 @@ int rf_approxmatch_lengths(int b, int n, int m, const float *xyz1, const float *
         if (!(levels_host[v] <= 0.f) || !isfinite(levels_host[v])) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
-    if (!xyz1 || !xyz2 || !match || !workspace || !rf::aligned16(workspace) || !rf::aligned4(len1) || !rf::aligned4(len2))
-        return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, match}) || !rf::workspace_ok(workspace) || !rf::all_aligned4({len1, len2})) return RF_EINVAL;
     if (workspace_bytes < rf_approxmatch_lengths_workspace_bytes(b, n, m, nlevels)) return RF_EWORKSPACE;
     return am_approxmatch<true>(b, n, m, xyz1, xyz2, match, levels_host, nlevels, workspace, (hipStream_t)stream, RF_EMD_SWEPT,
                                 len1, len2);
@@ -2834,7 +2833,7 @@ int rf_matchcost_lengths(int b, int n, int m, const float *xyz1, const float *xy
     if (b < 0 || b > MAX_BATCH || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !match || !cost || !workspace || !rf::aligned16(workspace) || !rf::aligned4(len1) || !rf::aligned4(len2))
+    if (!rf::all_given({xyz1, xyz2, match, cost}) || !rf::workspace_ok(workspace) || !rf::all_aligned4({len1, len2}))
         return RF_EINVAL;
     if (workspace_bytes < rf_matchcost_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     return mc_launch<true>(b, n, m, xyz1, xyz2, match, cost, workspace, (hipStream_t)stream, len1, len2);
@@ -2845,7 +2844,7 @@ int rf_matchcost_grad_lengths(int b, int n, int m, const float *xyz1, const floa
     if (b < 0 || b > MAX_BATCH || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !match || !grad1 || !grad2 || !rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, match, grad1, grad2}) || !rf::all_aligned4({len1, len2})) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     RF_ZERO(grad1, sizeof(float) * 3 * (size_t)b * n, s);
     RF_ZERO(grad2, sizeof(float) * 3 * (size_t)b * m, s);
@@ -2997,7 +2996,7 @@ int rf_earth_mover_mode(int b, int n, int m, const float *xyz1, const float *xyz
         RF_ZERO(cost, sizeof(float) * b, s);
         return RF_OK;
     }
-    if (!xyz1 || !xyz2 || !workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     if (workspace_bytes < rf_earth_mover_mode_workspace_bytes(b, n, m, mode)) return RF_EWORKSPACE;
     return emd_run<false>(b, n, m, xyz1, xyz2, cost, grad1, grad2, workspace, s, mode, nullptr, nullptr);
 }
@@ -3011,8 +3010,7 @@ int rf_earth_mover_lengths(int b, int n, int m, const float *xyz1, const float *
     if ((grad1 == nullptr) != (grad2 == nullptr)) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
-    if (!xyz1 || !xyz2 || !cost || !workspace || !rf::aligned16(workspace) || !rf::aligned4(len1) || !rf::aligned4(len2))
-        return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, cost}) || !rf::workspace_ok(workspace) || !rf::all_aligned4({len1, len2})) return RF_EINVAL;
     if (workspace_bytes < rf_earth_mover_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (grad1) {

@@ -301,7 +301,7 @@ int rf_auctionmatch(int b, int n, const float *xyz1, const float *xyz2, int *mat
     if (b < 0 || n < 0) return RF_EINVAL;
     if (b == 0 || n == 0) return RF_OK;
     if (!rf_auctionmatch_supported(n)) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !matchl || !matchr) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, matchl, matchr})) return RF_EINVAL;
     (void)workspace; (void)workspace_bytes;
     RF_LAUNCH("auction_match", auction_kernel, dim3(b), dim3(AT), 0, (hipStream_t)stream, n, xyz1, xyz2,
               matchl, matchr);
@@ -314,7 +314,7 @@ int rf_selectionsort(int b, int n, int m, int k, const float *dist, int *outi, f
     const long nrows = (long)b * m;
     if (nrows == 0 || n == 0) return RF_OK;
     if (n > SS_MAXN) return RF_EINVAL;
-    if (!dist || !outi || !out) return RF_EINVAL;
+    if (!rf::all_given({dist, outi, out})) return RF_EINVAL;
     RF_LAUNCH("selection_sort", selection_sort_kernel, dim3((unsigned)nrows), dim3(64), 0, (hipStream_t)stream,
               n, k, nrows, dist, outi, out);
     return RF_OK;

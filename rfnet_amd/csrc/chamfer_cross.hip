@@ -324,8 +324,22 @@ __global__ __launch_bounds__(CX_WAVES * 64) void chamfer_cross_reduce_kernel(CxR
     }
 }
 
-size_t cx_rec_bytes(int s, int r, int npad) {
-    return rf::align256((size_t)s * (size_t)r * (size_t)(npad / 64) * CX_REC * sizeof(unsigned));
+size_t cx_rec_bytes(int s, int r, int npad) { return (size_t)s * (size_t)r * (size_t)(npad / 64) * CX_REC * sizeof(unsigned); }
+
+// sorted(s, n) | sorted(r, m) | cloud boxes (s + r, 8) | records of direction 1 | records of direction 2
+struct CxLayout {
+    size_t sorted1, sorted2, cbox, rec1, rec2, total;
+};
+CxLayout cx_layout(int s, int r, int n, int m) {
+    rf::Layout w;
+    CxLayout l;
+    l.sorted1 = w.add(rfp::sorted_bytes(s, n));
+    l.sorted2 = w.add(rfp::sorted_bytes(r, m));
+    l.cbox = w.add(((size_t)s + (size_t)r) * 8 * sizeof(float));
+    l.rec1 = w.add(cx_rec_bytes(s, r, rfp::sorted_npad(n)));
+    l.rec2 = w.add(cx_rec_bytes(s, r, rfp::sorted_npad(m)));
+    l.total = w.total;
+    return l;
 }
 
 }  // namespace
@@ -334,8 +348,7 @@ extern "C" {
 
 size_t rf_chamfer_cross_workspace_bytes(int s, int r, int n, int m) {
     if (s <= 0 || r <= 0 || n <= 0 || m <= 0 || n > rfp::kMaxPoints || m > rfp::kMaxPoints) return 0;
-    return rfp::sorted_bytes(s, n) + rfp::sorted_bytes(r, m) + rf::align256(((size_t)s + (size_t)r) * 8 * sizeof(float)) +
-           cx_rec_bytes(s, r, rfp::sorted_view(s, n, nullptr).npad) + cx_rec_bytes(s, r, rfp::sorted_view(r, m, nullptr).npad);
+    return cx_layout(s, r, n, m).total;
 }
 
 int rf_chamfer_cross(int s, int r, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
@@ -343,25 +356,18 @@ int rf_chamfer_cross(int s, int r, int n, int m, const float *xyz1, const float 
     if (s < 0 || r < 0 || n < 0 || m < 0) return RF_EINVAL;
     if (s == 0 || r == 0) return RF_OK;
     if (n < 1 || m < 1 || n > rfp::kMaxPoints || m > rfp::kMaxPoints || s > 65535 || r > 65535) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !out) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(out) || !rf::aligned4(len1) || !rf::aligned4(len2))
-        return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
-    if (workspace_bytes < rf_chamfer_cross_workspace_bytes(s, r, n, m)) return RF_EWORKSPACE;
+    if (!rf::tensors_ok({xyz1, xyz2, out}, {len1, len2}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
+    const CxLayout l = cx_layout(s, r, n, m);
+    if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
 
-    // workspace: sorted(s, n) | sorted(r, m) | cloud boxes (s + r, 8) | records of direction 1 | records of direction 2
     const bool self = xyz1 == xyz2 && len1 == len2 && s == r && n == m;
     char *w = (char *)workspace;
-    const rfp::Sorted s1 = rfp::sorted_view(s, n, w);
-    w += rfp::sorted_bytes(s, n);
-    const rfp::Sorted s2 = self ? s1 : rfp::sorted_view(r, m, w);
-    w += rfp::sorted_bytes(r, m);
-    float *cbox = (float *)w;
-    w += rf::align256(((size_t)s + (size_t)r) * 8 * sizeof(float));
-    unsigned *rec1 = (unsigned *)w;
-    w += cx_rec_bytes(s, r, s1.npad);
-    unsigned *rec2 = self ? rec1 : (unsigned *)w;
+    const rfp::Sorted s1 = rfp::sorted_view(s, n, w + l.sorted1);
+    const rfp::Sorted s2 = self ? s1 : rfp::sorted_view(r, m, w + l.sorted2);
+    float *cbox = (float *)(w + l.cbox);
+    unsigned *rec1 = (unsigned *)(w + l.rec1);
+    unsigned *rec2 = self ? rec1 : (unsigned *)(w + l.rec2);
 
     // the sorts: each collection once, with its counts; no ball query reads these sets (flag = false)
     if (int e = rfp::sort_sets(s, 1, &n, &xyz1, &s1, st, nullptr, len1 ? &len1 : nullptr, false)) return e;

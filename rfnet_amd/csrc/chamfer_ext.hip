@@ -224,7 +224,7 @@ int run_forward(int b, int n, int m, const float *xyz1, const float *xyz2, const
                 hipStream_t s) {
     const FwdPlan p = plan_forward(b, n, m, dirs, sorted1 != nullptr, sorted2 != nullptr);
     if (workspace_bytes < p.bytes || (p.bytes && !workspace)) return RF_EWORKSPACE;
-    if (!rf::aligned16(workspace) || !rf::aligned16(sorted1) || !rf::aligned16(sorted2)) return RF_EINVAL;
+    if (!rf::all_aligned16({workspace, sorted1, sorted2})) return RF_EINVAL;
     char *w = (char *)workspace;
     if (!p.culled)
         return rfd::dense_nn_distance(b, n, m, xyz1, xyz2, dist1, idx1, dist2, idx2, w + p.off_dense,
@@ -283,7 +283,7 @@ int rf_nn_distance_dir(int b, int n, int m, const float *xyz1, const float *xyz2
 size_t rf_nn_sort_bytes(int b, int n) { return rfp::sorted_bytes(b, n); }
 
 int rf_nn_sort(int b, int n, const float *xyz, void *sorted, size_t sorted_bytes, rf_stream_t stream) {
-    if (b <= 0 || n <= 0 || n > rfp::kMaxPoints || !xyz || !sorted || !rf::aligned16(sorted)) return RF_EINVAL;
+    if (b <= 0 || n <= 0 || n > rfp::kMaxPoints || !xyz || !rf::workspace_ok(sorted)) return RF_EINVAL;
     if (sorted_bytes < rfp::sorted_bytes(b, n)) return RF_EWORKSPACE;
     const rfp::Sorted v = rfp::sorted_view(b, n, sorted);
     return rfp::sort_sets(b, 1, &n, &xyz, &v, (hipStream_t)stream, nullptr);
@@ -291,7 +291,7 @@ int rf_nn_sort(int b, int n, const float *xyz, void *sorted, size_t sorted_bytes
 
 int rf_nn_distance_sorted(int b, int n, int m, const void *sorted1, const void *sorted2, float *dist1, int *idx1,
                           float *dist2, int *idx2, rf_stream_t stream) {
-    if (!rfp::pruned_supported(b, n, m) || !sorted1 || !sorted2 || !rf::aligned16(sorted1) || !rf::aligned16(sorted2)) return RF_EINVAL;
+    if (!rfp::pruned_supported(b, n, m) || !rf::workspace_ok(sorted1) || !rf::workspace_ok(sorted2)) return RF_EINVAL;
     const int dirs = dirs_of(dist1 && idx1, dist2 && idx2);
     if (!dirs) return RF_EINVAL;
     return rfp::sweep_sorted(b, n, m, rfp::sorted_view(b, n, sorted1), rfp::sorted_view(b, m, sorted2),
@@ -313,8 +313,7 @@ int rf_chamfer_step(int b, int n, int m, const float *xyz1, const float *xyz2, c
     // sorted position and its upstream gradient, and the backward runs in sorted index space
     // (nnp_grad_sorted_kernel).  Other shapes: the two ops back to back.
     if (b > 0 && n > 0 && m > 0 && rfd::resolve_mode(b, n, m, RF_NN_AUTO) == RF_NN_CULLED) {
-        if (!xyz1 || !xyz2 || !dist1 || !idx1 || !dist2 || !idx2 || !workspace || !grad_dist1 || !grad_dist2 ||
-            !grad_xyz1 || !grad_xyz2)
+        if (!rf::all_given({xyz1, xyz2, dist1, idx1, dist2, idx2, workspace, grad_dist1, grad_dist2, grad_xyz1, grad_xyz2}))
             return RF_EINVAL;
         // A caller that sized the workspace with rf_nn_distance_workspace_bytes (rounds 1-2: the two sizes were equal)
         // still gets its step: the two ops back to back, same results -- not RF_EWORKSPACE.
@@ -340,7 +339,7 @@ int rf_chamfer_loss(int b, int n, int m, const float *xyz1, const float *xyz2, c
                     void *workspace, size_t workspace_bytes, rf_stream_t stream) {
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (n == 0 || m == 0 || !xyz1 || !xyz2 || !loss) return RF_EINVAL;
+    if (n == 0 || m == 0 || !rf::all_given({xyz1, xyz2, loss})) return RF_EINVAL;
     const int dirs = dirs_of(dist1 && idx1, dist2 && idx2);
     if (!dirs) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
@@ -375,10 +374,10 @@ int rf_chamfer_loss_lengths(int b, int n, int m, const float *xyz1, const float 
                             void *workspace, size_t workspace_bytes, rf_stream_t stream) {
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (n == 0 || m == 0 || !xyz1 || !xyz2 || !loss || !workspace) return RF_EINVAL;
+    if (n == 0 || m == 0 || !rf::all_given({xyz1, xyz2, loss, workspace})) return RF_EINVAL;
     const int dirs = dirs_of(dist1 && idx1, dist2 && idx2);
     if (!dirs) return RF_EINVAL;
-    if (!rf::aligned16(workspace) || !rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
+    if (!rf::aligned16(workspace) || !rf::all_aligned4({len1, len2})) return RF_EINVAL;
     if (workspace_bytes < rfd::ragged_workspace_bytes(b, n, m, RF_NN_AUTO, dirs)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     float *d1 = (dirs & 1) ? dist1 : nullptr, *d2 = (dirs & 2) ? dist2 : nullptr;
@@ -401,7 +400,7 @@ int rf_chamfer_loss_grad_lengths(int b, int n, int m, const float *xyz1, const f
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0 || !grad_loss) return RF_EINVAL;
-    if (!rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
+    if (!rf::all_aligned4({len1, len2})) return RF_EINVAL;
     const rfd::GradSource g{nullptr, nullptr, dist1, dist2, grad_loss};
     // both count arrays NULL: the kernel of rf_chamfer_loss_grad, same results
     return rfd::nn_distance_grad(b, n, m, xyz1, xyz2, g, dist1 ? idx1 : nullptr, dist2 ? idx2 : nullptr, grad_xyz1,
@@ -419,7 +418,7 @@ int rf_merge_layer(int b, int n, int m, const float *rawpts, const float *newpts
                    rf_stream_t stream) {
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0 || m == 0) return RF_OK;
-    if (n == 0 || !rawpts || !newpts || !decfactor_dev || !refined || !idx2 || !workspace) return RF_EINVAL;
+    if (n == 0 || !rf::all_given({rawpts, newpts, decfactor_dev, refined, idx2, workspace})) return RF_EINVAL;
     const size_t dbytes = merge_dist_bytes(b, m);
     if (workspace_bytes < dbytes) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -440,7 +439,7 @@ int rf_merge_layer_grad(int b, int n, int m, const float *rawpts, const float *n
     const bool empty = m == 0 || n == 0;
     if (int e = merge_grad_zero(b, n, empty, grad_dec, grad_raw, s)) return e;
     if (empty) return RF_OK;
-    if (!rawpts || !newpts || !decfactor_dev || !idx2 || !grad_refined || !grad_newpts) return RF_EINVAL;
+    if (!rf::all_given({rawpts, newpts, decfactor_dev, idx2, grad_refined, grad_newpts})) return RF_EINVAL;
     RF_LAUNCH("merge_pull_grad", merge_pull_grad_kernel<false>, dim3(b), dim3(MG_TPB), 0, s, n, m, rawpts, newpts, idx2,
               decfactor_dev, grad_refined, grad_newpts, grad_dec, grad_raw, nullptr, nullptr);
     return RF_OK;
@@ -457,8 +456,8 @@ int rf_merge_layer_lengths(int b, int n, int m, const float *rawpts, const float
                            size_t workspace_bytes, rf_stream_t stream) {
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0 || m == 0) return RF_OK;
-    if (n == 0 || !rawpts || !newpts || !decfactor_dev || !refined || !idx2 || !workspace) return RF_EINVAL;
-    if (!rf::aligned16(workspace) || !rf::aligned4(len_raw) || !rf::aligned4(len_new)) return RF_EINVAL;
+    if (n == 0 || !rf::all_given({rawpts, newpts, decfactor_dev, refined, idx2, workspace})) return RF_EINVAL;
+    if (!rf::aligned16(workspace) || !rf::all_aligned4({len_raw, len_new})) return RF_EINVAL;
     const size_t dbytes = merge_dist_bytes(b, m);
     if (workspace_bytes < rf_merge_layer_lengths_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -476,9 +475,9 @@ int rf_merge_layer_grad_lengths(int b, int n, int m, const float *rawpts, const 
                                 rf_stream_t stream) {
     if (bad_sizes(b, n, m)) return RF_EINVAL;
     if (b == 0) return RF_OK;
-    if (!grad_dec || !rf::aligned4(len_raw) || !rf::aligned4(len_new)) return RF_EINVAL;
+    if (!grad_dec || !rf::all_aligned4({len_raw, len_new})) return RF_EINVAL;
     const bool empty = m == 0 || n == 0;
-    if (!empty && (!rawpts || !newpts || !decfactor_dev || !idx2 || !grad_refined || !grad_newpts)) return RF_EINVAL;
+    if (!empty && !rf::all_given({rawpts, newpts, decfactor_dev, idx2, grad_refined, grad_newpts})) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (int e = merge_grad_zero(b, n, empty, grad_dec, grad_raw, s)) return e;
     if (empty) return RF_OK;

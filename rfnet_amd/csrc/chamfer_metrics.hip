@@ -237,7 +237,7 @@ __global__ void chamfer_metrics_gradw_kernel(int b, int n, int m, const int *__r
 // the argument rules shared by the three entries (all before any HIP call); RF_OK with b == 0 is the caller's
 int cm_check(int b, int n, int m, const int *len1, const int *len2, const void *workspace, float alpha) {
     if (b < 0 || n < 1 || m < 1 || b > 65535) return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace) || !rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
+    if (!rf::workspace_ok(workspace) || !rf::all_aligned4({len1, len2})) return RF_EINVAL;
     if (!(alpha >= 0.f) || !isfinite(alpha)) return RF_EINVAL;
     return RF_OK;
 }
@@ -259,10 +259,14 @@ int cm_epilogue(int b, int n, int m, float *dist1, int *idx1, float *dist2, int 
     return RF_OK;
 }
 
-bool any_unaligned4(std::initializer_list<const void *> ps) {
-    for (const void *p : ps)
-        if (!rf::aligned4(p)) return true;
-    return false;
+// rf_chamfer_metrics_grad's workspace: the per-point weights of the two directions, which nn_distance_grad then scatters
+struct CmGradLayout {
+    size_t gd1, gd2, total;
+};
+CmGradLayout cm_grad_layout(int b, int n, int m) {
+    rf::Layout w;
+    const size_t gd1 = w.add(sizeof(float) * (size_t)b * n), gd2 = w.add(sizeof(float) * (size_t)b * m);
+    return {gd1, gd2, w.total};
 }
 
 }  // namespace
@@ -283,8 +287,7 @@ int rf_nn_metrics(int b, int n, int m, const float *dist1, const int *idx1, cons
     if (b == 0) return RF_OK;
     if (int e = cm_check(b, n, m, len1, len2, workspace, alpha)) return e;
     if (!(thr2 >= 0.f)) return RF_EINVAL;  // NaN or negative; +inf is "every point"
-    if (!dist1 || !idx1 || !dist2 || !idx2 || !metrics || !count1 || !count2) return RF_EINVAL;
-    if (any_unaligned4({dist1, idx1, dist2, idx2, metrics, count1, count2})) return RF_EINVAL;
+    if (!rf::tensors_ok({dist1, idx1, dist2, idx2, metrics, count1, count2})) return RF_EINVAL;
     if (workspace_bytes < rf_nn_metrics_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     // (pad = 0: nothing is written through the const inputs)
     return cm_epilogue(b, n, m, const_cast<float *>(dist1), const_cast<int *>(idx1), const_cast<float *>(dist2),
@@ -303,8 +306,7 @@ int rf_chamfer_metrics(int b, int n, int m, const float *xyz1, const float *xyz2
     if (b == 0) return RF_OK;
     if (int e = cm_check(b, n, m, len1, len2, workspace, alpha)) return e;
     if (!(thr2 >= 0.f)) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !dist1 || !idx1 || !dist2 || !idx2 || !metrics || !count1 || !count2) return RF_EINVAL;
-    if (any_unaligned4({xyz1, xyz2, dist1, idx1, dist2, idx2, metrics, count1, count2})) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2, dist1, idx1, dist2, idx2, metrics, count1, count2})) return RF_EINVAL;
     if (workspace_bytes < rf_chamfer_metrics_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     // the culled route leaves the padded slots to the epilogue (the dense sweep writes them itself)
@@ -318,7 +320,7 @@ int rf_chamfer_metrics(int b, int n, int m, const float *xyz1, const float *xyz2
 
 size_t rf_chamfer_metrics_grad_workspace_bytes(int b, int n, int m) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
-    return rf::align256(sizeof(float) * (size_t)b * n) + rf::align256(sizeof(float) * (size_t)b * m);
+    return cm_grad_layout(b, n, m).total;
 }
 
 int rf_chamfer_metrics_grad(int b, int n, int m, const float *xyz1, const float *xyz2, const int *len1, const int *len2,
@@ -327,15 +329,13 @@ int rf_chamfer_metrics_grad(int b, int n, int m, const float *xyz1, const float 
                             float *grad_xyz2, void *workspace, size_t workspace_bytes, rf_stream_t stream) {
     if (b == 0) return RF_OK;
     if (int e = cm_check(b, n, m, len1, len2, workspace, alpha)) return e;
-    if (!xyz1 || !xyz2 || !dist1 || !idx1 || !dist2 || !idx2 || !count1 || !count2 || !grad_metrics || !grad_xyz1 ||
-        !grad_xyz2)
+    if (!rf::tensors_ok({xyz1, xyz2, dist1, idx1, dist2, idx2, count1, count2, grad_metrics, grad_xyz1, grad_xyz2}))
         return RF_EINVAL;
-    if (any_unaligned4({xyz1, xyz2, dist1, idx1, dist2, idx2, count1, count2, grad_metrics, grad_xyz1, grad_xyz2}))
-        return RF_EINVAL;
-    if (workspace_bytes < rf_chamfer_metrics_grad_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
+    const CmGradLayout l = cm_grad_layout(b, n, m);
+    if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    float *gd1 = (float *)workspace;
-    float *gd2 = (float *)((char *)workspace + rf::align256(sizeof(float) * (size_t)b * n));
+    float *gd1 = (float *)((char *)workspace + l.gd1);
+    float *gd2 = (float *)((char *)workspace + l.gd2);
     const long total = (long)b * n + (long)b * m;
     RF_LAUNCH("chamfer_metrics_gradw", chamfer_metrics_gradw_kernel, dim3(rf::ceil_div(total, 256)), dim3(256), 0, s, b,
               n, m, len1, len2, dist1, idx1, dist2, idx2, count1, count2, alpha, grad_metrics, gd1, gd2);

@@ -9,7 +9,8 @@
 #include <string.h>
 
 #include "../../include/rfops.h"
-#include "wave.hpp"  // ragged_count, align256 and the wave reductions / scans, each once
+#include "boundary.hpp"  // the pointer rules of the C ABI and the workspace Layout, each once (host only)
+#include "wave.hpp"      // ragged_count, align256 and the wave reductions / scans, each once
 
 namespace rf {
 
@@ -41,12 +42,6 @@ int require_device();
 // from the second replay on (tools/experiments/graph_memset_probe.py), and callers may be capturing.
 // Returns an RF_* / hipError status (runtime.hip).
 int zero_async(void *p, size_t bytes, hipStream_t s);
-
-// Workspaces and sorted-set handles are read with 16-byte vector loads at offsets that are multiples of 256: the pointer the
-// caller hands over must be 16-byte aligned (include/rfops.h; anything hipMalloc returns is).  Checked at the boundary -- a
-// misaligned sub-allocation would otherwise be a memory fault inside a kernel.
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 // Workgroup ids go round the 8 XCDs (id % 8), each with an L2 of its own.  Logical position of workgroup `id` of `total` such that
 // every XCD owns a CONTIGUOUS eighth of the logical order: workgroups that read the same sample then share one L2 instead of

@@ -322,11 +322,9 @@ int rf_emd_assign(int b, int n, const float *xyz1, const float *xyz2, const int 
     if (b < 0 || n < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n < 1 || n > RF_EA_MAX_POINTS || b > 65535) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !match12 || !match21 || !dist || !val || !cert || !info) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(len) || !rf::aligned4(match12) || !rf::aligned4(match21) ||
-        !rf::aligned4(dist) || !rf::aligned4(val) || !rf::aligned4(info) || (reinterpret_cast<uintptr_t>(cert) & 7u) != 0)
-        return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace) || max_rounds < 0) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2, match12, match21, dist, val, cert, info}, {len})) return RF_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(cert) & 7u) != 0) return RF_EINVAL;  // 64-bit words
+    if (!rf::workspace_ok(workspace) || max_rounds < 0) return RF_EINVAL;
     if (workspace_bytes < rf_emd_assign_workspace_bytes(b, n)) return RF_EWORKSPACE;
     RF_HIP(hipFuncSetAttribute((const void *)emd_assign_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)ea_lds_bytes(RF_EA_MAX_POINTS)));
@@ -340,10 +338,7 @@ int rf_emd_assign_grad(int b, int n, const float *xyz1, const float *xyz2, const
     if (b < 0 || n < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n < 1 || n > RF_EA_MAX_POINTS || b > 65535) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !match12 || !match21 || !gcost || !grad1 || !grad2) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(match12) || !rf::aligned4(match21) || !rf::aligned4(len) ||
-        !rf::aligned4(gcost) || !rf::aligned4(grad1) || !rf::aligned4(grad2))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2, match12, match21, gcost, grad1, grad2}, {len})) return RF_EINVAL;
     RF_LAUNCH("emd_assign_grad", emd_assign_grad_kernel, dim3(rf::ceil_div(n, EA_GTPB), b), dim3(EA_GTPB), 0,
               (hipStream_t)stream, n, xyz1, xyz2, match12, match21, len, gcost, grad1, grad2);
     return RF_OK;

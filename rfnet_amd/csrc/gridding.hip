@@ -309,12 +309,8 @@ int rf_gridding_loss(int b, int n, int m, int res, float lo, float hi, int mode,
     if (!gr_sizes_ok(b, n, res) || !gr_sizes_ok(b, m, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
     if (mode != RF_GR_COUNTS && mode != RF_GR_DENSITY) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !loss || !inside) return RF_EINVAL;
-    if ((grad1 == nullptr) != (grad2 == nullptr)) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(loss) || !rf::aligned4(inside) || !rf::aligned4(grad1) ||
-        !rf::aligned4(grad2) || !rf::aligned4(len1) || !rf::aligned4(len2))
-        return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2, loss, inside}, {grad1, grad2, len1, len2})) return RF_EINVAL;
+    if ((grad1 == nullptr) != (grad2 == nullptr) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     const bool grad = grad1 != nullptr;
     const GrLayout l = gr_layout(b, n, m, res, 2, grad);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;
@@ -353,9 +349,7 @@ int rf_gridding(int b, int n, int res, float lo, float hi, const float *xyz, con
     if (b == 0) return RF_OK;
     if (!gr_sizes_ok(b, n, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
-    if (!xyz || !grid || !inside) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(grid) || !rf::aligned4(inside) || !rf::aligned4(len)) return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, grid, inside}, {len}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     const GrLayout l = gr_layout(b, n, 0, res, 1, false);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -378,8 +372,7 @@ int rf_gridding_grad(int b, int n, int res, float lo, float hi, const float *xyz
     if (b == 0) return RF_OK;
     if (!gr_sizes_ok(b, n, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
-    if (!xyz || !grad_grid || !grad_xyz) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(grad_grid) || !rf::aligned4(grad_xyz) || !rf::aligned4(len)) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, grad_grid, grad_xyz}, {len})) return RF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const GrLayerGrad a{n, gr_box(res, lo, hi), xyz, len, grad_grid, grad_xyz};
     RF_LAUNCH("gridding_grad", gr_layer_grad_kernel, dim3(rf::ceil_div(n, GR_PT_TPB), b), dim3(GR_PT_TPB), 0, st, a);

@@ -286,8 +286,7 @@ int rf_cubic_feature_sampling(int b, int n, int c, int res, float lo, float hi, 
     if (b == 0) return RF_OK;
     if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
-    if (!xyz || !vol || !feat || !inside) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(vol) || !rf::aligned4(feat) || !rf::aligned4(inside) || !rf::aligned4(len)) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, vol, feat, inside}, {len})) return RF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const CfsFwd a{n, c, gr_box(res, lo, hi), xyz, len, (const unsigned *)vol, (unsigned *)feat, inside};
     RF_LAUNCH("cfs_gather", cfs_gather_kernel, dim3(rf::ceil_div(n, CFS_FWD_PTS), b), dim3(CFS_TPB), 0, st, a);
@@ -306,9 +305,7 @@ int rf_cubic_feature_sampling_grad(int b, int n, int c, int res, float lo, float
     if (b == 0) return RF_OK;
     if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
-    if (!xyz || !grad_feat || !grad_vol) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(grad_feat) || !rf::aligned4(grad_vol) || !rf::aligned4(len)) return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, grad_feat, grad_vol}, {len}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     const GrSortLayout l = gr_sort_layout(b, n, res);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -337,9 +334,7 @@ int rf_gridding_reverse(int b, int res, float lo, float hi, float eps, int compa
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
     if (!(isfinite(eps) && eps > 0.f)) return RF_EINVAL;
     if (compact != 0 && compact != 1) return RF_EINVAL;
-    if (!grid || !points || !row || !count) return RF_EINVAL;
-    if (!rf::aligned4(grid) || !rf::aligned4(points) || !rf::aligned4(row) || !rf::aligned4(count)) return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!rf::tensors_ok({grid, points, row, count}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     if (workspace_bytes < rf_gridding_reverse_workspace_bytes(b, res)) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
 
@@ -359,8 +354,7 @@ int rf_gridding_reverse_grad(int b, int res, float lo, float hi, const float *gr
     if (b == 0) return RF_OK;
     if (!gv_sizes_ok(b, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
-    if (!grid || !row || !grad_points || !grad_grid) return RF_EINVAL;
-    if (!rf::aligned4(grid) || !rf::aligned4(row) || !rf::aligned4(grad_points) || !rf::aligned4(grad_grid)) return RF_EINVAL;
+    if (!rf::tensors_ok({grid, row, grad_points, grad_grid})) return RF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const double h = ((double)hi - (double)lo) / (double)(res - 1);
     const GvGrad a{res, h, grid, row, grad_points, grad_grid};

@@ -723,8 +723,8 @@ int rf_queryballpoint_boxes(int b, int n, int m, float radius, const float *radi
     if (b < 0 || n < 0 || m < 0 || nsample <= 0) return RF_EINVAL;
     if ((long)b * m == 0) return RF_OK;
     if (n < 64 || nsample > 64 || b > 65535 || !rfp::pruned_supported(b, n, n)) return RF_EINVAL;  // the scan kernels' domain
-    if (!xyz1 || !xyz2 || !idx || !pts_cnt || !workspace || !rf::aligned16(workspace)) return RF_EINVAL;
-    if (sorted1 && !rf::aligned16(sorted1)) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, idx, pts_cnt}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
+    if (!rf::all_aligned16({sorted1})) return RF_EINVAL;
     if (workspace_bytes < rf_queryballpoint_boxes_workspace_bytes(b, n)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     rfp::Sorted so;
@@ -763,10 +763,7 @@ int rf_queryballpoint_lengths(int b, int n, int m, float radius, const float *ra
     if (b < 0 || n < 0 || m < 0 || nsample <= 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
-    if (!xyz1 || !xyz2 || !idx || !pts_cnt) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(idx) ||
-        !rf::aligned4(pts_cnt) || !rf::aligned4(radius_dev) || !rf::aligned16(workspace))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2, idx, pts_cnt}, {len1, len2, radius_dev}) || !rf::aligned16(workspace)) return RF_EINVAL;
     const int route = qb_lengths_form(b, n, nsample, form);
     if (route < 0) return RF_EINVAL;
     if (route == RF_GROUP_SCAN)
@@ -786,7 +783,7 @@ int rf_grouppoint(int b, int n, int c, int m, int nsample, const float *points, 
     long per_batch = (long)m * nsample;
     long total = (long)b * per_batch * c;
     if (total == 0) return RF_OK;
-    if (!points || !idx || !out) return RF_EINVAL;
+    if (!rf::all_given({points, idx, out})) return RF_EINVAL;
     if (c == 3 && per_batch < (1L << 30) && b <= 65535) {
         RF_LAUNCH("group_point", group_point3_kernel, dim3(rf::ceil_div((int)per_batch, 256), b), dim3(256), 0,
                   (hipStream_t)stream, n, (int)per_batch, points, idx, out);

@@ -376,8 +376,8 @@ int rf_threenn_boxes(int b, int n, int m, const float *xyz1, const float *xyz2, 
     if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0 || n == 0) return RF_OK;
     if (b > 65535 || !rfp::pruned_supported(b, n, m)) return RF_EINVAL;  // (m = 0 and huge clouds: rf_threenn)
-    if (!xyz1 || !xyz2 || !dist || !idx || !workspace || !rf::aligned16(workspace)) return RF_EINVAL;
-    if ((sorted1 && !rf::aligned16(sorted1)) || (sorted2 && !rf::aligned16(sorted2))) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, dist, idx}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
+    if (!rf::all_aligned16({sorted1, sorted2})) return RF_EINVAL;
     if (workspace_bytes < rf_threenn_boxes_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     rfp::Sorted sv[2];
@@ -413,10 +413,7 @@ int rf_threenn_lengths(int b, int n, int m, const float *xyz1, const float *xyz2
     if (b < 0 || b > 65535 || n < 0 || m < 0) return RF_EINVAL;  // the batch is grid.y
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
-    if (!xyz1 || !xyz2 || !dist || !idx) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(dist) ||
-        !rf::aligned4(idx) || !rf::aligned16(workspace))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2, dist, idx}, {len1, len2}) || !rf::aligned16(workspace)) return RF_EINVAL;
     const int route = tn_lengths_form(b, n, m, form);
     if (route < 0) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
@@ -444,7 +441,7 @@ int rf_threeinterpolate(int b, int m, int c, int n, const float *points, const i
     if (b < 0 || n < 0 || m < 0 || c < 0) return RF_EINVAL;
     long total = (long)b * n * c;
     if (total == 0) return RF_OK;
-    if (!points || !idx || !weight || !out) return RF_EINVAL;
+    if (!rf::all_given({points, idx, weight, out})) return RF_EINVAL;
     if (b <= 65535 && (long)n * c < (1L << 31) && (long)m * c < (1L << 31) && (long)n * 3 < (1L << 31)) {
         const bool vec = rf::lane_rows_vec_ok(c, {points, out});
         const int tx_log2 = rf::lane_rows_tx_log2(vec ? c / 4 : c);

@@ -288,7 +288,7 @@ extern "C" {
 
 int rf_knn(int b, int n, int m, int k, const float *xyz1, const float *xyz2, float *val, int *idx, rf_stream_t stream) {
     if (!kn_supported(b, n, m, k)) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !val || !idx) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, val, idx})) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid(rf::ceil_div(m, KN_TPB), b);
 #define KN_GO(KB) RF_LAUNCH("knn", knn_scan_kernel<KB>, grid, dim3(KN_TPB), 0, s, n, m, k, xyz1, xyz2, val, idx, rfi::Counts<false>{})
@@ -305,8 +305,8 @@ size_t rf_knn_boxes_workspace_bytes(int b, int n, int m) {
 int rf_knn_boxes(int b, int n, int m, int k, const float *xyz1, const float *xyz2, const void *sorted1, const void *sorted2,
                  float *val, int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream) {
     if (!kn_supported(b, n, m, k)) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !val || !idx || !workspace || !rf::aligned16(workspace)) return RF_EINVAL;
-    if ((sorted1 && !rf::aligned16(sorted1)) || (sorted2 && !rf::aligned16(sorted2))) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, val, idx}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
+    if (!rf::all_aligned16({sorted1, sorted2})) return RF_EINVAL;
     if (workspace_bytes < rf_knn_boxes_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     rfp::Sorted sv[2];
@@ -330,8 +330,7 @@ size_t rf_knn_grad_workspace_bytes(int b, int n, int m, int k) {
 int rf_knn_grad(int b, int n, int m, int k, const float *xyz1, const float *xyz2, const int *idx, const float *grad_val,
                 float *grad_xyz1, float *grad_xyz2, void *workspace, size_t workspace_bytes, rf_stream_t stream) {
     if (!kn_supported(b, n, m, k)) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !idx || !grad_val || !grad_xyz1 || !grad_xyz2 || !workspace || !rf::aligned16(workspace))
-        return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, idx, grad_val, grad_xyz1, grad_xyz2}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     if (workspace_bytes < rf_knn_grad_workspace_bytes(b, n, m, k)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     RF_LAUNCH("knn_grad_query", knn_grad_query_kernel<false>, dim3(rf::ceil_div(m, KG_TPB), b), dim3(KG_TPB), 0, s, n, m, k, xyz1,
@@ -359,10 +358,7 @@ int rf_knn_lengths(int b, int n, int m, int k, const float *xyz1, const float *x
                    int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream, int form) {
     if (b == 0 && n >= 0 && m >= 0 && k >= 0) return RF_OK;
     if (!kn_supported(b, n, m, k)) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !val || !idx) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(val) ||
-        !rf::aligned4(idx) || !rf::aligned16(workspace))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2, val, idx}, {len1, len2}) || !rf::aligned16(workspace)) return RF_EINVAL;
     const int route = kn_lengths_form(n, m, k, form);
     if (route < 0) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
@@ -398,9 +394,8 @@ int rf_knn_grad_lengths(int b, int n, int m, int k, const float *xyz1, const flo
                         size_t workspace_bytes, rf_stream_t stream) {
     if (b == 0 && n >= 0 && m >= 0 && k >= 0) return RF_OK;
     if (!kn_supported(b, n, m, k)) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !idx || !grad_val || !grad_xyz1 || !grad_xyz2 || !workspace || !rf::aligned16(workspace))
-        return RF_EINVAL;
-    if (!rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, idx, grad_val, grad_xyz1, grad_xyz2}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
+    if (!rf::all_aligned4({len1, len2})) return RF_EINVAL;
     if (workspace_bytes < rf_knn_grad_lengths_workspace_bytes(b, n, m, k)) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     RF_LAUNCH("knn_grad_query_lengths", knn_grad_query_kernel<true>, dim3(rf::ceil_div(m, KG_TPB), b), dim3(KG_TPB), 0, s, n, m, k,

@@ -242,7 +242,14 @@ bool kf_supported(int b, int n, int m, int c, int k) {
     return b >= 1 && b <= 65535 && n >= 1 && n <= 65536 && m >= 1 && m <= 65536 && c >= 1 && c <= KF_MAXC && k >= 1 &&
            k <= KN_MAXK && k <= n;
 }
-size_t kf_sq1_bytes(int b, int n) { return rf::align256((size_t)b * n * sizeof(float)); }
+struct KfLayout {
+    size_t sq1, sq2, total;  // the squared norms of feat1's rows, of feat2's
+};
+KfLayout kf_layout(int b, int n, int m) {
+    rf::Layout w;
+    const size_t sq1 = w.add((size_t)b * n * sizeof(float)), sq2 = w.add((size_t)b * m * sizeof(float));
+    return {sq1, sq2, w.total};
+}
 
 }  // namespace
 
@@ -250,20 +257,18 @@ extern "C" {
 
 size_t rf_knn_feature_workspace_bytes(int b, int n, int m, int c, int k) {
     if (!kf_supported(b, n, m, c, k)) return 0;
-    return kf_sq1_bytes(b, n) + rf::align256((size_t)b * m * sizeof(float));
+    return kf_layout(b, n, m).total;
 }
 
 int rf_knn_feature(int b, int n, int m, int c, int k, const float *feat1, const float *feat2, const int *len1, const int *len2,
                    float *val, int *idx, void *workspace, size_t workspace_bytes, rf_stream_t stream) {
     if (!kf_supported(b, n, m, c, k)) return RF_EINVAL;
-    if (!feat1 || !feat2 || !val || !idx || !workspace || !rf::aligned16(workspace)) return RF_EINVAL;
-    if (!rf::aligned4(feat1) || !rf::aligned4(feat2) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(val) ||
-        !rf::aligned4(idx))
-        return RF_EINVAL;
-    if (workspace_bytes < rf_knn_feature_workspace_bytes(b, n, m, c, k)) return RF_EWORKSPACE;
+    if (!rf::tensors_ok({feat1, feat2, val, idx}, {len1, len2}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
+    const KfLayout l = kf_layout(b, n, m);
+    if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    float *sq1 = (float *)workspace;
-    float *sq2 = (float *)((char *)workspace + kf_sq1_bytes(b, n));
+    float *sq1 = (float *)((char *)workspace + l.sq1);
+    float *sq2 = (float *)((char *)workspace + l.sq2);
     const long rows1 = (long)b * n, rows2 = (long)b * m;
     RF_LAUNCH("knn_feature_sq", knn_feature_sq_kernel, dim3(rf::ceil_div(rows1 + rows2, KF_SQ_TPB)), dim3(KF_SQ_TPB), 0, s, rows1,
               rows2, c, feat1, feat2, sq1, sq2);

@@ -347,10 +347,7 @@ int rf_expansion_penalty(int b, int n, int S, float alpha, const float *xyz, flo
     if (b < 0 || n < 0 || S < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (!rf_expansion_penalty_supported(n, S) || !alpha_ok(alpha)) return RF_EINVAL;
-    if (!xyz || !dist || !father || !length || !mean || !info) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(dist) || !rf::aligned4(father) || !rf::aligned4(length) || !rf::aligned4(mean) ||
-        !rf::aligned4(info))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, dist, father, length, mean, info})) return RF_EINVAL;
     const int P = n / S;
     const long long patches = (long long)b * P;
     if (patches > 2147483647LL) return RF_EINVAL;
@@ -372,9 +369,7 @@ int rf_expansion_penalty_grad(int b, int n, int S, const float *xyz, const int *
     if (b < 0 || n < 0 || S < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (!rf_expansion_penalty_supported(n, S)) return RF_EINVAL;
-    if (!xyz || !father || !dist || !gdist || !grad) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(father) || !rf::aligned4(dist) || !rf::aligned4(gdist) || !rf::aligned4(grad))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, father, dist, gdist, grad})) return RF_EINVAL;
     const int P = n / S;
     const long long patches = (long long)b * P;
     if (patches > 2147483647LL) return RF_EINVAL;
@@ -390,10 +385,7 @@ int rf_mds(int b, int n, int m, const float *xyz, const float *sigma, const int 
     if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (!rf_mds_supported(n) || m < 1) return RF_EINVAL;
-    if (!xyz || !sigma || !out || !info) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(sigma) || !rf::aligned4(len) || !rf::aligned4(out) || !rf::aligned4(info) ||
-        !rf::aligned4(new_xyz))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, sigma, out, info}, {len, new_xyz})) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
 #define MDS_GO(NT, PPT)                                                                                              \
     do {                                                                                                             \

@@ -883,7 +883,7 @@ int rf_nn_distance_mode(int b, int n, int m, const float *xyz1, const float *xyz
     if (mode != RF_NN_AUTO && mode != RF_NN_DENSE && mode != RF_NN_CULLED) return RF_EINVAL;
     if (b == 0 || (n == 0 && m == 0)) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // a nearest neighbour in an empty set is undefined
-    if (!xyz1 || !xyz2 || !dist1 || !idx1 || !dist2 || !idx2 || !workspace) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, dist1, idx1, dist2, idx2, workspace})) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     mode = rfd::resolve_mode(b, n, m, mode);
     if (mode == RF_NN_CULLED) {
@@ -895,9 +895,6 @@ int rf_nn_distance_mode(int b, int n, int m, const float *xyz1, const float *xyz
 }
 
 // ------------------------------------------------------------------ ragged batches -------
-namespace {
-}  // namespace
-
 size_t rf_nn_distance_lengths_workspace_bytes(int b, int n, int m, int mode) {
     if (b <= 0 || n <= 0 || m <= 0) return 0;
     if (mode != RF_NN_AUTO && mode != RF_NN_DENSE && mode != RF_NN_CULLED) return 0;
@@ -919,10 +916,7 @@ int rf_nn_distance_lengths(int b, int n, int m, const float *xyz1, const float *
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
     const int dirs = ((dist1 || idx1) ? 1 : 0) | ((dist2 || idx2) ? 2 : 0);
     if (!dirs || ((dirs & 1) && (!dist1 || !idx1)) || ((dirs & 2) && (!dist2 || !idx2))) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !workspace) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(dist1) ||
-        !rf::aligned4(idx1) || !rf::aligned4(dist2) || !rf::aligned4(idx2) || !rf::aligned16(workspace))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2}, {len1, len2, dist1, idx1, dist2, idx2}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     if (rfd::resolve_mode(b, n, m, mode) == RF_NN_CULLED && !rfp::pruned_supported(b, n, m)) return RF_EINVAL;
     if (workspace_bytes < rfd::ragged_workspace_bytes(b, n, m, mode, dirs)) return RF_EWORKSPACE;
     return rfd::ragged_nn_distance(b, n, m, xyz1, xyz2, len1, len2, dist1, idx1, dist2, idx2, workspace,
@@ -935,8 +929,8 @@ int rf_nn_distance_grad_lengths(int b, int n, int m, const float *xyz1, const fl
     if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !grad_dist1 || !idx1 || !grad_dist2 || !idx2 || !grad_xyz1 || !grad_xyz2) return RF_EINVAL;
-    if (!rf::aligned4(len1) || !rf::aligned4(len2)) return RF_EINVAL;
+    if (!rf::all_given({xyz1, xyz2, grad_dist1, idx1, grad_dist2, idx2, grad_xyz1, grad_xyz2})) return RF_EINVAL;
+    if (!rf::all_aligned4({len1, len2})) return RF_EINVAL;
     const rfd::GradSource g{grad_dist1, grad_dist2, nullptr, nullptr, nullptr};
     // (a NULL count array stands for "all": with both NULL this is rf_nn_distance_grad's kernel)
     return rfd::nn_distance_grad(b, n, m, xyz1, xyz2, g, idx1, idx2, grad_xyz1, grad_xyz2, (hipStream_t)stream, len1,

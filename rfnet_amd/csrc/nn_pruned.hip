@@ -2335,29 +2335,34 @@ bool pruned_supported(int b, int n, int m) {
 
 // One sorted set (b clouds of n points) in a caller-owned buffer: xyz | orig | box16 | box64, each
 // part 256-byte aligned.  The layout is a pure function of (b, n): a "handle" is just that buffer.
+struct SortedLayout {
+    size_t xyz, orig, box16, box64, pos0, total;
+};
+static SortedLayout sorted_layout(int b, int n) {
+    const size_t npad = npad_of(n);
+    rf::Layout w;
+    SortedLayout l;
+    l.xyz = w.add((size_t)b * npad * 3 * sizeof(float) + 256);  // + prefetch overrun
+    l.orig = w.add((size_t)b * npad * sizeof(int));
+    l.box16 = w.add((size_t)b * (npad / SB) * B16F * sizeof(float));
+    l.box64 = w.add((size_t)b * (npad / SB) * B64F * sizeof(float));
+    l.pos0 = w.add((size_t)3 * b * sizeof(int));  // pos0 (b) | crowded (b) | non-finite (b)
+    l.total = w.total;
+    return l;
+}
+
+int sorted_npad(int n) { return (int)npad_of(n); }
+
 size_t sorted_bytes(int b, int n) {
     if (b <= 0 || n <= 0 || n > kMaxPoints) return 0;
-    const size_t npad = npad_of(n);
-    return rf::align256((size_t)b * npad * 3 * sizeof(float) + 256)  // + prefetch overrun
-           + rf::align256((size_t)b * npad * sizeof(int)) + rf::align256((size_t)b * (npad / SB) * B16F * sizeof(float)) +
-           rf::align256((size_t)b * (npad / SB) * B64F * sizeof(float)) + rf::align256((size_t)3 * b * sizeof(int));  // pos0 (b) | crowded (b) | non-finite (b)
+    return sorted_layout(b, n).total;
 }
 
 Sorted sorted_view(int b, int n, const void *buf) {
-    const size_t npad = npad_of(n);
+    const SortedLayout l = sorted_layout(b, n);
     const char *w = (const char *)buf;
-    Sorted v;
-    v.npad = (int)npad;
-    v.xyz = (const float *)w;
-    w += rf::align256((size_t)b * npad * 3 * sizeof(float) + 256);
-    v.orig = (const int *)w;
-    w += rf::align256((size_t)b * npad * sizeof(int));
-    v.box16 = (const float *)w;
-    w += rf::align256((size_t)b * (npad / SB) * B16F * sizeof(float));
-    v.box64 = (const float *)w;
-    w += rf::align256((size_t)b * (npad / SB) * B64F * sizeof(float));
-    v.pos0 = (const int *)w;
-    return v;
+    return {(const float *)(w + l.xyz),   (const int *)(w + l.orig), (const float *)(w + l.box16),
+            (const float *)(w + l.box64), (const int *)(w + l.pos0), sorted_npad(n)};
 }
 
 size_t pruned_workspace_bytes(int b, int n, int m) {
@@ -2501,7 +2506,7 @@ size_t pruned_step_workspace_bytes(int b, int n, int m) {
 int pruned_step(int b, int n, int m, const float *xyz1, const float *xyz2, const float *gd1, const float *gd2,
                 float *dist1, int *idx1, float *dist2, int *idx2, float *grad_xyz1, float *grad_xyz2, void *workspace,
                 size_t workspace_bytes, hipStream_t s) {
-    if (!pruned_supported(b, n, m) || !gd1 || !gd2 || !grad_xyz1 || !grad_xyz2 || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!pruned_supported(b, n, m) || !rf::all_given({gd1, gd2, grad_xyz1, grad_xyz2}) || !rf::aligned16(workspace)) return RF_EINVAL;
     if (workspace_bytes < pruned_step_workspace_bytes(b, n, m)) return RF_EWORKSPACE;
     char *w = (char *)workspace;
     const Sorted so[2] = {sorted_view(b, n, w), sorted_view(b, m, w + sorted_bytes(b, n))};
@@ -2568,7 +2573,7 @@ int pruned_nn_distance(int b, int n, int m, const float *xyz1, const float *xyz2
 size_t sort_workspace_bytes(int b, int n) { return sorted_bytes(b, n); }
 
 int sort_clouds(int b, int n, const float *src, void *workspace, size_t workspace_bytes, hipStream_t s, Sorted *out) {
-    if (b <= 0 || n <= 0 || n > kMaxPoints || !src || !workspace || !out || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (b <= 0 || n <= 0 || n > kMaxPoints || !src || !out || !rf::workspace_ok(workspace)) return RF_EINVAL;
     if (workspace_bytes < sorted_bytes(b, n)) return RF_EWORKSPACE;
     *out = sorted_view(b, n, workspace);
     return sort_sets(b, 1, &n, &src, out, s, nullptr);

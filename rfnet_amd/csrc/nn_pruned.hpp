@@ -44,8 +44,10 @@ int sort_clouds(int b, int n, const float *src, void *workspace, size_t workspac
 // caller whose sorted sets never reach one (the Chamfer's private sorts) passes false and saves that pass.
 // The pieces, for callers that keep a sorted set across several sweeps (a "handle" is a caller-owned
 // buffer of sorted_bytes(b, n) bytes whose layout is a pure function of (b, n)).
+// sorted_bytes (0 outside 1..kMaxPoints points) and sorted_view read ONE layout of (b, n); sorted_npad is its record count.
 size_t sorted_bytes(int b, int n);
 Sorted sorted_view(int b, int n, const void *buf);
+int sorted_npad(int n);
 int sort_sets(int b, int nsets, const int *n, const float *const *src, const Sorted *out, hipStream_t s,
               unsigned long long *dbg, const int *const *lens = nullptr, bool flag = true);
 // Sort the sets of a pair (xyz1 -> s1, xyz2 -> s2) that did not come from the caller as handles (have1 / have2), in one

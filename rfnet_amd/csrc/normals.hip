@@ -235,14 +235,6 @@ __global__ __launch_bounds__(NC_TPB) void normal_consistency_kernel(NcArgs a) {
     }
 }
 
-bool any_bad4(std::initializer_list<const void *> required, std::initializer_list<const void *> optional) {
-    for (const void *p : required)
-        if (!p || !rf::aligned4(p)) return true;
-    for (const void *p : optional)
-        if (!rf::aligned4(p)) return true;
-    return false;
-}
-
 }  // namespace
 
 extern "C" {
@@ -251,7 +243,7 @@ int rf_local_pca(int b, int n, int m, int k, const float *xyz, const int *idx, c
                  const float *viewpoint, float *normals, float *eigenvalues, float *axes, rf_stream_t stream) {
     if (b == 0) return RF_OK;
     if (b < 0 || b > 65535 || n < 1 || n > 65536 || m < 1 || m > 65536 || k < 1 || k > PCA_MAX_K) return RF_EINVAL;
-    if (any_bad4({xyz, idx, normals, eigenvalues}, {len1, len2, viewpoint, axes})) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, idx, normals, eigenvalues}, {len1, len2, viewpoint, axes})) return RF_EINVAL;
     const int bpb = rf::ceil_div(m, PCA_TPB);
     const PcaArgs a{n, m, k, xyz, idx, len1, len2, viewpoint, normals, eigenvalues, axes};
     if (int dv = rf::require_device()) return dv;
@@ -267,7 +259,7 @@ int rf_nn_normal_consistency(int b, int n, int m, const float *nrm1, const float
                              const int *len1, const int *len2, float *out, rf_stream_t stream) {
     if (b == 0) return RF_OK;
     if (b < 0 || n < 1 || m < 1 || b > 65535) return RF_EINVAL;
-    if (any_bad4({nrm1, nrm2, idx1, idx2, out}, {len1, len2})) return RF_EINVAL;
+    if (!rf::tensors_ok({nrm1, nrm2, idx1, idx2, out}, {len1, len2})) return RF_EINVAL;
     const NcArgs a{n, m, nrm1, nrm2, idx1, idx2, len1, len2, out};
     RF_LAUNCH("nn_normal_consistency", normal_consistency_kernel, dim3(2 * b), dim3(NC_TPB), 0, (hipStream_t)stream, a);
     return RF_OK;

@@ -360,10 +360,7 @@ int rf_voxelize_mean(int b, int n, int c, int res, float lo, float hi, const flo
     if (b == 0) return RF_OK;
     if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
-    if (!xyz || !feat || !vol || !cnt || !inside) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(feat) || !rf::aligned4(vol) || !rf::aligned4(cnt) || !rf::aligned4(inside) || !rf::aligned4(len))
-        return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, feat, vol, cnt, inside}, {len}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     const GrSortLayout l = gr_sort_layout(b, n, res);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
@@ -385,8 +382,7 @@ int rf_voxelize_mean_grad(int b, int n, int c, int res, float lo, float hi, cons
     if (b == 0) return RF_OK;
     if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
-    if (!xyz || !cnt || !grad_vol || !grad_feat) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(cnt) || !rf::aligned4(grad_vol) || !rf::aligned4(grad_feat) || !rf::aligned4(len)) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, cnt, grad_vol, grad_feat}, {len})) return RF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const PvVoxGrad a{n, c, gr_box(res, lo, hi), xyz, len, cnt, grad_vol, grad_feat};
     RF_LAUNCH("voxelize_grad", pv_vox_grad_kernel, dim3(rf::ceil_div(n, PV_PTS), b), dim3(PV_TPB), 0, st, a);
@@ -399,8 +395,7 @@ int rf_trilinear_devoxelize(int b, int n, int c, int res, float lo, float hi, co
     if (b == 0) return RF_OK;
     if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
-    if (!xyz || !vol || !feat || !inside) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(vol) || !rf::aligned4(feat) || !rf::aligned4(inside) || !rf::aligned4(len)) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, vol, feat, inside}, {len})) return RF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const PvDevox a{n, c, gr_box(res, lo, hi), xyz, len, vol, feat, inside};
     RF_LAUNCH("devoxelize", pv_devox_kernel, dim3(rf::ceil_div(n, PV_PTS), b), dim3(PV_TPB), 0, st, a);
@@ -419,11 +414,8 @@ int rf_trilinear_devoxelize_grad(int b, int n, int c, int res, float lo, float h
     if (b == 0) return RF_OK;
     if (!gr_sizes_ok(b, n, c, res)) return RF_EINVAL;
     if (!gr_box_ok(lo, hi)) return RF_EINVAL;
-    if (!xyz || !vol || !grad_feat || !grad_vol) return RF_EINVAL;  // (grad_xyz may be NULL: it is then not computed)
-    if (!rf::aligned4(xyz) || !rf::aligned4(vol) || !rf::aligned4(grad_feat) || !rf::aligned4(grad_vol) || !rf::aligned4(grad_xyz) ||
-        !rf::aligned4(len))
-        return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    // (grad_xyz may be NULL: it is then not computed)
+    if (!rf::tensors_ok({xyz, vol, grad_feat, grad_vol}, {grad_xyz, len}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     const GrSortLayout l = gr_sort_layout(b, n, res);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;

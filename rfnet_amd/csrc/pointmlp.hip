@@ -260,10 +260,8 @@ int maxpool_run(int b, int n, int c, const float *x, const int *len, float *out,
     if (b < 0 || n < 0 || c < 0) return RF_EINVAL;
     if ((size_t)b * c == 0) return RF_OK;
     if (n == 0 || c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
-    if (!x || !out || (IDX && !idx) || !workspace) return RF_EINVAL;
-    // x, workspace: float4 rows
-    if (!rf::aligned16(x) || !rf::aligned16(workspace) || !rf::aligned4(out) || !rf::aligned4(idx) || !rf::aligned4(len))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({x, out}, {idx, len}) || (IDX && !idx)) return RF_EINVAL;
+    if (!rf::aligned16(x) || !rf::workspace_ok(workspace)) return RF_EINVAL;  // x, workspace: float4 rows
     const int nstrips = rf::ceil_div(n, MP_STRIP);
     const size_t floats = (size_t)b * nstrips * c;
     if (workspace_bytes < (IDX ? 2 : 1) * floats * sizeof(float)) return RF_EWORKSPACE;
@@ -327,10 +325,10 @@ int rf_act_grad_colsum(int b, int n, int c, const float *grad, const float *out,
     if (b < 0 || n < 0 || c < 0 || act < 0 || act > 3) return RF_EINVAL;
     if ((size_t)b * c == 0) return RF_OK;
     if (c % 4 != 0 || c / 4 > MP_TPB || b > 65535) return RF_EINVAL;
-    if (!sums || !rf::aligned4(sums)) return RF_EINVAL;
+    if (!rf::tensors_ok({sums})) return RF_EINVAL;
     // grad, out and g are read and written as float4 rows, the workspace too.  Deliberately unconditional, as the header states
     // it: `out` is checked with act == 0 as well, where no kernel reads it (NULL passes)
-    if (!rf::aligned16(grad) || !rf::aligned16(out) || !rf::aligned16(g) || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!rf::all_aligned16({grad, out, g, workspace})) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
         RF_ZERO(sums, sizeof(float) * (size_t)b * c, s);
@@ -362,8 +360,7 @@ int rf_point_affine(int b, int n, int c, const float *y, const float *p, int kp,
     if (!r || !out || (kp > 0 && (!p || !w))) return RF_EINVAL;
     // y, w, r and out are read and written as float4 rows; p by the word (checked with kp == 0 too, where it is not read:
     // the rule does not depend on the attributes)
-    if (!rf::aligned16(y) || !rf::aligned16(r) || !rf::aligned16(out) || !rf::aligned4(p) || (kp > 0 && !rf::aligned16(w)))
-        return RF_EINVAL;
+    if (!rf::all_aligned16({y, r, out}) || !rf::aligned4(p) || (kp > 0 && !rf::aligned16(w))) return RF_EINVAL;
     const dim3 grid(rf::ceil_div(n, PA_STRIP), b);
     const long rs = r_per_sample ? c : 0;
     hipStream_t s = (hipStream_t)stream;

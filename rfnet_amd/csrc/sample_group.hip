@@ -18,6 +18,17 @@
 
 namespace {
 
+// FPS's running distances (none where it keeps them in registers) | the sorted dataset
+struct SgLayout {
+    size_t temp_floats, temp, sorted, total;
+};
+SgLayout sg_layout(int b, int n) {
+    rf::Layout w;
+    const size_t temp_floats = rf_farthestpointsampling_temp_floats(b, n);
+    const size_t temp = w.add(sizeof(float) * temp_floats), sorted = w.add(rf_queryballpoint_boxes_workspace_bytes(b, n));
+    return {temp_floats, temp, sorted, w.total};
+}
+
 // The chain on checked arguments.  ragged (rf_sample_and_group_lengths): the sort, FPS and the ball query take the counts -- len
 // (b) points per cloud for all three, len_out (b) samples per cloud as FPS's row length and the ball query's query count --
 // through the ragged launchers; the streams are used exactly as in the plain chain.
@@ -27,10 +38,9 @@ int chain(int b, int n, int npoint, float radius, const float *radius_dev, int n
     const int *lens[1] = {len};
     const int *const *sort_lens = (ragged && len) ? lens : nullptr;
     char *w = (char *)workspace;
-    const size_t temp_floats = rf_farthestpointsampling_temp_floats(b, n);
-    float *temp = temp_floats ? (float *)w : nullptr;
-    w += rf::align256(sizeof(float) * temp_floats);
-    const rfp::Sorted so = rfp::sorted_view(b, n, w);
+    const SgLayout l = sg_layout(b, n);
+    float *temp = l.temp_floats ? (float *)(w + l.temp) : nullptr;
+    const rfp::Sorted so = rfp::sorted_view(b, n, w + l.sorted);
     const int nn[1] = {n};
     const float *src[1] = {xyz};
     if (rfi::fps_sorted_pays(n, npoint)) {
@@ -92,9 +102,8 @@ extern "C" {
 
 size_t rf_sample_and_group_workspace_bytes(int b, int n) {
     if (b <= 0 || n <= 0) return 0;
-    const size_t sorted = rf_queryballpoint_boxes_workspace_bytes(b, n);
-    if (!sorted) return 0;
-    return rf::align256(sizeof(float) * rf_farthestpointsampling_temp_floats(b, n)) + sorted;
+    if (!rf_queryballpoint_boxes_workspace_bytes(b, n)) return 0;
+    return sg_layout(b, n).total;
 }
 
 int rf_sample_and_group(int b, int n, int npoint, float radius, const float *radius_dev, int nsample, const float *xyz,
@@ -103,8 +112,7 @@ int rf_sample_and_group(int b, int n, int npoint, float radius, const float *rad
     if (b < 0 || n < 0 || npoint < 0 || nsample <= 0) return RF_EINVAL;
     if ((long)b * npoint == 0) return RF_OK;
     if (n < 64 || nsample > 64 || b > 65535 || !rfp::pruned_supported(b, n, n)) return RF_EINVAL;
-    if (!xyz || !fps_idx || !new_xyz || !idx || !pts_cnt || !grouped_xyz || !workspace || !rf::aligned16(workspace))
-        return RF_EINVAL;
+    if (!rf::all_given({xyz, fps_idx, new_xyz, idx, pts_cnt, grouped_xyz}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     if (workspace_bytes < rf_sample_and_group_workspace_bytes(b, n)) return RF_EWORKSPACE;
     return chain(b, n, npoint, radius, radius_dev, nsample, xyz, false, nullptr, nullptr, fps_idx, new_xyz, idx, pts_cnt,
                  grouped_xyz, workspace, (hipStream_t)stream, (hipStream_t)aux_stream);
@@ -122,11 +130,8 @@ int rf_sample_and_group_lengths(int b, int n, int npoint, float radius, const fl
     if (b == 0) return RF_OK;
     if (npoint == 0) return RF_EINVAL;  // counts are at least 1
     if (n < 64 || nsample > 64 || b > 65535 || !rfp::pruned_supported(b, n, n)) return RF_EINVAL;
-    if (!xyz || !fps_idx || !new_xyz || !idx || !pts_cnt || !grouped_xyz || !workspace) return RF_EINVAL;
-    if (!rf::aligned4(xyz) || !rf::aligned4(len) || !rf::aligned4(len_out) || !rf::aligned4(fps_idx) || !rf::aligned4(new_xyz) ||
-        !rf::aligned4(idx) || !rf::aligned4(pts_cnt) || !rf::aligned4(grouped_xyz) || !rf::aligned4(radius_dev) ||
-        !rf::aligned16(workspace))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({xyz, fps_idx, new_xyz, idx, pts_cnt, grouped_xyz}, {len, len_out, radius_dev})) return RF_EINVAL;
+    if (!rf::workspace_ok(workspace)) return RF_EINVAL;
     if (workspace_bytes < rf_sample_and_group_lengths_workspace_bytes(b, n)) return RF_EWORKSPACE;
     return chain(b, n, npoint, radius, radius_dev, nsample, xyz, true, len, len_out, fps_idx, new_xyz, idx, pts_cnt, grouped_xyz,
                  workspace, (hipStream_t)stream, (hipStream_t)aux_stream);

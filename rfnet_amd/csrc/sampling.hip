@@ -849,10 +849,7 @@ int rf_farthestpointsampling_lengths(int b, int n, int m, const float *inp, cons
     if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n == 0 || m == 0) return RF_EINVAL;  // counts are at least 1
-    if (!inp || !out) return RF_EINVAL;
-    if (!rf::aligned4(inp) || !rf::aligned4(len) || !rf::aligned4(len_out) || !rf::aligned4(out) || !rf::aligned4(new_xyz) ||
-        !rf::aligned16(workspace))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({inp, out}, {len, len_out, new_xyz}) || !rf::aligned16(workspace)) return RF_EINVAL;
     const size_t need = rf_farthestpointsampling_lengths_workspace_bytes(b, n, m);
     if (need && !workspace) return RF_EINVAL;
     if (workspace_bytes < need) return RF_EWORKSPACE;
@@ -871,7 +868,7 @@ int rf_gatherpoint(int b, int n, int m, const float *inp, const int *idx, float 
     if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
     long total = (long)b * m;
     if (total == 0) return RF_OK;
-    if (!inp || !idx || !out) return RF_EINVAL;
+    if (!rf::all_given({inp, idx, out})) return RF_EINVAL;
     RF_LAUNCH("gather_point", gather_kernel, dim3(rf::ceil_div(total, 256)), dim3(256), 0,
               (hipStream_t)stream, n, m, total, inp, idx, out);
     return RF_OK;
@@ -898,7 +895,7 @@ int rf_probsample(int b, int n, int m, const float *inp_p, const float *inp_r, f
     if (b < 0 || n < 0 || m < 0) return RF_EINVAL;
     if (b == 0 || m == 0) return RF_OK;
     if (n == 0) return RF_EINVAL;
-    if (!inp_p || !inp_r || !temp || !out) return RF_EINVAL;
+    if (!rf::all_given({inp_p, inp_r, temp, out})) return RF_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     RF_LAUNCH("prob_sample", prob_sample_kernel, dim3(b), dim3(PS_T), 0, s, n, m, inp_p, inp_r, temp, out);
     return RF_OK;

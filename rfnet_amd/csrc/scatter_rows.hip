@@ -262,15 +262,28 @@ bool rows_csr_supported(int b, int n, int c, long S, int K) {
            (long)n * c < (1L << 31) && (S / K) * (long)c < (1L << 31);
 }
 
+// the row starts (b, n + 1), at 0 | the slots in row order (b, S), the last section: -> the layout up to where it starts
+static rf::Layout rows_csr_row_starts(int b, int n) {
+    rf::Layout w;
+    w.add(sizeof(int) * (size_t)b * ((size_t)n + 1));
+    return w;
+}
+
 size_t rows_csr_workspace_bytes(int b, int n, long S) {
-    return rf::align256(sizeof(int) * (size_t)b * ((size_t)n + 1)) + rf::align256(sizeof(int) * (size_t)b * (size_t)S);
+    rf::Layout w = rows_csr_row_starts(b, n);
+    w.add(sizeof(int) * (size_t)b * (size_t)S);
+    return w.total;
+}
+
+const int *rows_csr_perm(int b, int n, const void *workspace) {
+    return (const int *)((const char *)workspace + rows_csr_row_starts(b, n).total);
 }
 
 template <bool MASKED>
 static int rows_csr_sort_impl(int b, int n, long S, const int *idx, void *workspace, const char *build_name, hipStream_t s,
                               SlotMask<MASKED> mask) {
     int *row_start = (int *)workspace;
-    int *perm = (int *)((char *)workspace + rf::align256(sizeof(int) * (size_t)b * ((size_t)n + 1)));
+    int *perm = const_cast<int *>(rows_csr_perm(b, n, workspace));
     // workgroups per sample: enough to put ~128 CUs to work, every range at least 2048 bins, at most 32768
     int H = rf::ceil_div(n, CB_MAXBINS);
     while ((long)b * H < 128 && n / (2 * H) >= 2048 && H < 8) H *= 2;
@@ -296,10 +309,6 @@ int rows_csr_sort(int b, int n, long S, const int *idx, void *workspace, const c
 int rows_csr_sort_masked(int b, int n, int m, int k, const int *idx, const int *len1, const int *len2, void *workspace,
                          const char *build_name, hipStream_t s) {
     return rows_csr_sort_impl<true>(b, n, (long)m * k, idx, workspace, build_name, s, {len1, len2, k, m});
-}
-
-const int *rows_csr_perm(int b, int n, const void *workspace) {
-    return (const int *)((const char *)workspace + rf::align256(sizeof(int) * (size_t)b * ((size_t)n + 1)));
 }
 
 int rows_csr_scatter(int b, int n, int c, long S, int K, const float *src, const int *idx, const float *weight, float *dst,

@@ -238,16 +238,19 @@ __global__ __launch_bounds__(SK_FIN_TPB) void sk_finish_kernel(SkFin a) {
 }
 
 struct SkLayout {
-    size_t pot, part, gpart, total;
+    size_t pot[2], part[2], gpart, total;
 };
 
+// the potentials (two buffers of b rows f | g | fx | gy) | the (max, sum) partials of every (row, chunk), two buffers | the
+// gradient numerators of the final soft-min
 SkLayout sk_layout(int b, int n, int m) {
     const size_t rows = (size_t)b * 2 * ((size_t)n + (size_t)m);
+    rf::Layout w;
     SkLayout l;
-    l.pot = 0;
-    l.part = l.pot + 2 * rf::align256(rows * sizeof(float));
-    l.gpart = l.part + 2 * rf::align256(rows * SK_NSPLIT * sizeof(float2));
-    l.total = l.gpart + rf::align256(rows * SK_NSPLIT * 3 * sizeof(float));
+    for (size_t &o : l.pot) o = w.add(rows * sizeof(float));
+    for (size_t &o : l.part) o = w.add(rows * SK_NSPLIT * sizeof(float2));
+    l.gpart = w.add(rows * SK_NSPLIT * 3 * sizeof(float));
+    l.total = w.total;
     return l;
 }
 
@@ -274,22 +277,15 @@ int rf_sinkhorn(int b, int n, int m, const float *xyz1, const float *xyz2, const
     if (T < 1 || T > RF_SK_MAX_ITERS || !eps) return RF_EINVAL;
     for (int t = 0; t < T; t++)
         if (!(eps[t] > 0.f) || !isfinite(eps[t])) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !loss || !pot || !delta) return RF_EINVAL;
-    if ((grad1 == nullptr) != (grad2 == nullptr)) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(loss) || !rf::aligned4(pot) || !rf::aligned4(delta) ||
-        !rf::aligned4(grad1) || !rf::aligned4(grad2) || !rf::aligned4(len1) || !rf::aligned4(len2))
-        return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2, loss, pot, delta}, {grad1, grad2, len1, len2})) return RF_EINVAL;
+    if ((grad1 == nullptr) != (grad2 == nullptr) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     const SkLayout l = sk_layout(b, n, m);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
 
-    // workspace: the potentials (two buffers of b rows f | g | fx | gy) | the (max, sum) partials of every (row, chunk), two
-    // buffers | the gradient numerators of the final soft-min
     char *w = (char *)workspace;
-    const size_t rows = (size_t)b * 2 * ((size_t)n + (size_t)m);
-    float *potb[2] = {(float *)(w + l.pot), (float *)(w + l.pot + rf::align256(rows * sizeof(float)))};
-    float2 *partb[2] = {(float2 *)(w + l.part), (float2 *)(w + l.part + rf::align256(rows * SK_NSPLIT * sizeof(float2)))};
+    float *potb[2] = {(float *)(w + l.pot[0]), (float *)(w + l.pot[1])};
+    float2 *partb[2] = {(float2 *)(w + l.part[0]), (float2 *)(w + l.part[1])};
     float *gpart = grad1 ? (float *)(w + l.gpart) : nullptr;
 
     const int big = n > m ? n : m;

@@ -259,12 +259,8 @@ int rf_sliced_wasserstein(int b, int n, int m, int nproj, const float *xyz1, con
     if (b < 0 || n < 0 || m < 0 || nproj < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (n < 1 || m < 1 || nproj < 1 || n > RF_SW_MAX_POINTS || m > RF_SW_MAX_POINTS || b > 65535) return RF_EINVAL;
-    if (!xyz1 || !xyz2 || !dirs || !loss) return RF_EINVAL;
+    if (!rf::tensors_ok({xyz1, xyz2, dirs, loss}, {grad1, grad2, len1, len2}) || !rf::workspace_ok(workspace)) return RF_EINVAL;
     if ((grad1 == nullptr) != (grad2 == nullptr)) return RF_EINVAL;
-    if (!rf::aligned4(xyz1) || !rf::aligned4(xyz2) || !rf::aligned4(dirs) || !rf::aligned4(loss) || !rf::aligned4(grad1) ||
-        !rf::aligned4(grad2) || !rf::aligned4(len1) || !rf::aligned4(len2))
-        return RF_EINVAL;
-    if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
     const int want_grad = grad1 != nullptr;
     const SwLayout l = sw_layout(b, n, m, nproj, want_grad);
     if (workspace_bytes < l.total) return RF_EWORKSPACE;

@@ -409,10 +409,7 @@ int rf_neighbor_sub(int b, int n, int m, int k, int c, const float *feat_q, cons
     if (b < 0 || n < 0 || m < 0 || k < 0 || c < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (!va_sizes_ok(b, n, m, k) || !va_channels_ok(n, m, k, c, 1)) return RF_EINVAL;
-    if (!feat_q || !feat_src || !idx || !out) return RF_EINVAL;
-    if (!rf::aligned4(feat_q) || !rf::aligned4(feat_src) || !rf::aligned4(idx) || !rf::aligned4(len1) || !rf::aligned4(len2) ||
-        !rf::aligned4(out))
-        return RF_EINVAL;
+    if (!rf::tensors_ok({feat_q, feat_src, idx, out}, {len1, len2})) return RF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const bool vec = rf::lane_rows_vec_ok(c, {feat_q, feat_src, out});
     const int tx = rf::lane_rows_tx_log2(vec ? c / 4 : c);
@@ -431,12 +428,10 @@ int rf_neighbor_sub_grad(int b, int n, int m, int k, int c, const int *idx, cons
     if (b < 0 || n < 0 || m < 0 || k < 0 || c < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (!va_sizes_ok(b, n, m, k) || !va_channels_ok(n, m, k, c, 1)) return RF_EINVAL;
-    if (!idx || !grad_out) return RF_EINVAL;  // (grad_q and grad_src may be NULL: what is NULL is not computed)
-    if (!rf::aligned4(idx) || !rf::aligned4(len1) || !rf::aligned4(len2) || !rf::aligned4(grad_out) || !rf::aligned4(grad_q) ||
-        !rf::aligned4(grad_src))
-        return RF_EINVAL;
+    // (grad_q and grad_src may be NULL: what is NULL is not computed)
+    if (!rf::tensors_ok({idx, grad_out}, {len1, len2, grad_q, grad_src})) return RF_EINVAL;
     if (grad_src) {
-        if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+        if (!rf::workspace_ok(workspace)) return RF_EINVAL;
         if (workspace_bytes < rf_neighbor_sub_grad_workspace_bytes(b, n, m, k)) return RF_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -462,10 +457,8 @@ int rf_neighbor_aggregate(int b, int n, int m, int k, int c, int cw, const float
     if (b < 0 || n < 0 || m < 0 || k < 0 || c < 0 || cw < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (!va_sizes_ok(b, n, m, k) || !va_channels_ok(n, m, k, c, cw)) return RF_EINVAL;
-    if (!value || !weight || !idx || !out) return RF_EINVAL;  // (pos may be NULL: the values are then taken as they are)
-    if (!rf::aligned4(value) || !rf::aligned4(pos) || !rf::aligned4(weight) || !rf::aligned4(idx) || !rf::aligned4(len1) ||
-        !rf::aligned4(len2) || !rf::aligned4(out))
-        return RF_EINVAL;
+    // (pos may be NULL: the values are then taken as they are)
+    if (!rf::tensors_ok({value, weight, idx, out}, {pos, len1, len2})) return RF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const bool vec = rf::lane_rows_vec_ok(c, {value, pos, out});
     const bool wv = vec && rf::lane_rows_vec_ok(cw, {weight});
@@ -488,13 +481,10 @@ int rf_neighbor_aggregate_grad(int b, int n, int m, int k, int c, int cw, const 
     if (b < 0 || n < 0 || m < 0 || k < 0 || c < 0 || cw < 0) return RF_EINVAL;
     if (b == 0) return RF_OK;
     if (!va_sizes_ok(b, n, m, k) || !va_channels_ok(n, m, k, c, cw)) return RF_EINVAL;
-    if (!value || !weight || !idx || !grad_out) return RF_EINVAL;  // (pos and each of the three outputs may be NULL)
-    if (!rf::aligned4(value) || !rf::aligned4(pos) || !rf::aligned4(weight) || !rf::aligned4(idx) || !rf::aligned4(len1) ||
-        !rf::aligned4(len2) || !rf::aligned4(grad_out) || !rf::aligned4(grad_value) || !rf::aligned4(grad_pos) ||
-        !rf::aligned4(grad_weight))
-        return RF_EINVAL;
+    // (pos and each of the three outputs may be NULL)
+    if (!rf::tensors_ok({value, weight, idx, grad_out}, {pos, len1, len2, grad_value, grad_pos, grad_weight})) return RF_EINVAL;
     if (grad_value) {
-        if (!workspace || !rf::aligned16(workspace)) return RF_EINVAL;
+        if (!rf::workspace_ok(workspace)) return RF_EINVAL;
         if (workspace_bytes < rf_neighbor_aggregate_grad_workspace_bytes(b, n, m, k)) return RF_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;

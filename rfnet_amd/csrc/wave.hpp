@@ -19,7 +19,7 @@ __device__ __forceinline__ int ragged_count(const int *__restrict__ len, int bi,
     return v < 1 ? 1 : (v > n ? n : v);
 }
 
-// Sections of a workspace start at multiples of 256 bytes (common.hpp: aligned16).
+// Sections of a workspace start at multiples of 256 bytes (boundary.hpp: workspace_ok, Layout).
 __host__ __device__ inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // running minimum as ONE v_min3_f32.  Written as asm so that LLVM cannot re-associate the chain
