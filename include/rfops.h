@@ -27,7 +27,8 @@
  *     Tensor arguments need their element's natural alignment (4 bytes), except the (.., c) feature tensors of the
  *     model graph helpers, which are read and written in rows of c % 4 == 0 floats and need 16 bytes:
  *     rf_point_affine's y, w, r and out, rf_maxpool_points' and rf_maxpool_points_idx's x (their _lengths forms too), rf_act_grad_colsum's grad,
- *     out and g (their p, out / idx and sums need 4).  A less aligned one is RF_EINVAL before anything is launched.
+ *     out and g (their p, out / idx and sums need 4).  rf_grid_cluster's int64 code needs its own 8 bytes.  A less aligned
+ *     one is RF_EINVAL before anything is launched.
  *
  * Status codes: 0 = success; > 0 = the hipError_t of the failing HIP call;
  *               < 0 = RF_EINVAL-style argument errors below.
@@ -1155,6 +1156,80 @@ int rf_local_pca(int b, int n, int m, int k, const float *xyz, const int *idx, c
                  const float *viewpoint, float *normals, float *eigenvalues, float *axes, rf_stream_t stream);
 int rf_nn_normal_consistency(int b, int n, int m, const float *nrm1, const float *nrm2, const int *idx1, const int *idx2,
                              const int *len1, const int *len2, float *out, rf_stream_t stream);
+
+/* ---- grid pooling on a sparse voxel grid, and the point order along a space-filling curve (grid_pool.hip) ----
+ * rf_grid_cluster: xyz (b,n,3) -> per sample the occupied cells of an unbounded grid of edge `cell`, by a sort of integer
+ * cell keys: which cell every point is in, the points in key order, where every cell's points begin.  One workgroup per
+ * sample with its 64-bit words in LDS, hence 1 <= n <= RF_GC_MAX_POINTS (the cap RF_SW_MAX_POINTS has for the same reason),
+ * b <= 65535.  One launch, no workspace, no atomics, no memset: every element of every output is written exactly once on
+ * every call; the counts stay on the device (capturable).  Two calls return the same bits, a sample does not depend on its
+ * batch, a ragged call equals the call on the slices.  Every operation is prescribed:
+ *   usable   L = len[i] clamped into [1, n] (len NULL: n), read on the device.  A row below L is USABLE when its three
+ *            coordinates are finite.  Rows behind L are not read and may hold anything.
+ *   origin   origin (b,3) fp32 on the device, or NULL: then per axis the fp32 minimum over the sample's usable rows (exact,
+ *            so free of any order), + 0.0f (-0 becomes +0), and +0 when no row is usable.  The origin used is written to
+ *            origin_out (b,3).
+ *   cell     per axis t = ((double)x - (double)o) / (double)cell, three separately rounded double operations, k = floor(t).
+ *            A usable row is INSIDE when -32768 <= t < 32768 on all three axes, compared in double before any conversion to
+ *            an integer (a NaN or infinite origin leaves no row inside).  u = k + 32768 in [0, 65535].
+ *   key      48 bits.  RF_GC_XYZ: u_x << 32 | u_y << 16 | u_z.  RF_GC_Z (Morton): bit 3j+2 = bit j of u_x, 3j+1 of u_y, 3j of
+ *            u_z.  RF_GC_HILBERT: Skilling's axes-to-transpose on 16 bits with X[0] = u_x, X[1] = u_y, X[2] = u_z -- for Q =
+ *            2^15 down to 2 and i = 0, 1, 2: if X[i] & Q then X[0] ^= Q-1 else { t = (X[0] ^ X[i]) & (Q-1); X[0] ^= t;
+ *            X[i] ^= t }; then X[1] ^= X[0]; X[2] ^= X[1]; then t = 0 and for Q = 2^15 down to 2: if X[2] & Q then t ^= Q-1;
+ *            X[i] ^= t -- and X interleaved as for RF_GC_Z.  Both curves: a bijection with code 0 at cell (0,0,0) of the
+ *            16-bit cube, code >> 3s is the code of the cell >> s on 16 - s bits (coarsening a code coarsens the cell), and
+ *            consecutive Hilbert codes are face-adjacent cells.  Other axis conventions are a column permutation of xyz in
+ *            front of the call.
+ *   sort     words key << 16 | i (the point index i < 16384 in the low bits), ascending: the order is ascending (key, index).
+ *   outputs  inside (b) int32: the inside count I.  nclusters (b) int32: the number of distinct keys M.
+ *            point_order (b,n) int32: the inside points in sorted order, zeros from I on.
+ *            starts (b,n+1) int32: entry j < M is where cluster j begins in point_order; every entry from M on holds I, so
+ *            starts[j+1] - starts[j] is the size of cluster j and 0 behind M.
+ *            cluster (b,n) int32: the rank of the point's cell among the sample's occupied cells in key order; -1 for a row
+ *            that is not inside.
+ *            coords (b,n,3) int32: k of each cluster, zeros behind M.
+ *            code (b,n) int64 or NULL: the key per point, -1 for a row that is not inside.
+ * Argument rules, all checked before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for n
+ * outside 1 ... RF_GC_MAX_POINTS, b above 65535, a cell that is not a finite fp32 > 0, an unknown order, a NULL tensor (len,
+ * origin and code may be NULL), a tensor or count array not 4-byte aligned, a code not 8-byte aligned.
+ *
+ * rf_grid_pool: feat (b,n,c), 1 <= c <= RF_GP_MAX_CHANNELS, and rf_grid_cluster's point_order, starts and nclusters ->
+ * out (b,n,c): row j < M reduces the rows of cluster j, point_order[starts[j] .. starts[j+1]), in that order (ascending
+ * point index); rows behind M are +0.  RF_GP_SUM: acc = +0.0; acc = acc + (double)x; rounded to fp32 once.  RF_GP_MEAN: the
+ * same sum divided by the count in double, rounded once.  RF_GP_MAX: the first member, replaced by a later one when it is
+ * strictly greater; a NaN member is taken and ends the walk; arg (b,n,c) int32 receives the winning point index (0 behind M)
+ * -- required for RF_GP_MAX, NULL otherwise.  The pooled coordinates are this entry with c = 3 and RF_GP_MEAN.  The arrays are
+ * read defensively: nclusters is clamped into [0, n], a list's bounds into [0, n], a member outside [0, n) is skipped, an
+ * empty list gives +0 -- nothing outside the tensors is touched whatever they hold.  One launch, no workspace.
+ *
+ * rf_grid_unpool: src (b,n,c) pooled rows, cluster (b,n) -> dst (b,n,c), row i from row cluster[i] of src; +0 where
+ * cluster[i] is outside [0, n) (-1: not inside).  RF_GU_COPY: the row.  RF_GU_MEAN: (float)((double)src / count), count =
+ * starts[cluster[i]+1] - starts[cluster[i]] (+0 when that is not positive); starts is required.  RF_GU_MAX: src[..][ch] where
+ * arg[cluster[i]][ch] == i, else +0; arg (b,n,c) is required.  starts and arg may be NULL where they are not read.  This one
+ * entry is the forward of an unpooling and the backward of all three reductions; the backward of RF_GU_COPY is rf_grid_pool
+ * with RF_GP_SUM: no float atomics and no memset anywhere, so the gradients have prescribed bits too.  One launch.
+ * Argument rules of both, before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for n outside
+ * 1 ... RF_GC_MAX_POINTS, c outside 1 ... RF_GP_MAX_CHANNELS, b above 65535, an unknown reduce / mode, a NULL tensor (those
+ * named optional aside), arg given without RF_GP_MAX, a tensor not 4-byte aligned.  When c is a multiple of 4 and every
+ * (b,n,c) tensor is 16-byte aligned the rows move as 16-byte vectors; the results are the same. */
+#define RF_GC_MAX_POINTS 16384
+#define RF_GP_MAX_CHANNELS 2048
+#define RF_GC_XYZ 0
+#define RF_GC_Z 1
+#define RF_GC_HILBERT 2
+#define RF_GP_SUM 0
+#define RF_GP_MEAN 1
+#define RF_GP_MAX 2
+#define RF_GU_COPY 0
+#define RF_GU_MEAN 1
+#define RF_GU_MAX 2
+int rf_grid_cluster(int b, int n, float cell, int order, const float *xyz, const int *len, const float *origin,
+                    float *origin_out, int *inside, int *nclusters, int *point_order, int *starts, int *cluster, int *coords,
+                    long long *code, rf_stream_t stream);
+int rf_grid_pool(int b, int n, int c, int reduce, const float *feat, const int *point_order, const int *starts,
+                 const int *nclusters, float *out, int *arg, rf_stream_t stream);
+int rf_grid_unpool(int b, int n, int c, int mode, const float *src, const int *cluster, const int *starts, const int *arg,
+                   float *dst, rf_stream_t stream);
 
 /* -------------------------------------------------- interpolation (tf_ops/interpolation) - */
 /* Replace threenn_cpu / threeinterpolate_cpu / threeinterpolate_grad_cpu

@@ -150,6 +150,9 @@ SIGNATURES = {
     "rf_knn_feature": (_i, [_i, _i, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
     "rf_local_pca": (_i, [_i, _i, _i, _i] + [_vp] * 9),
     "rf_nn_normal_consistency": (_i, [_i, _i, _i] + [_vp] * 8),
+    "rf_grid_cluster": (_i, [_i, _i, _f, _i] + [_vp] * 12),
+    "rf_grid_pool": (_i, [_i, _i, _i, _i] + [_vp] * 7),
+    "rf_grid_unpool": (_i, [_i, _i, _i, _i] + [_vp] * 6),
     "rf_threenn": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_threenn_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_threenn_lengths": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp, _i]),

@@ -2047,6 +2047,123 @@ def nn_normal_consistency(normals1, normals2, idx1, idx2, lengths1=None, lengths
     return st.give(out)
 
 
+GC_MAX_POINTS, GP_MAX_CHANNELS = 16384, 2048  # RF_GC_MAX_POINTS, RF_GP_MAX_CHANNELS (include/rfops.h)
+GC_ORDERS = {"xyz": 0, "z": 1, "hilbert": 2}   # RF_GC_XYZ, RF_GC_Z, RF_GC_HILBERT
+GP_REDUCES = {"sum": 0, "mean": 1, "max": 2}   # RF_GP_SUM, RF_GP_MEAN, RF_GP_MAX
+GU_MODES = {"copy": 0, "mean": 1, "max": 2}    # RF_GU_COPY, RF_GU_MEAN, RF_GU_MAX
+
+
+@H.on_input_device
+def grid_cluster(xyz, cell, order="xyz", lengths=None, origin=None, want_code=False):
+    """rf_grid_cluster: the occupied cells of edge `cell` of every cloud of xyz (b,n,3), n <= 16384, by a sort of integer cell
+    keys along `order` ("xyz" row-major, "z" Morton, "hilbert") -> a dict of device tensors: "origin" (b,3) the origin used
+    (`origin` (b,3), or the per-axis minimum of the sample), "inside" (b,) and "nclusters" (b,) int32, "order" (b,n) the inside
+    points in key order, "starts" (b,n+1), "cluster" (b,n) with -1 for rows that are not inside, "coords" (b,n,3) int32 and,
+    with want_code, "code" (b,n) int64 (include/rfops.h states every operation).  lengths: points per sample."""
+    op = "GridCluster"
+    st = H.Staged()
+    a = st.take(xyz, F32)
+    if not _shape3(a, 3):
+        raise H.invalid(f"{op} expects (b,n,3) xyz shape")
+    b, n = a.shape[0], a.shape[1]
+    if not (1 <= b <= 65535 and 1 <= n <= GC_MAX_POINTS):
+        raise H.invalid(f"{op} takes 1 <= b <= 65535 and 1 <= n <= {GC_MAX_POINTS} points")
+    cell = float(np.float32(cell))
+    if not (np.isfinite(cell) and cell > 0):
+        raise H.invalid(f"{op} takes a finite cell > 0")
+    if order not in GC_ORDERS:
+        raise H.invalid(f"{op} takes order in {sorted(GC_ORDERS)}")
+    og = None
+    if origin is not None:
+        og = st.take(origin, F32)
+        if tuple(og.shape) != (b, 3):
+            raise H.invalid(f"{op} expects (b,3) origin shape")
+    ln = _check_lengths(lengths, b, n, "lengths")
+    dev = st.device_()
+    a, = st.up(a)
+    if og is not None:
+        og, = st.up(og)
+    ln = _lengths_up(ln, dev, n)
+    r = {"origin": H.empty((b, 3), F32, dev), "inside": H.empty((b,), I32, dev), "nclusters": H.empty((b,), I32, dev),
+         "order": H.empty((b, n), I32, dev), "starts": H.empty((b, n + 1), I32, dev), "cluster": H.empty((b, n), I32, dev),
+         "coords": H.empty((b, n, 3), I32, dev)}
+    if want_code:
+        r["code"] = H.empty((b, n), torch.int64, dev)
+    check(lib.rf_grid_cluster(b, n, cell, GC_ORDERS[order], H.ptr(a), H.ptr(ln), H.ptr(og), H.ptr(r["origin"]),
+                              H.ptr(r["inside"]), H.ptr(r["nclusters"]), H.ptr(r["order"]), H.ptr(r["starts"]),
+                              H.ptr(r["cluster"]), H.ptr(r["coords"]), H.ptr(r.get("code")), H.stream(dev)), "rf_grid_cluster")
+    return {k: st.give(v) for k, v in r.items()}
+
+
+def _gp_rows(op, st, t, name, dtype=F32):
+    a = st.take(t, dtype)
+    if not _shape3(a):
+        raise H.invalid(f"{op} expects (b,n,c) {name} shape")
+    b, n, c = a.shape
+    if not (1 <= b <= 65535 and 1 <= n <= GC_MAX_POINTS and 1 <= c <= GP_MAX_CHANNELS):
+        raise H.invalid(f"{op} takes 1 <= b <= 65535, 1 <= n <= {GC_MAX_POINTS} and 1 <= c <= {GP_MAX_CHANNELS}")
+    return a
+
+
+def _gp_index(op, st, t, name, shape):
+    a = st.take(t, I32)
+    if tuple(a.shape) != shape:
+        raise H.invalid(f"{op} expects {name} of shape {shape}")
+    return a
+
+
+@H.on_input_device
+def grid_pool(feat, order, starts, nclusters, reduce="mean"):
+    """rf_grid_pool: feat (b,n,c) reduced per cluster of grid_cluster's order (b,n), starts (b,n+1) and nclusters (b,) ->
+    out (b,n,c), rows behind the cluster count +0; reduce "sum" / "mean" (double sums, rounded once) or "max", which returns
+    (out, arg (b,n,c) int32 the winning point index)."""
+    op = "GridPool"
+    st = H.Staged()
+    f = _gp_rows(op, st, feat, "feat")
+    b, n, c = f.shape
+    if reduce not in GP_REDUCES:
+        raise H.invalid(f"{op} takes reduce in {sorted(GP_REDUCES)}")
+    od, ss = _gp_index(op, st, order, "order", (b, n)), _gp_index(op, st, starts, "starts", (b, n + 1))
+    nc = _gp_index(op, st, nclusters, "nclusters", (b,))
+    dev = st.device_()
+    f, od, ss, nc = st.up(f, od, ss, nc)
+    out = H.empty((b, n, c), F32, dev)
+    arg = H.empty((b, n, c), I32, dev) if reduce == "max" else None
+    check(lib.rf_grid_pool(b, n, c, GP_REDUCES[reduce], H.ptr(f), H.ptr(od), H.ptr(ss), H.ptr(nc), H.ptr(out), H.ptr(arg),
+                           H.stream(dev)), "rf_grid_pool")
+    return (st.give(out), st.give(arg)) if reduce == "max" else st.give(out)
+
+
+@H.on_input_device
+def grid_unpool(src, cluster, starts=None, arg=None, mode="copy"):
+    """rf_grid_unpool: src (b,n,c) pooled rows back to the points -> (b,n,c): row i is row cluster[i] of src ("copy"), that row
+    divided by the cluster's size from starts ("mean"), or its channels whose arg names point i ("max"); +0 where cluster[i] is
+    -1.  The forward of an unpooling and the backward of grid_pool's three reductions."""
+    op = "GridUnpool"
+    st = H.Staged()
+    s = _gp_rows(op, st, src, "src")
+    b, n, c = s.shape
+    if mode not in GU_MODES:
+        raise H.invalid(f"{op} takes mode in {sorted(GU_MODES)}")
+    cl = _gp_index(op, st, cluster, "cluster", (b, n))
+    if mode == "mean" and starts is None:
+        raise H.invalid(f"{op} needs starts for mode mean")
+    if mode == "max" and arg is None:
+        raise H.invalid(f"{op} needs arg for mode max")
+    ss = _gp_index(op, st, starts, "starts", (b, n + 1)) if mode == "mean" else None
+    ag = _gp_index(op, st, arg, "arg", (b, n, c)) if mode == "max" else None
+    dev = st.device_()
+    s, cl = st.up(s, cl)
+    if ss is not None:
+        ss, = st.up(ss)
+    if ag is not None:
+        ag, = st.up(ag)
+    dst = H.empty((b, n, c), F32, dev)
+    check(lib.rf_grid_unpool(b, n, c, GU_MODES[mode], H.ptr(s), H.ptr(cl), H.ptr(ss), H.ptr(ag), H.ptr(dst), H.stream(dev)),
+          "rf_grid_unpool")
+    return st.give(dst)
+
+
 @H.on_input_device
 def knn_point_grad(xyz1, xyz2, idx, grad_val, lengths1=None, lengths2=None):
     """The gradient of knn_point's val -> (grad_xyz1 (b,n,3), grad_xyz2 (b,m,3)) (rf_knn_grad).  lengths1 / lengths2: the counts

@@ -15,6 +15,8 @@ using Pointers = std::initializer_list<const void *>;
 
 inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// NULL or 8-byte aligned: an optional tensor of 64-bit elements (rf_grid_cluster's code), read and written by the element
+inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 // no pointer is NULL
 inline bool all_given(Pointers ps) {

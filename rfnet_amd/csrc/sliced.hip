@@ -18,11 +18,12 @@
 //
 // Directions are processed in chunks of RF_SW_DIR_CHUNK so that the workspace does not grow with nproj.  No atomics anywhere.
 #include "common.hpp"
+#include "lds_sort.hpp"  // sw_at, sw_sort: the bitonic network over LDS words
 
 namespace {
 
 constexpr int SW_CHUNK = RF_SW_DIR_CHUNK;
-constexpr int SW_SORT_TPB = 1024;  // at most; a thread per 4 words below 8192 words, per 16 from there on
+constexpr int SW_SORT_TPB = 1024;  // at most (sw_sort_threads, lds_sort.hpp)
 constexpr int SW_TPB = 256;        // accumulate, and the merge of small clouds
 constexpr int SW_MERGE_MAX = 1024; // the merge of large ones: its walks are chains of dependent loads, so waves hide them
 constexpr unsigned long long SW_PAD = ~0ull;
@@ -33,41 +34,6 @@ __device__ __forceinline__ unsigned sw_key(float p) {
     return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 __device__ __forceinline__ float sw_unkey(unsigned k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
-
-__device__ __forceinline__ void sw_cx(unsigned long long &a, unsigned long long &b) {  // ascending
-    const bool lt = a < b;
-    const unsigned long long lo = lt ? a : b, hi = lt ? b : a;
-    a = lo, b = hi;
-}
-
-// Where word i lives in LDS: the low four bits are XORed with the next four, so that the 16 consecutive words a thread
-// takes in the passes over the lowest strides fall on different banks from lane to lane.  A bijection inside each block of
-// 256 words (of 64: P >= 64).
-__device__ __forceinline__ int sw_at(int i) { return i ^ ((i >> 4) & 15); }
-
-// One pass over the words: the R strides jl << (R - 1) ... jl of stage k, each thread 2^R words in registers.  The words of
-// a group share every bit of their index above the strides, so they share the direction too (all strides are below k); a
-// descending group is an ascending one on the complemented words, which keeps the direction out of the compare-exchanges
-// (the sort is bound by their VALU work: a 64-bit compare and four selects each).
-template <int R>
-__device__ __forceinline__ void sw_pass(unsigned long long *__restrict__ w, int P, int k, int jl, int tid, int nt) {
-    constexpr int E = 1 << R;
-    for (int q = tid; q < (P >> R); q += nt) {
-        const int lo = q & (jl - 1), i = ((q - lo) << R) | lo;
-        const unsigned long long flip = (i & k) == 0 ? 0ull : ~0ull;
-        unsigned long long a[E];
-#pragma unroll
-        for (int e = 0; e < E; e++) a[e] = w[sw_at(i + e * jl)] ^ flip;
-#pragma unroll
-        for (int t = R - 1; t >= 0; t--)
-#pragma unroll
-            for (int e = 0; e < E; e++)
-                if (!(e & (1 << t))) sw_cx(a[e], a[e | (1 << t)]);
-#pragma unroll
-        for (int e = 0; e < E; e++) w[sw_at(i + e * jl)] = a[e] ^ flip;
-    }
-    __syncthreads();
-}
 
 // ---- the sort --------------------------------------------------------------------------------------------------------------
 // grid (directions of the chunk, b, 2).  Every loop bound is P (a power of two from the clamped count) or the count itself.
@@ -99,20 +65,7 @@ __global__ __launch_bounds__(SW_SORT_TPB) void sliced_sort_kernel(int b, int n, 
     }
     __syncthreads();
 
-    // stage k merges bitonic runs of k words with the strides k / 2 ... 1; a pass takes up to four of them (two below 8192
-    // words, where the longer passes measured no faster)
-    const int rmax = P >= 8192 ? 4 : 2;
-    for (int s2 = 1; (1 << s2) <= P; s2++) {
-        const int k = 1 << s2;
-        for (int rem = s2; rem > 0;) {
-            const int r = rem >= rmax ? rmax : rem, jl = 1 << (rem - r);
-            if (r == 4) sw_pass<4>(sw_words, P, k, jl, tid, nt);
-            else if (r == 3) sw_pass<3>(sw_words, P, k, jl, tid, nt);
-            else if (r == 2) sw_pass<2>(sw_words, P, k, jl, tid, nt);
-            else sw_pass<1>(sw_words, P, k, jl, tid, nt);
-            rem -= r;
-        }
-    }
+    sw_sort(sw_words, P, tid, nt);
 
     // a valid word is below every padding word (its index is below 2^32 - 1): the first L words are the sample's points
     for (int r = tid; r < L; r += nt) {
@@ -279,8 +232,7 @@ int rf_sliced_wasserstein(int b, int n, int m, int nproj, const float *xyz1, con
     const int big = n > m ? n : m;
     int P = 64;
     while (P < big) P <<= 1;
-    const int per = P >= 8192 ? 16 : 4;  // words per thread and pass (the kernel's rmax)
-    const int sort_tpb = P / per < 64 ? 64 : (P / per > SW_SORT_TPB ? SW_SORT_TPB : P / per);
+    const int sort_tpb = sw_sort_threads(P);
     const int merge_tpb = big > 4096 ? SW_MERGE_MAX : SW_TPB;
     RF_HIP(hipFuncSetAttribute((const void *)sliced_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
     for (int d0 = 0; d0 < nproj; d0 += SW_CHUNK) {

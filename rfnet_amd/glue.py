@@ -750,6 +750,139 @@ def normal_consistency(pcd1, pcd2, normals1=None, normals2=None, k=16, lengths1=
             "signed21": raw[:, 3]}
 
 
+def _origin_tensor(origin, b, dev):
+    """A (3,) or (b, 3) grid origin, tensor or sequence -> a contiguous (b, 3) fp32 tensor on `dev`, or None."""
+    if origin is None:
+        return None
+    o = origin if isinstance(origin, torch.Tensor) else torch.as_tensor(origin, dtype=torch.float32)
+    o = o.detach().to(device=dev, dtype=torch.float32)
+    if o.dim() == 1 and o.shape[0] == 3:
+        o = o.unsqueeze(0).expand(b, 3)
+    if tuple(o.shape) != (b, 3):
+        raise ValueError("origin must be of shape (3,) or (batch, 3)")
+    return o.contiguous()
+
+
+def grid_cluster(pcd, cell, origin=None, order="xyz", lengths=None, return_code=False):
+    """The occupied cells of a sparse, unbounded voxel grid of edge `cell` over every cloud of pcd (b, n, 3), n <= 16384: a
+    point with finite coordinates falls in cell floor((x - origin) / cell) per axis (in double), and is `inside` when every
+    cell index fits 16 bits (+-32768 cells round the origin).  origin: (3,) or (b, 3), default the per-axis minimum of each
+    sample's points.  Returns a dict of device tensors: "cluster" (b, n) int32, the rank of each point's cell among the
+    sample's occupied cells in the order of `order` ("xyz" row-major, "z" Morton, "hilbert"), -1 for rows that are not inside;
+    "order" (b, n) the inside points sorted by (cell, index); "starts" (b, n + 1) where each cell's points begin in "order"
+    (entries behind the cell count hold the inside count); "coords" (b, n, 3) int32 each cell's indices; "nclusters" and
+    "inside" (b,) int32; "origin" (b, 3); with return_code "code" (b, n) int64, each point's 48-bit key.  Other axis
+    conventions ("trans" orders, a z-major Morton) are a column permutation of pcd in front of the call.  lengths: points
+    per sample of a ragged batch.  One launch per call, no host synchronisation (capturable), the same bits on every call
+    and for every batch (rf_grid_cluster).  Non-differentiable."""
+    x = _cloud_tensor(pcd).detach()
+    return _raw.grid_cluster(x, cell, order, lengths, _origin_tensor(origin, x.shape[0], x.device), want_code=return_code)
+
+
+_GP_BACKWARD = {"sum": "copy", "mean": "mean", "max": "max"}
+
+
+class _GridPoolRows(torch.autograd.Function):
+    """rf_grid_pool at a fixed clustering; its backward is rf_grid_unpool in the mode that belongs to the reduction."""
+
+    @staticmethod
+    def forward(ctx, rows, order, starts, nclusters, cluster, reduce):
+        if reduce == "max":
+            out, arg = _raw.grid_pool(rows, order, starts, nclusters, "max")
+            ctx.save_for_backward(cluster, starts, arg)
+            ctx.mark_non_differentiable(arg)
+        else:
+            out, arg = _raw.grid_pool(rows, order, starts, nclusters, reduce), None
+            ctx.save_for_backward(cluster, starts)
+        ctx.reduce = reduce
+        return out, arg
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _):
+        cluster, starts = ctx.saved_tensors[:2]
+        arg = ctx.saved_tensors[2] if ctx.reduce == "max" else None
+        return _raw.grid_unpool(grad_out.contiguous(), cluster, starts, arg, _GP_BACKWARD[ctx.reduce]), None, None, None, None, None
+
+
+def grid_pool(pcd, cell, feat=None, reduce="mean", origin=None, order="xyz", lengths=None):
+    """Voxel-grid subsampling (KPConv's grid_subsampling, Point Transformer's GridPool, Open3D's voxel_down_sample): one row
+    per occupied cell of edge `cell` -> (points (b, n, 3), feat_pooled (b, n, c) or None, lengths_out, info).  points are the
+    means of each cell's points, valid rows in front in the order of `order`, zeros behind; feat (b, n, c), c <= 2048, is
+    reduced per cell with `reduce` "mean", "sum" or "max".  lengths_out is the device int32 count of cells per sample, ready
+    for every `lengths=` argument of this library (farthest_point_sample, knn_point, ...) without a host synchronisation;
+    info is `grid_cluster`'s dict (with "arg", the winning point per cell and channel, under "max").  Sums are double in
+    ascending point index and rounded once: the same bits on every call and for every batch.  Differentiable in pcd (through
+    the mean, at the fixed clustering) and in feat; only the gradients that are needed are computed, by rf_grid_unpool: no
+    atomics.  n <= 16384; rows that are not inside (NaN / inf rows, padding, cells beyond +-32768) are in no cell and get a
+    zero gradient."""
+    if reduce not in _GP_BACKWARD:
+        raise ValueError("reduce must be 'mean', 'sum' or 'max'")
+    x = _cloud_tensor(pcd)
+    info = grid_cluster(x, cell, origin, order, lengths)
+    keys = (info["order"], info["starts"], info["nclusters"], info["cluster"])
+    points, _ = _GridPoolRows.apply(x, *keys, "mean")
+    pooled = None
+    if feat is not None:
+        f = feat if isinstance(feat, torch.Tensor) else torch.as_tensor(feat)
+        pooled, arg = _GridPoolRows.apply(f.to(torch.float32).contiguous(), *keys, reduce)
+        if reduce == "max":
+            info = dict(info, arg=arg)
+    return points, pooled, info["nclusters"], info
+
+
+class _GridUnpool(torch.autograd.Function):
+    """rf_grid_unpool (copy); its backward is rf_grid_pool's sum over each cluster's points."""
+
+    @staticmethod
+    def forward(ctx, src, cluster, starts, order, nclusters):
+        ctx.save_for_backward(cluster, starts, *(() if order is None else (order, nclusters)))
+        return _raw.grid_unpool(src, cluster, mode="copy")
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_dst):
+        cluster, starts = ctx.saved_tensors[:2]
+        if len(ctx.saved_tensors) == 4:
+            order, nclusters = ctx.saved_tensors[2:]
+        else:  # the points by (cluster, index), rows that are in no cluster last: a stable sort in torch, on the device
+            n = cluster.shape[1]
+            order = torch.argsort(torch.where(cluster < 0, n, cluster), dim=1, stable=True).to(torch.int32)
+            nclusters = (cluster.max(dim=1).values + 1).clamp(min=0).to(torch.int32)
+        return _raw.grid_pool(grad_dst.contiguous(), order, starts, nclusters, "sum"), None, None, None, None
+
+
+def grid_unpool(feat_pooled, cluster, starts, order=None, nclusters=None):
+    """Pooled rows back to the points: feat_pooled (b, n, c), one row per cell as `grid_pool` returns them -> (b, n, c), row i
+    the row of point i's cell, zeros for points in no cell (rf_grid_unpool).  cluster (b, n) and starts (b, n + 1) are
+    `grid_cluster`'s.  Differentiable in feat_pooled: the gradient of a cell is the double sum over its points in ascending
+    index (rf_grid_pool), for which `grid_cluster`'s "order" and "nclusters" are taken from the arguments or -- given neither
+    -- rebuilt from `cluster` by a stable torch sort in the backward."""
+    if (order is None) != (nclusters is None):
+        raise ValueError("grid_unpool takes order and nclusters together")
+    f = feat_pooled if isinstance(feat_pooled, torch.Tensor) else torch.as_tensor(feat_pooled)
+    return _GridUnpool.apply(f.to(torch.float32).contiguous(), _index_tensor(cluster), _index_tensor(starts),
+                             None if order is None else _index_tensor(order), None if order is None else _index_tensor(nclusters))
+
+
+def serialize(pcd, cell, order="z", origin=None, lengths=None):
+    """The point order along a space-filling curve over the grid of edge `cell` (Point Transformer v3's serialisation):
+    -> (code (b, n) int64, order (b, n) int32, inverse (b, n) int32).  code is each point's 48-bit key along `order` ("z"
+    Morton, "hilbert", "xyz" row-major; code >> 3 s is the code on the grid of edge cell * 2^s for both curves), -1 for rows
+    that are not inside; order lists the inside points by ascending (code, index), zeros behind them; inverse[order[r]] = r
+    for the inside points and -1 elsewhere.  code and order come from the cluster kernel (`grid_cluster`); inverse is torch
+    code on order -- one scatter on the device, rows behind the inside count into a spare column: no host synchronisation.
+    Other axis conventions are a column permutation of pcd in front of the call."""
+    info = grid_cluster(pcd, cell, origin, order, lengths, return_code=True)
+    od, inside = info["order"], info["inside"]
+    b, n = od.shape
+    r = torch.arange(n, device=od.device, dtype=torch.int32).expand(b, n)
+    live = r < inside[:, None]
+    inverse = torch.full((b, n + 1), -1, device=od.device, dtype=torch.int32)
+    inverse.scatter_(1, torch.where(live, od, n).long(), torch.where(live, r, -1))
+    return info["code"], od, inverse[:, :n].contiguous()
+
+
 class _NeighborAggregation(torch.autograd.Function):
     """rf_neighbor_aggregate / rf_neighbor_aggregate_grad: value, weight and pos carry gradients, idx does not."""
 
