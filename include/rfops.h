@@ -1231,6 +1231,66 @@ int rf_grid_pool(int b, int n, int c, int reduce, const float *feat, const int *
 int rf_grid_unpool(int b, int n, int c, int mode, const float *src, const int *cluster, const int *starts, const int *arg,
                    float *dst, rf_stream_t stream);
 
+/* ---- submanifold sparse convolution on the cells of that grid (sparse_conv.hip) ----
+ * The output cells are the input cells: no strided or transposed form, rf_grid_pool is the downsampling.  A kernel of edge
+ * ks in {3, 5} has K = ks^3 slots; with r = ks / 2, slot t = ((dx + r) ks + (dy + r)) ks + (dz + r) has the offset
+ * dilation (dx, dy, dz), so offset[K-1-t] = -offset[t] and the centre is slot (K-1)/2.
+ *
+ * rf_sparse_conv_map: coords (b,n,3) int32 -- rf_grid_cluster's, in any order, or those of a coarser level -- and count (b)
+ * -> nbr (b,n,K) int32.  M = count[i] clamped into [0, n] (NULL: n), read on the device; rows behind M are never read.  A
+ * row below M is LIVE when (a) its three coordinates are in [-32768, 32767] and (b) no row of lower index has the same
+ * coordinates; (c) a duplicate of an earlier row is not live: its row of nbr is all -1 and no row names it.  For a live row
+ * i, nbr[i][t] is the live row j with coords[j] = coords[i] + offset[t] (the sum range-checked: a target outside
+ * [-32768, 32767] is absent), or -1.  Every other row of nbr, the rows from M on included, is -1.  Hence for live i, j:
+ * nbr[i][t] == j exactly when nbr[j][K-1-t] == i, on which the gradient below rests.  One workgroup per sample sorts
+ * (48-bit key << 16 | row) in LDS, as rf_grid_cluster does, and answers every (row, slot) by a binary search: n <=
+ * RF_GC_MAX_POINTS.  One launch, no workspace, no atomics, no memset, every element of nbr written once, capturable.
+ * Argument rules, before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for n outside
+ * 1 ... RF_GC_MAX_POINTS, b above 65535, ks outside {3, 5}, dilation outside 1 ... RF_SC_MAX_DILATION, a NULL tensor (count
+ * may be NULL), a tensor or count array not 4-byte aligned.
+ *
+ * rf_sparse_conv: feat (b,n,cin), weight, nbr (b,n,K), count (b) -> out (b,n,cout), K in {27, 125}, 1 <= cin, cout <=
+ * RF_SC_MAX_CHANNELS.  RF_SC_FORWARD, weight (K,cin,cout): per row i < M and output channel o
+ *     acc = +0; for t = 0 .. K-1 ascending: j = nbr[i][t]; if 0 <= j < M:
+ *         for ch = 0 .. cin-1 ascending: acc = fmaf(feat[j][ch], weight[t][ch][o], acc)
+ *     out[i][o] = acc
+ * an fp32 fmaf chain (v_mfma_f32_32x32x2_f32 computes exactly that, subnormals kept).  Rows from M on are +0.  An entry of
+ * nbr outside [0, M) is absent, so nothing outside the tensors is touched whatever nbr holds; a non-finite feature row
+ * reaches exactly the outputs whose map names it.  An absent slot, and the padding of an odd cin to the instruction's two
+ * channels, may be realised as skipped steps or as steps with zeros.  The two differ in this only: an accumulator that is
+ * exactly -0 may become +0 -- zeros compare equal regardless of sign, NaNs as NaN regardless of payload -- and the weights
+ * must be finite: a precondition that is not checked (nothing outside out is touched if it is broken).
+ * RF_SC_GRAD_INPUT is the same kernel for the gradient to the features: feat is grad_out (b,n,cin), weight the forward's
+ * weight, which is (K,cout,cin) in this call's sizes, out is grad_feat (b,n,cout), and weight[K-1-t][o][ch] stands where
+ * weight[t][ch][o] stands above.  By the map's symmetry that mirrored gather chain is the gradient; it is prescribed as
+ * such, not as a scatter: no atomics, every row stored once.  One launch, no workspace.
+ *
+ * rf_sparse_conv_grad_weight: feat (b,n,cin), grad_out (b,n,cout), nbr, count -> grad_weight (K,cin,cout),
+ *     grad_weight[t][ci][co] = sum over samples and rows i < M with 0 <= j = nbr[i][t] < M of feat[j][ci] grad_out[i][co]:
+ * per sample the rows in chunks of RF_SC_WGRAD_ROWS; inside a chunk acc = +0 and acc = fmaf(feat[j][ci], grad_out[i][co],
+ * acc) over the chunk's rows ascending, absent slots skipped (or taken with zeros on both sides, with the same latitude for
+ * -0); a sample's chunks added in double from +0.0 ascending, the samples' totals added in double from +0.0 ascending,
+ * rounded to fp32 once.  The result is a sum over the batch and depends on nothing else.  Two launches (a double partial per
+ * sample into the workspace, then the sum over the samples), no atomics, no memset, the same bits on every call.
+ * workspace: rf_sparse_conv_grad_weight_workspace_bytes(b, K, cin, cout) bytes, 16-byte aligned (0 = outside the domain).
+ * Argument rules of both, before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for n outside
+ * 1 ... RF_GC_MAX_POINTS, b above 65535, K outside {27, 125}, cin or cout outside 1 ... RF_SC_MAX_CHANNELS, an unknown mode,
+ * a NULL tensor (count may be NULL), a tensor or count array not 4-byte aligned, a workspace that is NULL or not 16-byte
+ * aligned; a workspace smaller than the query says is RF_EWORKSPACE.  When cin and cout are multiples of 4 and feat and
+ * weight are 16-byte aligned, rf_sparse_conv loads rows as 16-byte vectors; the results are the same. */
+#define RF_SC_MAX_CHANNELS 256
+#define RF_SC_MAX_DILATION 1024
+#define RF_SC_WGRAD_ROWS 1024
+#define RF_SC_FORWARD 0
+#define RF_SC_GRAD_INPUT 1
+int rf_sparse_conv_map(int b, int n, int ks, int dilation, const int *coords, const int *count, int *nbr, rf_stream_t stream);
+int rf_sparse_conv(int b, int n, int K, int cin, int cout, int mode, const float *feat, const float *weight, const int *nbr,
+                   const int *count, float *out, rf_stream_t stream);
+size_t rf_sparse_conv_grad_weight_workspace_bytes(int b, int K, int cin, int cout);
+int rf_sparse_conv_grad_weight(int b, int n, int K, int cin, int cout, const float *feat, const float *grad_out, const int *nbr,
+                               const int *count, float *grad_weight, void *workspace, size_t workspace_bytes,
+                               rf_stream_t stream);
+
 /* -------------------------------------------------- interpolation (tf_ops/interpolation) - */
 /* Replace threenn_cpu / threeinterpolate_cpu / threeinterpolate_grad_cpu
  * (tf_interpolate.cpp:60-153; CPU-only ops in the reference).  xyz1 (b,n,3) unknown,

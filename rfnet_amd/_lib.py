@@ -153,6 +153,10 @@ SIGNATURES = {
     "rf_grid_cluster": (_i, [_i, _i, _f, _i] + [_vp] * 12),
     "rf_grid_pool": (_i, [_i, _i, _i, _i] + [_vp] * 7),
     "rf_grid_unpool": (_i, [_i, _i, _i, _i] + [_vp] * 6),
+    "rf_sparse_conv_map": (_i, [_i, _i, _i, _i] + [_vp] * 4),
+    "rf_sparse_conv": (_i, [_i] * 6 + [_vp] * 6),
+    "rf_sparse_conv_grad_weight_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "rf_sparse_conv_grad_weight": (_i, [_i] * 5 + [_vp] * 6 + [_sz, _vp]),
     "rf_threenn": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_threenn_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_threenn_lengths": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp, _i]),

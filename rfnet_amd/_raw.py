@@ -2164,6 +2164,128 @@ def grid_unpool(src, cluster, starts=None, arg=None, mode="copy"):
     return st.give(dst)
 
 
+SC_MAX_CHANNELS, SC_MAX_DILATION, SC_WGRAD_ROWS = 256, 1024, 1024  # RF_SC_MAX_CHANNELS, RF_SC_MAX_DILATION, RF_SC_WGRAD_ROWS
+SC_MODES = {"forward": 0, "grad_input": 1}  # RF_SC_FORWARD, RF_SC_GRAD_INPUT
+
+
+def _sc_check_counts(x, b, n, name="nclusters"):
+    """The cell counts of the sparse convolution entries -> None or a (b,) integer tensor, before any GPU work.  Unlike the
+    point counts of the ragged entries a count may be 0 (a sample without a cell): host-given counts are checked into
+    [0, n], device counts are only shape-checked (grid_cluster's nclusters: no host round trip; the kernels clamp them)."""
+    if x is None:
+        return None
+    t = x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise H.invalid(f"{name} must hold integer cell counts")
+    if t.dim() != 1 or t.shape[0] != b:
+        raise H.invalid(f"{name} must be of shape (batch,)")
+    if not t.is_cuda and (int(t.min()) < 0 or int(t.max()) > n):
+        raise H.invalid(f"{name} must lie in [0, {n}]")
+    return t
+
+
+def _sc_counts_up(t, dev, n):
+    """checked counts -> a contiguous int32 tensor on `dev` (a device int32 tensor stays as it is)"""
+    if t is None:
+        return None
+    if t.is_cuda and t.device != dev:
+        raise ValueError(f"all GPU inputs of one op must live on the same device: got {dev} and {t.device}")
+    t = t.to(device=dev)
+    if t.dtype != I32:
+        t = t.clamp(0, n).to(I32)
+    return t.contiguous()
+
+
+def _sc_sizes(op, b, n, K=27, cin=1, cout=1):
+    if not (1 <= b <= 65535 and 1 <= n <= GC_MAX_POINTS):
+        raise H.invalid(f"{op} takes 1 <= b <= 65535 and 1 <= n <= {GC_MAX_POINTS} cells")
+    if K not in (27, 125):
+        raise H.invalid(f"{op} takes K = 27 or 125 slots (kernel_size 3 or 5)")
+    if not (1 <= cin <= SC_MAX_CHANNELS and 1 <= cout <= SC_MAX_CHANNELS):
+        raise H.invalid(f"{op} takes 1 to {SC_MAX_CHANNELS} channels")
+
+
+@H.on_input_device
+def sparse_conv_map(coords, nclusters=None, kernel_size=3, dilation=1):
+    """rf_sparse_conv_map: coords (b,n,3) int32 cell indices (grid_cluster's "coords") and the cell counts nclusters (b,) ->
+    nbr (b,n,K) int32, K = kernel_size^3: per live row the row of the cell at each of the K offsets, or -1 (include/rfops.h)."""
+    op = "SparseConvMap"
+    st = H.Staged()
+    c = st.take(coords, I32)
+    if not _shape3(c, 3):
+        raise H.invalid(f"{op} expects (b,n,3) coords shape")
+    b, n = c.shape[0], c.shape[1]
+    _sc_sizes(op, b, n)
+    ks, dilation = int(kernel_size), int(dilation)
+    if ks not in (3, 5):
+        raise H.invalid(f"{op} takes kernel_size 3 or 5")
+    if not 1 <= dilation <= SC_MAX_DILATION:
+        raise H.invalid(f"{op} takes 1 <= dilation <= {SC_MAX_DILATION}")
+    cnt = _sc_check_counts(nclusters, b, n)
+    dev = st.device_()
+    c, = st.up(c)
+    cnt = _sc_counts_up(cnt, dev, n)
+    nbr = H.empty((b, n, ks ** 3), I32, dev)
+    check(lib.rf_sparse_conv_map(b, n, ks, dilation, H.ptr(c), H.ptr(cnt), H.ptr(nbr), H.stream(dev)), "rf_sparse_conv_map")
+    return st.give(nbr)
+
+
+@H.on_input_device
+def sparse_conv(feat, weight, nbr, nclusters=None, mode="forward"):
+    """rf_sparse_conv: feat (b,n,cin), nbr (b,n,K) -> (b,n,cout).  mode "forward": weight (K,cin,cout); "grad_input": feat is
+    grad_out, weight the forward's weight (K,cout,cin) and the result the gradient to the forward's features."""
+    op = "SparseConv"
+    st = H.Staged()
+    f, w, nb = st.take(feat, F32), st.take(weight, F32), st.take(nbr, I32)
+    if mode not in SC_MODES:
+        raise H.invalid(f"{op} takes mode in {sorted(SC_MODES)}")
+    if not _shape3(f):
+        raise H.invalid(f"{op} expects (b,n,c) feat shape")
+    b, n, cin = f.shape
+    red = 1 if mode == "forward" else 2  # where weight holds this call's reduction width
+    if not (_shape3(w) and w.shape[red] == cin):
+        raise H.invalid(f"{op} expects (K,cin,cout) weight shape, and the channels must match feat")
+    K, cout = w.shape[0], w.shape[3 - red]
+    _sc_sizes(op, b, n, K, cin, cout)
+    if tuple(nb.shape) != (b, n, K):
+        raise H.invalid(f"{op} expects nbr of shape {(b, n, K)}")
+    cnt = _sc_check_counts(nclusters, b, n)
+    dev = st.device_()
+    f, w, nb = st.up(f, w, nb)
+    cnt = _sc_counts_up(cnt, dev, n)
+    out = H.empty((b, n, cout), F32, dev)
+    check(lib.rf_sparse_conv(b, n, K, cin, cout, SC_MODES[mode], H.ptr(f), H.ptr(w), H.ptr(nb), H.ptr(cnt), H.ptr(out),
+                             H.stream(dev)), "rf_sparse_conv")
+    return st.give(out)
+
+
+@H.on_input_device
+def sparse_conv_grad_weight(feat, grad_out, nbr, nclusters=None):
+    """rf_sparse_conv_grad_weight: feat (b,n,cin), grad_out (b,n,cout), nbr (b,n,K) -> grad_weight (K,cin,cout): fmaf chains
+    over chunks of 1024 rows, the chunks and the samples added in double, rounded once (include/rfops.h)."""
+    op = "SparseConvGradWeight"
+    st = H.Staged()
+    f, g, nb = st.take(feat, F32), st.take(grad_out, F32), st.take(nbr, I32)
+    if not _shape3(f):
+        raise H.invalid(f"{op} expects (b,n,cin) feat shape")
+    b, n, cin = f.shape
+    if not (_shape3(g) and tuple(g.shape[:2]) == (b, n)):
+        raise H.invalid(f"{op} expects (b,n,cout) grad_out shape")
+    if not (nb.dim() == 3 and tuple(nb.shape[:2]) == (b, n)):
+        raise H.invalid(f"{op} expects (b,n,K) nbr shape")
+    cout, K = g.shape[2], nb.shape[2]
+    _sc_sizes(op, b, n, K, cin, cout)
+    cnt = _sc_check_counts(nclusters, b, n)
+    dev = st.device_()
+    f, g, nb = st.up(f, g, nb)
+    cnt = _sc_counts_up(cnt, dev, n)
+    gw = H.empty((K, cin, cout), F32, dev)
+    ws, wsz = H.workspace(lib.rf_sparse_conv_grad_weight_workspace_bytes(b, K, cin, cout), dev, "sparse_conv_grad_weight")
+    check(lib.rf_sparse_conv_grad_weight(b, n, K, cin, cout, H.ptr(f), H.ptr(g), H.ptr(nb), H.ptr(cnt), H.ptr(gw), H.ptr(ws), wsz,
+                                         H.stream(dev)), "rf_sparse_conv_grad_weight")
+    return st.give(gw)
+
+
 @H.on_input_device
 def knn_point_grad(xyz1, xyz2, idx, grad_val, lengths1=None, lengths2=None):
     """The gradient of knn_point's val -> (grad_xyz1 (b,n,3), grad_xyz2 (b,m,3)) (rf_knn_grad).  lengths1 / lengths2: the counts

@@ -883,6 +883,86 @@ def serialize(pcd, cell, order="z", origin=None, lengths=None):
     return info["code"], od, inverse[:, :n].contiguous()
 
 
+def sparse_conv_map(coords, nclusters=None, kernel_size=3, dilation=1):
+    """The kernel map of a submanifold sparse convolution over the occupied cells of `grid_cluster`: coords (b, n, 3) int32
+    cell indices ("coords" of its dict, in any order; `coords >> s` of a coarser level too) and nclusters (b,), the cells per
+    sample (its "nclusters"; None: all n) -> nbr (b, n, K) int32, K = kernel_size^3, kernel_size 3 or 5.  With r =
+    kernel_size // 2, slot t = ((dx + r) ks + (dy + r)) ks + (dz + r) names the cell at offset dilation * (dx, dy, dz):
+    nbr[i, t] is its row, or -1 where no cell is there.  Rows behind a count, rows with an index outside +-32768 and
+    duplicates of an earlier row are all -1 and nobody names them, so nbr[i, t] == j exactly when nbr[j, K-1-t] == i.  One
+    launch: a sort of the cell keys in LDS and a binary search per slot, no host synchronisation (capturable), n <= 16384
+    (rf_sparse_conv_map).  Build it once per grid level and dilation; every convolution of that level shares it."""
+    return _raw.sparse_conv_map(_index_tensor(coords), nclusters, kernel_size, dilation)
+
+
+class _SparseConv(torch.autograd.Function):
+    """rf_sparse_conv; the gradient to the features is the same kernel on the mirrored slots and the transposed weight, the
+    gradient to the weight rf_sparse_conv_grad_weight.  nbr and the counts carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, nbr, nclusters):
+        ctx.save_for_backward(feat, weight, nbr)
+        ctx.nclusters = nclusters
+        return _raw.sparse_conv(feat, weight, nbr, nclusters)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        feat, weight, nbr = ctx.saved_tensors
+        g = grad_out.contiguous()
+        gf = _raw.sparse_conv(g, weight, nbr, ctx.nclusters, "grad_input") if ctx.needs_input_grad[0] else None
+        gw = _raw.sparse_conv_grad_weight(feat, g, nbr, ctx.nclusters) if ctx.needs_input_grad[1] else None
+        return gf, gw, None, None
+
+
+def sparse_conv(feat, weight, nbr, nclusters=None):
+    """Submanifold sparse convolution (spconv's SubMConv3d, MinkowskiEngine's stride-1 convolution, the 3 x 3 x 3 layers of
+    SPVCNN and MinkUNet, Point Transformer v3's xCPE): feat (b, n, cin), one row per occupied cell as `grid_pool` returns
+    them, weight (K, cin, cout) and `sparse_conv_map`'s nbr (b, n, K) -> (b, n, cout): out[i] = sum over the slots t whose
+    cell nbr[i, t] exists of feat[nbr[i, t]] @ weight[t]; the output cells are the input cells, rows behind nclusters are
+    zeros.  cin, cout <= 256.  The sum is one fp32 fmaf chain over (slot, channel) in ascending order, run on the fp32 matrix
+    instruction: the same bits on every call, for every batch and shard.  Weights must be finite.  Differentiable in feat
+    and weight; only the gradients that are needed are computed: the gradient to feat by the same kernel (no atomics), the
+    gradient to weight by fmaf chains over 1024 rows summed in double over chunks and samples -- a sum over the batch, and
+    dependent on nothing else.  nclusters may be a device tensor: no host synchronisation, capturable."""
+    return _SparseConv.apply(_feature_tensor(feat), _feature_tensor(weight), _index_tensor(nbr), nclusters)
+
+
+class SubMConv3d(torch.nn.Module):
+    """`sparse_conv` as a layer: weight (kernel_size^3, cin, cout), kernel_size 3 or 5, an optional bias (added by torch, to
+    the rows in front of the counts only).  forward(feat (b, n, cin), coords or nbr, nclusters=None): given coords (b, n, 3)
+    the map is built with the layer's kernel_size and dilation; a stack of layers on one grid level builds it once with
+    `sparse_conv_map` and passes nbr (b, n, K)."""
+
+    def __init__(self, cin, cout, kernel_size=3, dilation=1, bias=True):
+        super().__init__()
+        if kernel_size not in (3, 5):
+            raise ValueError("kernel_size must be 3 or 5")
+        self.cin, self.cout, self.kernel_size, self.dilation = int(cin), int(cout), int(kernel_size), int(dilation)
+        K = self.kernel_size ** 3
+        self.weight = torch.nn.Parameter(torch.empty(K, self.cin, self.cout))
+        self.bias = torch.nn.Parameter(torch.zeros(self.cout)) if bias else None
+        bound = (K * self.cin) ** -0.5  # torch's convolution default: uniform in +-1 / sqrt(fan_in)
+        torch.nn.init.uniform_(self.weight, -bound, bound)
+        if bias:
+            torch.nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, feat, coords_or_nbr, nclusters=None):
+        nbr = coords_or_nbr
+        if nbr.shape[-1] == 3:  # coords (K is 27 or 125)
+            nbr = sparse_conv_map(nbr, nclusters, self.kernel_size, self.dilation)
+        out = sparse_conv(feat, self.weight, nbr, nclusters)
+        if self.bias is not None:
+            if nclusters is None:
+                out = out + self.bias
+            else:
+                n = out.shape[1]
+                cnt = torch.as_tensor(nclusters, device=out.device)
+                live = torch.arange(n, device=out.device)[None, :] < cnt[:, None]
+                out = out + live.unsqueeze(-1).to(out.dtype) * self.bias
+        return out
+
+
 class _NeighborAggregation(torch.autograd.Function):
     """rf_neighbor_aggregate / rf_neighbor_aggregate_grad: value, weight and pos carry gradients, idx does not."""
 
