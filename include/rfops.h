@@ -1232,7 +1232,7 @@ int rf_grid_unpool(int b, int n, int c, int mode, const float *src, const int *c
                    float *dst, rf_stream_t stream);
 
 /* ---- submanifold sparse convolution on the cells of that grid (sparse_conv.hip) ----
- * The output cells are the input cells: no strided or transposed form, rf_grid_pool is the downsampling.  A kernel of edge
+ * The output cells are the input cells; the strided form and its transpose are the next block (sparse_stride.hip).  A kernel of edge
  * ks in {3, 5} has K = ks^3 slots; with r = ks / 2, slot t = ((dx + r) ks + (dy + r)) ks + (dz + r) has the offset
  * dilation (dx, dy, dz), so offset[K-1-t] = -offset[t] and the centre is slot (K-1)/2.
  *
@@ -1290,6 +1290,71 @@ size_t rf_sparse_conv_grad_weight_workspace_bytes(int b, int K, int cin, int cou
 int rf_sparse_conv_grad_weight(int b, int n, int K, int cin, int cout, const float *feat, const float *grad_out, const int *nbr,
                                const int *count, float *grad_weight, void *workspace, size_t workspace_bytes,
                                rf_stream_t stream);
+
+/* ---- strided sparse convolution and its transpose: the change of level on that grid (sparse_stride.hip) ----
+ * Kernel 2, stride 2 only: a coarse cell (x >> 1, y >> 1, z >> 1) -- the arithmetic shift, a floor -- has up to eight children,
+ * the child (x, y, z) in slot t = (x & 1) 4 + (y & 1) 2 + (z & 1).  Kernel 3 / stride 2, other strides and a "generative"
+ * transposed convolution that creates cells are not provided: the transpose writes to the cells of the finer level it came from.
+ *
+ * rf_sparse_stride_map: coords (b,n,3) int32 and count (b), read exactly as rf_sparse_conv_map reads them (the same LIVE rule:
+ * below the clamped count M, in [-32768, 32767], no row of lower index with the same coordinates; any order) -> the coarse
+ * level.  The coarse cells of a sample are the distinct coarse cells of its live rows in ascending row-major key order (the
+ * order RF_GC_XYZ gives), D of them: total_out[s] = D, count_out[s] = min(D, n_coarse).  Cells of rank >= n_coarse are DROPPED:
+ * they have no row, and their children count as not live for child and up.  coords_out (b,n_coarse,3) holds the cells, zeros
+ * behind count_out.  child (b,n_coarse,8): child[j][t] is the live fine row in coarse cell j at slot t, or -1; rows behind
+ * count_out are all -1.  up (b,n): 8 j + t for a live, kept fine row, -1 for every other row, the rows from M on included.
+ * Hence up[i] == 8 j + t exactly when child[j][t] == i.  coords_out / count_out go as they are into rf_sparse_conv_map for the
+ * coarse level's submanifold layers and into another rf_sparse_stride_map for the next level.  One workgroup per sample sorts
+ * ((45-bit coarse key << 3 | t) << 16 | row) in LDS; a scan of the words at which the coarse key changes gives the rank.  n <=
+ * RF_GC_MAX_POINTS, 1 <= n_coarse <= n, b <= 65535.  One launch, no workspace, no atomics, no memset, every element of every
+ * output written exactly once, capturable.  Argument rules, before any HIP call: RF_EINVAL for a negative size; then b == 0 is
+ * RF_OK; RF_EINVAL for n outside 1 ... RF_GC_MAX_POINTS, n_coarse outside 1 ... n, b above 65535, a NULL tensor (count may be
+ * NULL), a tensor or count array not 4-byte aligned.
+ *
+ * rf_sparse_conv_strided: weight is always the layer's (8, ci, co) tensor; cin is the reduction width of this call and cout the
+ * width of out, both in 1 ... RF_SC_MAX_CHANNELS; M and Mc are count and count_coarse clamped into [0, n] and [0, n_coarse]
+ * (NULL: n, n_coarse).  Every sum is ONE fp32 fmaf chain from +0 in the stated order, with rf_sparse_conv's latitude for absent
+ * slots and odd widths (-0 may become +0); weights must be finite.
+ *   RF_SS_DOWN             src (b,n,cin) -> out (b,n_coarse,cout).  Per j < Mc and o: t ascending, skipping i = child[j][t]
+ *                          outside [0, M); then ch ascending: acc = fmaf(src[i][ch], weight[t][ch][o], acc).  Rows from Mc on: +0.
+ *   RF_SS_UP               the transposed convolution onto the fine cells: src (b,n_coarse,cin) -> out (b,n,cout).  A fine row i
+ *                          is SERVED when i < M, up[i] = 8 j + t with 0 <= j < Mc, and child[j][t] == i; then out[i][o] is the
+ *                          chain over ch ascending of src[j][ch] weight[t][ch][o].  A row that is not served is +0.
+ *   RF_SS_DOWN_GRAD_INPUT  src is the coarse grad_out (b,n_coarse,cin) -> out (b,n,cout): as RF_SS_UP with weight[t][o][ch].
+ *   RF_SS_UP_GRAD_INPUT    src is the fine grad_out (b,n,cin) -> out (b,n_coarse,cout): as RF_SS_DOWN with weight[t][o][ch].
+ * The served rule makes the result well defined and keeps every store inside out with no two writers of a row, whatever child
+ * and up hold: garbage in the maps is tolerated as rf_sparse_conv tolerates it in nbr.  DOWN and UP_GRAD_INPUT gather (a wave
+ * owns 32 coarse rows and carries its accumulators over the eight slots); UP and DOWN_GRAD_INPUT fan out (a workgroup owns 32
+ * coarse rows, each of its waves two slots: one chain per slot some row of the tile has, each accumulator row stored to the fine
+ * row child[j][t] that up confirms; further workgroups of the same launch store +0 to the fine rows that are not served).  One launch, no workspace, no
+ * atomics, no memset, every element of out written once.
+ *
+ * rf_sparse_conv_strided_grad_weight -> grad_weight (8,cin,cout), the layer's layout.  Both modes walk the coarse rows j < Mc
+ * ascending with i = child[j][t] in [0, M), otherwise skipped.  RF_SS_DOWN: fine is the forward's feat (b,n,cin), coarse is
+ * grad_out (b,n_coarse,cout), the terms are fine[i][ci] coarse[j][co].  RF_SS_UP: coarse is the forward's feat (b,n_coarse,cin),
+ * fine is grad_out (b,n,cout), the terms are coarse[j][ci] fine[i][co].  The sum is rf_sparse_conv_grad_weight's: an fmaf chain
+ * per chunk of RF_SC_WGRAD_ROWS coarse rows, the chunks added in double, a double partial per sample in the workspace, the
+ * samples added in double in ascending order, rounded once.  Two launches, no atomics, no memset.
+ * workspace: rf_sparse_conv_strided_grad_weight_workspace_bytes(b, cin, cout) bytes, 16-byte aligned (0 = outside the domain).
+ * Argument rules of both, before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for n outside
+ * 1 ... RF_GC_MAX_POINTS, n_coarse outside 1 ... n, b above 65535, cin or cout outside 1 ... RF_SC_MAX_CHANNELS, an unknown mode
+ * (the weight gradient takes RF_SS_DOWN and RF_SS_UP), a NULL tensor (count and count_coarse may be NULL), a tensor or count
+ * array not 4-byte aligned, a workspace that is NULL or not 16-byte aligned; a workspace smaller than the query says is
+ * RF_EWORKSPACE.  When cin and cout are multiples of 4 and src and weight are 16-byte aligned, rf_sparse_conv_strided loads rows
+ * as 16-byte vectors; the results are the same. */
+#define RF_SS_DOWN 0
+#define RF_SS_UP 1
+#define RF_SS_DOWN_GRAD_INPUT 2
+#define RF_SS_UP_GRAD_INPUT 3
+int rf_sparse_stride_map(int b, int n, int n_coarse, const int *coords, const int *count, int *coords_out, int *count_out,
+                         int *total_out, int *child, int *up, rf_stream_t stream);
+int rf_sparse_conv_strided(int b, int n, int n_coarse, int cin, int cout, int mode, const float *src, const float *weight,
+                           const int *child, const int *up, const int *count, const int *count_coarse, float *out,
+                           rf_stream_t stream);
+size_t rf_sparse_conv_strided_grad_weight_workspace_bytes(int b, int cin, int cout);
+int rf_sparse_conv_strided_grad_weight(int b, int n, int n_coarse, int cin, int cout, int mode, const float *fine,
+                                       const float *coarse, const int *child, const int *count, const int *count_coarse,
+                                       float *grad_weight, void *workspace, size_t workspace_bytes, rf_stream_t stream);
 
 /* -------------------------------------------------- interpolation (tf_ops/interpolation) - */
 /* Replace threenn_cpu / threeinterpolate_cpu / threeinterpolate_grad_cpu

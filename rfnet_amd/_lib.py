@@ -157,6 +157,10 @@ SIGNATURES = {
     "rf_sparse_conv": (_i, [_i] * 6 + [_vp] * 6),
     "rf_sparse_conv_grad_weight_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_sparse_conv_grad_weight": (_i, [_i] * 5 + [_vp] * 6 + [_sz, _vp]),
+    "rf_sparse_stride_map": (_i, [_i, _i, _i] + [_vp] * 8),
+    "rf_sparse_conv_strided": (_i, [_i] * 6 + [_vp] * 8),
+    "rf_sparse_conv_strided_grad_weight_workspace_bytes": (_sz, [_i, _i, _i]),
+    "rf_sparse_conv_strided_grad_weight": (_i, [_i] * 6 + [_vp] * 7 + [_sz, _vp]),
     "rf_threenn": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_threenn_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_threenn_lengths": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp, _i]),

@@ -2286,6 +2286,111 @@ def sparse_conv_grad_weight(feat, grad_out, nbr, nclusters=None):
     return st.give(gw)
 
 
+SS_MODES = {"down": 0, "up": 1, "down_grad_input": 2, "up_grad_input": 3}  # RF_SS_DOWN ... RF_SS_UP_GRAD_INPUT
+
+
+def _ss_sizes(op, b, n, nc, cin=1, cout=1):
+    if not (1 <= b <= 65535 and 1 <= n <= GC_MAX_POINTS):
+        raise H.invalid(f"{op} takes 1 <= b <= 65535 and 1 <= n <= {GC_MAX_POINTS} cells")
+    if not 1 <= nc <= n:
+        raise H.invalid(f"{op} takes 1 <= max_cells <= n coarse rows")
+    if not (1 <= cin <= SC_MAX_CHANNELS and 1 <= cout <= SC_MAX_CHANNELS):
+        raise H.invalid(f"{op} takes 1 to {SC_MAX_CHANNELS} channels")
+
+
+@H.on_input_device
+def sparse_stride_map(coords, nclusters=None, max_cells=None):
+    """rf_sparse_stride_map: coords (b,n,3) int32 cell indices and the cell counts nclusters (b,) -> (coords_out (b,nc,3),
+    count_out (b,), total_out (b,), child (b,nc,8), up (b,n)), all int32, nc = max_cells (default n): the level of the cells
+    coords >> 1 (include/rfops.h)."""
+    op = "SparseStrideMap"
+    st = H.Staged()
+    c = st.take(coords, I32)
+    if not _shape3(c, 3):
+        raise H.invalid(f"{op} expects (b,n,3) coords shape")
+    b, n = c.shape[0], c.shape[1]
+    nc = n if max_cells is None else int(max_cells)
+    _ss_sizes(op, b, n, nc)
+    cnt = _sc_check_counts(nclusters, b, n)
+    dev = st.device_()
+    c, = st.up(c)
+    cnt = _sc_counts_up(cnt, dev, n)
+    co, cn, tot = H.empty((b, nc, 3), I32, dev), H.empty((b,), I32, dev), H.empty((b,), I32, dev)
+    child, up = H.empty((b, nc, 8), I32, dev), H.empty((b, n), I32, dev)
+    check(lib.rf_sparse_stride_map(b, n, nc, H.ptr(c), H.ptr(cnt), H.ptr(co), H.ptr(cn), H.ptr(tot), H.ptr(child), H.ptr(up),
+                                   H.stream(dev)), "rf_sparse_stride_map")
+    return tuple(st.give(t) for t in (co, cn, tot, child, up))
+
+
+def _ss_maps(op, st, child, up):
+    ch, u = st.take(child, I32), st.take(up, I32)
+    if not (ch.dim() == 3 and ch.shape[2] == 8 and u.dim() == 2 and u.shape[0] == ch.shape[0]):
+        raise H.invalid(f"{op} expects child of shape (b,n_coarse,8) and up of shape (b,n)")
+    return ch, u
+
+
+@H.on_input_device
+def sparse_conv_strided(src, weight, child, up, nclusters=None, nclusters_coarse=None, mode="down"):
+    """rf_sparse_conv_strided: weight is the layer's (8,ci,co).  "down": src (b,n,ci) -> (b,nc,co); "up": src (b,nc,ci) ->
+    (b,n,co); "down_grad_input": src the coarse grad_out (b,nc,co) -> (b,n,ci); "up_grad_input": src the fine grad_out (b,n,co) ->
+    (b,nc,ci).  child (b,nc,8) and up (b,n) are `sparse_stride_map`'s, the counts those of the fine and of the coarse level."""
+    op = "SparseConvStrided"
+    st = H.Staged()
+    f, w = st.take(src, F32), st.take(weight, F32)
+    ch, u = _ss_maps(op, st, child, up)
+    if mode not in SS_MODES:
+        raise H.invalid(f"{op} takes mode in {sorted(SS_MODES)}")
+    if not _shape3(f):
+        raise H.invalid(f"{op} expects (b,rows,c) src shape")
+    b, nc, n = ch.shape[0], ch.shape[1], u.shape[1]
+    rows_in, rows_out = (n, nc) if mode in ("down", "up_grad_input") else (nc, n)
+    if f.shape[0] != b or f.shape[1] != rows_in:
+        raise H.invalid(f"{op} ({mode}) expects src of {rows_in} rows per sample, as child and up say")
+    cin = f.shape[2]
+    red = 1 if mode in ("down", "up") else 2  # where weight holds this call's reduction width
+    if not (_shape3(w) and w.shape[0] == 8 and w.shape[red] == cin):
+        raise H.invalid(f"{op} expects (8,ci,co) weight shape, and the channels must match src")
+    cout = w.shape[3 - red]
+    _ss_sizes(op, b, n, nc, cin, cout)
+    cnt, cntc = _sc_check_counts(nclusters, b, n), _sc_check_counts(nclusters_coarse, b, nc, "nclusters_coarse")
+    dev = st.device_()
+    f, w, ch, u = st.up(f, w, ch, u)
+    cnt, cntc = _sc_counts_up(cnt, dev, n), _sc_counts_up(cntc, dev, nc)
+    out = H.empty((b, rows_out, cout), F32, dev)
+    check(lib.rf_sparse_conv_strided(b, n, nc, cin, cout, SS_MODES[mode], H.ptr(f), H.ptr(w), H.ptr(ch), H.ptr(u), H.ptr(cnt),
+                                     H.ptr(cntc), H.ptr(out), H.stream(dev)), "rf_sparse_conv_strided")
+    return st.give(out)
+
+
+@H.on_input_device
+def sparse_conv_strided_grad_weight(fine, coarse, child, nclusters=None, nclusters_coarse=None, mode="down"):
+    """rf_sparse_conv_strided_grad_weight -> (8,ci,co).  "down": fine is the forward's feat (b,n,ci), coarse grad_out (b,nc,co);
+    "up": coarse is the forward's feat (b,nc,ci), fine grad_out (b,n,co).  fmaf chains over chunks of 1024 coarse rows, the
+    chunks and the samples added in double, rounded once (include/rfops.h)."""
+    op = "SparseConvStridedGradWeight"
+    st = H.Staged()
+    f, c, ch = st.take(fine, F32), st.take(coarse, F32), st.take(child, I32)
+    if mode not in ("down", "up"):
+        raise H.invalid(f"{op} takes mode 'down' or 'up'")
+    if not (_shape3(f) and _shape3(c) and f.shape[0] == c.shape[0]):
+        raise H.invalid(f"{op} expects (b,n,c) fine and (b,n_coarse,c) coarse shapes")
+    b, n, nc = f.shape[0], f.shape[1], c.shape[1]
+    if tuple(ch.shape) != (b, nc, 8):
+        raise H.invalid(f"{op} expects child of shape {(b, nc, 8)}")
+    cin, cout = (f.shape[2], c.shape[2]) if mode == "down" else (c.shape[2], f.shape[2])
+    _ss_sizes(op, b, n, nc, cin, cout)
+    cnt, cntc = _sc_check_counts(nclusters, b, n), _sc_check_counts(nclusters_coarse, b, nc, "nclusters_coarse")
+    dev = st.device_()
+    f, c, ch = st.up(f, c, ch)
+    cnt, cntc = _sc_counts_up(cnt, dev, n), _sc_counts_up(cntc, dev, nc)
+    gw = H.empty((8, cin, cout), F32, dev)
+    ws, wsz = H.workspace(lib.rf_sparse_conv_strided_grad_weight_workspace_bytes(b, cin, cout), dev, "sparse_conv_strided_grad_weight")
+    check(lib.rf_sparse_conv_strided_grad_weight(b, n, nc, cin, cout, SS_MODES[mode], H.ptr(f), H.ptr(c), H.ptr(ch), H.ptr(cnt),
+                                                 H.ptr(cntc), H.ptr(gw), H.ptr(ws), wsz, H.stream(dev)),
+          "rf_sparse_conv_strided_grad_weight")
+    return st.give(gw)
+
+
 @H.on_input_device
 def knn_point_grad(xyz1, xyz2, idx, grad_val, lengths1=None, lengths2=None):
     """The gradient of knn_point's val -> (grad_xyz1 (b,n,3), grad_xyz2 (b,m,3)) (rf_knn_grad).  lengths1 / lengths2: the counts

@@ -963,6 +963,112 @@ class SubMConv3d(torch.nn.Module):
         return out
 
 
+def sparse_stride_map(coords, nclusters=None, max_cells=None):
+    """The next coarser level of the voxel grid, for a 2 x 2 x 2 stride-2 convolution and its transpose: coords (b, n, 3) int32
+    cell indices (`grid_cluster`'s "coords", or a level dict's, in any order) and nclusters (b,) (None: all n) -> a dict of
+    device tensors: "coords" (b, nc, 3) the distinct cells coords >> 1 of the live rows in ascending row-major order, zeros
+    behind the count; "nclusters" (b,) their count, at most nc = max_cells (default n: nothing is dropped); "total" (b,) the
+    count before that cap; "child" (b, nc, 8), child[j, t] the fine row in coarse cell j at slot t = (x & 1) 4 + (y & 1) 2 +
+    (z & 1), or -1; "up" (b, n), 8 j + t for a live fine row whose coarse cell was kept and -1 for every other row.  "coords"
+    and "nclusters" go as they are into `sparse_conv_map` for the level's submanifold layers and into another
+    `sparse_stride_map`.  One launch, no host synchronisation (capturable), n <= 16384 (rf_sparse_stride_map)."""
+    co, cn, tot, child, up = _raw.sparse_stride_map(_index_tensor(coords), nclusters, max_cells)
+    return {"coords": co, "nclusters": cn, "total": tot, "child": child, "up": up}
+
+
+class _SparseConvStrided(torch.autograd.Function):
+    """rf_sparse_conv_strided in the direction `mode` ("down" or "up"); the gradient to the features is the mode
+    `mode`_grad_input, the gradient to the weight rf_sparse_conv_strided_grad_weight.  The maps and counts carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, feat, weight, child, up, nclusters, nclusters_coarse, mode):
+        ctx.save_for_backward(feat, weight, child, up)
+        ctx.counts, ctx.mode = (nclusters, nclusters_coarse), mode
+        return _raw.sparse_conv_strided(feat, weight, child, up, nclusters, nclusters_coarse, mode)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        feat, weight, child, up = ctx.saved_tensors
+        g = grad_out.contiguous()
+        gf = gw = None
+        if ctx.needs_input_grad[0]:
+            gf = _raw.sparse_conv_strided(g, weight, child, up, *ctx.counts, ctx.mode + "_grad_input")
+        if ctx.needs_input_grad[1]:
+            fine, coarse = (feat, g) if ctx.mode == "down" else (g, feat)
+            gw = _raw.sparse_conv_strided_grad_weight(fine, coarse, child, *ctx.counts, ctx.mode)
+        return gf, gw, None, None, None, None, None
+
+
+def _strided(feat, weight, level, nclusters, mode):
+    return _SparseConvStrided.apply(_feature_tensor(feat), _feature_tensor(weight), _index_tensor(level["child"]),
+                                    _index_tensor(level["up"]), nclusters, level["nclusters"], mode)
+
+
+def sparse_conv_down(feat, weight, level, nclusters=None):
+    """Strided sparse convolution, kernel 2, stride 2 (MinkowskiEngine's Convolution(kernel_size=2, stride=2), spconv's
+    SparseConv3d(2, 2), the downsampling of MinkUNet and SPVCNN): feat (b, n, cin) on the fine cells, weight (8, cin, cout) and
+    `sparse_stride_map`'s level dict -> (b, nc, cout) on the level's cells: out[j] = sum over the slots t with a child of
+    feat[child[j, t]] @ weight[t], zeros behind the level's count.  nclusters is the fine level's count.  One fp32 fmaf chain
+    over (slot, channel) ascending on the fp32 matrix instruction: the same bits on every call and for every batch.
+    Differentiable in feat and weight; only the gradients that are needed are computed, without atomics."""
+    return _strided(feat, weight, level, nclusters, "down")
+
+
+def sparse_conv_up(feat, weight, level, nclusters=None):
+    """The transpose of `sparse_conv_down` onto the fine level's cells (MinkowskiEngine's ConvolutionTranspose(kernel_size=2,
+    stride=2) onto the encoder's coordinates, spconv's SparseInverseConv3d): feat (b, nc, cin) on the level's cells, weight
+    (8, cin, cout) -> (b, n, cout): out[i] = feat[j] @ weight[t] for the fine row i = child[j, t], zeros for rows in no kept
+    coarse cell and behind nclusters, the fine level's count.  No cell is created.  One fmaf chain over the channels per row;
+    every fine row has one writer: no atomics.  Differentiable in feat and weight."""
+    return _strided(feat, weight, level, nclusters, "up")
+
+
+class _SparseStrided(torch.nn.Module):
+    def __init__(self, cin, cout, bias=True):
+        super().__init__()
+        self.cin, self.cout = int(cin), int(cout)
+        self.weight = torch.nn.Parameter(torch.empty(8, self.cin, self.cout))
+        self.bias = torch.nn.Parameter(torch.zeros(self.cout)) if bias else None
+        bound = (8 * self.cin) ** -0.5  # torch's convolution default: uniform in +-1 / sqrt(fan_in)
+        torch.nn.init.uniform_(self.weight, -bound, bound)
+        if bias:
+            torch.nn.init.uniform_(self.bias, -bound, bound)
+
+    @staticmethod
+    def _level(coords_or_level, nclusters):
+        return coords_or_level if isinstance(coords_or_level, dict) else sparse_stride_map(coords_or_level, nclusters)
+
+    def _add_bias(self, out, cnt):
+        if self.bias is None:
+            return out
+        if cnt is None:
+            return out + self.bias
+        live = torch.arange(out.shape[1], device=out.device)[None, :] < torch.as_tensor(cnt, device=out.device)[:, None]
+        return out + live.unsqueeze(-1).to(out.dtype) * self.bias
+
+
+class SparseConv3d(_SparseStrided):
+    """`sparse_conv_down` as a layer: kernel 2, stride 2, weight (8, cin, cout), an optional bias (added by torch, to the rows
+    in front of the level's count only).  forward(feat (b, n, cin), coords or level, nclusters=None) -> (b, nc, cout): given
+    coords (b, n, 3) the level is built here; an encoder builds it once with `sparse_stride_map` and passes the dict, which the
+    decoder's `SparseConvTranspose3d` takes too."""
+
+    def forward(self, feat, coords_or_level, nclusters=None):
+        level = self._level(coords_or_level, nclusters)
+        return self._add_bias(sparse_conv_down(feat, self.weight, level, nclusters), level["nclusters"])
+
+
+class SparseConvTranspose3d(_SparseStrided):
+    """`sparse_conv_up` as a layer: kernel 2, stride 2, weight (8, cin, cout), an optional bias (to the rows in front of
+    nclusters, the fine level's count, only).  forward(feat (b, nc, cin), coords or level, nclusters=None) -> (b, n, cout),
+    coords being the FINE level's (b, n, 3) and feat living on the cells `sparse_stride_map` makes of them."""
+
+    def forward(self, feat, coords_or_level, nclusters=None):
+        level = self._level(coords_or_level, nclusters)
+        return self._add_bias(sparse_conv_up(feat, self.weight, level, nclusters), nclusters)
+
+
 class _NeighborAggregation(torch.autograd.Function):
     """rf_neighbor_aggregate / rf_neighbor_aggregate_grad: value, weight and pos carry gradients, idx does not."""
 
