@@ -1,5 +1,6 @@
 """GPU: rf_grid_cluster, rf_grid_pool and rf_grid_unpool against the numpy restatement of tests/grid_pool_ref.py AS BYTES, for
-every output, over n in {1, 63, 64, 65, 1000, 16384} (b = 5, b = 2 at the largest), the three orders, c in {1, 3, 5, 64, 130}
+every output, over n in {1, 63, 64, 65, 1000, 2049, 4097, 8193, 16384} (b = 5, b = 2 above 1000; 2049, 4097 and 8193 are the
+first n of the LDS sort's sizes 4096, 8192 and 16384, with lengths n // 2 + 1 beside them), the three orders, c in {1, 3, 5, 64, 130}
 and the input families of the contract: everything in one cell, every point in its own cell, exact duplicates, points exactly
 on cell faces (j / 64 with cell 1 / 16), cell 0.03 on random cubes, an explicit origin with negative cell indices, cells beyond
 +-32768, rows of NaN / +-inf, -0, counts 0, 1 and n with NaN behind them, NaN features under max.  Then the properties: alone
@@ -14,13 +15,13 @@ from grid_pool_ref import F32, I32
 
 pytestmark = pytest.mark.gpu
 
-NS = [1, 63, 64, 65, 1000, 16384]
+NS = [1, 63, 64, 65, 1000, 16384, 2049, 4097, 8193]  # (the last three: the first n of the sort sizes 4096, 8192 and 16384)
 CS = [1, 3, 5, 64, 130]
 CLUSTER_KEYS = ("origin", "inside", "nclusters", "order", "starts", "cluster", "coords", "code")
 
 
 def batch_of(n):
-    return 2 if n == 16384 else 5
+    return 2 if n > 1000 else 5
 
 
 # ---- the input families ------------------------------------------------------------------------------------------------------

@@ -4,14 +4,18 @@ says, every tensor and count array at the residues the header allows (4 bytes; 1
 and the full size among them, NaN rows and garbage map entries behind them.  After the call every byte outside the outputs and
 the workspace is unchanged, every output element is written (the poison is gone: the map equals the restatement of
 tests/sparse_conv_ref.py as bytes, the fp32 outputs bit for bit with zeros of either sign equal), and the four runs of a case
-agree bit for bit -- the aligned variant loads rows of 12 and 8 channels as 16-byte vectors, the natural one as floats.
+agree bit for bit -- the aligned variant loads rows of 12 and 8 channels as 16-byte vectors, the natural one as floats.  Two
+cases repeat the map and the forward at n = 16384, the top of the range, where the guards stand directly behind row 16383.
 
 The cases use the machinery of tests/test_gpu_memory_contract.py and register themselves in its CASES table when this module is
 imported, exactly as tests/test_gpu_memory_contract_grid_pool.py does; `test_memory_contract_sparse_conv` runs them."""
+import functools
+
 import numpy as np
 import pytest
 
 import sparse_conv_ref as R
+import sparse_sizes as Z
 import test_gpu_memory_contract as T
 from test_gpu_memory_contract import F32, I32, case
 
@@ -142,6 +146,57 @@ def sparse_conv_grad_weight_ragged(x):
 @own("rf_sparse_conv_grad_weight")
 def sparse_conv_grad_weight_dense(x):
     _grad_weight(x, False)
+
+
+# ---- the top of the range: n = 16384, where a store past nbr or past the last rows of out is what a wrong row number writes ----
+NB, CB = 16384, np.array([16384, 8191, 4096, 77], I32)
+
+
+@functools.lru_cache(maxsize=1)
+def _inputs_at_size():
+    """shared by the two cases below (never written to: the arena copies)"""
+    rng = np.random.RandomState(29)
+    coords = Z.family("lattice", NB, 29, b=B)
+    r = dict(coords=coords, nbr=R.map_ref(coords, CB, 3, 1))
+    r["feat"], r["weight"] = rng.randn(B, NB, 3).astype(F32), rng.randn(27, 3, 5).astype(F32)
+    r["hostile"] = r["nbr"].copy()
+    for s in range(B):  # what the convolution must ignore
+        M = int(CB[s])
+        r["feat"][s, M:] = np.nan
+        r["hostile"][s, M:] = rng.randint(-3, NB + 3, (NB - M, 27))
+        hole = r["hostile"][s, :M] == -1
+        r["hostile"][s, :M][hole] = rng.choice([-1, -9, M, NB, 1 << 30], int(hole.sum()))
+    r["out"] = R.conv_ref(r["feat"], r["weight"], r["nbr"], CB)
+    return r
+
+
+@own("rf_sparse_conv_map")
+def sparse_conv_map_16384_rows(x):
+    r = x.ref(_inputs_at_size)
+    A = x.arena()
+    A.add("coords", r["coords"], I32, "in", x.T)
+    A.add("count", CB, I32, "in", x.L)
+    A.add("nbr", (B, NB, 27), I32, "out", x.res(12))
+    A.build()
+    x.call(A, "rf_sparse_conv_map", B, NB, 3, 1, "coords", "count", "nbr", None)
+    got = A.get("nbr")
+    assert got.shape == r["nbr"].shape and got.tobytes() == r["nbr"].tobytes(), f"{x.cid}: nbr differs from the restatement"
+    assert got[0].max() == NB - 1 and (got[0, NB - 1] >= 0).any()  # the last row is named and has neighbours
+    x.keep("nbr", got)
+
+
+@own("rf_sparse_conv")
+def sparse_conv_forward_16384_rows(x):
+    r = x.ref(_inputs_at_size)
+    A = x.arena()
+    A.add("feat", r["feat"], F32, "in", x.T)
+    A.add("weight", r["weight"], F32, "in", x.res(8))
+    A.add("nbr", r["hostile"], I32, "in", x.res(12))
+    A.add("count", CB, I32, "in", x.L)
+    A.add("out", (B, NB, 5), F32, "out", x.T)
+    A.build()
+    x.call(A, "rf_sparse_conv", B, NB, 27, 3, 5, 0, "feat", "weight", "nbr", "count", "out", None)
+    _same(x, "out", A.get("out"), r["out"])
 
 
 # =============================================================================== the runs =====

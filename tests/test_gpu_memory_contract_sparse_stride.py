@@ -6,13 +6,17 @@ behind the counts, hostile child / up: garbage behind the counts, entries outsid
 child does not confirm.  After the call every byte outside the outputs and the workspace is unchanged, every output element is
 written (the poison is gone: the int outputs equal the restatement of tests/sparse_stride_ref.py as bytes, the fp32 outputs bit
 for bit with zeros of either sign equal), and the four runs of a case agree bit for bit -- the aligned variant loads rows of 12
-and 8 channels as 16-byte vectors, the natural one as floats.
+and 8 channels as 16-byte vectors, the natural one as floats.  Two cases repeat the map and the mode "up" at n = n_coarse =
+16384, the top of the range, where the guards stand directly behind the last row of child, up and the fine rows.
 
 The cases use the machinery of tests/test_gpu_memory_contract.py and register themselves in its CASES table when this module is
 imported, exactly as tests/test_gpu_memory_contract_sparse_conv.py does; `test_memory_contract_sparse_stride` runs them."""
+import functools
+
 import numpy as np
 import pytest
 
+import sparse_sizes as Z
 import sparse_stride_ref as R
 import test_gpu_memory_contract as T
 from test_gpu_memory_contract import F32, I32, case
@@ -174,6 +178,67 @@ def sparse_conv_strided_grad_weight_down_ragged(x):
 @own("rf_sparse_conv_strided_grad_weight")
 def sparse_conv_strided_grad_weight_up_dense_truncating(x):
     _grad_weight(x, R.UP, 40, False)
+
+
+# ---- the top of the range: n = n_coarse = 16384, every row alone in its coarse cell, so child, up and the fine rows of "up" are
+# written up to their last element: a store past them is what a wrong row number writes ----
+NB, CB = 16384, np.array([16384, 8191, 4096, 77], I32)
+
+
+@functools.lru_cache(maxsize=1)
+def _inputs_at_size():
+    """shared by the two cases below (never written to: the arena copies)"""
+    rng = np.random.RandomState(31)
+    coords = Z.family("spread", NB, 31, b=B)
+    m = R.map_ref(coords, CB, NB)
+    assert np.array_equal(m["count"], CB)
+    r = dict(coords=coords, m=m, child=m["child"].copy(), up=m["up"].copy())
+    r["coarse_in"], r["weight"] = rng.randn(B, NB, 3).astype(F32), rng.randn(8, 3, 5).astype(F32)
+    for s in range(B):  # what the convolution must ignore
+        M = int(CB[s])
+        r["coarse_in"][s, M:] = np.nan
+        r["child"][s, M:] = rng.randint(-3, NB + 3, (NB - M, 8))
+        hole = r["child"][s, :M] == -1
+        r["child"][s, :M][hole] = rng.choice([-1, -9, M, NB, 1 << 30], int(hole.sum()))
+        r["up"][s, M:] = rng.randint(-3, 8 * NB + 9, NB - M)
+    r["out_up"] = R.conv_ref(R.UP, r["coarse_in"], r["weight"], m["child"], m["up"], NB, CB, m["count"])
+    return r
+
+
+@own("rf_sparse_stride_map")
+def sparse_stride_map_16384_rows(x):
+    r = x.ref(_inputs_at_size)
+    A = x.arena()
+    A.add("coords", r["coords"], I32, "in", x.T)
+    A.add("count", CB, I32, "in", x.L)
+    A.add("coords_out", (B, NB, 3), I32, "out", x.res(12))
+    A.add("count_out", (B,), I32, "out", x.L)
+    A.add("total_out", (B,), I32, "out", x.res(8))
+    A.add("child", (B, NB, 8), I32, "out", x.T)
+    A.add("up", (B, NB), I32, "out", x.res(12))
+    A.build()
+    x.call(A, "rf_sparse_stride_map", B, NB, NB, "coords", "count", "coords_out", "count_out", "total_out", "child", "up", None)
+    for name, key in (("coords_out", "coords"), ("count_out", "count"), ("total_out", "total"), ("child", "child"), ("up", "up")):
+        got, exp = A.get(name), r["m"][key]
+        assert got.shape == exp.shape and got.tobytes() == exp.tobytes(), f"{x.cid}: {name} differs from the restatement"
+        x.keep(name, got)
+    assert (A.get("child")[0, NB - 1] >= 0).sum() == 1 and A.get("up")[0].max() >= 8 * (NB - 1)  # the last coarse row is in use
+
+
+@own("rf_sparse_conv_strided")
+def sparse_conv_strided_up_16384_rows(x):
+    r = x.ref(_inputs_at_size)
+    A = x.arena()
+    A.add("src", r["coarse_in"], F32, "in", x.T)
+    A.add("weight", r["weight"], F32, "in", x.res(8))
+    A.add("child", r["child"], I32, "in", x.res(12))
+    A.add("up", r["up"], I32, "in", x.T)
+    A.add("count", CB, I32, "in", x.L)
+    A.add("count_coarse", r["m"]["count"], I32, "in", x.L)
+    A.add("out", (B, NB, 5), F32, "out", x.T)
+    A.build()
+    x.call(A, "rf_sparse_conv_strided", B, NB, NB, 3, 5, R.UP, "src", "weight", "child", "up", "count", "count_coarse", "out", None)
+    _same(x, "out", A.get("out"), r["out_up"])
 
 
 # =============================================================================== the runs =====

@@ -111,7 +111,8 @@ def test_ties_go_to_the_lower_index():
 
 
 # ---- 3. - 5. sizes --------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("b, n, m, nproj", [(2, 1, 1, 3), (2, 64, 65, 4), (2, 65, 1, 2), (1, 1025, 130, CHUNK + 1)])
+@pytest.mark.parametrize("b, n, m, nproj", [(2, 1, 1, 3), (2, 64, 65, 4), (2, 65, 1, 2), (1, 1025, 130, CHUNK + 1),
+                                            (1, 4097, 2049, 2), (1, 8193, 4096, 2)])  # sorts of 8192 and 4096, of 16384 and 4096 words
 def test_small_and_odd_sizes(b, n, m, nproj):
     a, c, d = exact_inputs(n * 7 + m, b, n, m, nproj)
     check(run(a, c, d), ref(a, c, d), f"{n} x {m}")

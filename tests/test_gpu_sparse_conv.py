@@ -5,7 +5,17 @@ the header gives to the realisation of absent slots).  Shapes are the smallest a
 gradient's second chunk, cin in {1, 3, 5, 64, 256} (odd, below a slab, slabs, the scalar and the 16-byte loads), cout in {1, 7,
 33, 64, 256} (one block, two, two passes), ks in {3, 5}, dilation in {1, 2}; a ragged batch with counts 0, 1, 77 and n, NaN
 rows and garbage in nbr behind the counts, entries of nbr outside [0, M), a NaN and an inf feature row.  Then the properties:
-symmetry of the map, alone equals in-batch, ragged equals sliced, glue and the layer, no host synchronisation, graph capture."""
+symmetry of the map, alone equals in-batch, ragged equals sliced, glue and the layer, no host synchronisation, graph capture.
+
+Section 5 repeats the comparisons on the size ladder of tests/sparse_sizes.py, n in {2049, 4097, 8193, 16384} with the counts
+[n, n // 2 - 1, n // 4, 77]: each rung is the smallest n at which the shared LDS sort changes (2049: P = 4096, 1024 threads
+of 4 words, two-stride passes, and a third chunk of the weight gradient; 4097: P = 8192 under 512 threads of 16 words,
+four-stride passes with their r == 3 and r == 1 remainders; 8193: P = 16384 under 1024 threads; 16384: the contract's limit,
+row numbers up to 16383 in the map's 16-bit field, V * K lookups of depth 14, 16 chunks), and the ragged counts run the sorts
+of 128 ... 8192 words under the launch of the larger one.  The families there: "lattice" (every row live, 92 % of the slots
+present at 16384), "spread", "cube" and "one" (n - 1 duplicates) for the map, "lattice" and "cube" for the convolutions with
+few channels -- the rows are under test, the channel paths are covered above.  A kernel change that moves a threshold of the
+sort, of the chunks or of the row field must keep the rung that reaches it."""
 import functools
 
 import numpy as np
@@ -13,6 +23,7 @@ import pytest
 import torch
 
 import sparse_conv_ref as R
+import sparse_sizes as Z
 from sparse_conv_ref import F32, F64, I32
 
 pytestmark = pytest.mark.gpu
@@ -27,12 +38,20 @@ def host(t):
 
 
 def counts_of(n):
-    return np.array([0, 1, min(77, n), n], I32)
+    return Z.counts_at(n) if n in Z.SIZES else np.array([0, 1, min(77, n), n], I32)
+
+
+def full_of(n):
+    """the sample that has all n rows"""
+    return 0 if n in Z.SIZES else 3
 
 
 def make_coords(kind, n, seed):
     """(4, n, 3) int32.  "cube": random cells of a small cube (neighbours and duplicates), sample 0 with rows at the edge of the
-    range, out of range and a duplicate pair in front; "line": cells along z with gaps (three live slots at most)"""
+    range, out of range and a duplicate pair in front; "line": cells along z with gaps (three live slots at most); "lattice",
+    "spread" and "one": the families of tests/sparse_sizes.py"""
+    if kind in ("lattice", "spread", "one"):
+        return Z.family(kind, n, seed)
     rng = np.random.RandomState(seed)
     if kind == "line":
         z = np.cumsum(rng.randint(1, 3, (4, n)), 1)
@@ -61,8 +80,9 @@ def case(n, cin, cout, ks, dilation, kind="cube"):
     gout = rng.randn(4, n, cout).astype(F32)
     weight = (rng.randn(K, cin, cout) / np.sqrt(cin)).astype(F32)
     if n >= 33:  # a NaN and an inf row among the live rows of the full sample
-        feat[3, 0], feat[3, 9, 0] = np.nan, np.inf
-        gout[3, 5] = np.nan
+        full = full_of(n)
+        feat[full, 0], feat[full, 9, 0] = np.nan, np.inf
+        gout[full, 5] = np.nan
     hostile = nbr.copy()  # what the convolution must ignore: garbage behind the counts and outside [0, M) in absent slots
     for s in range(4):
         M = int(count[s])
@@ -144,10 +164,15 @@ SHAPES = [(1, 1, 1, 3, 1, "cube"), (33, 3, 7, 3, 1, "cube"), (65, 5, 33, 3, 2, "
 def test_conv_and_gradients_equal_the_restatement(n, cin, cout, ks, dilation, kind):
     from rfnet_amd import _raw
     c = case(n, cin, cout, ks, dilation, kind)
-    what = f"n={n} {cin}->{cout} ks={ks} d={dilation}"
+    conv_and_gradients(c, f"n={n} {cin}->{cout} ks={ks} d={dilation}", {name: dev(c[name]) for name in ("nbr", "hostile")})
+
+
+def conv_and_gradients(c, what, maps):
+    """forward, grad_input and grad_weight of a case under every map of `maps` (name -> device nbr), against its references"""
+    from rfnet_amd import _raw
+    n, full = c["feat"].shape[1], full_of(c["feat"].shape[1])
     cnt, feat, gout, weight = dev(c["count"]), dev(c["feat"]), dev(c["gout"]), dev(c["weight"])
-    for name in ("nbr", "hostile"):
-        nbr = dev(c[name])
+    for name, nbr in maps.items():
         out = _raw.sparse_conv(feat, weight, nbr, cnt)
         assert_same(host(out), c["out"], f"forward {what} {name}")
         assert torch.equal(_raw.sparse_conv(feat, weight, nbr, cnt).view(torch.int32), out.view(torch.int32))
@@ -160,26 +185,30 @@ def test_conv_and_gradients_equal_the_restatement(n, cin, cout, ks, dilation, ki
         M = int(c["count"][s])
         assert not host(out)[s, M:].view(np.uint32).any() and not host(gf)[s, M:].view(np.uint32).any()
     if n >= 33:  # the NaN row 0 and the inf row 9 of the full sample reach exactly the rows that name them
-        named = (c["nbr"][3] == 0).any(1) | (c["nbr"][3] == 9).any(1)
-        bad = ~np.isfinite(host(out)[3]).all(1)
+        named = (c["nbr"][full] == 0).any(1) | (c["nbr"][full] == 9).any(1)
+        bad = ~np.isfinite(host(out)[full]).all(1)
         assert named[0] and np.array_equal(bad, named)
 
 
 def test_alone_equals_in_batch_and_ragged_equals_sliced():
+    alone_and_sliced(case(65, 5, 33, 3, 2), 3, 2, range(4))
+
+
+def alone_and_sliced(c, ks, dilation, sliced):
+    """every sample of a case alone, and the samples of `sliced` cut to their counts with no counts given"""
     from rfnet_amd import _raw
-    c = case(65, 5, 33, 3, 2)
     weight = dev(c["weight"])
     for s in range(4):
         M = int(c["count"][s])
         one = slice(s, s + 1)
         cnt = dev(c["count"][one])
-        nbr = _raw.sparse_conv_map(dev(c["coords"][one]), cnt, 3, 2)
+        nbr = _raw.sparse_conv_map(dev(c["coords"][one]), cnt, ks, dilation)
         assert host(nbr).tobytes() == c["nbr"][one].tobytes()
         assert_same(host(_raw.sparse_conv(dev(c["feat"][one]), weight, nbr, cnt)), c["out"][one], f"alone {s}")
         assert_same(host(_raw.sparse_conv(dev(c["gout"][one]), weight, nbr, cnt, "grad_input")), c["gfeat"][one], f"alone {s}")
-        if M == 0:
+        if M == 0 or s not in sliced:
             continue
-        cut = _raw.sparse_conv_map(dev(c["coords"][one, :M]), None, 3, 2)
+        cut = _raw.sparse_conv_map(dev(c["coords"][one, :M]), None, ks, dilation)
         assert host(cut).tobytes() == c["nbr"][one, :M].tobytes()
         assert_same(host(_raw.sparse_conv(dev(c["feat"][one, :M]), weight, cut)), c["out"][one, :M], f"sliced {s}")
         assert_same(host(_raw.sparse_conv(dev(c["gout"][one, :M]), weight, cut, None, "grad_input")), c["gfeat"][one, :M], f"sliced {s}")
@@ -299,3 +328,72 @@ def test_graph_capture_with_new_inputs_and_device_counts():
     torch.cuda.synchronize()
     assert same(out, call()) and not same(out[:2], eager[:2])
     assert host(out[0]).tobytes() == R.map_ref(host(tc), host(tn), 3, 1).tobytes()
+
+
+# ---- 5. the size ladder: 2049, 4097, 8193 and 16384 rows, counts [n, n // 2 - 1, n // 4, 77] -------------------------------------
+def same_ints(got, want, what):
+    assert got.dtype == want.dtype and got.shape == want.shape, what
+    if got.tobytes() != want.tobytes():
+        bad = np.argwhere(got != want)
+        raise AssertionError(f"{what}: differs at {len(bad)} places, first {bad[:3].tolist()}: got {got[tuple(bad[0])]!r}, "
+                             f"want {want[tuple(bad[0])]!r}")
+
+
+def family_is_alive(kind, coords, count):
+    """a family that has quietly degenerated must not turn a case into a no-op"""
+    live = R.live_rows(coords, count).sum(1)
+    if kind in ("lattice", "spread"):
+        assert np.array_equal(live, count), kind  # every row live
+    elif kind == "one":
+        assert (live == 1).all()
+    else:  # "cube": about one row in five repeats an earlier one
+        assert 0.1 * count[0] < count[0] - live[0] < 0.3 * count[0], (kind, live)
+
+
+@pytest.mark.parametrize("kind", Z.FAMILIES)
+@pytest.mark.parametrize("n", Z.SIZES)
+def test_map_at_size_equals_the_restatement(n, kind):
+    from rfnet_amd import _raw
+    coords, count = make_coords(kind, n, n + 11), counts_of(n)
+    family_is_alive(kind, coords, count)
+    tc = dev(coords)
+    for ks, dilation in ((3, 1), (5, 2)):
+        K = ks ** 3
+        for cnt in (count, None):
+            want = R.map_ref(coords, cnt, ks, dilation)
+            got = host(_raw.sparse_conv_map(tc, dev(cnt), ks, dilation))
+            same_ints(got, want, f"{kind} n={n} ks={ks} d={dilation} counts={cnt is not None}")
+            again = host(_raw.sparse_conv_map(tc, dev(cnt), ks, dilation))
+            assert again.tobytes() == got.tobytes()  # two calls, the same bytes
+        if kind == "lattice" and n == 16384 and ks == 3:
+            assert (got[0] >= 0).mean() > 0.9  # a dense block: 92 % of the slots are present
+        live = R.live_rows(coords)  # the symmetry, on what the GPU returned (all rows)
+        assert (got[~live] == -1).all()
+        for s in range(4):
+            i, t = np.nonzero(got[s] >= 0)
+            assert len(i) >= live[s].sum() and np.array_equal(got[s, got[s, i, t], K - 1 - t], i)
+
+
+# (3 -> 33 on the "lattice" of 16384 rows is left out: its three references take 12 s on the CPU, the "cube" there takes 7 s)
+AT_SIZE = [(n, cin, cout, kind) for n in Z.SIZES for cin, cout in ((3, 5), (4, 8), (3, 33)) for kind in ("lattice", "cube")
+           if (n, cout, kind) != (16384, 33, "lattice")]
+
+
+@pytest.mark.parametrize("n,cin,cout,kind", AT_SIZE)
+def test_conv_and_gradients_at_size_equal_the_restatement(n, cin, cout, kind):
+    """cin = 3: scalar loads, cin = 4: 16-byte loads, cout = 33: two output blocks.  Under the restatement's map, the hostile
+    one and the map the GPU made of the same coordinates: the composition is what runs at size, and when it fails the first two
+    say whether the map or the convolution did."""
+    from rfnet_amd import _raw
+    c = case(n, cin, cout, 3, 1, kind)
+    family_is_alive(kind, c["coords"], c["count"])
+    assert (c["nbr"][0, :, 13] >= 0).sum() > n // 2 and (kind == "cube" or c["nbr"][0, -1, 13] == n - 1)  # (the last chunk's row)
+    maps = {name: dev(c[name]) for name in ("nbr", "hostile")}
+    maps["gpu map"] = _raw.sparse_conv_map(dev(c["coords"]), dev(c["count"]), 3, 1)
+    conv_and_gradients(c, f"n={n} {cin}->{cout} {kind}", maps)
+
+
+@pytest.mark.parametrize("n", [8193, 16384])
+def test_alone_equals_in_batch_and_ragged_equals_sliced_at_size(n):
+    """sample 1 has n // 2 - 1 rows: sliced, it is sorted under its own launch; in the batch, under the launch of n rows"""
+    alone_and_sliced(case(n, 3, 5, 3, 1, "lattice"), 3, 1, (1,))

@@ -6,13 +6,25 @@ fine row its own coarse cell), a workgroup of 128 and one more, odd widths, a se
 a second pass of 64 output channels with a second reduction slab, and more than 1024 coarse rows for the weight gradient's
 second chunk; a ragged batch with counts 0, 1, 77 and n, NaN rows and garbage in child / up behind the counts and in the
 absent entries, a truncating n_coarse.  Then the properties: alone equals in-batch, ragged equals sliced, glue and the layers,
-an encoder / decoder chain without a host synchronisation and under graph capture."""
+an encoder / decoder chain without a host synchronisation and under graph capture.
+
+Section 5 repeats the comparisons on the size ladder of tests/sparse_sizes.py, n in {2049, 4097, 8193, 16384} with the counts
+[n, n // 2 - 1, n // 4, 77]: each rung is the smallest n at which the shared LDS sort changes (2049: P = 4096, 1024 threads
+of 4 words, two-stride passes; 4097: P = 8192 under 512 threads of 16 words, four-stride passes with their r == 3 and r == 1
+remainders, and the map's head scan walks 16 steps over its two-deep totals; 8193: P = 16384 under 1024 threads, 16 steps
+with all 16 waves; 16384: the contract's limit), and the ragged counts run the sorts of 128 ... 8192 words under the launch of
+the larger one.  The families there: "spread" (every row alone in its coarse cell: n_coarse = n, at 16384 the fan-out form's
+512 tiles of 32 coarse rows beside its 128 workgroups of fine rows, and 16 chunks of 1024 coarse rows in the weight
+gradients), "lattice" (eight children per coarse cell), "cube" and "one" for the map.  A kernel change that moves a threshold
+of the sort, of the scan, of the tiles or of the chunks must keep the rung that reaches it."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
+import sparse_conv_ref as C
+import sparse_sizes as Z
 import sparse_stride_ref as R
 from sparse_stride_ref import F32, I32
 
@@ -30,13 +42,21 @@ def host(t):
 
 
 def counts_of(n):
-    return np.array([0, 1, min(77, n), n], I32)
+    return Z.counts_at(n) if n in Z.SIZES else np.array([0, 1, min(77, n), n], I32)
+
+
+def full_of(n):
+    """the sample that has all n rows"""
+    return 0 if n in Z.SIZES else 3
 
 
 def make_coords(kind, n, seed):
     """(4, n, 3) int32.  "cube": random cells of a small cube round the origin (negative coordinates, several children per coarse
     cell, duplicates), every sample with rows at the edges of the range, out of range and a duplicate pair in front; "iso":
-    every row a coarse cell of its own; "pairs": distinct cells, about two to a coarse cell, in a shuffled order"""
+    every row a coarse cell of its own; "pairs": distinct cells, about two to a coarse cell, in a shuffled order; "lattice",
+    "spread" and "one": the families of tests/sparse_sizes.py ("iso" leaves the range above 4681 rows)"""
+    if kind in ("lattice", "spread", "one"):
+        return Z.family(kind, n, seed)
     rng = np.random.RandomState(seed)
     if kind == "iso":
         i = np.stack([rng.permutation(n) for _ in range(4)])[..., None]
@@ -93,8 +113,9 @@ def case(n, cin, cout, kind="cube", nc=None):
     fine_g, coarse_g = rng.randn(4, n, cout).astype(F32), rng.randn(4, nc, cout).astype(F32)
     weight = (rng.randn(8, cin, cout) / np.sqrt(cin)).astype(F32)
     if n >= 33:  # a NaN and an inf row among the live rows of the full sample
-        fine_in[3, 0], fine_in[3, 9, 0] = np.nan, np.inf
-        coarse_in[3, 0] = np.nan
+        full = full_of(n)
+        fine_in[full, 0], fine_in[full, 9, 0] = np.nan, np.inf
+        coarse_in[full, 0] = np.nan
     for s in range(4):
         M, Mc = int(count[s]), int(m["count"][s])
         fine_in[s, M:], fine_g[s, M:] = np.nan, np.nan
@@ -177,17 +198,24 @@ SHAPES = [(1, 1, 1, "cube", None), (33, 3, 7, "iso", None), (129, 5, 33, "iso", 
 
 @pytest.mark.parametrize("n,cin,cout,kind,nc", SHAPES)
 def test_modes_and_weight_gradients_equal_the_restatement(n, cin, cout, kind, nc):
-    from rfnet_amd import _raw
     c = case(n, cin, cout, kind, nc)
-    m, what = c["m"], f"n={n} {cin}->{cout} {kind} nc={nc}"
+    m = c["m"]
     if n == 2100:
         assert m["count"][3] > R.WGRAD_ROWS  # the weight gradient's second chunk
     if nc is not None:
         assert m["total"][3] > nc
+    maps = {"maps": (dev(m["child"]), dev(m["up"])), "hostile": (dev(c["hchild"]), dev(c["hup"]))}
+    modes_and_weight_gradients(c, f"n={n} {cin}->{cout} {kind} nc={nc}", maps, nc is not None)
+
+
+def modes_and_weight_gradients(c, what, maps, truncated):
+    """the four modes and both weight gradients of a case under every pair of `maps` (name -> device child, up), against its
+    references"""
+    from rfnet_amd import _raw
+    m, n, full = c["m"], c["coords"].shape[1], full_of(c["coords"].shape[1])
     cnt, cntc, weight = dev(c["count"]), dev(m["count"]), dev(c["weight"])
     src = {k: dev(v) for k, v in c["src"].items()}
-    for name, (child, up) in (("maps", (m["child"], m["up"])), ("hostile", (c["hchild"], c["hup"]))):
-        child, up = dev(child), dev(up)
+    for name, (child, up) in maps.items():
         out = {}
         for mode in MODES:
             out[mode] = _raw.sparse_conv_strided(src[mode], weight, child, up, cnt, cntc, mode)
@@ -207,15 +235,19 @@ def test_modes_and_weight_gradients_equal_the_restatement(n, cin, cout, kind, nc
         for mode in ("up", "down_grad_input"):
             assert not host(out[mode])[s][m["up"][s] < 0].view(np.uint32).any()
     if n >= 33:  # the NaN row 0 and the inf row 9 of the full sample reach exactly the coarse rows that hold them
-        named = np.isin(m["child"][3], [0, 9]).any(1) & (np.arange(m["child"].shape[1]) < m["count"][3])
-        assert np.array_equal(~np.isfinite(host(out["down"])[3]).all(1), named) and (named.any() or nc is not None)
-        kids = m["child"][3, 0][m["child"][3, 0] >= 0]  # the NaN coarse row 0 reaches exactly its children
-        assert np.array_equal(np.nonzero(~np.isfinite(host(out["up"])[3]).all(1))[0], np.sort(kids))
+        named = np.isin(m["child"][full], [0, 9]).any(1) & (np.arange(m["child"].shape[1]) < m["count"][full])
+        assert np.array_equal(~np.isfinite(host(out["down"])[full]).all(1), named) and (named.any() or truncated)
+        kids = m["child"][full, 0][m["child"][full, 0] >= 0]  # the NaN coarse row 0 reaches exactly its children
+        assert np.array_equal(np.nonzero(~np.isfinite(host(out["up"])[full]).all(1))[0], np.sort(kids))
 
 
 def test_alone_equals_in_batch_and_ragged_equals_sliced():
+    alone_and_sliced(case(129, 5, 33, "iso"), range(4))
+
+
+def alone_and_sliced(c, sliced):
+    """every sample of a case alone, and the samples of `sliced` cut to their counts with no counts given"""
     from rfnet_amd import _raw
-    c = case(129, 5, 33, "iso")
     m, weight = c["m"], dev(c["weight"])
     for s in range(4):
         M, Mc = int(c["count"][s]), int(m["count"][s])
@@ -226,7 +258,7 @@ def test_alone_equals_in_batch_and_ragged_equals_sliced():
         for mode in MODES:
             got = _raw.sparse_conv_strided(dev(c["src"][mode][one]), weight, child, up, cnt, cntc, mode)
             assert_same(host(got), c["out"][mode][one], f"alone {s} {mode}")
-        if M == 0:
+        if M == 0 or s not in sliced:
             continue
         cut = gpu_map(c["coords"][one, :M])  # no counts: n = M rows, n_coarse = M
         assert cut["count"][0] == Mc and same_map({k: cut[k] for k in ("child", "coords")}, {k: m[k][one, :M] for k in ("child", "coords")})
@@ -295,16 +327,16 @@ class _UNet(torch.nn.Module):
         self.sub0, self.down = glue.SubMConv3d(4, 8), glue.SparseConv3d(8, 16, bias=False)
         self.sub1, self.up = glue.SubMConv3d(16, 16), glue.SparseConvTranspose3d(16, 8, bias=False)
 
-    def forward(self, xyz, feat, lengths):
+    def forward(self, xyz, feat, lengths, cell=0.11):
         from rfnet_amd import glue
-        points, pooled, ncl, info = glue.grid_pool(xyz, 0.11, feat, reduce="mean", order="z", lengths=lengths)  # (grid_cluster)
+        points, pooled, ncl, info = glue.grid_pool(xyz, cell, feat, reduce="mean", order="z", lengths=lengths)  # (grid_cluster)
         f0 = self.sub0(pooled, info["coords"], ncl)
         level = glue.sparse_stride_map(info["coords"], ncl)
         d = self.down(f0, level, ncl)
         f1 = self.sub1(d, glue.sparse_conv_map(level["coords"], level["nclusters"]), level["nclusters"])
         u = self.up(f1, level, ncl)
         back = glue.grid_unpool(torch.cat([f0, u], -1), info["cluster"], info["starts"], info["order"], ncl)
-        return [info["coords"], ncl, level["coords"], level["nclusters"], level["child"], level["up"], f0, d, f1, u, back]
+        return [info["coords"], ncl, level["coords"], level["nclusters"], level["child"], level["up"], f0, d, f1, u, pooled, back]
 
 
 def _chain_inputs(seed):
@@ -313,14 +345,25 @@ def _chain_inputs(seed):
 
 
 def _check_chain(net, outs, lengths):
-    coords, ncl, ccoords, cncl, child, up, f0, d, f1, u, back = (host(t) for t in outs)
+    coords, ncl, ccoords, cncl, child, up, f0, d, f1, u, pooled, back = (host(t) for t in outs)
+    b, n = up.shape
     m = R.map_ref(coords, ncl)
     assert same_map(dict(coords=ccoords, count=cncl, child=child, up=up), {k: m[k] for k in ("coords", "count", "child", "up")})
-    a = (child, up, 331, ncl, cncl)
+    a = (child, up, n, ncl, cncl)
     assert_same(d, R.conv_ref(R.DOWN, f0, host(net.down.weight), *a), "chain down")
     assert_same(u, R.conv_ref(R.UP, f1, host(net.up.weight), *a), "chain up")
-    assert back.shape == (3, 331, 16) and np.abs(back[0, :, 8:]).max() > 0 and cncl[0] > 32
+    assert back.shape == (b, n, 16) and np.abs(back[0, :, 8:]).max() > 0 and cncl[0] > 32
     assert not any(back[s, L:].any() for s, L in enumerate(lengths))  # points behind a length are in no cell
+
+
+def _check_chain_submanifold(net, outs):
+    """the two submanifold layers of the chain against the restatement of tests/sparse_conv_ref.py on the restatement's own map
+    of the coordinates the chain produced, the bias as one fp32 add to the rows in front of the counts"""
+    coords, ncl, ccoords, cncl, child, up, f0, d, f1, u, pooled, back = (host(t) for t in outs)
+    for layer, src, cells, cnt, got, what in ((net.sub0, pooled, coords, ncl, f0, "chain sub0"), (net.sub1, d, ccoords, cncl, f1, "chain sub1")):
+        live = (np.arange(cells.shape[1])[None, :] < cnt[:, None])[:, :, None].astype(F32)
+        want = C.conv_ref(src, host(layer.weight), C.map_ref(cells, cnt, 3, 1), cnt) + live * host(layer.bias)
+        assert_same(got, want.astype(F32), what)
 
 
 def test_unet_chain_without_a_host_sync():
@@ -375,3 +418,102 @@ def test_unet_chain_under_graph_capture_with_new_inputs_and_device_counts():
     ncl = host(out[1])
     assert ncl[2] == 1 and ncl[1] > ncl[0]
     _check_chain(net, out, [200, 331, 1])
+
+
+# ---- 5. the size ladder: 2049, 4097, 8193 and 16384 rows, counts [n, n // 2 - 1, n // 4, 77] -------------------------------------
+def assert_map(got, want, what):
+    for k in want:
+        assert got[k].dtype == I32 and got[k].shape == want[k].shape, (what, k)
+        if got[k].tobytes() != want[k].tobytes():
+            bad = np.argwhere(got[k] != want[k])
+            raise AssertionError(f"{what}: {k} differs at {len(bad)} places, first {bad[:3].tolist()}: got "
+                                 f"{got[k][tuple(bad[0])]!r}, want {want[k][tuple(bad[0])]!r}")
+
+
+def family_is_alive(kind, coords, count, m):
+    """a family that has quietly degenerated must not turn a case into a no-op; m is the restatement's map at n_coarse = n"""
+    live, n = R.live_rows(coords, count).sum(1), coords.shape[1]
+    if kind == "spread":  # every row alone in its coarse cell
+        assert np.array_equal(live, count) and np.array_equal(m["count"], count)
+    elif kind == "lattice":  # every row live, several children to a coarse cell, all eight at 16384
+        assert np.array_equal(live, count) and 8 * m["count"][0] >= count[0] > 1.2 * m["count"][0]
+        assert n < 16384 or (m["child"][0, :2048] >= 0).all()
+    elif kind == "one":
+        assert (live == 1).all() and (m["count"] == 1).all()
+    else:  # "cube": about one row in five repeats an earlier one
+        assert 0.1 * count[0] < count[0] - live[0] < 0.3 * count[0] and m["count"][0] > n // 8, (kind, live)
+
+
+@pytest.mark.parametrize("kind", Z.FAMILIES)
+@pytest.mark.parametrize("n", Z.SIZES)
+def test_map_at_size_equals_the_restatement(n, kind):
+    coords, count = make_coords(kind, n, n + 13), counts_of(n)
+    whole = R.map_ref(coords, count)
+    family_is_alive(kind, coords, count, whole)
+    D = int(whole["total"].max())
+    for nc in sorted({n, max(1, D // 3), D}):  # all rows; truncating; just enough
+        want = whole if nc == n else R.map_ref(coords, count, nc)
+        got = gpu_map(coords, count, nc)
+        assert_map(got, want, f"{kind} n={n} nc={nc}")
+        assert_map(gpu_map(coords, count, nc), got, "second call")  # two calls, the same bytes
+    got = gpu_map(coords, None, n)  # and no counts: every sample sorts n rows
+    assert_map(got, R.map_ref(coords, None, n), f"{kind} n={n} no counts")
+    assert_map(gpu_map(coords, None, n), got, "second call")
+    live = R.live_rows(coords)  # up and child are inverse, on what the GPU returned
+    for s in range(4):
+        up, child = got["up"][s], got["child"][s]
+        i = np.nonzero(up >= 0)[0]
+        assert np.array_equal(i, np.nonzero(live[s])[0]) and np.array_equal(child[up[i] >> 3, up[i] & 7], i)
+
+
+AT_SIZE = [(n, cin, cout, kind, None) for n in Z.SIZES for cin, cout in ((3, 5), (4, 8)) for kind in ("spread", "lattice")]
+AT_SIZE.append((16384, 3, 5, "lattice", 683))  # a third of the 2048 coarse cells of the full block
+
+
+@pytest.mark.parametrize("n,cin,cout,kind,nc", AT_SIZE)
+def test_modes_and_weight_gradients_at_size_equal_the_restatement(n, cin, cout, kind, nc):
+    """cin = 3: scalar loads, cin = 4: 16-byte loads.  Under the restatement's maps, the hostile ones and the maps the GPU made
+    of the same coordinates: the composition is what runs at size, and when it fails the first two say whether the map or the
+    convolution did."""
+    from rfnet_amd import _raw
+    c = case(n, cin, cout, kind, nc)
+    m = c["m"]
+    if nc is None:
+        family_is_alive(kind, c["coords"], c["count"], m)
+        if kind == "spread":
+            assert -(-m["count"][0] // R.WGRAD_ROWS) == -(-n // R.WGRAD_ROWS) >= 3  # the weight gradient's chunks: 3, 5, 9, 16
+    else:
+        assert m["total"][0] > nc == m["count"][0]
+    made = _raw.sparse_stride_map(dev(c["coords"]), dev(c["count"]), nc)
+    assert np.array_equal(host(made[1]), m["count"])
+    maps = {"maps": (dev(m["child"]), dev(m["up"])), "hostile": (dev(c["hchild"]), dev(c["hup"])), "gpu maps": (made[3], made[4])}
+    modes_and_weight_gradients(c, f"n={n} {cin}->{cout} {kind} nc={nc}", maps, nc is not None)
+
+
+@pytest.mark.parametrize("n", [8193, 16384])
+def test_alone_equals_in_batch_and_ragged_equals_sliced_at_size(n):
+    """sample 1 has n // 2 - 1 rows: sliced, it is sorted under its own launch; in the batch, under the launch of n rows"""
+    alone_and_sliced(case(n, 3, 5, "lattice"), (1,))
+
+
+def test_unet_chain_at_16384_points_without_a_host_sync():
+    """grid_pool -> sparse_conv_map -> SubMConv3d -> sparse_stride_map -> down -> SubMConv3d -> up -> grid_unpool on 16384 random
+    points with more than 8192 occupied cells (a sort of 16384 words in every map), each layer against its restatement"""
+    torch.manual_seed(7)
+    net = _UNet().cuda()
+    rng = np.random.RandomState(12)
+    n, lens, cell = 16384, [16384, 4097], 0.03
+    xyz, feat, lengths = dev(rng.rand(2, n, 3).astype(F32)), dev(rng.randn(2, n, 4).astype(F32)), dev(np.array(lens, I32))
+    with torch.no_grad():
+        first = net(xyz, feat, lengths, cell)
+        torch.cuda.synchronize()
+        torch.cuda.set_sync_debug_mode("error")
+        try:
+            second = net(xyz, feat, lengths, cell)
+        finally:
+            torch.cuda.set_sync_debug_mode("default")
+    assert all(torch.equal(x, y) for x, y in zip(first, second))
+    ncl, cncl = host(second[1]), host(second[3])
+    assert ncl[0] > 8192 and 1024 < cncl[0] < ncl[0] and ncl[1] > 2048
+    _check_chain(net, second, lens)
+    _check_chain_submanifold(net, second)

@@ -233,13 +233,16 @@ def _gu(b=2, n=100, c=8, mode=0, null=None, at=None):
 
 def test_argument_rules_are_answered_without_a_device():
     OK, EINVAL = 0, -1
+    # an optional tensor left out passes the rules and the call goes on to the device: it is made only where there is none --
+    # with a device it would launch a kernel on the made-up pointers
+    launches = torch.cuda.is_available()
     assert _gc(b=0) == OK and _gc(b=0, n=0, cell=0.0, order=9) == OK
     for bad in (dict(b=-1), dict(b=0, n=-1), dict(b=65536), dict(n=0), dict(n=-3), dict(n=16385), dict(cell=0.0), dict(cell=-1.0),
                 dict(cell=float("nan")), dict(cell=float("inf")), dict(order=3), dict(order=-1)):
         assert _gc(**bad) == EINVAL, bad
     for t in range(11):
         optional = t in (1, 2, 10)  # len, origin, code
-        assert (_gc(null=t) == EINVAL) == (not optional), f"rf_grid_cluster: NULL tensor {t}"
+        assert (optional and launches) or (_gc(null=t) == EINVAL) == (not optional), f"rf_grid_cluster: NULL tensor {t}"
         assert _gc(at=(t, PTR + 2)) == EINVAL, f"rf_grid_cluster: tensor {t} not 4-byte aligned"
     assert _gc(at=(10, PTR + 4)) == EINVAL  # code: 8 bytes
     assert _gp(b=0) == OK and _gp(b=0, n=0, c=0, reduce=7) == OK
@@ -255,7 +258,7 @@ def test_argument_rules_are_answered_without_a_device():
         assert _gu(**bad) == EINVAL, bad
     for t in range(5):
         optional = t in (2, 3)  # starts, arg (mode copy)
-        assert (_gu(null=t) == EINVAL) == (not optional), f"rf_grid_unpool: NULL tensor {t}"
+        assert (optional and launches) or (_gu(null=t) == EINVAL) == (not optional), f"rf_grid_unpool: NULL tensor {t}"
         assert _gu(at=(t, PTR + 2)) == EINVAL, f"rf_grid_unpool: tensor {t} not 4-byte aligned"
     assert _gu(mode=1, null=2) == EINVAL and _gu(mode=2, null=3) == EINVAL
     if not torch.cuda.is_available():  # a call that passes the rules gets as far as the device check

@@ -313,20 +313,23 @@ def _nc(b=2, n=100, m=50, null=None, at=None):
 
 def test_argument_rules_are_answered_without_a_device():
     OK, EINVAL = 0, -1
+    # an optional tensor left out passes the rules and the call goes on to the device: it is made only where there is none --
+    # with a device it would launch a kernel on the made-up pointers
+    launches = torch.cuda.is_available()
     assert _pca(b=0) == OK and _pca(b=0, n=0, m=0, k=0) == OK
     for bad in (dict(b=-1), dict(b=65536), dict(n=0), dict(n=-3), dict(n=65537), dict(m=0), dict(m=65537), dict(k=0), dict(k=-1),
                 dict(k=65)):
         assert _pca(**bad) == EINVAL, bad
     for t in range(8):
         optional = t in (2, 3, 4, 7)  # len1, len2, viewpoint, axes
-        assert (_pca(null=t) == EINVAL) == (not optional), f"rf_local_pca: NULL tensor {t}"
+        assert (optional and launches) or (_pca(null=t) == EINVAL) == (not optional), f"rf_local_pca: NULL tensor {t}"
         assert _pca(at=(t, PTR + 2)) == EINVAL, f"rf_local_pca: tensor {t} not 4-byte aligned"
     assert _nc(b=0) == OK and _nc(b=0, n=0, m=0) == OK
     for bad in (dict(b=-1), dict(b=65536), dict(n=0), dict(n=-3), dict(m=0), dict(m=-1)):
         assert _nc(**bad) == EINVAL, bad
     for t in range(7):
         optional = t in (4, 5)
-        assert (_nc(null=t) == EINVAL) == (not optional), f"rf_nn_normal_consistency: NULL tensor {t}"
+        assert (optional and launches) or (_nc(null=t) == EINVAL) == (not optional), f"rf_nn_normal_consistency: NULL tensor {t}"
         assert _nc(at=(t, PTR + 2)) == EINVAL, f"rf_nn_normal_consistency: tensor {t} not 4-byte aligned"
     if not torch.cuda.is_available():  # a call that passes the rules gets as far as the device check
         assert _pca() == -3 and _pca(null=7) == -3 and _nc() == -3

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import sparse_conv_ref as R
+import sparse_sizes as Z
 from sparse_conv_ref import F32, F64, I32, I64
 
 
@@ -212,6 +213,44 @@ def test_restatements_within_the_chain_bound_of_float64():
     assert (err <= (g + u + g * u + 2.0 ** -50) * mag_gw).all() and err.max() > 0
 
 
+# ---- the restatement at the contract's limit: the GPU tests trust it at 16384 rows, so it is held there too ----------------------
+@pytest.mark.parametrize("kind", ["lattice", "cube"])
+def test_map_ref_at_16384_rows_against_a_dictionary(kind):
+    """a plain lookup of cell -> lowest row: "lattice" has every row live and most slots present, "cube" a fifth duplicates"""
+    n = 16384
+    coords = Z.family("lattice", n, 3, b=2) if kind == "lattice" else cells(3, 2, n, span=16)
+    count = np.array([n // 2 + 1, n], I32)
+    nbr = R.map_ref(coords, count, 3, 1)
+    assert np.array_equal(nbr, brute_map(coords, count, 3, 1))
+    live = R.live_rows(coords, count).sum(1)
+    if kind == "lattice":
+        assert np.array_equal(live, count) and (nbr[1] >= 0).mean() > 0.9 and nbr[1].max() == n - 1
+    else:
+        assert 0.1 * n < n - live[1] < 0.3 * n and live[0] < count[0]
+
+
+def test_grad_weight_ref_over_16_chunks_within_the_chain_bound_of_float64():
+    """n = 16384: sixteen chains of 1024 steps per slot and sample, added in double.  The bound is that of the test above: every
+    chunk's chain is within gamma_1024 of its exact sum, so their sum is within gamma_1024 of sum |terms|; then one rounding."""
+    rng = np.random.RandomState(11)
+    b, n, cin, cout = 2, 16384, 3, 5
+    coords = Z.family("lattice", n, 5, b=b)
+    count = np.array([n // 2 + 1, n], I32)
+    nbr = R.map_ref(coords, count, 3, 1)
+    feat, gout = rng.randn(b, n, cin).astype(F32), rng.randn(b, n, cout).astype(F32)
+    M = count[:, None, None]
+    use = (np.arange(n)[None, :, None] < M) & (nbr >= 0) & (nbr < M)
+    assert use[1, -R.WGRAD_ROWS:].any(0).all() and use[0, 8 * R.WGRAD_ROWS].any()  # the sixteenth chunk; the ninth's one row
+    fpad = np.concatenate([feat, np.zeros((b, 1, cin), F32)], 1).astype(F64)
+    col = fpad[np.arange(b)[:, None, None], np.where(use, nbr, n)]  # (b, n, K, cin), zeros in absent slots
+    g64 = gout.astype(F64) * (np.arange(n)[None, :, None] < count[:, None, None])
+    exact = np.einsum("bnkc,bno->kco", col, g64)
+    mag = np.einsum("bnkc,bno->kco", np.abs(col), np.abs(g64))
+    err = np.abs(R.grad_weight_ref(feat, gout, nbr, count).astype(F64) - exact)
+    g, u = gamma(R.WGRAD_ROWS), 2.0 ** -24
+    assert (err <= (g + u + g * u + 2.0 ** -50) * mag).all() and err.max() > 0
+
+
 # ---- the ABI -------------------------------------------------------------------------------------------------------------
 ENTRIES = ("rf_sparse_conv_map", "rf_sparse_conv", "rf_sparse_conv_grad_weight", "rf_sparse_conv_grad_weight_workspace_bytes")
 
@@ -271,6 +310,14 @@ def _wgrad(b=2, n=100, K=27, cin=8, cout=8, null=None, at=None, ws=WS, wsz=BIG):
     return lib.rf_sparse_conv_grad_weight(b, n, K, cin, cout, *t, ws, wsz, None)
 
 
+def null_rule(call, t, optional, what):
+    """A mandatory tensor left out is RF_EINVAL.  An optional one left out passes the rules, and the call goes on to the device:
+    it is made only where there is none -- with a device it would launch a kernel on the made-up pointers."""
+    if optional and torch.cuda.is_available():
+        return
+    assert (call(null=t) == -1) == (not optional), what
+
+
 def test_argument_rules_are_answered_without_a_device():
     from rfnet_amd._lib import lib
     OK, EINVAL, EWORKSPACE = 0, -1, -2
@@ -279,21 +326,21 @@ def test_argument_rules_are_answered_without_a_device():
                 dict(dilation=0), dict(dilation=-1), dict(dilation=1025)):
         assert _map(**bad) == EINVAL, bad
     for t in range(3):
-        assert (_map(null=t) == EINVAL) == (t != 1), f"rf_sparse_conv_map: NULL tensor {t}"  # count may be NULL
+        null_rule(_map, t, t == 1, f"rf_sparse_conv_map: NULL tensor {t}")  # count may be NULL
         assert _map(at=(t, PTR + 2)) == EINVAL, f"rf_sparse_conv_map: tensor {t} not 4-byte aligned"
     assert _conv(b=0) == OK and _conv(b=0, n=0, K=5, cin=0, cout=0, mode=9) == OK
     for bad in (dict(b=-1), dict(b=0, cin=-1), dict(b=65536), dict(n=0), dict(n=16385), dict(K=26), dict(K=9), dict(K=343), dict(cin=0),
                 dict(cin=257), dict(cout=0), dict(cout=257), dict(mode=2), dict(mode=-1)):
         assert _conv(**bad) == EINVAL, bad
     for t in range(5):
-        assert (_conv(null=t) == EINVAL) == (t != 3), f"rf_sparse_conv: NULL tensor {t}"
+        null_rule(_conv, t, t == 3, f"rf_sparse_conv: NULL tensor {t}")
         assert _conv(at=(t, PTR + 2)) == EINVAL, f"rf_sparse_conv: tensor {t} not 4-byte aligned"
     assert _wgrad(b=0) == OK and _wgrad(b=0, n=0, K=5, cin=0, cout=0, ws=None, wsz=0) == OK
     for bad in (dict(b=-1), dict(b=0, cout=-1), dict(b=65536), dict(n=0), dict(n=16385), dict(K=28), dict(cin=0), dict(cin=257),
                 dict(cout=0), dict(cout=257), dict(ws=None), dict(ws=WS + 8), dict(ws=WS + 4)):
         assert _wgrad(**bad) == EINVAL, bad
     for t in range(5):
-        assert (_wgrad(null=t) == EINVAL) == (t != 3), f"rf_sparse_conv_grad_weight: NULL tensor {t}"
+        null_rule(_wgrad, t, t == 3, f"rf_sparse_conv_grad_weight: NULL tensor {t}")
         assert _wgrad(at=(t, PTR + 2)) == EINVAL, f"rf_sparse_conv_grad_weight: tensor {t} not 4-byte aligned"
     need = lib.rf_sparse_conv_grad_weight_workspace_bytes(2, 27, 8, 8)
     assert _wgrad(wsz=need - 1) == EWORKSPACE and _wgrad(wsz=0) == EWORKSPACE

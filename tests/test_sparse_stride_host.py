@@ -9,9 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+import sparse_sizes as Z
 import sparse_stride_ref as R
 from sparse_stride_ref import F32, F64, I32
-from test_sparse_conv_host import gamma
+from test_sparse_conv_host import gamma, null_rule
 
 
 def cells(seed, b, n, span=6, extra=True):
@@ -108,6 +109,34 @@ def test_up_and_child_are_inverse_on_the_live_set():
             assert np.array_equal(up[child[j, t]], 8 * j + t) and (j < m["count"][s]).all()
             dropped = live[s] & (up < 0)  # live rows without a parent: only under truncation
             assert dropped.any() == (m["total"][s] > nc)
+
+
+@pytest.mark.parametrize("kind", ["spread", "lattice"])
+def test_map_ref_at_16384_rows_against_unique_coarse_cells(kind):
+    """The GPU tests trust map_ref at the contract's limit, so it is held there to another route: np.unique over the rows of
+    the coarse cells themselves (lexicographic, which is row-major ascending) instead of over packed keys.  Every row of these
+    two families is live, so the route needs no rule for duplicates."""
+    n = 16384
+    coords = Z.family(kind, n, 7, b=2)
+    count = np.array([n // 2 + 1, n], I32)
+    assert np.array_equal(R.live_rows(coords, count).sum(1), count)
+    D = []
+    for nc in (n, 700):  # all cells; truncating
+        m = R.map_ref(coords, count, nc)
+        for s, M in enumerate(count):
+            c = coords[s, :M].astype(np.int64)
+            cells_, rank = np.unique(np.floor_divide(c, 2), axis=0, return_inverse=True)
+            rank, t = rank.reshape(-1), (c[:, 0] % 2) * 4 + (c[:, 1] % 2) * 2 + c[:, 2] % 2
+            child, up = np.full((nc, 8), -1, I32), np.full(n, -1, I32)
+            kept = rank < nc
+            child[rank[kept], t[kept]] = np.arange(M)[kept]
+            up[:M][kept] = (8 * rank + t)[kept]
+            Dk = min(len(cells_), nc)
+            assert m["total"][s] == len(cells_) and m["count"][s] == Dk
+            assert np.array_equal(m["coords"][s, :Dk], cells_[:nc]) and not m["coords"][s, Dk:].any()
+            assert np.array_equal(m["child"][s], child) and np.array_equal(m["up"][s], up)
+            D.append(len(cells_))
+    assert D[:2] == [n // 2 + 1, n] if kind == "spread" else 1900 < D[0] <= D[1] == 2048  # (the block has 2048 coarse cells)
 
 
 # ---- the chains on integers: exact, so they must equal float64 einsum ----------------------------------------------------------
@@ -323,20 +352,20 @@ def test_argument_rules_are_answered_without_a_device():
     for bad in sizes:
         assert _map(**bad) == EINVAL, bad
     for t in range(7):
-        assert (_map(null=t) == EINVAL) == (t != 1), f"rf_sparse_stride_map: NULL tensor {t}"  # count may be NULL
+        null_rule(_map, t, t == 1, f"rf_sparse_stride_map: NULL tensor {t}")  # count may be NULL
         assert _map(at=(t, PTR + 2)) == EINVAL, f"rf_sparse_stride_map: tensor {t} not 4-byte aligned"
     assert _conv(b=0) == OK and _conv(b=0, n=0, nc=7, cin=0, cout=0, mode=9) == OK
     for bad in sizes + (dict(b=0, cin=-1), dict(cin=0), dict(cin=257), dict(cout=0), dict(cout=257), dict(mode=4), dict(mode=-1)):
         assert _conv(**bad) == EINVAL, bad
     for t in range(7):
-        assert (_conv(null=t) == EINVAL) == (t not in (4, 5)), f"rf_sparse_conv_strided: NULL tensor {t}"
+        null_rule(_conv, t, t in (4, 5), f"rf_sparse_conv_strided: NULL tensor {t}")
         assert _conv(at=(t, PTR + 2)) == EINVAL, f"rf_sparse_conv_strided: tensor {t} not 4-byte aligned"
     assert _wgrad(b=0) == OK and _wgrad(b=0, n=0, nc=3, cin=0, cout=0, mode=7, ws=None, wsz=0) == OK
     for bad in sizes + (dict(b=0, cout=-1), dict(cin=0), dict(cin=257), dict(cout=0), dict(cout=257), dict(mode=2), dict(mode=3),
                         dict(mode=-1), dict(ws=None), dict(ws=WS + 8), dict(ws=WS + 4)):
         assert _wgrad(**bad) == EINVAL, bad
     for t in range(6):
-        assert (_wgrad(null=t) == EINVAL) == (t not in (3, 4)), f"rf_sparse_conv_strided_grad_weight: NULL tensor {t}"
+        null_rule(_wgrad, t, t in (3, 4), f"rf_sparse_conv_strided_grad_weight: NULL tensor {t}")
         assert _wgrad(at=(t, PTR + 2)) == EINVAL, f"rf_sparse_conv_strided_grad_weight: tensor {t} not 4-byte aligned"
     need = lib.rf_sparse_conv_strided_grad_weight_workspace_bytes(2, 8, 8)
     assert _wgrad(wsz=need - 1) == EWORKSPACE and _wgrad(wsz=0) == EWORKSPACE
