@@ -1293,8 +1293,9 @@ int rf_sparse_conv_grad_weight(int b, int n, int K, int cin, int cout, const flo
 
 /* ---- strided sparse convolution and its transpose: the change of level on that grid (sparse_stride.hip) ----
  * Kernel 2, stride 2 only: a coarse cell (x >> 1, y >> 1, z >> 1) -- the arithmetic shift, a floor -- has up to eight children,
- * the child (x, y, z) in slot t = (x & 1) 4 + (y & 1) 2 + (z & 1).  Kernel 3 / stride 2, other strides and a "generative"
- * transposed convolution that creates cells are not provided: the transpose writes to the cells of the finer level it came from.
+ * the child (x, y, z) in slot t = (x & 1) 4 + (y & 1) 2 + (z & 1).  Kernel 3 / stride 2 and other strides are not provided.  With
+ * rf_sparse_stride_map's maps the transpose writes to the cells of the finer level it came from; with rf_sparse_generate_map's (the
+ * next block) the same entries are the "generative" transposed convolution that creates cells.
  *
  * rf_sparse_stride_map: coords (b,n,3) int32 and count (b), read exactly as rf_sparse_conv_map reads them (the same LIVE rule:
  * below the clamped count M, in [-32768, 32767], no row of lower index with the same coordinates; any order) -> the coarse
@@ -1355,6 +1356,68 @@ size_t rf_sparse_conv_strided_grad_weight_workspace_bytes(int b, int cin, int co
 int rf_sparse_conv_strided_grad_weight(int b, int n, int n_coarse, int cin, int cout, int mode, const float *fine,
                                        const float *coarse, const int *child, const int *count, const int *count_coarse,
                                        float *grad_weight, void *workspace, size_t workspace_bytes, rf_stream_t stream);
+
+/* ---- generative transposed convolution, pruning and cell lookup: the decoder's step on that grid (sparse_generate.hip) ----
+ * A sparse completion decoder creates all eight children of every coarse cell, convolves onto them, classifies every new cell
+ * and prunes the unoccupied ones (MinkowskiEngine's GenerativeConvolutionTranspose + MinkowskiPruning).  The convolution is the
+ * block above: with child / up of rf_sparse_generate_map, count = its count_out and count_coarse = the coarse count, RF_SS_UP is
+ * the generative transposed convolution, RF_SS_UP_GRAD_INPUT its gradient to the features and
+ * rf_sparse_conv_strided_grad_weight(RF_SS_UP) its gradient to the weight.  The four entries here are one launch each, no
+ * workspace, no atomics in memory, no memset, every element of every output stored exactly once on every call, every count read
+ * on the device (capturable); b <= 65535 and every row count <= RF_GC_MAX_POINTS.  Counts are clamped into [0, rows] (NULL: all
+ * rows); rows behind a count are never read.  LIVE is rf_sparse_conv_map's rule: below the clamped count, the three coordinates
+ * in [-32768, 32767], no row of lower index with the same coordinates.
+ *
+ * rf_sparse_generate_map: coords (b,n_coarse,3), count (b) -> coords_out (b,n_fine,3), count_out (b), total_out (b), child
+ * (b,n_coarse,8), up (b,n_fine), 8 <= n_fine <= RF_GC_MAX_POINTS, 1 <= n_coarse <= n_fine.  A coarse row is a PARENT when it is
+ * live and its three coordinates are in [-16384, 16383] (its children 2 c + bit then stay in range).  The rank r of a parent is
+ * the number of parents of lower ROW index (not key order: with no dead rows the fine row of parent j, slot t is 8 j + t and the
+ * input order is kept).  Parents with r < n_fine / 8 (integer division) are KEPT: a parent gets all eight children or none.
+ * For a kept parent j and slot t = 0 .. 7 (the slot rule of the block above, t = (x & 1) 4 + (y & 1) 2 + (z & 1) of the child):
+ *     child[j][t] = 8 r + t,  up[8 r + t] = 8 j + t,  coords_out[8 r + t] = 2 coords[j] + ((t >> 2) & 1, (t >> 1) & 1, t & 1).
+ * Every other row of child is all -1; behind count_out up is -1 and coords_out is 0.  total_out = 8 #parents, count_out =
+ * 8 #kept.  Hence up[i] == 8 j + t exactly when child[j][t] == i, on which rf_sparse_conv_strided rests.  One workgroup per
+ * sample sorts (48-bit key << 16 | row) in LDS to find the duplicates, marks the live rows in LDS and scans them in row order.
+ * Argument rules, all checked before any HIP call: RF_EINVAL for a negative size; then b == 0 is RF_OK; RF_EINVAL for n_fine
+ * outside 8 ... RF_GC_MAX_POINTS, n_coarse outside 1 ... n_fine, b above 65535, a NULL tensor (count may be NULL), a tensor or
+ * count array not 4-byte aligned.
+ *
+ * rf_sparse_prune_map: coords (b,n,3), keep (b,n) uint8, count (b) -> coords_out (b,n_out,3), count_out (b), total_out (b), src
+ * (b,n_out), dst (b,n), 1 <= n_out <= n <= RF_GC_MAX_POINTS.  Row i < M is SELECTED when keep[i] != 0; there is no liveness test,
+ * rows are carried as they are; keep behind M is not read.  The rank r of a selected row is the number of selected rows of lower
+ * index (the compaction is stable); it is KEPT when r < n_out: src[r] = i, dst[i] = r, coords_out[r] = coords[i].  Every other
+ * entry of src and dst is -1, coords_out is 0 behind the count.  total_out = #selected, count_out = min(total_out, n_out).  One
+ * workgroup per sample scans keep in row order.  Argument rules, all checked before any HIP call: RF_EINVAL for a negative size;
+ * then b == 0 is RF_OK; RF_EINVAL for n outside 1 ... RF_GC_MAX_POINTS, n_out outside 1 ... n, b above 65535, a NULL tensor (count
+ * may be NULL; keep may not), an int32 tensor or count array not 4-byte aligned.  keep has no alignment requirement.
+ *
+ * rf_sparse_lookup: coords (b,n,3), count (b), table (b,m,3), tcount (b), 0 <= shift <= 15 -> idx (b,n), 1 <= n, m <=
+ * RF_GC_MAX_POINTS.  A table row is USABLE when it is below its clamped count and its coordinates are in [-32768, 32767]; its
+ * cell is table >> shift, the arithmetic shift (a floor) per axis.  For a query row i below its clamped count with coordinates
+ * in [-32768, 32767], idx[i] is the LOWEST usable table row whose shifted cell equals coords[i], or -1 when there is none; for
+ * every other query row idx[i] is -1.  Query rows are not de-duplicated.  shift = 0 is the map between two cell sets of one
+ * level (a skip connection); shift = s tells whether a cell of level s is occupied among the FINEST cells, with no pyramid of
+ * the target.  One workgroup per sample sorts the table's (key << 16 | row) in LDS and answers every query by a lower-bound
+ * binary search, as rf_sparse_conv_map does.  Argument rules, all checked before any HIP call: RF_EINVAL for a negative n, m or
+ * b; then b == 0 is RF_OK; RF_EINVAL for n or m outside 1 ... RF_GC_MAX_POINTS, b above 65535, shift outside 0 ... 15, a NULL
+ * tensor (count and tcount may be NULL), a tensor or count array not 4-byte aligned.
+ *
+ * rf_sparse_take_rows: src (b,n_src,c), idx (b,n_dst), count_dst (b) -> dst (b,n_dst,c), 1 <= c <= RF_GP_MAX_CHANNELS, 1 <=
+ * n_src, n_dst <= RF_GC_MAX_POINTS.  dst[r] = src[idx[r]] bit for bit where r is below the clamped count and 0 <= idx[r] < n_src;
+ * every other row is +0, so nothing outside the tensors is touched whatever idx holds; idx behind the count is not read.  It is
+ * rf_grid_unpool's RF_GU_COPY with two row counts: features through a pruning (by src forward, by dst backward) and through a
+ * skip (by the lookup's idx).  Argument rules, all checked before any HIP call: RF_EINVAL for a negative size; then b == 0 is
+ * RF_OK; RF_EINVAL for n_src or n_dst outside 1 ... RF_GC_MAX_POINTS, c outside 1 ... RF_GP_MAX_CHANNELS, b above 65535, a NULL
+ * tensor (count_dst may be NULL), a tensor or count array not 4-byte aligned.  When c is a multiple of 4 and src and dst are
+ * 16-byte aligned the rows move as 16-byte vectors; the results are the same. */
+int rf_sparse_generate_map(int b, int n_coarse, int n_fine, const int *coords, const int *count, int *coords_out, int *count_out,
+                           int *total_out, int *child, int *up, rf_stream_t stream);
+int rf_sparse_prune_map(int b, int n, int n_out, const int *coords, const unsigned char *keep, const int *count, int *coords_out,
+                        int *count_out, int *total_out, int *src, int *dst, rf_stream_t stream);
+int rf_sparse_lookup(int b, int n, int m, int shift, const int *coords, const int *count, const int *table, const int *tcount,
+                     int *idx, rf_stream_t stream);
+int rf_sparse_take_rows(int b, int n_src, int n_dst, int c, const float *src, const int *idx, const int *count_dst, float *dst,
+                        rf_stream_t stream);
 
 /* -------------------------------------------------- interpolation (tf_ops/interpolation) - */
 /* Replace threenn_cpu / threeinterpolate_cpu / threeinterpolate_grad_cpu

@@ -161,6 +161,10 @@ SIGNATURES = {
     "rf_sparse_conv_strided": (_i, [_i] * 6 + [_vp] * 8),
     "rf_sparse_conv_strided_grad_weight_workspace_bytes": (_sz, [_i, _i, _i]),
     "rf_sparse_conv_strided_grad_weight": (_i, [_i] * 6 + [_vp] * 7 + [_sz, _vp]),
+    "rf_sparse_generate_map": (_i, [_i, _i, _i] + [_vp] * 8),
+    "rf_sparse_prune_map": (_i, [_i, _i, _i] + [_vp] * 9),
+    "rf_sparse_lookup": (_i, [_i, _i, _i, _i] + [_vp] * 6),
+    "rf_sparse_take_rows": (_i, [_i, _i, _i, _i] + [_vp] * 5),
     "rf_threenn": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "rf_threenn_lengths_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "rf_threenn_lengths": (_i, [_i, _i, _i] + [_vp] * 7 + [_sz, _vp, _i]),

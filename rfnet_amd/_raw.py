@@ -2391,6 +2391,111 @@ def sparse_conv_strided_grad_weight(fine, coarse, child, nclusters=None, ncluste
     return st.give(gw)
 
 
+def _sg_coords(op, st, t, name="coords"):
+    c = st.take(t, I32)
+    if not _shape3(c, 3):
+        raise H.invalid(f"{op} expects (b,n,3) {name} shape")
+    if not (1 <= c.shape[0] <= 65535 and 1 <= c.shape[1] <= GC_MAX_POINTS):
+        raise H.invalid(f"{op} takes 1 <= b <= 65535 and 1 <= n <= {GC_MAX_POINTS} cells in {name}")
+    return c
+
+
+@H.on_input_device
+def sparse_generate_map(coords, nclusters=None, max_cells=None):
+    """rf_sparse_generate_map: coords (b,nc,3) int32 cells of the COARSE level and their counts nclusters (b,) -> (coords_out
+    (b,nf,3), count_out (b,), total_out (b,), child (b,nc,8), up (b,nf)), all int32, nf = max_cells (default min(8 nc, 16384)):
+    all eight children 2 c + bit of every live coarse row in [-16384, 16383], in row order (include/rfops.h)."""
+    op = "SparseGenerateMap"
+    st = H.Staged()
+    c = _sg_coords(op, st, coords)
+    b, nc = c.shape[0], c.shape[1]
+    nf = min(8 * nc, GC_MAX_POINTS) if max_cells is None else int(max_cells)
+    if not (8 <= nf <= GC_MAX_POINTS and nc <= nf):
+        raise H.invalid(f"{op} takes max(8, n) <= max_cells <= {GC_MAX_POINTS} fine rows")
+    cnt = _sc_check_counts(nclusters, b, nc)
+    dev = st.device_()
+    c, = st.up(c)
+    cnt = _sc_counts_up(cnt, dev, nc)
+    co, cn, tot = H.empty((b, nf, 3), I32, dev), H.empty((b,), I32, dev), H.empty((b,), I32, dev)
+    child, up = H.empty((b, nc, 8), I32, dev), H.empty((b, nf), I32, dev)
+    check(lib.rf_sparse_generate_map(b, nc, nf, H.ptr(c), H.ptr(cnt), H.ptr(co), H.ptr(cn), H.ptr(tot), H.ptr(child), H.ptr(up),
+                                     H.stream(dev)), "rf_sparse_generate_map")
+    return tuple(st.give(t) for t in (co, cn, tot, child, up))
+
+
+@H.on_input_device
+def sparse_prune_map(coords, keep, nclusters=None, max_cells=None):
+    """rf_sparse_prune_map: coords (b,n,3) int32, keep (b,n) (bool / uint8 as they are, any other dtype as > 0) and the counts
+    nclusters (b,) -> (coords_out (b,no,3), count_out (b,), total_out (b,), src (b,no), dst (b,n)), no = max_cells (default n):
+    the selected rows in front, in their order (include/rfops.h)."""
+    op = "SparsePruneMap"
+    st = H.Staged()
+    c = _sg_coords(op, st, coords)
+    b, n = c.shape[0], c.shape[1]
+    k = keep if isinstance(keep, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(keep)))
+    if tuple(k.shape) != (b, n):
+        raise H.invalid(f"{op} expects keep of shape {(b, n)}")
+    if k.dtype not in (torch.bool, torch.uint8):
+        k = k.detach() > 0
+    k = st.take(k, torch.uint8)
+    no = n if max_cells is None else int(max_cells)
+    if not 1 <= no <= n:
+        raise H.invalid(f"{op} takes 1 <= max_cells <= n rows")
+    cnt = _sc_check_counts(nclusters, b, n)
+    dev = st.device_()
+    c, k = st.up(c, k)
+    cnt = _sc_counts_up(cnt, dev, n)
+    co, cn, tot = H.empty((b, no, 3), I32, dev), H.empty((b,), I32, dev), H.empty((b,), I32, dev)
+    src, dst = H.empty((b, no), I32, dev), H.empty((b, n), I32, dev)
+    check(lib.rf_sparse_prune_map(b, n, no, H.ptr(c), H.ptr(k), H.ptr(cnt), H.ptr(co), H.ptr(cn), H.ptr(tot), H.ptr(src), H.ptr(dst),
+                                  H.stream(dev)), "rf_sparse_prune_map")
+    return tuple(st.give(t) for t in (co, cn, tot, src, dst))
+
+
+@H.on_input_device
+def sparse_lookup(coords, table, nclusters=None, table_nclusters=None, shift=0):
+    """rf_sparse_lookup: coords (b,n,3) and table (b,m,3) int32 with their counts -> idx (b,n) int32: the lowest usable row of
+    table whose cell >> shift (the arithmetic shift) equals coords[i], or -1 (include/rfops.h)."""
+    op = "SparseLookup"
+    st = H.Staged()
+    c, t = _sg_coords(op, st, coords), _sg_coords(op, st, table, "table")
+    b, n, m = c.shape[0], c.shape[1], t.shape[1]
+    if t.shape[0] != b:
+        raise H.invalid(f"{op} expects coords and table of the same batch size")
+    shift = int(shift)
+    if not 0 <= shift <= 15:
+        raise H.invalid(f"{op} takes 0 <= shift <= 15")
+    cnt, tcnt = _sc_check_counts(nclusters, b, n), _sc_check_counts(table_nclusters, b, m, "table_nclusters")
+    dev = st.device_()
+    c, t = st.up(c, t)
+    cnt, tcnt = _sc_counts_up(cnt, dev, n), _sc_counts_up(tcnt, dev, m)
+    idx = H.empty((b, n), I32, dev)
+    check(lib.rf_sparse_lookup(b, n, m, shift, H.ptr(c), H.ptr(cnt), H.ptr(t), H.ptr(tcnt), H.ptr(idx), H.stream(dev)),
+          "rf_sparse_lookup")
+    return st.give(idx)
+
+
+@H.on_input_device
+def sparse_take_rows(src, idx, nclusters=None):
+    """rf_sparse_take_rows: src (b,n_src,c), idx (b,n_dst) int32 and the counts nclusters (b,) of the DESTINATION rows ->
+    (b,n_dst,c): row r is a copy of row idx[r] of src where r is below the count and 0 <= idx[r] < n_src, +0 elsewhere."""
+    op = "SparseTakeRows"
+    st = H.Staged()
+    s = _gp_rows(op, st, src, "src")
+    b, ns, c = s.shape
+    ix = st.take(idx, I32)
+    if not (ix.dim() == 2 and ix.shape[0] == b and 1 <= ix.shape[1] <= GC_MAX_POINTS):
+        raise H.invalid(f"{op} expects idx of shape (b,n_dst), 1 <= n_dst <= {GC_MAX_POINTS}")
+    nd = ix.shape[1]
+    cnt = _sc_check_counts(nclusters, b, nd)
+    dev = st.device_()
+    s, ix = st.up(s, ix)
+    cnt = _sc_counts_up(cnt, dev, nd)
+    dst = H.empty((b, nd, c), F32, dev)
+    check(lib.rf_sparse_take_rows(b, ns, nd, c, H.ptr(s), H.ptr(ix), H.ptr(cnt), H.ptr(dst), H.stream(dev)), "rf_sparse_take_rows")
+    return st.give(dst)
+
+
 @H.on_input_device
 def knn_point_grad(xyz1, xyz2, idx, grad_val, lengths1=None, lengths2=None):
     """The gradient of knn_point's val -> (grad_xyz1 (b,n,3), grad_xyz2 (b,m,3)) (rf_knn_grad).  lengths1 / lengths2: the counts

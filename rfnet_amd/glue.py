@@ -1019,8 +1019,8 @@ def sparse_conv_up(feat, weight, level, nclusters=None):
     """The transpose of `sparse_conv_down` onto the fine level's cells (MinkowskiEngine's ConvolutionTranspose(kernel_size=2,
     stride=2) onto the encoder's coordinates, spconv's SparseInverseConv3d): feat (b, nc, cin) on the level's cells, weight
     (8, cin, cout) -> (b, n, cout): out[i] = feat[j] @ weight[t] for the fine row i = child[j, t], zeros for rows in no kept
-    coarse cell and behind nclusters, the fine level's count.  No cell is created.  One fmaf chain over the channels per row;
-    every fine row has one writer: no atomics.  Differentiable in feat and weight."""
+    coarse cell and behind nclusters, the fine level's count.  No cell is created (`sparse_conv_generate` does that).  One
+    fmaf chain over the channels per row; every fine row has one writer: no atomics.  Differentiable in feat and weight."""
     return _strided(feat, weight, level, nclusters, "up")
 
 
@@ -1067,6 +1067,106 @@ class SparseConvTranspose3d(_SparseStrided):
     def forward(self, feat, coords_or_level, nclusters=None):
         level = self._level(coords_or_level, nclusters)
         return self._add_bias(sparse_conv_up(feat, self.weight, level, nclusters), nclusters)
+
+
+def sparse_generate_map(coords, nclusters=None, max_cells=None):
+    """The next FINER level of the voxel grid with every cell created (MinkowskiEngine's GenerativeConvolutionTranspose,
+    the upsampling of SGNN-style completion decoders): coords (b, nc, 3) int32 coarse cells and nclusters (b,) (None: all nc)
+    -> a dict of device tensors for the FINE level: "coords" (b, nf, 3), the eight children 2 c + bit of every live coarse row
+    whose indices are in [-16384, 16383], parents in ROW order, the children of a parent in slot order t = (x & 1) 4 + (y & 1) 2
+    + (z & 1), zeros behind the count; "nclusters" (b,) = 8 x the parents kept, at most nf = max_cells (default min(8 nc, 16384));
+    a parent gets all eight children or none; "total" (b,) = 8 x all parents, the count without that cap; "child" (b, nc, 8), the
+    fine row 8 r + t of parent j's slot t (r = j when no row is dead) or -1; "up" (b, nf) = 8 j + t, -1 behind the count.  The
+    dict goes into `sparse_conv_generate`, its "coords" / "nclusters" into `sparse_conv_map`, `sparse_lookup`, `sparse_prune` and
+    the next `sparse_generate_map`.  One launch, no host synchronisation (capturable) (rf_sparse_generate_map)."""
+    co, cn, tot, child, up = _raw.sparse_generate_map(_index_tensor(coords), nclusters, max_cells)
+    return {"coords": co, "nclusters": cn, "total": tot, "child": child, "up": up}
+
+
+def sparse_conv_generate(feat, weight, gen, nclusters=None):
+    """Generative transposed convolution, kernel 2, stride 2: feat (b, nc, cin) on the coarse cells, weight (8, cin, cout) and
+    `sparse_generate_map`'s dict -> (b, nf, cout) on the created cells: out[8 r + t] = feat[j] @ weight[t] for parent j of rank
+    r, zeros behind the dict's count.  nclusters is the COARSE level's count (the dict's "nclusters" is the fine one: the
+    reverse of `sparse_conv_up`'s roles).  It is rf_sparse_conv_strided's "up" on the generated maps: one fmaf chain over the
+    channels per row, every fine row one writer, the same bits on every call.  Differentiable in feat and weight."""
+    return _SparseConvStrided.apply(_feature_tensor(feat), _feature_tensor(weight), _index_tensor(gen["child"]),
+                                    _index_tensor(gen["up"]), gen["nclusters"], nclusters, "up")
+
+
+class SparseGenerativeConvTranspose3d(_SparseStrided):
+    """`sparse_conv_generate` as a layer: weight (8, cin, cout), an optional bias (to the rows in front of the fine count only).
+    forward(feat (b, nc, cin), coords or gen, nclusters=None) -> (out (b, nf, cout), gen): given the coarse coords (b, nc, 3)
+    the level is generated here with the default max_cells; given `sparse_generate_map`'s dict it is used as it is.  nclusters
+    is the coarse level's count."""
+
+    def forward(self, feat, coords_or_gen, nclusters=None):
+        gen = coords_or_gen if isinstance(coords_or_gen, dict) else sparse_generate_map(coords_or_gen, nclusters)
+        return self._add_bias(sparse_conv_generate(feat, self.weight, gen, nclusters), gen["nclusters"]), gen
+
+
+class _SparseTake(torch.autograd.Function):
+    """rf_sparse_take_rows by idx under the count of the destination rows; its backward is the same entry by `inverse` under the
+    count of the source rows.  The maps and counts carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, feat, idx, inverse, count_dst, count_src):
+        ctx.save_for_backward(inverse)
+        ctx.count_src = count_src
+        return _raw.sparse_take_rows(feat, idx, count_dst)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        inverse, = ctx.saved_tensors
+        return _raw.sparse_take_rows(grad_out.contiguous(), inverse, ctx.count_src), None, None, None, None
+
+
+def sparse_take(feat, idx, inverse, nclusters=None):
+    """Rows by index: feat (b, n_src, c), idx (b, n_dst) int32 -> (b, n_dst, c), row r a copy of feat[idx[r]], zeros where
+    idx[r] is outside [0, n_src) (-1: no such cell) and behind nclusters, the count of the DESTINATION rows (rf_sparse_take_rows).
+    Differentiable in feat: the gradient is the same copy by `inverse` (b, n_src).  PRECONDITION, not checked: idx and inverse
+    are mutually inverse on their non-negative entries -- idx[r] == i >= 0 exactly when inverse[i] == r >= 0 -- so that every
+    gradient row has one source and nothing is summed.  This holds for `sparse_prune`'s "src" / "dst", and for the two
+    `sparse_lookup` calls at shift 0 between two levels neither of which has duplicate rows (a skip connection: idx =
+    sparse_lookup(decoder, encoder), inverse = sparse_lookup(encoder, decoder)).  With duplicates, a lookup names the lowest row
+    only and the gradient of the others would be lost."""
+    return _SparseTake.apply(_feature_tensor(feat), _index_tensor(idx), _index_tensor(inverse), nclusters, None)
+
+
+def sparse_prune(coords, keep, feat=None, nclusters=None, max_cells=None):
+    """Pruning (MinkowskiEngine's MinkowskiPruning): the rows of coords (b, n, 3) with keep (b, n) set, in their order, in
+    front -> a dict of device tensors: "coords" (b, no, 3), zeros behind the count; "nclusters" (b,), at most no = max_cells
+    (default n); "total" (b,) the count without that cap; "src" (b, no) the row each kept row came from, "dst" (b, n) where each
+    row went, -1 elsewhere; "feat" (b, no, c) the rows of feat (b, n, c) moved along, or None.  keep is a bool or uint8 tensor,
+    or any other dtype taken as > 0 (a classifier's logits); rows behind nclusters are not selected.  Nothing is tested but
+    keep: rows are carried as they are.  One launch for the map and one for the rows, the counts stay on the device: no
+    `nonzero`, no boolean mask, no host synchronisation (capturable) (rf_sparse_prune_map, rf_sparse_take_rows).  Differentiable
+    in feat: the gradient goes back by "dst"."""
+    co, cn, tot, src, dst = _raw.sparse_prune_map(_index_tensor(coords), keep, nclusters, max_cells)
+    moved = None if feat is None else _SparseTake.apply(_feature_tensor(feat), src, dst, cn, nclusters)
+    return {"coords": co, "nclusters": cn, "total": tot, "src": src, "dst": dst, "feat": moved}
+
+
+class SparsePrune(torch.nn.Module):
+    """`sparse_prune` as a layer: forward(coords, keep, feat=None, nclusters=None) -> its dict; max_cells is the layer's."""
+
+    def __init__(self, max_cells=None):
+        super().__init__()
+        self.max_cells = max_cells
+
+    def forward(self, coords, keep, feat=None, nclusters=None):
+        return sparse_prune(coords, keep, feat, nclusters, self.max_cells)
+
+
+def sparse_lookup(coords, table, nclusters=None, table_nclusters=None, shift=0):
+    """Where the cells of one set are in another: coords (b, n, 3) and table (b, m, 3) int32 with their counts -> idx (b, n)
+    int32, the LOWEST row of table whose cell `table >> shift` (the arithmetic shift, per axis) equals coords[i], -1 where there
+    is none, for rows behind nclusters and for rows outside +-32768.  shift = 0 maps a decoder level to the encoder's cells of
+    that level (a skip connection, with `sparse_take`); shift = s tells whether a generated cell of level s is occupied among
+    the ground truth's FINEST cells, without a pyramid of the target (`idx >= 0` is the occupancy label and the keep mask of
+    `sparse_prune`).  One launch: a sort of the table's keys in LDS and a binary search per row, no host synchronisation
+    (capturable), n, m <= 16384 (rf_sparse_lookup).  Non-differentiable."""
+    return _raw.sparse_lookup(_index_tensor(coords), _index_tensor(table), nclusters, table_nclusters, shift)
 
 
 class _NeighborAggregation(torch.autograd.Function):
